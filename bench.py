@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Gibbs sweeps/sec of the full W+V update (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one W half-sweep + one V half-sweep (model._resample_W then model._resample_V through
 the C ABI) on synthetic data that is already resident in HBM, with the normals drawn on the device
@@ -138,6 +138,9 @@ def parse_args(argv=None):
     ap.add_argument("--python-loop", action="store_true", help="drive the timed W+V steps from Python, call by call (default on one GPU with "
                     "Gaussian data: one btf_wv_steps call queues them all)")
     ap.add_argument("--master-port", type=int, default=29533)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what their last step "
+                    "computed - the factors W and V a caller of the step receives - as DIR/<name>.npy (float64; a fixed, seeded "
+                    "sample of any array beyond DUMP_MAX_BYTES): with the same arguments two builds can be compared output for output")
     return ap.parse_args(argv)
 
 
@@ -309,6 +312,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     model.sync()                      # raises if any factorisation failed inside the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"W": model.W, "V": model.V})
     py_per_s = None
     if c_driven and not args.lean:    # the same K steps driven from Python, call by call
         for _ in range(args.warmup):
@@ -607,6 +612,25 @@ def main():
     if world > 1 or exercise:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write each array as dirname/<name>.npy in float64.  An array past its share of DUMP_MAX_BYTES is written as a fixed
+    sample of its flattened elements (indices drawn with a fixed seed, so that the same shape gives the same sample) under
+    <name>_sample.npy, the indices beside it as <name>_sample_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // (2 * len(arrays))         # (a sampled array writes its indices too)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes <= share:
+            np.save(os.path.join(dirname, name + ".npy"), a)
+            continue
+        idx = np.sort(np.random.RandomState(0).choice(a.size, share // 8, replace=False))
+        np.save(os.path.join(dirname, name + "_sample.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(dirname, name + "_sample_index.npy"), idx.astype(np.float64))
 
 
 def host_rng_leg(Y, N, M, T, K, device, stream, fence, steps=40, sweeps=20):

@@ -170,6 +170,25 @@ def test_bench_launches_its_own_ranks_and_prints_one_line():
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 2
 
 
+def test_bench_dump_outputs_writes_float64_arrays_within_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays within their share of the cap are written whole; a larger one as the same seeded
+    sample (and its indices) on every call, so that two runs compare output for output."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    W = np.arange(64, dtype=np.float32).reshape(8, 8)
+    V = np.random.RandomState(3).normal(size=(16, 32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"W": W, "V": V})
+    assert sorted(os.listdir(tmp_path / "a")) == ["V_sample.npy", "V_sample_index.npy", "W.npy"]
+    w = np.load(tmp_path / "a" / "W.npy")
+    assert w.dtype == np.float64 and np.array_equal(w, W)
+    idx = np.load(tmp_path / "a" / "V_sample_index.npy").astype(np.int64)
+    assert len(idx) == 4096 // 4 // 8 and np.array_equal(np.load(tmp_path / "a" / "V_sample.npy"), V.reshape(-1)[idx])
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 4096 + 3 * 128
+
+
 def test_shard_plan_finds_the_one_halo_source_and_appends_it_to_the_slabs():
     """compat="reference" sharded (btf_set_shard_halo): per contiguous block at most one stale-weight source row and one
     source column lie outside it; ShardPlan.halo_of finds them from the reference's source patterns (factor.py:320,349 and
