@@ -15,18 +15,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")   # override: A/B builds
-SOURCES = [os.path.join(CSRC, "btf_abi.hip")]
+SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
 BTF_OK, BTF_EINVAL, BTF_EHIP, BTF_ENOTPD, BTF_ESTATE = 0, 1, 2, 3, 4
 COMPAT = {"reference": 0, "exact": 1}
 KERNEL_NAMES = ["stats", "w_accum", "w_solve", "v_accum", "v_banded", "gram", "products", "sse", "pg_draw", "nb_loglik",
-                "prior_band", "gram_eig", "hyper", "ess"]
+                "prior_band", "gram_eig", "hyper", "ess", "criteria"]
 COMM_ID_BYTES = 128               # BTF_COMM_ID_BYTES of include/btf.h
 PEER_DESC_BYTES = 256             # BTF_PEER_DESC_BYTES
 OPT_SAMPLER, OPT_NB_HISTOGRAMS, OPT_FUSE_GRAM, OPT_PG_EXACT, OPT_CURVE_COUNTS, OPT_SPLIT_ACCUM, OPT_FUSED_SWEEP, OPT_FUSED_STEP, OPT_FUSED_DATAFLOW = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ESS_HOST_LIKELIHOOD = -1          # BTF_ESS_HOST_LIKELIHOOD of include/btf.h
+CRIT_NOISE_PER_SAMPLE, CRIT_CURRENT = 1, 2   # BTF_CRIT_* flags of btf_crit_eval
 SAMPLERS = {"banded": 0, "spectral": 1, "chain": 2, "generic": 3, "banded_nopanel": 4}
 
 # every symbol include/btf.h declares: (name, restype, argtypes)
@@ -88,6 +89,8 @@ SIGNATURES = {
     "btf_collect_schedule": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
     "btf_collect_end": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
     "btf_collect_summary": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),
+    "btf_crit_set_data": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "btf_crit_eval": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
     "btf_sync": (C.c_int, [_ctx]),
     "btf_ess_begin": (C.c_int, [_ctx, C.c_int, _c_dp, C.c_uint64, C.c_double, C.c_int]),
     "btf_ess_eval": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, C.c_int, _c_dp]),
@@ -175,7 +178,7 @@ def build(force=False, verbose=False, jobs=None):
     base = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function",
             "-mllvm", "-amdgpu-kernarg-preload-count=16",
             "-I", os.path.join(ROOT, "include")] + os.environ.get("BTF_BUILD_DEFS", "").split()   # A/B builds: -DBTF_... tuning macros
-    units = [(SOURCES[0], os.path.join(OBJ_DIR, tag + "_abi.o"), [])]
+    units = [(SOURCES[0], os.path.join(OBJ_DIR, tag + "_abi.o"), []), (SOURCES[1], os.path.join(OBJ_DIR, tag + "_crit.o"), [])]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

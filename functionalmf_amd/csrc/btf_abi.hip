@@ -9,6 +9,7 @@
 #include "btf_spectral.h"
 #include "btf_gass.h"
 #include "btf_fused.h"
+#include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
 #include <hip/hip_ext.h>
@@ -120,6 +121,9 @@ struct btf_ctx {
   bool pg_has_small = true, pg_has_big = true, pg_has_frac = true;
   // on-device sample collection (run_gibbs, rng="device"): [nsamp] slots of W, V, Tau2 and the scalars
   double* smp_W = nullptr; double* smp_V = nullptr; double* smp_T = nullptr; double* smp_s = nullptr; int smp_n = 0;
+  // model-selection criteria (btf_crit_*): the compact statistics of slot 0 (bound data) / 1 (held-out data)
+  double* crit_S1[2] = {nullptr, nullptr}; double* crit_cnt[2] = {nullptr, nullptr};
+  double* crit_c0[2] = {nullptr, nullptr}; double* crit_c1[2] = {nullptr, nullptr};
   int col_every = 0, col_slot = 0, col_count = 0;       // btf_collect_schedule: btf_gibbs_sweeps keeps every col_every-th state
   double* hyp = nullptr;        // device-resident scalars [HYP_COUNT] (nu2, sigma2, lam2, lam2_a, ...)
   bool dev_scalars = false;     // kernels read nu2 / sigma2 / lam2 from hyp instead of the host copies
@@ -1000,6 +1004,9 @@ void btf_destroy(btf_ctx* c) {
   if (c->pin_hyp) (void)hipHostFree(c->pin_hyp);
   for (void* p : {(void*)c->nb_data, (void*)c->nb_S, (void*)c->nb_cnt, (void*)c->nb_R, (void*)c->nb_C, (void*)c->nb_tmp, (void*)c->nb_out, (void*)c->nb_H, (void*)c->nb_Hd, (void*)c->nb_Hs, (void*)c->nb_G, (void*)c->nb_L, (void*)c->nb_optr, (void*)c->nb_oval, (void*)c->fill_tab, (void*)c->C8_wT, (void*)c->C8_v, (void*)c->smp_W, (void*)c->smp_V, (void*)c->smp_T, (void*)c->smp_s})
     if (p) (void)hipFree(p);
+  for (int sl = 0; sl < 2; ++sl)
+    for (void* p : {(void*)c->crit_S1[sl], (void*)c->crit_cnt[sl], (void*)c->crit_c0[sl], (void*)c->crit_c1[sl]})
+      if (p) (void)hipFree(p);
   if (c->hyp) (void)hipFree(c->hyp);
   if (c->fz_words) (void)hipFree(c->fz_words);
   if (c->fz_pub) (void)hipFree(c->fz_pub);
@@ -3090,6 +3097,119 @@ int btf_collect_summary(btf_ctx* c, int nsamples, int transform, const double* q
   if (nq) CS(hipMemcpyAsync(q_out, dqo, (size_t)nq * cellsN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   CS(hipStreamSynchronize(c->stream));
 #undef CS
+  cleanup();
+  return BTF_OK;
+}
+
+// ---------------------------------------------------------- model-selection criteria (btf_criteria.h)
+int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt, const double* curve_c0, const double* curve_c1) {
+  if (!c || slot < 0 || slot > 1) return fail(c, BTF_EINVAL, "criteria slot must be 0 or 1");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistics)
+  double** bufs[4] = {&c->crit_S1[slot], &c->crit_cnt[slot], &c->crit_c0[slot], &c->crit_c1[slot]};
+  if (!S1 && !cnt && !curve_c0 && !curve_c1) {       // free the slot
+    for (double** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    return BTF_OK;
+  }
+  if (!S1 || !cnt || !curve_c0 || !curve_c1) return fail(c, BTF_EINVAL, "btf_crit_set_data: all four arrays, or none");
+  const size_t cells = (size_t)c->M * c->T * c->N, curves = (size_t)c->N * c->M;
+  const double* src[4] = {S1, cnt, curve_c0, curve_c1};
+  const size_t n[4] = {cells, cells, curves, curves};
+  for (int q = 0; q < 4; ++q) {
+    int rc;
+    if ((rc = dev_alloc(c, bufs[q], n[q]))) return rc;
+    HIPCHK(c, hipMemcpyAsync(*bufs[q], src[q], n[q] * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BTF_OK;
+}
+
+int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                  const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out) {
+  if (!c || slot < 0 || slot > 1 || family < 0 || family >= CRIT_FAM_COUNT || nsamples < 1 || !curve_out || !total_out ||
+      (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
+    return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
+  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, "btf_crit_eval: no statistics in this slot (btf_crit_set_data)");
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_crit_eval needs an unsharded context");
+  const bool current = (flags & BTF_CRIT_CURRENT) != 0, per_sample = (flags & BTF_CRIT_NOISE_PER_SAMPLE) != 0;
+  if (current && (Ws || nsamples != 1 || !c->have_W || !c->have_V))
+    return fail(c, BTF_EINVAL, "BTF_CRIT_CURRENT scores the context's own W, V: one sample, Ws = Vs = NULL");
+  if (!Ws && !current && (!c->smp_W || nsamples > c->smp_n)) return fail(c, BTF_ESTATE, "btf_crit_eval: not that many collected samples");
+  if (per_sample && family != CRIT_FAM_GAUSSIAN) return fail(c, BTF_EINVAL, "per-sample noise is the Gaussian family's");
+  if (per_sample && !noise && (Ws || current)) return fail(c, BTF_EINVAL, "per-sample noise of uploaded / current states: pass `noise`");
+  if (!per_sample && (family == CRIT_FAM_GAUSSIAN || family == CRIT_FAM_NEGBIN) && !(param > 0.0))
+    return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
+  HIPCHK(c, hipSetDevice(c->dev));
+  const int S = nsamples, N = c->N, M = c->M, T = c->T, K = c->K;
+  const dim3 grid((N + WAVE - 1) / WAVE, M);
+  const int nwg = (int)(grid.x * grid.y);
+  const size_t nW = (size_t)S * N * K, nV = (size_t)S * M * T * K, NM = (size_t)N * M;
+  double *dW = nullptr, *dV = nullptr, *dn = nullptr, *dmu = nullptr, *dcurve = nullptr, *dpart = nullptr, *dtot = nullptr, *dpw = nullptr;
+  auto cleanup = [&]() { for (double* p : {dW, dV, dn, dmu, dcurve, dpart, dtot, dpw}) if (p) (void)hipFree(p); };
+#define CE(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+#define CA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) { cleanup(); return rc__; } } while (0)
+  CritArgs a{};
+  a.S1 = c->crit_S1[slot]; a.cnt = c->crit_cnt[slot]; a.c0 = c->crit_c0[slot]; a.c1 = c->crit_c1[slot];
+  if (Ws) {
+    CA(dW, nW); CA(dV, nV);
+    CE(hipMemcpyAsync(dW, Ws, nW * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CE(hipMemcpyAsync(dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    a.W = dW; a.V = dV;
+  } else if (current) {
+    a.W = c->W; a.V = c->V;
+  } else {
+    a.W = c->smp_W; a.V = c->smp_V;
+  }
+  a.noise = nullptr; a.noise_stride = 1;
+  if (per_sample) {
+    if (noise) {
+      CA(dn, (size_t)S);
+      CE(hipMemcpyAsync(dn, noise, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      a.noise = dn;
+    } else {
+      a.noise = c->smp_s + HYP_NU2; a.noise_stride = HYP_COUNT;       // the collected nu2 of every kept state
+    }
+  }
+  a.par = param; a.S = S; a.N = N; a.M = M; a.T = T;
+  CA(dmu, (size_t)M * T * N); CA(dcurve, CRIT_OUT * NM); CA(dpart, (size_t)S * nwg); CA(dtot, (size_t)S);
+  if (pointwise_out) CA(dpw, (size_t)S * NM);
+  a.mu = dmu; a.curve = dcurve; a.tot_part = dpart; a.pw = dpw;
+#define CRIT_FAMS(KT_)                                                                                   \
+  switch (family) {                                                                                      \
+    case 0: p.launch(crit_kernel<KT_, 0>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
+    case 1: p.launch(crit_kernel<KT_, 1>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
+    case 2: p.launch(crit_kernel<KT_, 2>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
+    case 3: p.launch(crit_kernel<KT_, 3>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
+    default: p.launch(crit_kernel<KT_, 4>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                  \
+  }
+  {
+    Prof p(c, BTF_K_CRITERIA);
+    K_SWITCH(K, CRIT_FAMS(KT));
+  }
+#undef CRIT_FAMS
+  CE(hipGetLastError());
+  {
+    Prof p(c, BTF_K_CRITERIA);
+    switch (family) {
+      case 0: p.launch(crit_plugin_kernel<0>, grid, dim3(WAVE), 0, a); break;
+      case 1: p.launch(crit_plugin_kernel<1>, grid, dim3(WAVE), 0, a); break;
+      case 2: p.launch(crit_plugin_kernel<2>, grid, dim3(WAVE), 0, a); break;
+      case 3: p.launch(crit_plugin_kernel<3>, grid, dim3(WAVE), 0, a); break;
+      default: p.launch(crit_plugin_kernel<4>, grid, dim3(WAVE), 0, a); break;
+    }
+  }
+  CE(hipGetLastError());
+  {
+    Prof p(c, BTF_K_CRITERIA);
+    p.launch(crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)dpart, S, nwg, dtot);
+  }
+  CE(hipGetLastError());
+  CE(hipMemcpyAsync(curve_out, dcurve, CRIT_OUT * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  CE(hipMemcpyAsync(total_out, dtot, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (pointwise_out) CE(hipMemcpyAsync(pointwise_out, dpw, (size_t)S * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  CE(hipStreamSynchronize(c->stream));        // (not check_status: the sampler's status word is not this call's)
+#undef CE
+#undef CA
   cleanup();
   return BTF_OK;
 }

@@ -38,6 +38,7 @@ import ctypes
 import numpy as np
 
 from . import _native
+from . import criteria as _criteria
 from .genlasso import _BayesianModel, ConjugateInverseGammaPrior
 from .utils import bayes_grid_penalty, sample_horseshoe_plus, sample_horseshoe
 from .parallel import ShardPlan, Exchange
@@ -372,6 +373,7 @@ class BayesianTensorFiltering(_BayesianModel):
                           "sweeps used the previous contents (call set_data() right after editing the array in place)" % (now - self._data_uploaded),
                           RuntimeWarning, stacklevel=3)
         self._upload(data)
+        self._crit_drop(0)             # the criteria statistics of the previously bound data
         import time
         t0 = time.monotonic()
         self._data_digest = tuple(_digest(a) for a in arrays)
@@ -678,6 +680,142 @@ class BayesianTensorFiltering(_BayesianModel):
         self._ctx.call("btf_collect_summary", int(n), code, _native.dptr(qs), len(qs), _native.dptr(mean), _native.dptr(quant))
         return mean, quant
 
+    # ---- model selection: per-curve log-likelihood, WAIC, DIC (functionalmf_amd/criteria.py, csrc/btf_criteria.h) ----
+    def _crit_family(self):
+        """(family of btf_crit_eval, its parameter, per-sample noise?) of this model's likelihood."""
+        raise NotImplementedError("%s: no device log-likelihood for the model-selection criteria" % type(self).__name__)
+
+    def _crit_drop(self, slot):
+        keys = getattr(self, "_crit_keys", None)
+        if keys is not None and keys[slot] is not None:
+            self._ctx.call("btf_crit_set_data", slot, None, None, None, None)
+            keys[slot] = None
+
+    def _crit_slot(self, data, family, param):
+        """Upload the criteria statistics of `data` once (cached by identity, shape and fingerprint, as set_data
+        recognises the bound data); returns (slot, observed-curve mask).  Slot 0 holds the bound data, 1 held-out data."""
+        if data is None:
+            data = getattr(self, "_data_ref", None)
+            if data is None:
+                raise ValueError("no data bound to the model: pass data=")
+        arrays = data if isinstance(data, (tuple, list)) else (data,)
+        key = (family, param) + tuple((id(a), np.shape(a), _fingerprint(a)) for a in arrays)
+        if getattr(self, "_crit_keys", None) is None:
+            self._crit_keys, self._crit_obs, self._crit_refs = [None, None], [None, None], [None, None]
+        for slot in (0, 1):
+            if self._crit_keys[slot] == key:
+                return slot, self._crit_obs[slot]
+        bound = getattr(self, "_data_ref", None)
+        bound = bound if isinstance(bound, (tuple, list)) else (bound,)
+        slot = 0 if len(bound) == len(arrays) and all(a is b for a, b in zip(arrays, bound)) else 1
+        S1, cnt, c0, c1, obs = _criteria.statistics(family, data, (self.nrows, self.ncols, self.ndepth), param)
+        self._ctx.call("btf_crit_set_data", slot, _native.dptr(S1), _native.dptr(cnt), _native.dptr(c0), _native.dptr(c1))
+        self._crit_keys[slot], self._crit_obs[slot], self._crit_refs[slot] = key, obs, data     # (refs: ids stay unique)
+        return slot, obs
+
+    def _crit_check(self):
+        """Refusals before any work: sharded contexts, likelihoods without a device form."""
+        if self._plan.world > 1 or self._exchange.active:
+            raise NotImplementedError("model-selection criteria: unsharded models only")
+        return self._crit_family()
+
+    def _crit_eval(self, data, nsamples, Ws=None, Vs=None, noise=None, current=False, pointwise=False):
+        family, param, per_sample = self._crit_check()
+        slot, obs = self._crit_slot(data, family, param)
+        N, M = self.nrows, self.ncols
+        curve = np.zeros((_criteria.CURVE_OUTPUTS, N, M))
+        totals = np.zeros(nsamples)
+        pw = np.zeros((nsamples, N, M)) if pointwise else None
+        flags = (_native.CRIT_NOISE_PER_SAMPLE if per_sample else 0) | (_native.CRIT_CURRENT if current else 0)
+        noise = _native.as_f64(np.reshape(noise, -1)) if (per_sample and noise is not None) else None
+        Ws = None if Ws is None else _native.as_f64(Ws)
+        Vs = None if Vs is None else _native.as_f64(Vs)
+        self._ctx.call("btf_crit_eval", slot, int(family), float(param if param is not None else 0.0), int(nsamples),
+                       _native.dptr(Ws), _native.dptr(Vs), _native.dptr(noise), flags, _native.dptr(curve),
+                       _native.dptr(totals), _native.dptr(pw))
+        return curve, totals, obs, pw
+
+    def information_criteria(self, results=None, data=None, pointwise=False):
+        """WAIC and DIC of the posterior samples, from the per-curve log-likelihood (csrc/btf_criteria.h; replaces the
+        scoring of _BayesianModel.select_hyperparams_DIC, genlasso.py:69-136, and doseresponse/select_btf.py:9-23).
+
+        results: a run_gibbs result dict (W (S,N,K), V (S,M,T,K); Gaussian: nu2 (S,1)), uploaded; None: the samples the
+            last device-collecting run_gibbs left on the device (no upload).
+        data: the observations to score; None: the data the model is bound to.  Another tensor of the same shape scores
+            held-out observations (NaN everywhere else): `lppd` is then their log pointwise predictive density.
+
+        The pointwise unit is the curve (i,j): ll_s(i,j) = the normalised log-likelihood of all observed y_ijtr of the
+        curve under sample s.  Curves without observations count 0 and are left out of n_curves.
+            lppd_ij = logsumexp_s ll_s(i,j) - log S        p_waic_ij = var_s ll_s(i,j) (ddof 1; 0 when S = 1)
+            elpd_waic = sum (lppd_ij - p_waic_ij),  waic = -2 elpd_waic,  waic_se = 2 sqrt(n_curves var_ij(lppd - p_waic))
+            mean_deviance = -2 mean_s sum_ij ll_s,   deviance_at_mean = -2 sum_ij ll(Mu-bar, theta-bar)
+            p_dic = mean_deviance - deviance_at_mean,   dic = mean_deviance + p_dic
+        Mu-bar_ijt = mean_s w_i^s . v_jt^s is the posterior mean of the product, NOT W-bar V-bar': W and V are identified
+        only up to rotation and sign between samples, so their means are meaningless (doseresponse/select_btf.py plugs in
+        the mean of W V' too).  theta-bar: the mean sampled nu2 (Gaussian), the fixed likelihood_param otherwise.
+        A -inf sample (poisson_identity where w.v <= 0) follows scipy.special.logsumexp / np.var: that curve's p_waic is nan.
+
+        Returns a dict with waic, elpd_waic, p_waic, lppd, waic_se, dic, p_dic, mean_deviance, deviance_at_mean,
+        n_curves, nsamples, loglik_per_sample (S,) and curves = {lppd, p_waic, mean_ll, ll_at_mean} of (N,M) arrays;
+        pointwise=True adds loglik (S,N,M), the full matrix (for PSIS-LOO with outside tools; S*N*M doubles of host memory).
+        Device memory: the criteria statistics, 16 B per cell (functionalmf_amd/criteria.py), and 8 B per cell of scratch."""
+        self._crit_check()
+        if results is None:
+            n = getattr(self, "_collected", 0)
+            if n < 1:
+                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first)")
+            curve, totals, obs, pw = self._crit_eval(data, n, pointwise=pointwise)
+        else:
+            Ws, Vs, noise = self._crit_results(results)
+            curve, totals, obs, pw = self._crit_eval(data, Ws.shape[0], Ws, Vs, noise, pointwise=pointwise)
+        return _criteria.combine(curve, totals, obs, pw)
+
+    def _crit_results(self, results):
+        N, M, T, K = self.nrows, self.ncols, self.ndepth, self.nembeds
+        try:
+            Ws, Vs = np.asarray(results["W"], dtype=float), np.asarray(results["V"], dtype=float)
+        except (KeyError, TypeError):
+            raise ValueError("results must be a run_gibbs result dict with W (S,N,K) and V (S,M,T,K)")
+        S = Ws.shape[0] if Ws.ndim == 3 else -1
+        if Ws.shape != (S, N, K) or Vs.shape != (S, M, T, K) or S < 1:
+            raise ValueError("results: W %r / V %r do not match the model's (S,%d,%d) / (S,%d,%d,%d)" % (Ws.shape, Vs.shape, N, K, M, T, K))
+        noise = None
+        if self._crit_family()[2]:
+            if "nu2" not in results or np.size(results["nu2"]) != S:
+                raise ValueError("results: nu2 must hold one variance per sample, (S,1)")
+            noise = np.asarray(results["nu2"], dtype=float).reshape(S)
+        return Ws, Vs, noise
+
+    def logprob(self, data, reduce="sum", **state):
+        """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,
+        nu2=); further keys (Tau2, lam2, sigma2, ...: what the reference's DIC passes) are ignored.  reduce="sum": a
+        float; "curve": the (N,M) per-curve values (0 for curves without observations).  The criteria kernel with one sample.
+        Deviation: the reference (factor.py:262-264, :610-612, :1002-1005) returns an elementwise array built from an
+        undefined name, with sigma2 where the noise variance nu2 belongs."""
+        if reduce not in ("sum", "curve"):
+            raise ValueError("reduce must be 'sum' or 'curve'")
+        per_sample = self._crit_check()[2]
+        W, V = state.get("W"), state.get("V")
+        noise = None
+        if per_sample:
+            noise = np.array([_scalar(state["nu2"] if state.get("nu2") is not None else self.nu2)])
+        if W is None and V is None and not (self._W_host_new or self._V_host_new):
+            curve, totals, obs, _ = self._crit_eval(data, 1, noise=noise, current=True)       # the device's own W, V
+        else:
+            if W is None:
+                self._pull_W()
+                W = self._W
+            if V is None:
+                self._pull_V()
+                V = self._V
+            W, V = np.asarray(W, dtype=float), np.asarray(V, dtype=float)
+            if W.shape != (self.nrows, self.nembeds) or V.shape != (self.ncols, self.ndepth, self.nembeds):
+                raise ValueError("W %r / V %r do not match the model" % (W.shape, V.shape))
+            curve, totals, obs, _ = self._crit_eval(data, 1, W[None], V[None], noise)
+        if reduce == "sum":
+            return float(totals[0])
+        return np.where(obs, curve[2], 0.0)
+
     # ---- the two half-sweeps (device) ----------------------------------------------
     def _w_normals(self):
         if self.rng != "host":
@@ -840,6 +978,9 @@ class GaussianBayesianTensorFiltering(BayesianTensorFiltering):
 
     def _init_nu2(self):
         self.nu2 = 1 / self.nu2_model.draw_from_prior()
+
+    def _crit_family(self):
+        return _criteria.FAMILY_GAUSSIAN, None, True        # variance: the sampled nu2
 
     def _upload(self, Y):
         if Y.ndim not in (3, 4):
@@ -1079,6 +1220,9 @@ class BinomialBayesianTensorFiltering(GaussianBayesianTensorFiltering):
         self._set_stale_sources()
         self._omega_host_new = True
 
+    def _crit_family(self):
+        return _criteria.FAMILY_LOGIT, None, False         # y successes of n trials, logit link (factor.py:425-460)
+
     def _set_noise(self):
         if getattr(self, "_omega_host_new", False) and np.ndim(self._nu2) == 3:
             with np.errstate(divide='ignore'):
@@ -1128,6 +1272,10 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
         else:
             self._init_R()
         self._rate_key = None
+
+    def _crit_family(self):
+        raise NotImplementedError("model-selection criteria for the Negative-Binomial model: its lgamma(y + R) terms depend on "
+                                  "the sampled rate R at every observation (not supported yet)")
 
     def _rate_shape(self):
         return tuple(1 if i in self._shared else c for i, c in enumerate((self.nrows, self.ncols, self.ndepth)))
@@ -1308,6 +1456,12 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         self.ess, self.ess_max_rounds = ess, int(ess_max_rounds)
         self.ess_evaluations = 0          # likelihood evaluations of the last host-driven slice (diagnostic)
         self._ll_const = 0.0
+
+    def _crit_family(self):
+        if self._callback:
+            raise NotImplementedError("model-selection criteria need a device likelihood: a Python-callable loglikelihood "
+                                      "is evaluated on the host only")
+        return self._link, (self.likelihood_param if self._link in (3, 4) else None), False
 
     def _bind_data(self, data):
         if self._callback:           # the function's `data` is its own business (any object): nothing goes to the device

@@ -64,7 +64,8 @@ enum {
   BTF_K_EIG = 11,    /* eigen-system of the K x K Gram (spectral sampler)   */
   BTF_K_HYPER = 12,  /* device hyper-parameter draws: Tau2 chain, nu2/sigma2, lam2 */
   BTF_K_ESS = 13,    /* elliptical slice sampling: prior draws, proposals, likelihood passes, decisions */
-  BTF_K_COUNT = 14
+  BTF_K_CRITERIA = 14, /* model-selection criteria: per-curve log-likelihood over the kept samples (btf_crit_eval) */
+  BTF_K_COUNT = 15
 };
 
 /* btf_set_option keys / values */
@@ -570,6 +571,32 @@ int btf_collect(btf_ctx* ctx, int slot);
 int btf_collect_schedule(btf_ctx* ctx, int every, int first_slot, int countdown);
 int btf_collect_end(btf_ctx* ctx, int nsamples, double* W, double* V, double* Tau2, double* scalars8);
 int btf_collect_summary(btf_ctx* ctx, int nsamples, int transform, const double* q, int nq, double* mean_out, double* q_out);
+
+/* ---- model-selection criteria (replaces _BayesianModel.select_hyperparams_DIC's scoring, genlasso.py:69-136, on
+ * logprob, factor.py:262-264 / :610-612 / :1002-1005, and the hand-made DIC of doseresponse/select_btf.py:9-23) ----------
+ * The normalised log-likelihood ll_s(i,j) of every curve (i,j) - all its observed y_ijtr over depth and replicates -
+ * under every kept sample s, reduced on the device to what WAIC, DIC and held-out scoring need (csrc/btf_criteria.h).
+ * Touches none of the sampler's state (partials, caches, draw counters, status word): a chain continued after a
+ * criteria call walks the same path.  Unsharded contexts.
+ *
+ * btf_crit_set_data: the criteria's own statistics for slot 0 (the bound data) or 1 (held-out data), in the kernel's
+ *   layout: S1 [M][T][N] = sum_r y, cnt [M][T][N] = observed replicates (Binomial: trials), curve_c0 / curve_c1 [N][M]
+ *   the curve's constant (family 3: sum y^2 and the observation count; otherwise the state-independent log-likelihood
+ *   terms: - sum lgamma(y+1), sum log C(n,y), ...; curve_c1 unused).  16 B per cell + 16 B per curve on the device.
+ *   All four NULL frees the slot.  Synchronises.
+ * btf_crit_eval: families 0..4 as the ESS links (link 3: param = the VARIANCE here, not its inverse; link 4: the rate):
+ *   0 Poisson log, 1 Poisson identity (-inf where w.v <= 0), 2 logit (Binomial / Bernoulli), 3 Gaussian, 4 NB logit.
+ *   States: Ws (S,N,K) and Vs (S,M,T,K) uploaded from the host; or Ws = Vs = NULL: the first nsamples slots of
+ *   btf_collect_begin (no upload); or flags & BTF_CRIT_CURRENT: the context's current W, V (nsamples = 1).
+ *   flags & BTF_CRIT_NOISE_PER_SAMPLE (family 3): the variance of sample s is noise[s] (host), or with collected states
+ *   and noise = NULL the collected nu2; otherwise every sample has variance `param`.
+ *   curve_out [5][N][M]: per curve, over the samples in ascending order, the max-shifted sum of exp(ll_s), the max, the
+ *   mean, Welford's M2, and ll at the plug-in (mean_s w.v per cell, mean variance); total_out (S,): sum_ij ll_s;
+ *   pointwise_out (S,N,M) or NULL.  No floating-point atomics: two calls return identical bits.  Synchronises.       */
+enum { BTF_CRIT_NOISE_PER_SAMPLE = 1, BTF_CRIT_CURRENT = 2 };
+int btf_crit_set_data(btf_ctx* ctx, int slot, const double* S1, const double* cnt, const double* curve_c0, const double* curve_c1);
+int btf_crit_eval(btf_ctx* ctx, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                  const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out);
 
 /* ---- measurement ----------------------------------------------------------
  * With profiling on, every kernel launch is bracketed by hipEvents on the ctx
