@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")   # override: A/B builds
-SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip")]
+SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -91,6 +91,12 @@ SIGNATURES = {
     "btf_collect_summary": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),
     "btf_crit_set_data": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
     "btf_crit_eval": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "btf_nmf_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp,
+                                 C.POINTER(C.c_uint8), C.c_double]),
+    "btf_nmf_run": (C.c_int, [C.c_void_p, _c_dp, _c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _c_ip, _c_dp,
+                              _c_dp]),
+    "btf_nmf_destroy": (None, [C.c_void_p]),
+    "btf_nmf_pav": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp]),
     "btf_sync": (C.c_int, [_ctx]),
     "btf_ess_begin": (C.c_int, [_ctx, C.c_int, _c_dp, C.c_uint64, C.c_double, C.c_int]),
     "btf_ess_eval": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, C.c_int, _c_dp]),
@@ -179,6 +185,7 @@ def build(force=False, verbose=False, jobs=None):
             "-mllvm", "-amdgpu-kernarg-preload-count=16",
             "-I", os.path.join(ROOT, "include")] + os.environ.get("BTF_BUILD_DEFS", "").split()   # A/B builds: -DBTF_... tuning macros
     units = [(SOURCES[0], os.path.join(OBJ_DIR, tag + "_abi.o"), []), (SOURCES[1], os.path.join(OBJ_DIR, tag + "_crit.o"), [])]
+    units += [(SOURCES[2], os.path.join(OBJ_DIR, tag + "_nmf.o"), [])]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

@@ -202,6 +202,15 @@ int fail(btf_ctx* c, int code, const std::string& msg) {
   return code;
 }
 
+}  // namespace
+
+namespace btf {
+// the error text of the context-free entry points of other compilation units (btf_nmf.hip)
+int set_global_error(int code, const std::string& msg) { return fail(nullptr, code, msg); }
+}  // namespace btf
+
+namespace {
+
 #define HIPCHK(ctx, call)                                                                  \
   do {                                                                                     \
     hipError_t e__ = (call);                                                               \

@@ -1,0 +1,162 @@
+"""Non-negative tensor factorisation and the factor PAV projection on the GPU: the chain initialisers of the reference's
+examples (functionalmf.utils.tensor_nmf, utils.py:276-419, and factor_pav, utils.py:218-252).
+
+The host draws the starting point (numpy's legacy stream, in the reference's order) and builds compact statistics of the
+data once: per cell the sum of the observed replicates and their count, plus the within-cell sum of squares.  Every ALS
+step - the NNLS solves of all rows, of all (column, depth) cells, the PAV projection and the stopping rule - runs on the
+device (csrc/btf_nmf.h); the host reads the factors once, at the end.  There is no CPU fallback.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native
+
+MAX_NEMBEDS = 10
+
+
+def _check(rc, lib):
+    if rc != _native.BTF_OK:
+        raise _native.BTFError(rc, lib.btf_last_error(None).decode())
+
+
+def _as_Y4(Y):
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim == 3:
+        Y = Y[..., None]
+    if Y.ndim != 4 or min(Y.shape) < 1:
+        raise ValueError("Y must be (N, M, T) or (N, M, T, R) with every dimension at least 1, got %s" % (Y.shape,))
+    if Y.shape[3] > 255:
+        raise ValueError("at most 255 replicates per cell")
+    return Y
+
+
+def nmf_statistics(Y):
+    """(S, counts, ssw) of Y (N,M,T[,R]): S (N, M*T) float64 = sum of the observed replicates of each cell, counts
+    (N, M*T) uint8 = their number, or None when nothing is missing, and ssw = sum over observed entries of
+    (y - cell mean)^2."""
+    Y = _as_Y4(Y)
+    N, M, T, R = Y.shape
+    obs = ~np.isnan(Y)
+    Y0 = np.where(obs, Y, 0.0)
+    S = Y0.sum(axis=3)
+    cnt = obs.sum(axis=3)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(cnt > 0, S / np.maximum(cnt, 1), 0.0)
+    ssw = float(np.sum(np.where(obs, Y0 - mean[..., None], 0.0) ** 2)) if R > 1 else 0.0
+    counts = None if bool(obs.all()) else np.ascontiguousarray(cnt.reshape(N, M * T), dtype=np.uint8)
+    return np.ascontiguousarray(S.reshape(N, M * T)), counts, ssw
+
+
+class NMFData:
+    """The statistics of one data tensor uploaded to a device (btf_nmf_create); `run` can be called repeatedly."""
+
+    def __init__(self, Y, nembeds, device=0):
+        Y = _as_Y4(Y)
+        self.shape = Y.shape
+        self.nembeds = int(nembeds)
+        S, counts, ssw = nmf_statistics(Y)
+        self.complete = counts is None
+        self.lib = _native.load()
+        self.h = C.c_void_p()
+        N, M, T, R = Y.shape
+        cp = counts.ctypes.data_as(C.POINTER(C.c_uint8)) if counts is not None else None
+        _check(self.lib.btf_nmf_create(C.byref(self.h), int(device), N, M, T, R, self.nembeds, _native.dptr(S), cp, ssw),
+               self.lib)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.btf_nmf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, W, V, max_steps=30, monotone=False, tol=1e-4, verbose=False, fit_W=True, fit_V=True, timing=False):
+        """ALS from (W, V); returns (W, V, info) with new arrays.  info: steps, rmse (one per step run) and, with
+        timing=True, device_ms (device time of the queued steps)."""
+        W = np.array(W, dtype=np.float64, order="C", copy=True)
+        V = np.array(V, dtype=np.float64, order="C", copy=True)
+        steps = C.c_int32(0)
+        hist = np.zeros(max(int(max_steps), 1))
+        ms = np.zeros(1)
+        _check(self.lib.btf_nmf_run(self.h, _native.dptr(W), _native.dptr(V), int(bool(fit_W)), int(bool(fit_V)),
+                                    int(bool(monotone)), int(max_steps), float(tol), int(bool(verbose)), C.byref(steps),
+                                    _native.dptr(hist), _native.dptr(ms) if timing else None), self.lib)
+        info = {"steps": int(steps.value), "rmse": hist[:steps.value].copy()}
+        if timing:
+            info["device_ms"] = float(ms[0])
+        return W, V, info
+
+
+def _check_nembeds(nembeds):
+    if isinstance(nembeds, bool) or int(nembeds) != nembeds or not 1 <= int(nembeds) <= MAX_NEMBEDS:
+        raise ValueError("nembeds must be an integer in 1..%d, got %r" % (MAX_NEMBEDS, nembeds))
+    return int(nembeds)
+
+
+def tensor_nmf(Y, nembeds, max_steps=30, monotone=False, tol=1e-4, verbose=False, max_entry=None, W=None, V=None,
+               fit_W=True, fit_V=True, row_features=None, device=0, return_info=False):
+    """Non-negative factorisation Y[i,j,t,r] ~ W[i] . V[j,t] by alternating NNLS, optionally with each column's curves
+    W_i . V[j] non-increasing in t (monotone=True, factor_pav after every V step).  Drop-in for
+    functionalmf.utils.tensor_nmf (utils.py:276-419): the same starting point under np.random.seed, the same steps and
+    stopping rule.  Returns (W, V) float64 of shapes (N, K) and (M, T, K), or (W, V, info) with return_info=True: info
+    holds `steps` (ALS steps run) and `rmse` (per step: sqrt of the residual sum of squares).  Given W / V are not
+    modified.  `max_entry` and `row_features` (SLSQP projections in the reference) raise NotImplementedError."""
+    if max_entry is not None:
+        raise NotImplementedError("tensor_nmf: max_entry (the reference's SLSQP projection) is not supported on the GPU")
+    if row_features is not None:
+        raise NotImplementedError("tensor_nmf: row_features (side information) is not supported on the GPU")
+    K = _check_nembeds(nembeds)
+    Yarr = np.asarray(Y)
+    if Yarr.ndim not in (3, 4) or min(Yarr.shape) < 1:
+        raise ValueError("Y must be (N, M, T) or (N, M, T, R), got shape %s" % (Yarr.shape,))
+    N, M, T = Yarr.shape[:3]
+    if int(max_steps) != max_steps or max_steps < 0:
+        raise ValueError("max_steps must be a non-negative integer")
+    if W is not None and np.shape(W) != (N, K):
+        raise ValueError("W must be (%d, %d), got %s" % (N, K, np.shape(W)))
+    if V is not None and np.shape(V) != (M, T, K):
+        raise ValueError("V must be (%d, %d, %d), got %s" % (M, T, K, np.shape(V)))
+    # the reference's starting point, from the legacy global stream in its order (utils.py:283-292)
+    if W is None:
+        W = np.random.gamma(1, 1, size=(N, K))
+        if N > 1:
+            W[np.triu_indices(K, k=1)] = 0
+    if V is None:
+        V = np.random.gamma(1, 1, size=(M, T, K))
+    data = NMFData(Yarr, K, device=device)
+    try:
+        W, V, info = data.run(W, V, max_steps=int(max_steps), monotone=monotone, tol=tol, verbose=verbose, fit_W=fit_W,
+                              fit_V=fit_V)
+    finally:
+        data.close()
+    if return_info:
+        return W, V, info
+    return W, V
+
+
+def factor_pav(W, V, in_place=False, device=0):
+    """Pool-adjacent-violators projection of V so that W @ V[t] does not increase with t, for every row of W
+    (functionalmf.utils.factor_pav, utils.py:218-252).  V is one column's (T, K) block or a batch (M, T, K); each
+    column is projected on its own.  Returns V projected (the given array itself with in_place=True)."""
+    W = np.asarray(W)
+    Varr = np.asarray(V)
+    if W.ndim != 2 or Varr.ndim not in (2, 3) or W.shape[1] != Varr.shape[-1] or min(W.shape) < 1 or min(Varr.shape) < 1:
+        raise ValueError("W must be (N, K) and V (T, K) or (M, T, K) with the same K")
+    K = _check_nembeds(W.shape[1])
+    Wc = _native.as_f64(W)
+    out = np.array(Varr, dtype=np.float64, order="C", copy=True)
+    V3 = out.reshape((1,) + out.shape) if out.ndim == 2 else out
+    M, T = V3.shape[:2]
+    lib = _native.load()
+    _check(lib.btf_nmf_pav(int(device), W.shape[0], M, T, K, _native.dptr(Wc), _native.dptr(V3)), lib)
+    if in_place:
+        if not isinstance(V, np.ndarray):
+            raise ValueError("in_place=True needs V to be a numpy array")
+        V[...] = out
+        return V
+    return out

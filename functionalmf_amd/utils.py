@@ -100,3 +100,7 @@ def posterior_summary(Ws, Vs, q=(5, 95), transform=None, device=0):
     if rc != _native.BTF_OK:
         raise _native.BTFError(rc, lib.btf_last_error(None).decode())
     return mean, quant
+
+
+# chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
+from .nmf import factor_pav, tensor_nmf  # noqa: E402,F401

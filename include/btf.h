@@ -598,6 +598,30 @@ int btf_crit_set_data(btf_ctx* ctx, int slot, const double* S1, const double* cn
 int btf_crit_eval(btf_ctx* ctx, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
                   const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out);
 
+/* ---- non-negative tensor factorisation (replaces functionalmf.utils.tensor_nmf, utils.py:276-419, without its
+ * max_entry / row_features projections) and the factor PAV projection (factor_pav, utils.py:218-252) ------------------
+ * Context-free: a btf_nmf handle holds its own statistics, factors and a small device state on a stream of its own; no
+ * btf_ctx is touched (csrc/btf_nmf.h).
+ * btf_nmf_create: uploads the statistics of Y (N,M,T,R): S [N][M*T] = sum of the observed replicates per cell, counts
+ *   [N][M*T] = their number as bytes, or NULL when every cell has all R; ssw = the within-cell sum of squares about the
+ *   cell means.  K = nembeds in 1..10.  Synchronises.
+ * btf_nmf_run: up to max_steps ALS steps from W (N,K) / V (M,T,K), both overwritten with the result.  Per step: if fit_W,
+ *   each row i's first d = min(K, i+1) entries = max(NNLS, 1e-3) over its observed entries (utils.py:299-329); if fit_V,
+ *   each (j,t) = max(NNLS, 1e-3) (utils.py:332-355) and, if monotone, factor_pav on every column (utils.py:357-359); then
+ *   rmse = sqrt(residual sum of squares) and the step stops the run when (prev - rmse) / rmse <= tol (utils.py:381-390).
+ *   All steps are queued without a host synchronisation; the decision is taken on the device.  rmse_out[max_steps]: the
+ *   rmse of each step run; steps_out: the number run; device_ms (or NULL): device time of the queued steps.  verbose
+ *   synchronises per step and prints "Step n" / "delta: x".  A Lawson-Hanson NNLS that reaches its cap of 3 x unknowns
+ *   (scipy's default) returns BTF_EINVAL.  No floating-point atomics: two identical runs return identical bits.
+ * btf_nmf_pav: factor_pav of every column of V (M,T,K) against W (N,K), in place; T (8 K + 4) <= 65536.  Synchronises. */
+typedef struct btf_nmf btf_nmf;
+int btf_nmf_create(btf_nmf** out, int device, int nrows, int ncols, int ndepth, int nreps, int nembeds, const double* S,
+                   const unsigned char* counts, double ssw);
+int btf_nmf_run(btf_nmf* h, double* W, double* V, int fit_W, int fit_V, int monotone, int max_steps, double tol, int verbose,
+                int* steps_out, double* rmse_out, double* device_ms);
+void btf_nmf_destroy(btf_nmf* h);
+int btf_nmf_pav(int device, int nrows, int ncols, int ndepth, int nembeds, const double* W, double* V);
+
 /* ---- measurement ----------------------------------------------------------
  * With profiling on, every kernel launch is bracketed by hipEvents on the ctx
  * stream; btf_kernel_times drains them: total milliseconds and launch count per
