@@ -15,7 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")   # override: A/B builds
-SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip")]
+SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip"),
+           os.path.join(CSRC, "btf_gass_ep.hip")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -122,6 +123,7 @@ SIGNATURES = {
     "btf_gass_commit": (C.c_int, [_ctx, C.c_int, _c_dp, _c_ip]),
     "btf_gass_select": (C.c_int, [_ctx, C.c_int, C.c_uint64, _c_ip]),
     "btf_gass_run": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int]),
+    "btf_gass_set_ep": (C.c_int, [_ctx, _c_dp, _c_dp]),
     "btf_mvn_dense": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, C.c_uint64, C.c_double, C.c_int,
                                 _c_dp, _c_ip]),
     "btf_get_likelihood_form": (C.c_int, [_ctx, _c_ip]),
@@ -185,7 +187,7 @@ def build(force=False, verbose=False, jobs=None):
             "-mllvm", "-amdgpu-kernarg-preload-count=16",
             "-I", os.path.join(ROOT, "include")] + os.environ.get("BTF_BUILD_DEFS", "").split()   # A/B builds: -DBTF_... tuning macros
     units = [(SOURCES[0], os.path.join(OBJ_DIR, tag + "_abi.o"), []), (SOURCES[1], os.path.join(OBJ_DIR, tag + "_crit.o"), [])]
-    units += [(SOURCES[2], os.path.join(OBJ_DIR, tag + "_nmf.o"), [])]
+    units += [(SOURCES[2], os.path.join(OBJ_DIR, tag + "_nmf.o"), []), (SOURCES[3], os.path.join(OBJ_DIR, tag + "_gass_ep.o"), [])]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

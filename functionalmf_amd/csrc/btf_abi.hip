@@ -8,6 +8,7 @@
 #include "btf_banded_chunk.h"
 #include "btf_spectral.h"
 #include "btf_gass.h"
+#include "btf_gass_ep.h"
 #include "btf_fused.h"
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
@@ -84,6 +85,11 @@ struct btf_ctx {
   double* gs_thetas = nullptr; int* gs_ntheta = nullptr; double* gs_ll = nullptr; double* gs_llp = nullptr; size_t gs_llp_elems = 0; double* gs_hh = nullptr; double* gs_cur = nullptr;
   int* gs_nacc = nullptr; double* gs_u = nullptr;
   int gs_chains = 0, gs_what = -1, gs_link = 0;
+  // EP-centred GASS (btf_gass_set_ep): per-cell (Mu, p) in the row and the column layout, per-chain constants, the centre
+  // and the current state's correction of the last begin, the twisted envelope of the column systems
+  double2* ep_rows = nullptr; double2* ep_cols = nullptr; double* ep_crow = nullptr; double* ep_ccol = nullptr;
+  double* ep_mu = nullptr; double* ep_corr = nullptr; double* ep_pband = nullptr; double* ep_envg = nullptr;
+  int* ep_f = nullptr; int* ep_off = nullptr; int ep_env = 0, ep_bwe = 0; bool ep_on = false, gs_ep = false;
   double lik_par[ESS_FAM_COUNT] = {0, 0, 0, 1.0, 1.0};     // parameter per likelihood family (btf_set_likelihood_param)
   long long* dbg = nullptr;
   double* vc_scratch = nullptr; size_t vc_scratch_elems = 0;     // factor records of the chunked chain sampler
@@ -1006,7 +1012,8 @@ void btf_destroy(btf_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   void* ptrs[] = {c->A_wT, c->C_wT, c->A_v, c->C_v, c->B_wT, c->B_v, c->W, c->V, c->Tau2, c->part,
                   c->gpart, c->zbuf, c->bsum, c->gband, c->status, c->tries, c->st_ptr, c->st_row, c->st_coef,
-                  c->srcmap_w, c->srcmap_v, c->pband, c->pimg, c->dbg, c->gpart_w, c->gpart_v, c->gsum_v, c->eig, c->cv_cptr, c->cv_crow, c->cv_cdef, c->cv_rptr, c->cv_rcol, c->cv_rdef, c->eig_cols, c->cv_dcols, c->A8_wT, c->A8_v, c->gs_cons, c->gs_cc, c->gs_rc, c->gs_av, c->gs_mask, c->gs_info, c->gs_thetas, c->gs_ntheta, c->gs_ll, c->gs_llp, c->gs_hh, c->gs_cur, c->gs_nacc, c->gs_u, c->st_drow, c->st_dcoef, c->essX0, c->essNu, c->ess_st, c->ess_theta, c->ess_done, c->ess_part, c->Ta, c->Tb, c->Tc, c->lsum, c->dr_ptr, c->dr_col, c->dr_val, c->sse_cols, c->vs_rec, c->vc_scratch, c->gs_cptr, c->gs_cidx, c->gs_cval};
+                  c->srcmap_w, c->srcmap_v, c->pband, c->pimg, c->dbg, c->gpart_w, c->gpart_v, c->gsum_v, c->eig, c->cv_cptr, c->cv_crow, c->cv_cdef, c->cv_rptr, c->cv_rcol, c->cv_rdef, c->eig_cols, c->cv_dcols, c->A8_wT, c->A8_v, c->gs_cons, c->gs_cc, c->gs_rc, c->gs_av, c->gs_mask, c->gs_info, c->gs_thetas, c->gs_ntheta, c->gs_ll, c->gs_llp, c->gs_hh, c->gs_cur, c->gs_nacc, c->gs_u, c->st_drow, c->st_dcoef, c->essX0, c->essNu, c->ess_st, c->ess_theta, c->ess_done, c->ess_part, c->Ta, c->Tb, c->Tc, c->lsum, c->dr_ptr, c->dr_col, c->dr_val, c->sse_cols, c->vs_rec, c->vc_scratch, c->gs_cptr, c->gs_cidx, c->gs_cval,
+                  c->ep_rows, c->ep_cols, c->ep_crow, c->ep_ccol, c->ep_mu, c->ep_corr, c->ep_pband, c->ep_envg, c->ep_f, c->ep_off};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->pin_lsum) (void)hipHostFree(c->pin_lsum);
@@ -2349,7 +2356,20 @@ int gass_eval_launch(btf_ctx* c, int what, int link) {
   const dim3 grid(nch, nsplit);
   a.lf = LikFam{link, c->lik_par[link]};
   const int tl = ess_link_of(link);
-  if (what == 0) {
+  if (c->gs_ep) {        // EP-centred: the centre, the per-cell (Mu, p) and the chains' constants
+    a.Mu = c->ep_mu; a.ep = what == 0 ? c->ep_rows : c->ep_cols; a.epc = what == 0 ? c->ep_crow : c->ep_ccol;
+    if (what == 0) { a.F = c->V; a.A = c->A_v; a.C8 = c->C8_v; a.Cd = c->C_v; a.ld = c->ldv; }
+    else { a.F = c->W; a.A = c->A_wT; a.C8 = c->C8_wT; a.Cd = c->C_wT; a.ld = c->ldw; }
+    if (what == 0) {
+      if (tl == ESS_LINK_LOG) p.launch(gass_eval_kernel<ESS_LINK_LOG, true, true>, grid, dim3(GASS_THREADS), 0, a);
+      else if (tl == ESS_LINK_IDENTITY) p.launch(gass_eval_kernel<ESS_LINK_IDENTITY, true, true>, grid, dim3(GASS_THREADS), 0, a);
+      else p.launch(gass_eval_kernel<ESS_LINK_GENERIC, true, true>, grid, dim3(GASS_THREADS), 0, a);
+    } else {
+      if (tl == ESS_LINK_LOG) p.launch(gass_eval_kernel<ESS_LINK_LOG, false, true>, grid, dim3(GASS_THREADS), 0, a);
+      else if (tl == ESS_LINK_IDENTITY) p.launch(gass_eval_kernel<ESS_LINK_IDENTITY, false, true>, grid, dim3(GASS_THREADS), 0, a);
+      else p.launch(gass_eval_kernel<ESS_LINK_GENERIC, false, true>, grid, dim3(GASS_THREADS), 0, a);
+    }
+  } else if (what == 0) {
     a.F = c->V; a.A = c->A_v; a.C8 = c->C8_v; a.Cd = c->C_v; a.ld = c->ldv;
     if (tl == ESS_LINK_LOG) p.launch(gass_eval_kernel<ESS_LINK_LOG, true>, grid, dim3(GASS_THREADS), 0, a);
     else if (tl == ESS_LINK_IDENTITY) p.launch(gass_eval_kernel<ESS_LINK_IDENTITY, true>, grid, dim3(GASS_THREADS), 0, a);
@@ -2363,6 +2383,64 @@ int gass_eval_launch(btf_ctx* c, int what, int link) {
   if (nsplit > 1)
     hipLaunchKernelGGL(gass_ll_sum_kernel, dim3((nch * GASS_MAXC + 255) / 256), dim3(256), 0, c->stream, (const double*)c->gs_llp, nsplit,
                        (const int*)c->gs_ntheta, nch, c->gs_ll);
+  HIPCHK(c, hipGetLastError());
+  return BTF_OK;
+}
+// EP-centred begin: X0 <- state - mu, Nu <- L'^-1 z, ep_mu <- mu, ep_corr <- the current state's correction (btf_gass_ep.h)
+int gass_ep_begin(btf_ctx* c, int what, const double* z, uint64_t seed) {
+  int rc;
+  if ((rc = ess_alloc(c))) return rc;
+  const int K = c->K, T = c->T, n = T * K;
+  if (!c->ep_mu) {
+    if ((rc = dev_alloc(c, &c->ep_mu, std::max((size_t)c->N * K, (size_t)c->M * n)))) return rc;
+    if ((rc = dev_alloc(c, &c->ep_corr, (size_t)std::max(c->N, c->M)))) return rc;
+  }
+  GassEpArgs a{};
+  a.W = c->W; a.V = c->V; a.N = c->N; a.M = c->M; a.T = T; a.K = K; a.TF = c->TF;
+  a.X0 = c->essX0; a.Nu = c->essNu; a.Mu = c->ep_mu; a.corr = c->ep_corr; a.status = c->status;
+  a.seed = seed;
+  const size_t nz = what == 0 ? (size_t)w_z_offset(c->N, K) : (size_t)c->M * n;
+  if (z) {
+    if ((rc = ensure_z(c, nz))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->zbuf, z, nz * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    a.z = c->zbuf;
+  }
+  if (what == 0) {
+    a.ep = c->ep_rows; a.cconst = c->ep_crow;
+    a.sigma2 = c->sigma2; a.sigma2_dev = c->dev_scalars ? c->hyp + HYP_SIGMA2 : nullptr;
+    a.stream = 2 * c->sweep_w + 0x20000ULL;
+    Prof p(c, BTF_K_ESS);
+    p.launch(gass_ep_rows_fn(K), dim3(c->N), dim3(GEP_THREADS), 0, a);
+    c->sweep_w++;
+  } else {
+    const int TD1 = T * (c->TF + 2);
+    if (!c->ep_pband) { if ((rc = dev_alloc(c, &c->ep_pband, (size_t)c->M * TD1))) return rc; }
+    {
+      Prof p(c, BTF_K_ESS);
+      p.launch(prior_band_kernel, dim3((c->M * TD1 + 255) / 256), dim3(256), 0, (const double*)c->Tau2, c->lam2, c->nD,
+               (const int*)c->st_ptr, (const int*)c->st_row, (const double*)c->st_coef, TD1, 0, c->M, c->ep_pband,
+               (const double*)(c->dev_scalars ? c->hyp : nullptr), 0, (double*)nullptr, 0, 0, 0);
+    }
+    a.ep = c->ep_cols; a.cconst = c->ep_ccol; a.pband = c->ep_pband;
+    a.env_f = c->ep_f; a.env_off = c->ep_off; a.env_size = c->ep_env; a.bwe = c->ep_bwe;
+    a.stream = 2 * c->sweep_v + 0x10001ULL;
+    constexpr size_t LDS_MAX = 150 * 1024;
+    size_t lds = gass_ep_cols_lds(T, K, c->ep_env, true);
+    if (lds > LDS_MAX) {           // the envelope in HBM, the vectors on chip
+      lds = gass_ep_cols_lds(T, K, c->ep_env, false);
+      if (lds > LDS_MAX) return fail(c, BTF_EINVAL, "ndepth*nembeds too large for the EP-centred column systems");
+      if (!c->ep_envg) { if ((rc = dev_alloc(c, &c->ep_envg, (size_t)c->M * c->ep_env))) return rc; }
+      a.env_g = c->ep_envg;
+    }
+    static std::atomic<unsigned long long> attr_set[GEP_MAXK + 1] = {};
+    if (!dev_flag_is_set(attr_set[K], c->dev)) {
+      HIPCHK(c, hipFuncSetAttribute((const void*)gass_ep_cols_fn(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
+      dev_flag_set(attr_set[K], c->dev);
+    }
+    Prof p(c, BTF_K_ESS);
+    p.launch(gass_ep_cols_fn(K), dim3(c->M), dim3(GEP_THREADS), lds, a);
+    c->sweep_v++;
+  }
   HIPCHK(c, hipGetLastError());
   return BTF_OK;
 }
@@ -2411,6 +2489,68 @@ int btf_gass_set_constraints(btf_ctx* c, const double* cons, int J, const double
   return BTF_OK;
 }
 
+int btf_gass_set_ep(btf_ctx* c, const double* mu, const double* sigma) {
+  if (!c) return BTF_EINVAL;
+  if (!mu && !sigma) { c->ep_on = false; return BTF_OK; }
+  if (!mu || !sigma) return fail(c, BTF_EINVAL, "btf_gass_set_ep: both arrays, or neither");
+  if (c->K < 1 || c->K > GEP_MAXK) return fail(c, BTF_EINVAL, "btf_gass_set_ep: nembeds must be in 1..10");
+  const int N = c->N, M = c->M, T = c->T, K = c->K, S = c->TF + 1;
+  if (T < S) return fail(c, BTF_EINVAL, "btf_gass_set_ep: ndepth must be at least tf_order + 1");
+  const size_t ncell = (size_t)N * M * T;
+  for (size_t e = 0; e < ncell; ++e)
+    if (!std::isfinite(mu[e]) || !std::isfinite(sigma[e]) || !(sigma[e] > 0.0))
+      return fail(c, BTF_EINVAL, "btf_gass_set_ep: Mu_ep must be finite and Sigma_ep finite and positive");
+  HIPCHK(c, hipSetDevice(c->dev));
+  const double hl2pi = 0.5 * std::log(2.0 * 3.14159265358979323846);
+  std::vector<double2> rows(ncell), cols(ncell);
+  std::vector<double> crow((size_t)N, 0.0), ccol((size_t)M, 0.0);
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < M; ++j)
+      for (int t = 0; t < T; ++t) {
+        const size_t e = ((size_t)i * M + j) * T + t;
+        const double p = 1.0 / (sigma[e] * sigma[e]), lc = std::log(sigma[e]) + hl2pi;
+        rows[e] = make_double2(mu[e], p);
+        cols[((size_t)j * T + t) * N + i] = make_double2(mu[e], p);
+        crow[i] += lc;
+      }
+  for (int j = 0; j < M; ++j)
+    for (int i = 0; i < N; ++i)
+      for (int t = 0; t < T; ++t) { const size_t e = ((size_t)i * M + j) * T + t; ccol[j] += std::log(sigma[e]) + hl2pi; }
+  // the envelope of P Q P' in the twisted order (btf_gass_ep.h): first column of every row, offsets
+  const int n = T * K, ts = (T - S) / 2, nl = ts * K, nsep = n - S * K;
+  auto ord = [&](int r) { return r < nl ? r : (r < nsep ? n - 1 - (r - nl) : nl + (r - nsep)); };
+  auto pos = [&](int g) { return g < nl ? g : (g >= nl + S * K ? nl + (n - 1 - g) : nsep + (g - nl)); };
+  std::vector<int> f((size_t)n), off((size_t)n);
+  int tot = 0, bwe = 0;
+  for (int r = 0; r < n; ++r) {
+    const int g = ord(r), t = g / K, k = g - t * K;
+    int fr = r;
+    for (int l = 0; l < K; ++l) fr = std::min(fr, pos(t * K + l));
+    for (int dd = 1; dd <= c->TF + 1; ++dd) {
+      if (t + dd < T) fr = std::min(fr, pos((t + dd) * K + k));
+      if (t - dd >= 0) fr = std::min(fr, pos((t - dd) * K + k));
+    }
+    f[r] = fr; off[r] = tot; tot += r - fr + 1;
+    if (r < nsep) bwe = std::max(bwe, r - fr);
+  }
+  int rc;
+  if ((rc = dev_alloc(c, &c->ep_rows, ncell))) return rc;
+  if ((rc = dev_alloc(c, &c->ep_cols, ncell))) return rc;
+  if ((rc = dev_alloc(c, &c->ep_crow, (size_t)N))) return rc;
+  if ((rc = dev_alloc(c, &c->ep_ccol, (size_t)M))) return rc;
+  if ((rc = dev_alloc(c, &c->ep_f, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, &c->ep_off, (size_t)n))) return rc;
+  HIPCHK(c, hipMemcpy(c->ep_rows, rows.data(), ncell * sizeof(double2), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ep_cols, cols.data(), ncell * sizeof(double2), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ep_crow, crow.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ep_ccol, ccol.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ep_f, f.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ep_off, off.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  if (c->ep_envg && c->ep_env != tot) { (void)hipFree(c->ep_envg); c->ep_envg = nullptr; }
+  c->ep_env = tot; c->ep_bwe = bwe; c->ep_on = true;
+  return BTF_OK;
+}
+
 int btf_gass_begin(btf_ctx* c, int what, int link, const double* z, const double* u, uint64_t seed, double eps0, int attempts,
                    int pick_ngrid) {
   if (!c) return BTF_EINVAL;
@@ -2419,7 +2559,12 @@ int btf_gass_begin(btf_ctx* c, int what, int link, const double* z, const double
   if (pick_ngrid < 0 || pick_ngrid > GASS_MAXC) return fail(c, BTF_EINVAL, "at most 128 candidates per chain");
   HIPCHK(c, hipSetDevice(c->dev));
   if ((rc = gass_alloc(c))) return rc;
-  if ((rc = ess_begin(c, what, z, seed, eps0, attempts < 0 ? 0 : attempts))) return rc;     // X0 <- state, Nu <- prior draw
+  const bool ep = c->ep_on;
+  if (!ep) {
+    if ((rc = ess_begin(c, what, z, seed, eps0, attempts < 0 ? 0 : attempts))) return rc;     // X0 <- state, Nu <- prior draw
+  } else {
+    if ((rc = gass_ep_begin(c, what, z, seed))) return rc;     // X0 <- state - mu, Nu <- L'^-1 z, the centre, the correction
+  }
   const int nch = what == 0 ? c->N : c->M;
   // slice heights from the likelihood of the current state, chain by chain
   const EssDims d = ess_dims(c, what, 1);
@@ -2437,6 +2582,10 @@ int btf_gass_begin(btf_ctx* c, int what, int link, const double* z, const double
     Prof p(c, BTF_K_ESS);
     p.launch(gass_slice_kernel, dim3((nch + 255) / 256), dim3(256), 0, (const double*)c->ess_part, d.nsum, nch, du, dseed, c->gs_hh, c->gs_cur);
   }
+  if (ep) {
+    Prof p(c, BTF_K_ESS);
+    p.launch(gass_ep_fix_fn(), dim3((nch + 255) / 256), dim3(256), 0, (const double*)c->ep_corr, nch, c->gs_cur, c->gs_hh);
+  }
   GassArgs a{};
   a.X0 = c->essX0; a.Nu = c->essNu; a.Cons = c->gs_cons; a.Cc = c->gs_cc; a.J = c->gs_J;
   if (c->gs_cnnz > 0) { a.cs_ptr = c->gs_cptr; a.cs_idx = c->gs_cidx; a.cs_val = c->gs_cval; a.cs_nnz = c->gs_cnnz; }
@@ -2444,26 +2593,30 @@ int btf_gass_begin(btf_ctx* c, int what, int link, const double* z, const double
   a.N = c->N; a.M = c->M; a.T = c->T; a.K = c->K;
   a.vmask = c->gs_mask; a.info = c->gs_info; a.pick = pick_ngrid > 0 ? 1 : 0; a.ngrid = pick_ngrid;
   a.thetas = c->gs_thetas; a.ntheta = c->gs_ntheta; a.seed = dseed;
+  a.Mu = ep ? c->ep_mu : nullptr;
   {
     Prof p(c, BTF_K_ESS);
     if (what == 0) {
       p.launch(gass_av_kernel, dim3(c->M), dim3(GASS_THREADS), 0, (const double*)c->V, (const double*)c->gs_cons, c->T, c->K, c->gs_J, c->gs_av);
-      p.launch(gass_analyse_rows_kernel, dim3(c->N), dim3(GASS_THREADS), 0, a);
+      if (ep) p.launch(gass_analyse_rows_kernel<true>, dim3(c->N), dim3(GASS_THREADS), 0, a);
+      else p.launch(gass_analyse_rows_kernel<false>, dim3(c->N), dim3(GASS_THREADS), 0, a);
     } else {
-      const size_t dyn = ((size_t)2 * GASS_RT * c->T + (size_t)c->gs_J * c->T) * sizeof(double);
+      const size_t dyn = ((size_t)(ep ? 3 : 2) * GASS_RT * c->T + (size_t)c->gs_J * c->T) * sizeof(double);
       constexpr size_t GASS_DYN_MAX = 112 * 1024;      // (the kernel's static scratch takes the rest of the 160 KB)
       if (dyn > GASS_DYN_MAX || dyn + sizeof(GassScratch) > 158 * 1024)
         return fail(c, BTF_EINVAL, "constraint matrix too large for the column analysis");
       static std::atomic<unsigned long long> attr_set{0};
       if (!dev_flag_is_set(attr_set, c->dev)) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)gass_analyse_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GASS_DYN_MAX));
+        HIPCHK(c, hipFuncSetAttribute((const void*)gass_analyse_cols_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GASS_DYN_MAX));
+        HIPCHK(c, hipFuncSetAttribute((const void*)gass_analyse_cols_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GASS_DYN_MAX));
         dev_flag_set(attr_set, c->dev);
       }
-      p.launch(gass_analyse_cols_kernel, dim3(c->M), dim3(GASS_THREADS), dyn, a);
+      if (ep) p.launch(gass_analyse_cols_kernel<true>, dim3(c->M), dim3(GASS_THREADS), dyn, a);
+      else p.launch(gass_analyse_cols_kernel<false>, dim3(c->M), dim3(GASS_THREADS), dyn, a);
     }
   }
   HIPCHK(c, hipGetLastError());
-  c->gs_chains = nch; c->gs_what = what; c->gs_link = link;
+  c->gs_chains = nch; c->gs_what = what; c->gs_link = link; c->gs_ep = ep;
   return BTF_OK;
 }
 
@@ -2512,8 +2665,12 @@ int btf_gass_commit(btf_ctx* c, int what, const double* theta, const int32_t* ke
   const long long n = (long long)nch * per;
   {
     Prof p(c, BTF_K_ESS);
-    p.launch(ess_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)c->essX0, (const double*)c->essNu,
-             what == 0 ? c->W : c->V, n, per, (const double*)c->ess_theta, (const int*)c->ess_done, 0);
+    if (c->gs_ep)
+      p.launch(gass_ep_commit_fn(), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)c->essX0, (const double*)c->essNu,
+               (const double*)c->ep_mu, what == 0 ? c->W : c->V, n, per, (const double*)c->ess_theta, (const int*)c->ess_done);
+    else
+      p.launch(ess_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)c->essX0, (const double*)c->essNu,
+               what == 0 ? c->W : c->V, n, per, (const double*)c->ess_theta, (const int*)c->ess_done, 0);
   }
   HIPCHK(c, hipGetLastError());
   if (what == 0) c->ngp_w = 0; else c->ngp_v = 0;
@@ -2530,7 +2687,8 @@ int btf_gass_select(btf_ctx* c, int what, uint64_t seed, int32_t* naccept_out) {
     Prof p(c, BTF_K_ESS);
     p.launch(gass_select_kernel, dim3(nch), dim3(GASS_THREADS), 0, (const double*)c->gs_ll, (const int*)c->gs_ntheta, (const double*)c->gs_thetas,
              (const double*)c->gs_hh, (const double*)c->essX0, (const double*)c->essNu, what == 0 ? c->W : c->V, per,
-             (unsigned long long)(seed * 0x9E3779B97F4A7C15ULL + 0xBB67AE8584CAA73BULL), c->gs_nacc, (double*)nullptr);
+             (unsigned long long)(seed * 0x9E3779B97F4A7C15ULL + 0xBB67AE8584CAA73BULL), c->gs_nacc, (double*)nullptr,
+             (const double*)(c->gs_ep ? c->ep_mu : nullptr));
   }
   HIPCHK(c, hipGetLastError());
   if (what == 0) c->ngp_w = 0; else c->ngp_v = 0;

@@ -21,7 +21,7 @@
 //                             subsample (partial Fisher-Yates over the valid list, Philox)
 //   gass_eval_rows/cols       Poisson log-likelihood of every candidate of every chain: lanes = candidates, the cells
 //                             of a chain staged tile by tile in LDS (two dot products per cell, ngrid rates)
-//   gass_select_kernel        candidates above the slice, one uniformly; x = x0 cos + v sin
+//   gass_select_kernel        candidates above the slice, one uniformly; x = x0 cos + v sin (+ mu when EP-centred)
 // The likelihood is a device likelihood (Poisson, log or identity link, from the hoisted statistics) as for the
 // elliptical slice sampler (btf_ess.h).
 #pragma once
@@ -183,26 +183,34 @@ struct GassArgs {
   int N, M, T, K;
   unsigned char* vmask; int* info;           // [nchains][GASS_GRID], [nchains][2]
   int pick; int ngrid; double* thetas; int* ntheta; unsigned long long seed;
+  const double* Mu;                          // EP-centred ellipse (btf_gass_ep.h): the centre of every chain; X0 = x - Mu
 };
 
 // rows: chain i, x = W[i, :], constraints (AV[j,c,:] . x >= Cc[c]) for all (j, c), then the fixed row constraints
-static __global__ __launch_bounds__(GASS_THREADS) void gass_analyse_rows_kernel(GassArgs a) {
+// EP: c - A mu in place of c (gass.py:41), with the same row of A
+template <bool EP>
+__global__ __launch_bounds__(GASS_THREADS) void gass_analyse_rows_kernel(GassArgs a) {
   __shared__ GassScratch S;
   const int i = blockIdx.x, tid = threadIdx.x, K = a.K;
   for (int g = tid; g < GASS_GRID + 8; g += GASS_THREADS) S.diff[g] = 0;
-  double x[EIG_MAXK], v[EIG_MAXK];
+  double x[EIG_MAXK], v[EIG_MAXK], m[EP ? EIG_MAXK : 1];
 #pragma unroll
   for (int k = 0; k < EIG_MAXK; ++k) { x[k] = k < K ? a.X0[(size_t)i * K + k] : 0.0; v[k] = k < K ? a.Nu[(size_t)i * K + k] : 0.0; }
+  if constexpr (EP) {
+#pragma unroll
+    for (int k = 0; k < EIG_MAXK; ++k) m[k] = k < K ? a.Mu[(size_t)i * K + k] : 0.0;
+  }
   __syncthreads();
   double tmin = -INFINITY, tmax = INFINITY;
   int any = 0;
   const int ncon = a.M * a.J;
   for (int q = tid; q < ncon + a.nrc; q += GASS_THREADS) {
     const double* __restrict__ row = q < ncon ? a.AV + (size_t)q * K : a.Rc + (size_t)(q - ncon) * (K + 1);
-    double aa = 0.0, bb = 0.0;
+    double aa = 0.0, bb = 0.0, am = 0.0;
 #pragma unroll
-    for (int k = 0; k < EIG_MAXK; ++k) if (k < K) { aa = fma(row[k], x[k], aa); bb = fma(row[k], v[k], bb); }
-    const double cc = q < ncon ? a.Cc[q % a.J] : row[K];
+    for (int k = 0; k < EIG_MAXK; ++k) if (k < K) { aa = fma(row[k], x[k], aa); bb = fma(row[k], v[k], bb); if constexpr (EP) am = fma(row[k], m[k], am); }
+    double cc = q < ncon ? a.Cc[q % a.J] : row[K];
+    if constexpr (EP) cc -= am;
     gass_constraint(aa, bb, cc, S.diff, tmin, tmax, any);
   }
   __syncthreads();
@@ -213,13 +221,15 @@ static __global__ __launch_bounds__(GASS_THREADS) void gass_analyse_rows_kernel(
 
 // columns: chain j, x = V[j] (T x K), constraints  sum_t Cons[c,t] (w_i . x_t) >= Cc[c]  for all (i, c)  (factor.py:848-855)
 constexpr int GASS_RT = 32;      // rows of W per tile
-static __global__ __launch_bounds__(GASS_THREADS) void gass_analyse_cols_kernel(GassArgs a) {
+template <bool EP>
+__global__ __launch_bounds__(GASS_THREADS) void gass_analyse_cols_kernel(GassArgs a) {
   __shared__ GassScratch S;
-  extern __shared__ double dyn[];                   // E0[RT][T], E1[RT][T], Cons[J][T]
+  extern __shared__ double dyn[];                   // E0[RT][T], E1[RT][T], Cons[J][T] (EP: then Em[RT][T])
   const int j = blockIdx.x, tid = threadIdx.x, K = a.K, T = a.T, J = a.J;
   double* E0 = dyn;
   double* E1 = dyn + GASS_RT * T;
   double* Cn = dyn + 2 * GASS_RT * T;
+  double* Em = dyn + (size_t)(2 * GASS_RT + J) * T;
   for (int g = tid; g < GASS_GRID + 8; g += GASS_THREADS) S.diff[g] = 0;
   // sparse form staged in the dense matrix's area: [nnz values][nnz column indices][J + 1 row pointers]
   const bool sparse = a.cs_ptr != nullptr;
@@ -234,30 +244,41 @@ static __global__ __launch_bounds__(GASS_THREADS) void gass_analyse_cols_kernel(
   }
   const double* __restrict__ x0 = a.X0 + (size_t)j * T * K;
   const double* __restrict__ nu = a.Nu + (size_t)j * T * K;
+  const double* __restrict__ mu = EP ? a.Mu + (size_t)j * T * K : nullptr;
   double tmin = -INFINITY, tmax = INFINITY;
   int any = 0;
   for (int r0 = 0; r0 < a.N; r0 += GASS_RT) {
     __syncthreads();
     for (int e = tid; e < GASS_RT * T; e += GASS_THREADS) {
       const int r = e / T, t = e - r * T;
-      double s0 = 0.0, s1 = 0.0;
+      double s0 = 0.0, s1 = 0.0, sm = 0.0;
       if (r0 + r < a.N) {
         const double* __restrict__ w = a.W + (size_t)(r0 + r) * K;
-        for (int k = 0; k < K; ++k) { s0 = fma(w[k], x0[(size_t)t * K + k], s0); s1 = fma(w[k], nu[(size_t)t * K + k], s1); }
+        for (int k = 0; k < K; ++k) {
+          s0 = fma(w[k], x0[(size_t)t * K + k], s0); s1 = fma(w[k], nu[(size_t)t * K + k], s1);
+          if constexpr (EP) sm = fma(w[k], mu[(size_t)t * K + k], sm);
+        }
       }
       E0[e] = s0; E1[e] = s1;
+      if constexpr (EP) Em[e] = sm;
     }
     __syncthreads();
     const int nr = min(GASS_RT, a.N - r0);
     for (int q = tid; q < nr * J; q += GASS_THREADS) {
       const int r = q / J, c = q - r * J;
-      double aa = 0.0, bb = 0.0;
+      double aa = 0.0, bb = 0.0, am = 0.0;
       if (sparse) {          // the same sums without their zero terms (ascending t: bit-identical for finite predictors)
-        for (int e = cptr[c]; e < cptr[c + 1]; ++e) { const int t = cidx[e]; aa = fma(cval[e], E0[r * T + t], aa); bb = fma(cval[e], E1[r * T + t], bb); }
+        for (int e = cptr[c]; e < cptr[c + 1]; ++e) {
+          const int t = cidx[e]; aa = fma(cval[e], E0[r * T + t], aa); bb = fma(cval[e], E1[r * T + t], bb);
+          if constexpr (EP) am = fma(cval[e], Em[r * T + t], am);
+        }
       } else {
-        for (int t = 0; t < T; ++t) { aa = fma(Cn[c * T + t], E0[r * T + t], aa); bb = fma(Cn[c * T + t], E1[r * T + t], bb); }
+        for (int t = 0; t < T; ++t) {
+          aa = fma(Cn[c * T + t], E0[r * T + t], aa); bb = fma(Cn[c * T + t], E1[r * T + t], bb);
+          if constexpr (EP) am = fma(Cn[c * T + t], Em[r * T + t], am);
+        }
       }
-      gass_constraint(aa, bb, a.Cc[c], S.diff, tmin, tmax, any);
+      gass_constraint(aa, bb, EP ? a.Cc[c] - am : a.Cc[c], S.diff, tmin, tmax, any);
     }
   }
   __syncthreads();
@@ -278,11 +299,19 @@ struct GassEvalArgs {
   const double* thetas; const int* ntheta; double* ll;   // [nchains][GASS_MAXC] (nsplit == 1) or partial sums [nchains][nsplit][GASS_MAXC]
   int nsplit;                                           // workgroups per chain (blockIdx.y): tiles dealt round-robin
   LikFam lf;                                            // likelihood family and parameter (ESS_LINK_GENERIC)
+  // EP (btf_gass_ep.h): eta += the centre's predictor, + p (eta - Mu_ep)^2 / 2 per cell, + the chain's constant.  With
+  // eta - Mu_ep = cos e0 + sin e1 + r (r = e_mu - Mu_ep) the quadratic's sum over the cells is a quadratic form in
+  // (cos, sin, 1) whose six coefficients do not depend on the candidate: they are summed once per cell while the tile
+  // is staged, and each candidate adds its closed form at the end
+  const double* Mu; const double2* ep; const double* epc;
 };
 
-template <int LINK, bool ROWS>
+template <int LINK, bool ROWS, bool EP = false>
 __global__ __launch_bounds__(GASS_THREADS) void gass_eval_kernel(GassEvalArgs a) {
   __shared__ double e0s[GASS_CT], e1s[GASS_CT], s1s[GASS_CT], cns[GASS_CT];
+  __shared__ double ems[EP ? GASS_CT : 1];
+  __shared__ double q6s[EP ? GASS_THREADS / WAVE : 1][6];
+  double q6[EP ? 6 : 1] = {};
   __shared__ double red[GASS_THREADS / WAVE][GASS_MAXC];
   __shared__ double2 ltab[LOGTAB_N];
   if constexpr (LINK == ESS_LINK_IDENTITY) log_table_build(ltab); else if constexpr (LINK == ESS_LINK_LOG) exp_table_build(ltab);      // (the tile loop's first barrier publishes it)
@@ -299,7 +328,8 @@ __global__ __launch_bounds__(GASS_THREADS) void gass_eval_kernel(GassEvalArgs a)
     __syncthreads();
     for (int e = tid; e < GASS_CT; e += GASS_THREADS) {
       const int cell = base + e;
-      double d0 = 0.0, d1 = 0.0, sv = 0.0, cv = 0.0;
+      double d0 = 0.0, d1 = 0.0, sv = 0.0, cv = 0.0, dm = 0.0;
+      double2 mp = make_double2(0.0, 0.0);
       if (cell < ncell) {
         if constexpr (ROWS) {          // chain = row i; cell = (j,t); statistics A_v[i][cell]
           const double* __restrict__ f = a.F + (size_t)cell * K;
@@ -309,6 +339,11 @@ __global__ __launch_bounds__(GASS_THREADS) void gass_eval_kernel(GassEvalArgs a)
           const size_t o = (size_t)ch * a.ld + cell;
           sv = a.A[o];
           cv = a.C8 ? (double)a.C8[o] : (a.Cd ? a.Cd[o] : a.Rc);
+          if constexpr (EP) {
+            const double* __restrict__ mu = a.Mu + (size_t)ch * K;
+            for (int k = 0; k < K; ++k) dm = fma(mu[k], f[k], dm);
+            mp = a.ep[(size_t)ch * ncell + cell];
+          }
         } else {                       // chain = column j; cell = (t, i) with i fastest; statistics A_wT[(j,t)][i]
           const int t = cell / a.N, i = cell - t * a.N;
           const double* __restrict__ f = a.F + (size_t)i * K;
@@ -318,24 +353,58 @@ __global__ __launch_bounds__(GASS_THREADS) void gass_eval_kernel(GassEvalArgs a)
           const size_t o = ((size_t)ch * T + t) * a.ld + i;
           sv = a.A[o];
           cv = a.C8 ? (double)a.C8[o] : (a.Cd ? a.Cd[o] : a.Rc);
+          if constexpr (EP) {
+            const double* __restrict__ mu = a.Mu + ((size_t)ch * T + t) * K;
+            for (int k = 0; k < K; ++k) dm = fma(mu[k], f[k], dm);
+            mp = a.ep[(size_t)ch * ncell + cell];
+          }
         }
       }
       e0s[e] = d0; e1s[e] = d1; s1s[e] = sv; cns[e] = cv;
+      if constexpr (EP) {
+        ems[e] = dm;
+        const double hp = 0.5 * mp.y, r = dm - mp.x;
+        q6[0] = fma(hp * d0, d0, q6[0]); q6[1] = fma(hp * d1, d1, q6[1]); q6[2] = fma(hp * d0, d1, q6[2]);
+        q6[3] = fma(hp * d0, r, q6[3]); q6[4] = fma(hp * d1, r, q6[4]); q6[5] = fma(hp * r, r, q6[5]);
+      }
     }
     __syncthreads();
     const int lim = min(GASS_CT, ncell - base);
     for (int e = wave; e < lim; e += GASS_THREADS / WAVE) {
       const double d0 = e0s[e], d1 = e1s[e], sv = s1s[e], cv = cns[e];
-      acc0 += poisson_term<LINK>(sv, cv, fma(c0, d0, s0 * d1), ltab, a.lf);
-      acc1 += poisson_term<LINK>(sv, cv, fma(c1, d0, s1 * d1), ltab, a.lf);
+      if constexpr (EP) {
+        const double dm = ems[e];
+        acc0 += poisson_term<LINK>(sv, cv, fma(c0, d0, s0 * d1) + dm, ltab, a.lf);
+        acc1 += poisson_term<LINK>(sv, cv, fma(c1, d0, s1 * d1) + dm, ltab, a.lf);
+      } else {
+        acc0 += poisson_term<LINK>(sv, cv, fma(c0, d0, s0 * d1), ltab, a.lf);
+        acc1 += poisson_term<LINK>(sv, cv, fma(c1, d0, s1 * d1), ltab, a.lf);
+      }
     }
   }
   red[wave][lane] = acc0;
   red[wave][lane + 64] = acc1;
+  if constexpr (EP) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      double v = q6[q];
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+      if (lane == 0) q6s[wave][q] = v;
+    }
+  }
   __syncthreads();
   if (tid < GASS_MAXC) {
     double s = 0.0;
     for (int w = 0; w < GASS_THREADS / WAVE; ++w) s += red[w][tid];
+    if constexpr (EP) {
+      double Q[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) { double v = 0.0; for (int w = 0; w < GASS_THREADS / WAVE; ++w) v += q6s[w][q]; Q[q] = v; }
+      double sn = 0.0, cs = 1.0;
+      if (tid < nth) sincos(a.thetas[(size_t)ch * GASS_MAXC + tid], &sn, &cs);
+      s += cs * cs * Q[0] + sn * sn * Q[1] + 2.0 * (cs * sn * Q[2] + cs * Q[3] + sn * Q[4]) + Q[5];
+      if (blockIdx.y == 0) s += a.epc[ch];
+    }
     if (a.nsplit == 1) a.ll[(size_t)ch * GASS_MAXC + tid] = tid < nth ? s : -INFINITY;
     else a.ll[((size_t)ch * a.nsplit + blockIdx.y) * GASS_MAXC + tid] = s;
   }
@@ -371,7 +440,8 @@ static __global__ __launch_bounds__(GASS_THREADS) void gass_select_kernel(const 
                                                                    const double* __restrict__ thetas, const double* __restrict__ hh,
                                                                    const double* __restrict__ X0, const double* __restrict__ Nu,
                                                                    double* __restrict__ X, int per, unsigned long long seed,
-                                                                   int* __restrict__ naccept, double* __restrict__ newll) {
+                                                                   int* __restrict__ naccept, double* __restrict__ newll,
+                                                                   const double* __restrict__ Mu) {
   __shared__ int pick;
   __shared__ double th;
   __shared__ unsigned char above[GASS_MAXC];
@@ -397,7 +467,10 @@ static __global__ __launch_bounds__(GASS_THREADS) void gass_select_kernel(const 
   if (pick < 0) return;
   double sn, cs;
   sincos(th, &sn, &cs);
-  for (int e = tid; e < per; e += GASS_THREADS) X[(size_t)c * per + e] = fma(X0[(size_t)c * per + e], cs, Nu[(size_t)c * per + e] * sn);
+  for (int e = tid; e < per; e += GASS_THREADS) {
+    const double x = fma(X0[(size_t)c * per + e], cs, Nu[(size_t)c * per + e] * sn);
+    X[(size_t)c * per + e] = Mu ? x + Mu[(size_t)c * per + e] : x;      // (EP: the centred ellipse, gass.py:114)
+  }
 }
 
 }  // namespace btf

@@ -1604,7 +1604,13 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
     `[I_T | 0]`, monotonicity rows `e_t - e_{t+1} >= -1e-2`, examples/poisson_tensor_filtering.py:42-48).
     Row_constraints: optional (n, K+1) fixed constraints on every row of W.
     loglikelihood: a device likelihood name as for NonconjugateBayesianTensorFiltering (the constrained Poisson model of
-    the examples is "poisson_identity").  ep_approx (the optional Gaussian centering of the proposals) is not supported.
+    the examples is "poisson_identity").
+    ep_approx: optional (Mu_ep, Sigma_ep), each broadcastable to (nrows, ncols, ndepth) (utils.ep_from_mf builds it): the
+    proposals of every row / column are centred on the Gaussian fit of the likelihood (factor.py:677-688, :771-793) and
+    the likelihood is divided by that Gaussian (the target stays exact).  The attributes Mu_ep / Sigma_ep may be
+    reassigned (both, or both None to clear) and take effect at the next update; NaN is rejected (ValueError).  Limits
+    (ValueError up front): nembeds <= 10, ndepth >= tf_order + 1, and 8 (5 T K + T K (K+1)/2) + 8 T K <= 150 KB (the
+    column system's vectors and blocks on chip; its envelope moves to HBM when it does not fit beside them).
 
     rng="host": per row / column the slice height, the proposal normals, the grid subsample and the selection are drawn
     from `chain_rngs(what)[c]` (default: RandomState objects seeded from the global legacy generator) in the reference's
@@ -1614,7 +1620,12 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
     def __init__(self, nrows, ncols, ndepth, loglikelihood, Constraints, ep_approx=None, nthreads=3, gass_ngrid=100,
                  Row_constraints=None, multiprocessing=True, sharedprefix=None, worker_init=None, **kwargs):
         if ep_approx is not None:
-            raise NotImplementedError("ep_approx (EP-centred proposals, factor.py:677-688) is not supported")
+            if not isinstance(ep_approx, (tuple, list)) or len(ep_approx) != 2:
+                raise ValueError("ep_approx must be a pair (Mu_ep, Sigma_ep)")
+            ep = self._check_ep(ep_approx[0], ep_approx[1], (nrows, ncols, ndepth))
+            self._check_ep_shape(ndepth, kwargs.get("nembeds", 5), kwargs.get("tf_order", 2))
+        else:
+            ep = (None, None)
         kwargs.setdefault("ess", "joint")
         if callable(loglikelihood):
             raise NotImplementedError("ConstrainedNonconjugateBayesianTensorFiltering evaluates up to 100 candidate angles per curve "
@@ -1636,6 +1647,68 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
         self._cons_set = False
         self.chain_rngs = None            # optional: callable what -> list of RandomState, one per row / column
         self.gass_info = {}
+        self._Mu_ep, self._Sigma_ep = ep
+        self._ep_dirty = ep[0] is not None
+
+    @staticmethod
+    def _check_ep(Mu_ep, Sigma_ep, shape):
+        try:
+            Mu = np.ascontiguousarray(np.broadcast_to(np.asarray(Mu_ep, dtype=np.float64), shape))
+            Sig = np.ascontiguousarray(np.broadcast_to(np.asarray(Sigma_ep, dtype=np.float64), shape))
+        except (ValueError, TypeError) as e:
+            raise ValueError("Mu_ep and Sigma_ep must broadcast to (nrows, ncols, ndepth) = %s: %s" % (shape, e))
+        if not np.all(np.isfinite(Mu)):
+            raise ValueError("Mu_ep must be finite (missing cells are not supported)")
+        if not np.all(np.isfinite(Sig)) or not np.all(Sig > 0):
+            raise ValueError("Sigma_ep must be finite and positive")
+        return Mu, Sig
+
+    EP_LDS_MAX = 150 * 1024           # on-chip bytes of an EP-centred column system (btf_gass_ep.h: gass_ep_cols_lds)
+
+    @classmethod
+    def _check_ep_shape(cls, ndepth, nembeds, tf_order):
+        """The limits of the EP-centred updates: nembeds 1..10, ndepth >= tf_order + 1, and the column system's
+        vectors and per-depth blocks on chip (its envelope may go to HBM): 8 (6 T K + T K (K+1)/2) bytes within 150 KB."""
+        K, T = int(nembeds), int(ndepth)
+        if not 1 <= K <= 10:
+            raise ValueError("ep_approx needs nembeds in 1..10")
+        if T < int(tf_order) + 1:
+            raise ValueError("ep_approx needs ndepth >= tf_order + 1")
+        if 8 * (5 * T * K + T * K * (K + 1) // 2) + 8 * T * K > cls.EP_LDS_MAX:
+            raise ValueError("ep_approx: ndepth * nembeds too large for the EP-centred column systems")
+
+    @property
+    def Mu_ep(self):
+        return self._Mu_ep
+
+    @Mu_ep.setter
+    def Mu_ep(self, value):
+        self._Mu_ep = value
+        self._ep_dirty = True
+
+    @property
+    def Sigma_ep(self):
+        return self._Sigma_ep
+
+    @Sigma_ep.setter
+    def Sigma_ep(self, value):
+        self._Sigma_ep = value
+        self._ep_dirty = True
+
+    def _push_ep(self):
+        if not self._ep_dirty:
+            return
+        Mu, Sig = self._Mu_ep, self._Sigma_ep
+        if Mu is None and Sig is None:
+            self._ctx.call("btf_gass_set_ep", None, None)
+        elif Mu is None or Sig is None:
+            raise ValueError("set both Mu_ep and Sigma_ep (or both to None)")
+        else:
+            Mu, Sig = self._check_ep(Mu, Sig, (self.nrows, self.ncols, self.ndepth))
+            self._check_ep_shape(self.ndepth, self.nembeds, self.tf_order)
+            self._Mu_ep, self._Sigma_ep = Mu, Sig
+            self._ctx.call("btf_gass_set_ep", _native.dptr(Mu), _native.dptr(Sig))
+        self._ep_dirty = False
 
     def shutdown(self):
         """(the reference releases its worker pool and shared arrays here)"""
@@ -1651,6 +1724,7 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
             self._ctx.call("btf_gass_set_constraints", _native.dptr(self._cons), int(self._cons.shape[0]),
                            _native.dptr(rc), 0 if rc is None else int(rc.shape[0]))
             self._cons_set = True
+        self._push_ep()
         o = self.linalg_opts
         eps, att = float(o["force_psd_eps"]), int(o["force_psd_attempts"]) if o["force_psd"] else 0
         if self.rng == "device":

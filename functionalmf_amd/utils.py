@@ -104,3 +104,26 @@ def posterior_summary(Ws, Vs, q=(5, 95), transform=None, device=0):
 
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
 from .nmf import factor_pav, tensor_nmf  # noqa: E402,F401
+
+
+def ep_from_mf(Y, W, V, mode='max', multiplier=2):
+    """Gaussian approximation of the likelihood around a factorisation (utils.py:423-438): the means W.V and one
+    over-estimated standard deviation for every cell - the root of the largest (mode='max') or `multiplier` times the
+    root of the mean (mode='multiplier') per-cell mean squared error of the observed replicates.  Y: 3-D or 4-D with
+    NaN for missing entries.  Returns (Mu_ep, Sigma_ep), the ep_approx of ConstrainedNonconjugateBayesianTensorFiltering."""
+    import warnings
+    Y = np.asarray(Y, dtype=float)
+    if Y.ndim == 3:
+        Y = Y[..., None]
+    M = (W[:, None, None] * V[None]).sum(axis=-1, keepdims=True)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        sqerr = np.nanmean((Y - M) ** 2, axis=-1)
+        if mode == 'max':
+            overestimate = np.sqrt(np.nanmax(sqerr))
+        elif mode == 'multiplier':
+            overestimate = np.sqrt(np.nanmean(sqerr)) * multiplier
+        else:
+            raise ValueError("mode must be 'max' or 'multiplier'")
+    print('Estimated stdev: {}'.format(overestimate))
+    return M[..., 0], np.ones(Y.shape[:-1]) * overestimate

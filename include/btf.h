@@ -543,6 +543,14 @@ int btf_gass_eval(btf_ctx* ctx, int what, const double* thetas, const int32_t* n
 int btf_gass_commit(btf_ctx* ctx, int what, const double* theta, const int32_t* keep);
 int btf_gass_select(btf_ctx* ctx, int what, uint64_t seed, int32_t* naccept_out);
 int btf_gass_run(btf_ctx* ctx, int what, int link, uint64_t seed, int ngrid, double eps0, int attempts);
+/* btf_gass_set_ep: EP-centred proposals (ep_approx, factor.py:677-688 and :771-793).  mu, sigma [N][M][T] (Mu_ep and
+ * Sigma_ep, finite, sigma > 0; NULL, NULL clears).  While set, btf_gass_begin draws the proposal from N(0, Q^-1) with Q the
+ * likelihood-weighted precision (rows: sum p v v' + I_d / sigma2; columns: kron(I_K, Delta' Lambda Delta) + X' Sigma X,
+ * p = 1 / Sigma_ep^2; z in the same layouts as the plain update, columns in the twisted order), centres the ellipse
+ * on mu = Q^-1 X' Sigma Mu_ep, and every likelihood it reports (cur_ll, slice, ll_out) is the corrected
+ * ll - sum_cells log N(tau; Mu_ep, Sigma_ep) over every cell of the chain; commit and select write
+ * x0 cos + v sin + mu.  The kernels are counted under BTF_K_ESS. */
+int btf_gass_set_ep(btf_ctx* ctx, const double* mu, const double* sigma);
 
 /* ---- posterior summaries (stateless) --------------------------------
  * Mean and percentiles over the kept samples of f(w_s[i] . v_s[j,t]) for every cell: what the
