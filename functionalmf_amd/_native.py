@@ -16,7 +16,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")   # override: A/B builds
 SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip"),
-           os.path.join(CSRC, "btf_gass_ep.hip")]
+           os.path.join(CSRC, "btf_gass_ep.hip"), os.path.join(CSRC, "btf_gamma_grid.hip")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -134,6 +134,8 @@ SIGNATURES = {
     "btf_queue_scalars": (C.c_int, [_ctx, C.c_uint64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _c_ip]),
     "btf_host_selftest": (C.c_int, []),
     "btf_set_likelihood_param": (C.c_int, [_ctx, C.c_int, C.c_double]),
+    "btf_set_likelihood_table": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int]),
+    "btf_set_data_logsum": (C.c_int, [_ctx, _c_dp, _c_dp, C.c_int]),
     "btf_comm_fork": (C.c_int, [_ctx, C.c_void_p]),
     "btf_comm_join": (C.c_int, [_ctx, C.c_void_p]),
     "btf_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte), C.c_int]),
@@ -188,6 +190,7 @@ def build(force=False, verbose=False, jobs=None):
             "-I", os.path.join(ROOT, "include")] + os.environ.get("BTF_BUILD_DEFS", "").split()   # A/B builds: -DBTF_... tuning macros
     units = [(SOURCES[0], os.path.join(OBJ_DIR, tag + "_abi.o"), []), (SOURCES[1], os.path.join(OBJ_DIR, tag + "_crit.o"), [])]
     units += [(SOURCES[2], os.path.join(OBJ_DIR, tag + "_nmf.o"), []), (SOURCES[3], os.path.join(OBJ_DIR, tag + "_gass_ep.o"), [])]
+    units += [(SOURCES[4], os.path.join(OBJ_DIR, tag + "_gamma_grid.o"), [])]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

@@ -9,6 +9,7 @@
 #include "btf_spectral.h"
 #include "btf_gass.h"
 #include "btf_gass_ep.h"
+#include "btf_gamma_grid.h"    // the gamma-grid likelihood (instances in btf_gamma_grid.hip)
 #include "btf_fused.h"
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
@@ -90,7 +91,10 @@ struct btf_ctx {
   double2* ep_rows = nullptr; double2* ep_cols = nullptr; double* ep_crow = nullptr; double* ep_ccol = nullptr;
   double* ep_mu = nullptr; double* ep_corr = nullptr; double* ep_pband = nullptr; double* ep_envg = nullptr;
   int* ep_f = nullptr; int* ep_off = nullptr; int ep_env = 0, ep_bwe = 0; bool ep_on = false, gs_ep = false;
-  double lik_par[ESS_FAM_COUNT] = {0, 0, 0, 1.0, 1.0};     // parameter per likelihood family (btf_set_likelihood_param)
+  double lik_par[ESS_FAM_COUNT] = {0, 0, 0, 1.0, 1.0, 0};     // parameter per likelihood family (btf_set_likelihood_param)
+  // the gamma-grid family (btf_gamma_grid.h): component table, log sum p, and L = sum_r log y in both layouts of S1
+  GgComp* gg_tab = nullptr; int gg_G = 0; double gg_lsp = 0.0;
+  double* gg_Lw = nullptr; double* gg_Lv = nullptr; bool gg_have_L = false;
   long long* dbg = nullptr;
   double* vc_scratch = nullptr; size_t vc_scratch_elems = 0;     // factor records of the chunked chain sampler
 #ifdef BTF_ACC_STAMPS
@@ -764,6 +768,20 @@ void launch_ess_ll(btf_ctx* c, int what, int mode, int link, int nbx) {
   const LikFam lf{link, c->lik_par[link]};                 // `link` is the likelihood family (ESS_FAM_*)
   const int tl = ess_link_of(link);                        // the kernel instantiation that evaluates it
   const unsigned char* c8v = c->C8_v; const unsigned char* c8w = c->C8_wT;
+  if (tl == ESS_LINK_GAMMA_GRID) {   // its own kernels (btf_gamma_grid.hip), the same grids and partial-sum layouts
+    GgLLArgs a{};
+    a.Rc = Rc; a.W = c->W; a.V = c->V; a.T = c->T; a.done = c->ess_done; a.part = c->ess_part;
+    GgTab t{nullptr, c->gg_tab, c->gg_G, c->gg_lsp};
+    if (what == 1 && mode == 1) {
+      a.A = c->A_wT; a.C8 = c8w; a.Cd = c->C_wT; a.nl = c->N; a.ld = c->ldw; t.L = c->gg_Lw;
+      p.launch(gg_ll_cols_fn(K), dim3(nbx, c->M), dim3(ESS_THREADS), 0, a, t);
+    } else {
+      a.A = c->A_v; a.C8 = c8v; a.Cd = c->C_v; a.ncols = c->M * c->T; a.ld = c->ldv; a.per_row = (what == 0 && mode == 1) ? 1 : 0;
+      t.L = c->gg_Lv;
+      p.launch(gg_ll_rows_fn(K), dim3(nbx, c->N), dim3(ESS_THREADS), 0, a, t);
+    }
+    return;
+  }
   if (what == 1 && mode == 1) {      // per-column chains: W layout
     dim3 grid(nbx, c->M);
 #define ESS_COLS(LINK_)                                                                                                   \
@@ -1013,7 +1031,8 @@ void btf_destroy(btf_ctx* c) {
   void* ptrs[] = {c->A_wT, c->C_wT, c->A_v, c->C_v, c->B_wT, c->B_v, c->W, c->V, c->Tau2, c->part,
                   c->gpart, c->zbuf, c->bsum, c->gband, c->status, c->tries, c->st_ptr, c->st_row, c->st_coef,
                   c->srcmap_w, c->srcmap_v, c->pband, c->pimg, c->dbg, c->gpart_w, c->gpart_v, c->gsum_v, c->eig, c->cv_cptr, c->cv_crow, c->cv_cdef, c->cv_rptr, c->cv_rcol, c->cv_rdef, c->eig_cols, c->cv_dcols, c->A8_wT, c->A8_v, c->gs_cons, c->gs_cc, c->gs_rc, c->gs_av, c->gs_mask, c->gs_info, c->gs_thetas, c->gs_ntheta, c->gs_ll, c->gs_llp, c->gs_hh, c->gs_cur, c->gs_nacc, c->gs_u, c->st_drow, c->st_dcoef, c->essX0, c->essNu, c->ess_st, c->ess_theta, c->ess_done, c->ess_part, c->Ta, c->Tb, c->Tc, c->lsum, c->dr_ptr, c->dr_col, c->dr_val, c->sse_cols, c->vs_rec, c->vc_scratch, c->gs_cptr, c->gs_cidx, c->gs_cval,
-                  c->ep_rows, c->ep_cols, c->ep_crow, c->ep_ccol, c->ep_mu, c->ep_corr, c->ep_pband, c->ep_envg, c->ep_f, c->ep_off};
+                  c->ep_rows, c->ep_cols, c->ep_crow, c->ep_ccol, c->ep_mu, c->ep_corr, c->ep_pband, c->ep_envg, c->ep_f, c->ep_off,
+                  c->gg_tab, c->gg_Lw, c->gg_Lv};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->pin_lsum) (void)hipHostFree(c->pin_lsum);
@@ -1155,6 +1174,7 @@ static int finish_data(btf_ctx* c) {
     if (rc2) return rc2;
   }
   c->have_data = true;
+  c->gg_have_L = false;                // (new data: btf_set_data_logsum again for the gamma-grid family)
   c->w_part_valid = false; c->w_local_done = c->v_local_done = false; c->sse_cols_valid = false;
   return BTF_OK;
 }
@@ -2162,6 +2182,8 @@ int ess_check(btf_ctx* c, int what, int link, bool allow_host = false) {
   if (!c->have_data || c->binomial || !c->have_W || !c->have_V || !c->have_hyper)
     return fail(c, BTF_ESTATE, "elliptical slice sampling needs count data (btf_set_data_gaussian statistics), W, V and hyper-parameters");
   if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "elliptical slice sampling needs an unsharded context");
+  if (link == ESS_FAM_GAMMA_GRID && (!c->gg_tab || !c->gg_have_L))
+    return fail(c, BTF_ESTATE, "the gamma-grid likelihood needs its table (btf_set_likelihood_table) and L (btf_set_data_logsum)");
   return BTF_OK;
 }
 EssDims ess_dims(const btf_ctx* c, int what, int mode) {
@@ -2356,7 +2378,13 @@ int gass_eval_launch(btf_ctx* c, int what, int link) {
   const dim3 grid(nch, nsplit);
   a.lf = LikFam{link, c->lik_par[link]};
   const int tl = ess_link_of(link);
-  if (c->gs_ep) {        // EP-centred: the centre, the per-cell (Mu, p) and the chains' constants
+  if (tl == ESS_LINK_GAMMA_GRID) {       // btf_gamma_grid.hip: the same grid, partial sums and EP quadratic form
+    if (what == 0) { a.F = c->V; a.A = c->A_v; a.C8 = c->C8_v; a.Cd = c->C_v; a.ld = c->ldv; }
+    else { a.F = c->W; a.A = c->A_wT; a.C8 = c->C8_wT; a.Cd = c->C_wT; a.ld = c->ldw; }
+    if (c->gs_ep) { a.Mu = c->ep_mu; a.ep = what == 0 ? c->ep_rows : c->ep_cols; a.epc = what == 0 ? c->ep_crow : c->ep_ccol; }
+    const GgTab t{what == 0 ? c->gg_Lv : c->gg_Lw, c->gg_tab, c->gg_G, c->gg_lsp};
+    p.launch(gg_eval_fn(what == 0, c->gs_ep), grid, dim3(GASS_THREADS), 0, a, t);
+  } else if (c->gs_ep) {        // EP-centred: the centre, the per-cell (Mu, p) and the chains' constants
     a.Mu = c->ep_mu; a.ep = what == 0 ? c->ep_rows : c->ep_cols; a.epc = what == 0 ? c->ep_crow : c->ep_ccol;
     if (what == 0) { a.F = c->V; a.A = c->A_v; a.C8 = c->C8_v; a.Cd = c->C_v; a.ld = c->ldv; }
     else { a.F = c->W; a.A = c->A_wT; a.C8 = c->C8_wT; a.Cd = c->C_wT; a.ld = c->ldw; }
@@ -2756,8 +2784,70 @@ int btf_wv_steps(btf_ctx* c, int n, uint64_t seed_base, uint64_t draws0, int com
 
 int btf_set_likelihood_param(btf_ctx* c, int family, double par) {
   if (!c || family < 0 || family >= ESS_FAM_COUNT || !(par == par)) return fail(c, BTF_EINVAL, "bad likelihood family / parameter");
+  if (family == ESS_FAM_GAMMA_GRID) return fail(c, BTF_EINVAL, "the gamma-grid family takes a table: btf_set_likelihood_table");
   if ((family == ESS_FAM_GAUSSIAN || family == ESS_FAM_NEGBIN_LOGIT) && !(par > 0.0)) return fail(c, BTF_EINVAL, "the parameter must be positive");
   c->lik_par[family] = par;
+  return BTF_OK;
+}
+
+int btf_set_likelihood_table(btf_ctx* c, int family, const double* shape, const double* scale, const double* prob, int G) {
+  if (!c) return BTF_EINVAL;
+  if (family != ESS_FAM_GAMMA_GRID) return fail(c, BTF_EINVAL, "btf_set_likelihood_table: family 5 (gamma grid) only");
+  if (!shape || !scale || !prob || G < 1 || G > GG_MAXG) return fail(c, BTF_EINVAL, "the gamma grid has 1..128 components");
+  std::vector<GgComp> h;
+  double psum = 0.0;
+  for (int g = 0; g < G; ++g) {
+    const double a = shape[g], s = scale[g], p = prob[g];
+    if (!std::isfinite(a) || !std::isfinite(s) || !std::isfinite(p) || !(a > 0.0) || !(s > 0.0) || !(p >= 0.0))
+      return fail(c, BTF_EINVAL, "gamma grid: finite shape > 0, scale > 0 and weight >= 0 expected");
+    psum += p;
+    if (p > 0.0) h.push_back(GgComp{std::log(p), a, 1.0 / s, a * std::log(s) + std::lgamma(a)});    // (p = 0: no term)
+  }
+  if (h.empty()) return fail(c, BTF_EINVAL, "gamma grid: every weight is zero");
+  HIPCHK(c, hipSetDevice(c->dev));
+  int rc;
+  if ((rc = dev_alloc(c, &c->gg_tab, (size_t)GG_MAXG))) return rc;
+  HIPCHK(c, hipMemcpy(c->gg_tab, h.data(), h.size() * sizeof(GgComp), hipMemcpyHostToDevice));
+  c->gg_G = (int)h.size();
+  c->gg_lsp = std::log(psum);
+  return BTF_OK;
+}
+
+int btf_set_data_logsum(btf_ctx* c, const double* y_rows, const double* y_cols, int nreps) {
+  if (!c || !y_rows || !y_cols || nreps < 1) return fail(c, BTF_EINVAL, "bad data arguments");
+  if (!c->have_data || c->binomial || c->counts || nreps != c->R)
+    return fail(c, BTF_ESTATE, "btf_set_data_logsum follows btf_set_data_gaussian with the same Y");
+  HIPCHK(c, hipSetDevice(c->dev));
+  const int MT = c->M * c->T;
+  const int rows_w = slab_rows(c), cols_v = slab_cols(c) * c->T;
+  int rc;
+  if ((rc = dev_alloc(c, &c->gg_Lw, (size_t)MT * c->ldw))) return rc;
+  if ((rc = dev_alloc(c, &c->gg_Lv, (size_t)c->N * c->ldv))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->gg_Lw, 0, (size_t)MT * c->ldw * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->gg_Lv, 0, (size_t)c->N * c->ldv * sizeof(double), c->stream));
+  int zero = 0;
+  HIPCHK(c, hipMemcpy(c->status + 3, &zero, sizeof(int), hipMemcpyHostToDevice));
+  double* dY = nullptr;
+  auto one = [&](const double* hY, int rows, int cols, int ld, int transposed, double* L) -> int {
+    const size_t n = (size_t)rows * cols * nreps;
+    int r;
+    if ((r = dev_alloc(c, &dY, n))) return r;
+    HIPCHK(c, hipMemcpy(dY, hY, n * sizeof(double), hipMemcpyHostToDevice));
+    const int blocks = (int)std::min<size_t>(4096, ((size_t)rows * cols + 255) / 256);
+    Prof p(c, BTF_K_STATS);
+    p.launch(gg_logsum_fn(), dim3(blocks), dim3(256), 0, (const double*)dY, rows, cols, nreps, ld, transposed, L, c->status + 3);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BTF_OK;
+  };
+  rc = one(y_rows, rows_w, MT, c->ldw, 1, c->gg_Lw);
+  if (!rc) rc = one(y_cols, c->N, cols_v, c->ldv, 0, c->gg_Lv);
+  if (dY) (void)hipFree(dY);
+  if (rc) return rc;
+  int bad = 0;
+  HIPCHK(c, hipMemcpy(&bad, c->status + 3, sizeof(int), hipMemcpyDeviceToHost));
+  if (bad) return fail(c, BTF_EINVAL, "the gamma-grid likelihood needs every observed y > 0");
+  c->gg_have_L = true;
   return BTF_OK;
 }
 

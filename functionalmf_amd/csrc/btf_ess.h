@@ -29,13 +29,19 @@ namespace btf {
 //   2 Bernoulli / Binomial, logit link (S1 successes of cnt trials)   S1 eta - cnt softplus(eta)
 //   3 Gaussian, identity link, known variance (par = 1 / variance)    par (S1 eta - cnt eta^2 / 2)
 //   4 Negative-Binomial, logit link, known rate (par = r)             S1 eta - (S1 + cnt r) softplus(eta)
+//   5 gamma grid (doseresponse/empirical_bayes.py; table: btf_set_likelihood_table, L = sum_r log y: btf_set_data_logsum)
+//                                                                      logsumexp_g [log p_g + (a_g - 1) L - S1 / (s_g eta)
+//                                                                        - cnt (a_g log(s_g eta) + lgamma a_g)]   (complete)
 // Families 0 and 1 have kernels of their own (table-based exp / log); 2..4 share the ESS_LINK_GENERIC instantiation,
-// which takes the family and its parameter at run time (libm exp / log1p: one evaluation is still one pass).
-enum { ESS_LINK_LOG = 0, ESS_LINK_IDENTITY = 1, ESS_LINK_GENERIC = 2 };
+// which takes the family and its parameter at run time (libm exp / log1p: one evaluation is still one pass).  Family 5
+// is not a function of (S1, cnt) alone: its kernels are in a unit of their own (btf_gamma_grid.h, ESS_LINK_GAMMA_GRID).
+enum { ESS_LINK_LOG = 0, ESS_LINK_IDENTITY = 1, ESS_LINK_GENERIC = 2, ESS_LINK_GAMMA_GRID = 3 };
 enum { ESS_FAM_POISSON_LOG = 0, ESS_FAM_POISSON_IDENTITY = 1, ESS_FAM_BERNOULLI_LOGIT = 2, ESS_FAM_GAUSSIAN = 3, ESS_FAM_NEGBIN_LOGIT = 4,
-       ESS_FAM_COUNT = 5 };
+       ESS_FAM_GAMMA_GRID = 5, ESS_FAM_COUNT = 6 };
 struct LikFam { int fam; double par; };
-__host__ __device__ constexpr int ess_link_of(int fam) { return fam <= ESS_FAM_POISSON_IDENTITY ? fam : ESS_LINK_GENERIC; }
+__host__ __device__ constexpr int ess_link_of(int fam) {
+  return fam <= ESS_FAM_POISSON_IDENTITY ? fam : (fam == ESS_FAM_GAMMA_GRID ? ESS_LINK_GAMMA_GRID : ESS_LINK_GENERIC);
+}
 __device__ __forceinline__ double softplus(double x) { return x > 0.0 ? x + log1p(exp(-x)) : log1p(exp(x)); }
 constexpr int ESS_THREADS = 256;
 

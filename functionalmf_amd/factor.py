@@ -39,6 +39,7 @@ import numpy as np
 
 from . import _native
 from . import criteria as _criteria
+from . import likelihoods as _likelihoods
 from .genlasso import _BayesianModel, ConjugateInverseGammaPrior
 from .utils import bayes_grid_penalty, sample_horseshoe_plus, sample_horseshoe
 from .parallel import ShardPlan, Exchange
@@ -1417,7 +1418,12 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         "bernoulli_logit"           y in {0, 1} ~ Bernoulli(ilogit(w.v))      (scipy.stats.bernoulli.logpmf)
         "gaussian"                  y ~ N(w.v, likelihood_param)              (likelihood_param: the variance)
         "negbin_logit"              y ~ NB(likelihood_param, 1 - ilogit(w.v)) (scipy.stats.nbinom; likelihood_param: the rate r)
-    - all functions of the hoisted per-cell statistics (sum and count of the observed replicates).
+        "gamma_grid"                y > 0 ~ sum_g p_g Gamma(shape_g, scale_g * w.v), the replicates of a cell sharing the
+                                    component (doseresponse/empirical_bayes.py:9-33); likelihood_param: the reference's
+                                    (mean_grid, mean_probs, variance), or an object with shape_grid / scale_grid /
+                                    probs_grid (its GammaGridLikelihood).  -inf where w.v <= 0 on an observed cell.
+    - all functions of the hoisted per-cell statistics (sum and count of the observed replicates; gamma_grid: also the
+    sum of their logs).
     data: (N,M,T) or (N,M,T,R), NaN = missing.
 
     ess = "joint" (default): ONE slice over all of W, then one over all of V, as the reference; with rng="host" the
@@ -1427,7 +1433,8 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
           the other factor, as in the reference's constrained model (factor.py:665-720) - all brackets shrinking
           in lockstep on the device; mixes faster than the joint slice, whose step shrinks with the dimension."""
 
-    LINKS = {"poisson": 0, "poisson_log": 0, "poisson_identity": 1, "bernoulli_logit": 2, "gaussian": 3, "negbin_logit": 4}
+    LINKS = {"poisson": 0, "poisson_log": 0, "poisson_identity": 1, "bernoulli_logit": 2, "gaussian": 3, "negbin_logit": 4,
+             "gamma_grid": 5}
 
     def __init__(self, nrows, ncols, ndepth, loglikelihood, ess="joint", ess_max_rounds=40, likelihood_param=None, **kwargs):
         self._callback = callable(loglikelihood)
@@ -1436,6 +1443,8 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
                              "device likelihood %s" % sorted(self.LINKS))
         if ess not in ("joint", "rows"):
             raise ValueError("ess must be 'joint' or 'rows'")
+        # (checked before the context exists: a bad table raises ValueError with no device call)
+        table = _likelihoods.gamma_grid_table(likelihood_param) if loglikelihood == "gamma_grid" else None
         super().__init__(nrows, ncols, ndepth, **kwargs)
         if self._plan.world > 1:
             raise NotImplementedError("NonconjugateBayesianTensorFiltering: unsharded runs only")
@@ -1451,6 +1460,10 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
                 raise ValueError("loglikelihood=%r needs likelihood_param > 0 (the variance / the rate)" % loglikelihood)
             self.likelihood_param = float(likelihood_param)
             self._ctx.call("btf_set_likelihood_param", self._link, 1.0 / self.likelihood_param if self._link == 3 else self.likelihood_param)
+        elif table is not None:
+            self.likelihood_param = likelihood_param
+            self._gg_table = table
+            self._ctx.call("btf_set_likelihood_table", self._link, *(_native.dptr(v) for v in table), int(table[0].size))
         else:
             self.likelihood_param = None
         self.ess, self.ess_max_rounds = ess, int(ess_max_rounds)
@@ -1461,6 +1474,8 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         if self._callback:
             raise NotImplementedError("model-selection criteria need a device likelihood: a Python-callable loglikelihood "
                                       "is evaluated on the host only")
+        if self._link == 5:
+            raise NotImplementedError("model-selection criteria (WAIC / DIC) are not available for the gamma_grid likelihood")
         return self._link, (self.likelihood_param if self._link in (3, 4) else None), False
 
     def _bind_data(self, data):
@@ -1475,8 +1490,14 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         if Y4.shape[:3] != (self.nrows, self.ncols, self.ndepth):
             raise ValueError("data shape %r does not match the model" % (Y.shape,))
         from scipy.special import gammaln
+        if self._link == 5 and np.any(Y4 <= 0):           # (NaN compares False: missing replicates pass)
+            raise ValueError("the gamma_grid likelihood needs every observed y > 0")
         rows, cols = self._plan.slabs(Y4)
         self._ctx.call("btf_set_data_gaussian", _native.dptr(rows), _native.dptr(cols), int(Y4.shape[3]))
+        if self._link == 5:              # the per-cell sum of log y; the kernels return the complete log-likelihood
+            self._ctx.call("btf_set_data_logsum", _native.dptr(rows), _native.dptr(cols), int(Y4.shape[3]))
+            self._ll_const = 0.0
+            return
         obs = ~np.isnan(Y4)
         y = np.where(obs, Y4, 0.0)
         # the state-independent part of the log-likelihood (the device kernels leave it out)
@@ -1504,6 +1525,25 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         ll = ctypes.c_double()
         self._ctx.call("btf_ess_eval", 0, 0.0, 1, self._link, ctypes.byref(ll))
         return ll.value + self._ll_const
+
+    def logprob(self, data, reduce="sum", **state):
+        if self._callback or self._link != 5:
+            return super().logprob(data, reduce=reduce, **state)
+        # gamma_grid has no criteria kernel: the current state's sum on the device, anything else by the host class
+        if reduce not in ("sum", "curve"):
+            raise ValueError("reduce must be 'sum' or 'curve'")
+        W, V = state.get("W"), state.get("V")
+        if reduce == "sum" and W is None and V is None:
+            return self.log_likelihood(data)
+        W = np.asarray(self.W if W is None else W, dtype=float)
+        V = np.asarray(self.V if V is None else V, dtype=float)
+        if W.shape != (self.nrows, self.nembeds) or V.shape != (self.ncols, self.ndepth, self.nembeds):
+            raise ValueError("W %r / V %r do not match the model" % (W.shape, V.shape))
+        Y = np.asarray(data, dtype=float)
+        Y4 = Y[..., None] if Y.ndim == 3 else Y
+        ll = _likelihoods.GammaGridLikelihood.from_table(*self._gg_table).logpdf(Y4, np.einsum("nk,mtk->nmt", W, V)[..., None])
+        curve = ll.sum(axis=-1)
+        return float(curve.sum()) if reduce == "sum" else np.where(np.any(~np.isnan(Y4), axis=(2, 3)), curve, 0.0)
 
     def _ess_step(self, what, data):
         import ctypes

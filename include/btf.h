@@ -489,6 +489,17 @@ int btf_mvn_dense(int device, int batch, int n, const double* A, int form, const
  * - every one a function of the hoisted statistics S1 = sum_r y, cnt = observed replicates; the state-independent terms
  * (- sum lgamma(y+1), the Gaussian's - sum y^2 / 2 s2 - n log(2 pi s2) / 2, the Negative-Binomial's log binomial
  * coefficients) are left to the caller.  Parameters: btf_set_likelihood_param.  what: 0 = W, 1 = V.  Unsharded contexts.
+ *   link 5  gamma grid (the dose-response likelihood, doseresponse/empirical_bayes.py:9-33): an empirical-Bayes mixture of
+ *           gammas, component g = (shape a_g, scale s_g, weight p_g; weights used as given), per cell with observed
+ *           replicates y_r:  log sum_g p_g prod_r Gamma(y_r; a_g, scale = s_g (w.v))
+ *             = logsumexp_g [log p_g + (a_g - 1) L - S1 / (s_g w.v) - cnt (a_g log(s_g w.v) + lgamma a_g)],  L = sum_r log y
+ *           - the COMPLETE value (nothing is left to the caller).  A cell without observations contributes log sum_g p_g
+ *           (the reference's nansum; 0 for normalised weights); w.v <= 0 on an observed cell gives -inf (a deliberate
+ *           deviation: the reference's nansum would count the NaN as unobserved).  Needs the table
+ *           (btf_set_likelihood_table: 1 <= G <= 128, finite shape > 0, scale > 0, weight >= 0, not all zero; else
+ *           BTF_EINVAL) and L (btf_set_data_logsum, after btf_set_data_gaussian with the same Y: every observed y > 0,
+ *           else BTF_EINVAL); btf_ess_eval / btf_ess_run / btf_gass_begin / btf_gass_run return BTF_ESTATE without them.
+ *           L is allocated for this family only, in both layouts of S1.
  *
  * Host-driven form (rng="host": the uniforms come from the caller's generator, so a seeded chain walks the
  * reference's path): btf_ess_begin saves the current state x0 and draws nu (z: the normals of
@@ -508,6 +519,8 @@ int btf_mvn_dense(int device, int batch, int n, const double* A, int form, const
  * max_rounds (they keep the current state) and the log-likelihood the first chain ended on.                      */
 #define BTF_ESS_HOST_LIKELIHOOD (-1)
 int btf_set_likelihood_param(btf_ctx* ctx, int link, double parameter);   /* links 3 (1 / variance) and 4 (rate); > 0 */
+int btf_set_likelihood_table(btf_ctx* ctx, int link, const double* shape, const double* scale, const double* prob, int G);   /* link 5 */
+int btf_set_data_logsum(btf_ctx* ctx, const double* y_rows, const double* y_cols, int nreps);   /* link 5: L = sum_r log y */
 int btf_ess_begin(btf_ctx* ctx, int what, const double* z, uint64_t seed, double eps0, int attempts);
 int btf_ess_eval(btf_ctx* ctx, int what, double theta, int current, int link, double* ll);
 int btf_ess_run(btf_ctx* ctx, int what, int link, int mode, const double* z, uint64_t seed, int max_rounds,
@@ -517,7 +530,7 @@ int btf_ess_info(btf_ctx* ctx, int32_t* unfinished, double* ll_first);
 /* ---- generalized analytic slice sampling (gass.py:13-130) for the constrained non-conjugate model
  * (ConstrainedNonconjugateBayesianTensorFiltering._resample_W / _resample_V, factor.py:665-855): every row of W (what = 0)
  * or every column of V (what = 1) is one chain, all chains advance together.  Likelihood: the device likelihoods
- * of btf_ess_* (links 0..4) on the statistics of btf_set_data_gaussian.  Unsharded contexts.
+ * of btf_ess_* (links 0..5) on the statistics of btf_set_data_gaussian (link 5: and btf_set_data_logsum).  Unsharded contexts.
  *
  * btf_gass_set_constraints: cons [J][T+1], row q = (Cons_q, bound_q): every curve tau_ij = (w_i . v_jt)_t must satisfy
  *   Cons_q . tau_ij >= bound_q (the reference's `Constraints`, factor.py:910); row_cons [nrc][K+1]: fixed constraints on
