@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Gibbs sweeps/sec of the full W+V update (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one W half-sweep + one V half-sweep (model._resample_W then model._resample_V through
 the C ABI) on synthetic data that is already resident in HBM, with the normals drawn on the device
@@ -17,10 +17,16 @@ N > 1   workload C5 of BASELINE.json, STRONG scaling: the fixed tensor (4096,102
         `python bench.py --gpus N` launches its own ranks (one child `python -m torch.distributed.run`);
         under torchrun (WORLD_SIZE set) it is a rank.
 
-Besides the contract fields the JSON line carries `roofline` (the streaming accumulation kernel:
-algorithmic bytes / HIP-event time of exactly that dispatch against the 8 TB/s HBM peak, plus the
-whole-step fraction and a measured device-copy ceiling) and, at N=1, `cpu_baseline` (the numpy
-oracle's reference-faithful W+V update on the host cores, all BLAS threads and one thread).
+A plain run sets up (data, model, burn-in), warms up, times the K steps, writes --dump-outputs and prints
+the JSON line: the contract fields and a `config` block that takes no run of its own.
+
+--full adds everything that does take runs of its own: per-step and per-kernel HIP-event timing,
+`roofline` (the streaming accumulation kernel: algorithmic bytes / HIP-event time of exactly that
+dispatch against the 8 TB/s HBM peak, plus the whole-step fraction and measured copy / read ceilings),
+the Python-driven loop, full sweeps, the banded sampler, the rng="host" mode, the C4 Binomial leg,
+the --as-rank projection and, at N=1, `cpu_baseline` (the numpy oracle's reference-faithful W+V
+update on the host cores, all BLAS threads and one thread).  The timed steps and `value` are the
+same either way: the extra legs all run after them.
 """
 import argparse
 import json
@@ -115,8 +121,11 @@ def parse_args(argv=None):
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS), help="default: c3 at --gpus 1, c5 beyond")
     ap.add_argument("--weak", action="store_true", help="N>1: weak scaling over rows (one C3-sized slab per rank) instead of the fixed C5 tensor")
     ap.add_argument("--strong", action="store_true", help="(default for N>1; kept for compatibility)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-c4", action="store_true", help="skip the short BASELINE-config-4 (Binomial) leg of the default run")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, also run what takes runs of its own: per-step and "
+                    "per-kernel timing, roofline, the Python-driven loop, full sweeps, the banded-sampler and rng=host legs, "
+                    "the C4 leg, the --as-rank projection and the CPU baseline (default: the headline line alone)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-c4", action="store_true", help="--full: skip the short BASELINE-config-4 (Binomial) leg")
     ap.add_argument("--rpb", type=int, nargs=2, default=[0, 0], help="rows per workgroup (W, V) tuning override")
     ap.add_argument("--variant", default="complete", choices=["complete", "heldout", "curves5", "missing5", "binomial", "negbinom"],
                     help="complete: headline; heldout: Y[:3,:3]=NaN; curves5: 5%% of the (i,j) curves NaN; "
@@ -128,11 +137,11 @@ def parse_args(argv=None):
                     "(the default already draws integer counts up to 32 exactly)")
     ap.add_argument("--pg-series", action="store_true", help="binomial / negbinom: the approximate sum-of-gammas series for every count")
     ap.add_argument("--burn", type=int, default=10, help="full Gibbs sweeps before timing (leave the initial state)")
-    ap.add_argument("--lean", action="store_true", help="profiling runs: nothing but W+V steps after the burn-in - no full-sweep leg, no banded-"
-                    "sampler leg, no CPU baseline - so that a rocprofv3 --stats average is over the dispatches the HIP events time")
+    ap.add_argument("--lean", action="store_true", help="--full profiling runs: nothing but W+V steps after the burn-in - no full-sweep leg, no "
+                    "banded-sampler leg, no CPU baseline - so that a rocprofv3 --stats average is over the dispatches the HIP events time")
     ap.add_argument("--as-rank", default=None, metavar="R/P", help="ONE GPU plays rank R of a P-GPU run of --config (default c5): its "
                     "kernels on that rank's real slabs, every collective of the sharded step in a one-rank RCCL group at the full "
-                    "message size; adds a `projected` block (never `value`: that stays this GPU's own rate)")
+                    "message size; with --full adds a `projected` block (never `value`: that stays this GPU's own rate)")
     ap.add_argument("--overlap", action="store_true", help="sharded runs: all-gathers on a communication stream, own-block chunks of the "
                     "next accumulation ahead of them (BTF_OPT_SPLIT_ACCUM); default: collectives in line on the ctx's stream")
     ap.add_argument("--python-loop", action="store_true", help="drive the timed W+V steps from Python, call by call (default on one GPU with "
@@ -314,6 +323,17 @@ def main():
     model.sync()                      # raises if any factorisation failed inside the timed region
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, {"W": model.W, "V": model.V})
+    if world > 1:
+        tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+    out = headline(args, world, weak, dt, legacy_data, (N, M, T, R, K), model, c_driven, as_rank, plan)
+    if world > 1 or exercise:
+        out["config"].update({"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(),
+                              "exchange_transport": model._exchange.transport})
+    if not args.full:                 # a plain run: the headline line and nothing that takes a run of its own
+        return finish(out, rank, world > 1 or exercise, dist)
+
     py_per_s = None
     if c_driven and not args.lean:    # the same K steps driven from Python, call by call
         for _ in range(args.warmup):
@@ -325,10 +345,6 @@ def main():
         fence()
         py_per_s = args.steps / (time.perf_counter() - t0p)
         model.sync()
-    if world > 1:
-        tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
 
     # ---- per-step GPU time by events between the steps (median of >= 50: BASELINE.md section 4) ----
     nmed = max(50, min(args.steps, 200))
@@ -410,16 +426,11 @@ def main():
         fence()
         full_per_s = nfull / (time.perf_counter() - t0)
 
-    sweeps_per_s = args.steps / dt
-    units = world if weak else 1
-    value = sweeps_per_s * units
-
     # algorithmic bytes: the local slab of the linear statistic once per accumulation launch
     # (8 B/cell complete data; + a byte of replicate count with missing data; Binomial: f64 weights + the pseudo-data
     #  as one byte when the counts are integers, else as f64) - asked of the context, which knows what it streams
     cells_local = plan.nl * M * T
     cells_local_v = N * plan.ml * T
-    form = model.likelihood_form()     # "curve_counts": held-out whole curves run the complete-data stream (no counts read)
     import ctypes as _C
     _b = _C.c_double()
     model._ctx.call("btf_get_accum_bytes_per_cell", _C.byref(_b))
@@ -464,53 +475,29 @@ def main():
     ms_step = 1e3 * dt / args.steps
     kernels_us = {k: round(1e3 * v[0] / max(v[1], 1), 2) for k, v in kt.items() if v[1] > 0}
     sampler = model.v_sampler()
-    out = {
-        "metric": metric_for(args.config, world),
-        "value": round(value, 2),
-        "unit": "sweeps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak" if (weak or world == 1) else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic" + (" (SURVEY 8(d): legacy np.random.seed(1) stream)" if legacy_data else " (per-row / per-block streams: rank slabs)"),
-        "config": {"workload": "%s_btf %s (%d,%d,%d,%d) nembeds=%d tf_order=2 %s data, W+V update, rng=device%s"
-                               % ({"binomial": "binomial", "negbinom": "negbinom"}.get(args.variant, "gaussian"), args.config, N, M, T,
-                                  {"binomial": 1}.get(args.variant, R), K, args.variant + (" (4 trials per cell)" if args.variant == "binomial" else ""),
-                                  "; %d-way row/column shards, %s all-gather of W and V" % (
-                                      world, {"rccl": "RCCL", "peer": "peer-window", "host": "host-staged"}.get(model._exchange.transport, "?"))
-                                  if world > 1 else ""),
-                   "global_sweeps_per_s": round(sweeps_per_s, 2), "units_per_sweep": units,
-                   "median_ms_per_step": round(float(np.median(per_step_ms)), 4), "median_over_steps": int(nmed),
-                   "burn_in_sweeps": args.burn,
-                   "full_resample_sweeps_per_s": None if full_per_s is None else round(full_per_s, 2),
-                   "step_loop": "C side (btf_wv_steps: one call queues the K steps)" if c_driven else "Python (one _resample_W / _resample_V call pair per step)",
-                   "python_driven_sweeps_per_s": None if py_per_s is None else round(py_per_s, 2),
-                   "v_sampler": sampler, "banded_sweeps_per_s": None if banded_per_s is None else round(banded_per_s, 2),
-                   "likelihood_form": form,
-                   "launches_per_step": 4 - int(v_fused) - int(w_fused),
-                   # what pins the mode this line times: the device-RNG chain is checked statistically, the
-                   # reference-reproducible chain (rng="host", legacy numpy stream) bit-level against the reference's fixtures
-                   "parity_of_this_mode": "rng=device (Philox normals, %s square root): statistical - whitening, KS / Anderson-Darling, "
-                                          "moment and conditional-mean tests at this size (tests/test_gpu_fullsize.py); the same kernels under "
-                                          "rng=host reproduce the reference's fixtures to 1e-10 (W) / 1e-6 (V) (tests/golden, G1-G9)" % sampler,
-                   "parallelism": "rows(W)/cols(V) x%d" % world},
-        "roofline": {"bound": "hbm", "kernel": "accum_kernel (%s)" % (" + ".join(plain) + " launches" if len(plain) == 2 else
-                                                                       plain[0] + " launch; the other accumulation launch carries its "
-                                                                       "sampler / solve as a fused tail: kernels_us." +
-                                                                       ("v_accum" if v_fused else "w_accum") + " = stream + tail"),
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": None, "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": round(acc_us, 2),
-                     "timing": "hipExtLaunchKernelGGL start/stop events of each accumulation dispatch, %d steps (median of five block averages)" % nprof,
-                     "whole_step_bytes": b_wv,
-                     "whole_step_frac": round(b_wv / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                     "copy_ceiling_GBs": copy_ceiling(torch), "read_ceiling_GBs": read_ceiling(local_rank)},
-        "kernels_us": kernels_us,
-    }
+    out["config"].update({
+        "median_ms_per_step": round(float(np.median(per_step_ms)), 4), "median_over_steps": int(nmed),
+        "full_resample_sweeps_per_s": None if full_per_s is None else round(full_per_s, 2),
+        "python_driven_sweeps_per_s": None if py_per_s is None else round(py_per_s, 2),
+        "banded_sweeps_per_s": None if banded_per_s is None else round(banded_per_s, 2),
+        "launches_per_step": 4 - int(v_fused) - int(w_fused),
+        # what pins the mode this line times: the device-RNG chain is checked statistically, the
+        # reference-reproducible chain (rng="host", legacy numpy stream) bit-level against the reference's fixtures
+        "parity_of_this_mode": "rng=device (Philox normals, %s square root): statistical - whitening, KS / Anderson-Darling, "
+                               "moment and conditional-mean tests at this size (tests/test_gpu_fullsize.py); the same kernels under "
+                               "rng=host reproduce the reference's fixtures to 1e-10 (W) / 1e-6 (V) (tests/golden, G1-G9)" % sampler})
+    out["roofline"] = {"bound": "hbm", "kernel": "accum_kernel (%s)" % (" + ".join(plain) + " launches" if len(plain) == 2 else
+                                                                        plain[0] + " launch; the other accumulation launch carries its "
+                                                                        "sampler / solve as a fused tail: kernels_us." +
+                                                                        ("v_accum" if v_fused else "w_accum") + " = stream + tail"),
+                       "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 4),
+                       "traffic": None, "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": round(acc_us, 2),
+                       "timing": "hipExtLaunchKernelGGL start/stop events of each accumulation dispatch, %d steps (median of five block averages)" % nprof,
+                       "whole_step_bytes": b_wv,
+                       "whole_step_frac": round(b_wv / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                       "copy_ceiling_GBs": copy_ceiling(torch), "read_ceiling_GBs": read_ceiling(local_rank)}
+    out["kernels_us"] = kernels_us
     if host_rng is not None:
         out["host_rng"] = host_rng
     # ---- the roofline object against the committed profiles of THIS workload (profiles/README.md) --------------------------
@@ -547,14 +534,10 @@ def main():
                                 "avg_launch_us": va, "algorithmic_bytes": bpc * cells_local_v,
                                 "frac": round(bpc * cells_local_v / (va * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                                 "timing": "live HIP events"}
-    if args.variant in ("binomial", "negbinom"):
-        out["config"]["pg_sampler"] = getattr(model, "pg_sampler", "series")
     if world > 1 or exercise:
         # the data-path collectives are the library's own RCCL calls (btf_allgather_W / _V on the context's communicator);
         # torch.distributed carried the communicator id, the barrier and the max over ranks of the clock
-        out["config"].update({"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(),
-                              "exchange_transport": model._exchange.transport,
-                              "communicator": model._exchange.comm_info() if model._exchange.transport in ("rccl", "peer") else None,
+        out["config"].update({"communicator": model._exchange.comm_info() if model._exchange.transport in ("rccl", "peer") else None,
                               "collective_us": coll})
     if as_rank:
         # What ONE rank of a P-GPU run does per step, measured on one GPU: its kernels on its real slabs and the RCCL call
@@ -563,8 +546,6 @@ def main():
         # and assumes the ranks stay in step.  A rehearsal, not a measurement of P GPUs.
         ref = same_config_one_gpu(args.config, "complete")
         step_us = 1e3 * ms_step
-        out["config"]["workload"] += "; REHEARSAL of rank %d of %d on one GPU (row slab %d x %d, column slab %d x %d)" % (
-            as_rank[0], as_rank[1], plan.nl, M, N, plan.ml)
         out["projected"] = {"what": "rank %d of %d: W+V step with both all-gathers (btf_allgather_W / _V on a one-rank RCCL communicator of the context, full message sizes)" % as_rank,
                             "communicator": model._exchange.comm_info(),
                             "ranks": as_rank[1], "per_rank_step_us": round(step_us, 1),
@@ -581,7 +562,7 @@ def main():
         if ref is not None:
             ref["note"] = "builder-run committed figure of the SAME workload on one MI355X; the driver's --gpus 1 run is the C3 headline, another workload"
             out["config"]["one_gpu_same_workload"] = ref
-            out["config"]["speedup_vs_one_gpu_same_workload"] = round(sweeps_per_s / ref["value"], 3) if not weak else None
+            out["config"]["speedup_vs_one_gpu_same_workload"] = round(args.steps / dt / ref["value"], 3) if not weak else None
     if world == 1 and not as_rank and not args.no_cpu and not args.lean and args.variant not in ("binomial", "negbinom"):
         out["cpu_baseline"] = cpu_baseline(Y, model, cfg)
     if world == 1 and not as_rank and not args.no_cpu and not args.lean and args.variant == "binomial":
@@ -607,9 +588,55 @@ def main():
             out["config"]["c4_binomial"] = c4_leg(N, M, T, K, Vt, local_rank, stream, fence, torch)
         except Exception as e:         # pragma: no cover  (never let the extra leg cost the headline line)
             out["config"]["c4_binomial"] = {"error": repr(e)}
+    finish(out, rank, world > 1 or exercise, dist)
+
+
+def headline(args, world, weak, dt, legacy_data, shape, model, c_driven, as_rank, plan):
+    """The result line of a plain run: the contract fields of the K timed steps and a `config` block that the model answers
+    from what it holds (no run of its own).  --full adds its figures to this dict."""
+    N, M, T, R, K = shape
+    sweeps_per_s = args.steps / dt
+    units = world if weak else 1
+    out = {
+        "metric": metric_for(args.config, world),
+        "value": round(sweeps_per_s * units, 2),
+        "unit": "sweeps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak" if (weak or world == 1) else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic" + (" (SURVEY 8(d): legacy np.random.seed(1) stream)" if legacy_data else " (per-row / per-block streams: rank slabs)"),
+        "config": {"workload": "%s_btf %s (%d,%d,%d,%d) nembeds=%d tf_order=2 %s data, W+V update, rng=device%s"
+                               % ({"binomial": "binomial", "negbinom": "negbinom"}.get(args.variant, "gaussian"), args.config, N, M, T,
+                                  {"binomial": 1}.get(args.variant, R), K, args.variant + (" (4 trials per cell)" if args.variant == "binomial" else ""),
+                                  "; %d-way row/column shards, %s all-gather of W and V" % (
+                                      world, {"rccl": "RCCL", "peer": "peer-window", "host": "host-staged"}.get(model._exchange.transport, "?"))
+                                  if world > 1 else ""),
+                   "global_sweeps_per_s": round(sweeps_per_s, 2), "units_per_sweep": units,
+                   "burn_in_sweeps": args.burn,
+                   "step_loop": "C side (btf_wv_steps: one call queues the K steps)" if c_driven else "Python (one _resample_W / _resample_V call pair per step)",
+                   "v_sampler": model.v_sampler(),
+                   # "curve_counts": held-out whole curves run the complete-data stream (no counts read)
+                   "likelihood_form": model.likelihood_form(),
+                   "parallelism": "rows(W)/cols(V) x%d" % world},
+    }
+    if as_rank:
+        out["config"]["workload"] += "; REHEARSAL of rank %d of %d on one GPU (row slab %d x %d, column slab %d x %d)" % (
+            as_rank[0], as_rank[1], plan.nl, M, N, plan.ml)
+    if args.variant in ("binomial", "negbinom"):
+        out["config"]["pg_sampler"] = getattr(model, "pg_sampler", "series")
+    return out
+
+
+def finish(out, rank, grouped, dist):
+    """Rank 0 prints the one JSON line; with a process group every rank leaves it together."""
     if rank == 0:
         print(json.dumps(out))
-    if world > 1 or exercise:
+    if grouped:
         dist.barrier()
         dist.destroy_process_group()
 

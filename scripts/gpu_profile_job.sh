@@ -8,7 +8,7 @@ TAG=${1:-r03}; CFG=${2:-c3}; VAR=${3:-complete}; STEPS=${4:-100}
 NAME=${TAG}_${CFG}_${VAR}${SUFFIX:-}
 export PYTHONUNBUFFERED=1
 cd /tmp && export TMPDIR=/tmp
-ARGS="--config $CFG --variant $VAR --no-cpu ${EXTRA:-}"
+ARGS="--full --config $CFG --variant $VAR --no-cpu ${EXTRA:-}"
 PARGS="$ARGS --no-c4"      # profiled passes: this variant's kernels only (the default run's short C4 leg stays out)
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$NAME -o $NAME --output-format csv -- python3 $R/bench.py $PARGS --steps $STEPS --warmup 10 > $R/gpurun_out/prof_$NAME.log 2>&1 || exit 1
 echo "stats pass done"

@@ -189,6 +189,35 @@ def test_bench_dump_outputs_writes_float64_arrays_within_the_cap(tmp_path, monke
     assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 4096 + 3 * 128
 
 
+def test_bench_plain_line_is_the_headline_alone():
+    """A plain bench.py run prints the contract fields of its timed steps and a config block the model answers without a
+    run; the figures that take runs of their own (roofline, kernels_us, cpu_baseline, the extra legs) need --full."""
+    import bench
+
+    class Model:
+        class _exchange:
+            transport = None
+
+        def v_sampler(self):
+            return "spectral"
+
+        def likelihood_form(self):
+            return "complete"
+
+    args = bench.parse_args(["--steps", "400", "--warmup", "7"])
+    assert not args.full and bench.parse_args(["--full"]).full
+    args.config = "c3"
+    c = bench.CONFIGS["c3"]
+    d = bench.headline(args, 1, False, 0.02, True, (c["N"], c["M"], c["T"], c["R"], c["K"]), Model(), True, None, None)
+    assert d["metric"] == bench.METRIC and d["unit"] == "sweeps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] == 20000.0 and d["ms_per_step"] == 0.05 and d["steps"] == 400 and d["warmup"] == 7
+    assert d["config"]["v_sampler"] == "spectral" and "(512,256,64,4) nembeds=5" in d["config"]["workload"]
+    for k in ("roofline", "kernels_us", "cpu_baseline", "host_rng", "projected"):
+        assert k not in d
+    for k in ("median_ms_per_step", "full_resample_sweeps_per_s", "banded_sweeps_per_s", "c4_binomial"):
+        assert k not in d["config"]
+
+
 def test_shard_plan_finds_the_one_halo_source_and_appends_it_to_the_slabs():
     """compat="reference" sharded (btf_set_shard_halo): per contiguous block at most one stale-weight source row and one
     source column lie outside it; ShardPlan.halo_of finds them from the reference's source patterns (factor.py:320,349 and
