@@ -9,5 +9,5 @@ hand-written HIP kernels for gfx950 behind the C ABI in ``include/btf.h``.
 Module names mirror the reference package (``factor``, ``genlasso``,
 ``fast_mvn``, ``utils``) so user scripts only change the import root.
 """
-__all__ = ["factor", "genlasso", "fast_mvn", "utils", "nmf", "likelihoods"]
+__all__ = ["factor", "genlasso", "fast_mvn", "utils", "nmf", "likelihoods", "diagnostics"]
 __version__ = "0.1.0"

@@ -11,6 +11,7 @@
 #include "btf_gass_ep.h"
 #include "btf_gamma_grid.h"    // the gamma-grid likelihood (instances in btf_gamma_grid.hip)
 #include "btf_fused.h"
+#include "btf_diag.h"         // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
@@ -3757,6 +3758,81 @@ int btf_posterior_summary(int device, int nsamples, int nrows, int ncols, int nd
   PS(hipMemcpy(mean_out, dm, cellsN * sizeof(double), hipMemcpyDeviceToHost));
   if (nq) PS(hipMemcpy(q_out, dqo, (size_t)nq * cellsN * sizeof(double), hipMemcpyDeviceToHost));
 #undef PS
+  cleanup();
+  return BTF_OK;
+}
+
+// ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)
+int btf_diag_eval(int device, int nchains, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* const* Ws,
+                  const double* const* Vs, btf_ctx* const* ctxs, int transform, double* out) {
+  if (nchains < 1 || nchains > DIAG_MAX_CHAINS || nsamples < 4 || (long long)nchains * nsamples > DIAG_MAX_DRAWS || nrows < 1 ||
+      ncols < 1 || ndepth < 1 || nembeds < 1 || nembeds > MAX_K || transform < 0 || transform > 2 || !out ||
+      (long long)nrows * ncols * ndepth > 0x7fffffffLL)
+    return fail(nullptr, BTF_EINVAL, "bad btf_diag_eval arguments");
+  for (int c = 0; c < nchains; ++c) {
+    const btf_ctx* x = ctxs ? ctxs[c] : nullptr;
+    if (x) {
+      if (x->dev != device || x->N != nrows || x->M != ncols || x->T != ndepth || x->K != nembeds)
+        return fail(nullptr, BTF_EINVAL, "btf_diag_eval: a context of another device or shape");
+      if (x->nl != x->N || x->ml != x->M) return fail(nullptr, BTF_ESTATE, "btf_diag_eval needs unsharded contexts");
+      if (!x->smp_W || !x->smp_V || nsamples > x->smp_n) return fail(nullptr, BTF_ESTATE, "btf_diag_eval: not that many collected samples");
+    } else if (!Ws || !Vs || !Ws[c] || !Vs[c]) {
+      return fail(nullptr, BTF_EINVAL, "btf_diag_eval: chain without host arrays or a context");
+    }
+  }
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  const int MT = ncols * ndepth;
+  const size_t cells = (size_t)nrows * MT;
+  const size_t nW = (size_t)nsamples * nrows * nembeds, nV = (size_t)nsamples * MT * nembeds;
+  std::vector<double*> up;                                 // uploaded chains
+  std::vector<const double*> pw(nchains), pv(nchains);
+  const double** dpw = nullptr; const double** dpv = nullptr;
+  double* dout = nullptr;
+  auto cleanup = [&]() {
+    for (double* p : up) (void)hipFree(p);
+    for (void* p : {(void*)dpw, (void*)dpv, (void*)dout}) if (p) (void)hipFree(p);
+  };
+#define DG(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+  for (int c = 0; c < nchains; ++c) {
+    const btf_ctx* x = ctxs ? ctxs[c] : nullptr;
+    if (x) {                                               // the collection copies may still be in flight on its stream
+      DG(hipStreamSynchronize(x->stream));
+      pw[c] = x->smp_W; pv[c] = x->smp_V;
+    } else {
+      double *dW = nullptr, *dV = nullptr;
+      DG(hipMalloc((void**)&dW, nW * sizeof(double)));
+      up.push_back(dW);
+      DG(hipMalloc((void**)&dV, nV * sizeof(double)));
+      up.push_back(dV);
+      DG(hipMemcpy(dW, Ws[c], nW * sizeof(double), hipMemcpyHostToDevice));
+      DG(hipMemcpy(dV, Vs[c], nV * sizeof(double), hipMemcpyHostToDevice));
+      pw[c] = dW; pv[c] = dV;
+    }
+  }
+  DG(hipMalloc((void**)&dpw, nchains * sizeof(double*)));
+  DG(hipMalloc((void**)&dpv, nchains * sizeof(double*)));
+  DG(hipMalloc((void**)&dout, DIAG_OUT * cells * sizeof(double)));
+  DG(hipMemcpy(dpw, pw.data(), nchains * sizeof(double*), hipMemcpyHostToDevice));
+  DG(hipMemcpy(dpv, pv.data(), nchains * sizeof(double*), hipMemcpyHostToDevice));
+  int P = 2;
+  while (P < nchains * nsamples) P <<= 1;
+  DiagArgs a{dpw, dpv, nchains, nsamples, nrows, MT, P, transform, dout};
+  const size_t lds = (size_t)(nchains * nsamples + P) * sizeof(double);
+#define DG_LAUNCH(KT_)                                                                                             \
+  case KT_: {                                                                                                      \
+    DG(hipFuncSetAttribute((const void*)diag_kernel<KT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
+    hipLaunchKernelGGL(diag_kernel<KT_>, dim3((unsigned)cells), dim3(DIAG_THREADS), lds, 0, a);                   \
+  } break;
+  switch (nembeds) {
+    DG_LAUNCH(1) DG_LAUNCH(2) DG_LAUNCH(3) DG_LAUNCH(4) DG_LAUNCH(5) DG_LAUNCH(6) DG_LAUNCH(7) DG_LAUNCH(8) DG_LAUNCH(9) DG_LAUNCH(10)
+    default: break;
+  }
+#undef DG_LAUNCH
+  DG(hipGetLastError());
+  DG(hipDeviceSynchronize());
+  DG(hipMemcpy(out, dout, DIAG_OUT * cells * sizeof(double), hipMemcpyDeviceToHost));
+#undef DG
   cleanup();
   return BTF_OK;
 }

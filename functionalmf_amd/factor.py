@@ -681,6 +681,12 @@ class BayesianTensorFiltering(_BayesianModel):
         self._ctx.call("btf_collect_summary", int(n), code, _native.dptr(qs), len(qs), _native.dptr(mean), _native.dptr(quant))
         return mean, quant
 
+    def convergence_diagnostics(self, *others, transform=None):
+        """Split R-hat, bulk / tail ESS and MCSE per cell of f(W V') over this model's device-collected samples and
+        those of `others` (models or run_gibbs result dicts): functionalmf_amd.diagnostics.convergence([self, *others])."""
+        from . import diagnostics
+        return diagnostics.convergence([self] + list(others), transform=transform)
+
     # ---- model selection: per-curve log-likelihood, WAIC, DIC (functionalmf_amd/criteria.py, csrc/btf_criteria.h) ----
     def _crit_family(self):
         """(family of btf_crit_eval, its parameter, per-sample noise?) of this model's likelihood."""

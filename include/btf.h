@@ -576,6 +576,16 @@ int btf_posterior_summary(int device, int nsamples, int nrows, int ncols, int nd
                           const double* Ws, const double* Vs, int transform, const double* q, int nq,
                           double* mean_out, double* q_out);
 
+/* ---- convergence diagnostics (csrc/btf_diag.h) ----------------------------------------------------------------------
+ * Split R-hat (rank-normalised, max of bulk and folded), bulk ESS, tail ESS (min over the 5 % / 95 % indicators), MCSE of
+ * the mean and the mean, per cell of f(W V') over nchains chains of nsamples draws (Vehtari et al. 2021; one chain: its
+ * two halves).  Chain c is ctxs[c]'s first nsamples collected samples (btf_collect_*, read where they lie, same device and
+ * shape, unsharded) when ctxs && ctxs[c], else the host arrays Ws[c] (S,N,K) / Vs[c] (S,M,T,K), uploaded.  transform as
+ * btf_posterior_summary; out (5,N,M,T): rhat, ess_bulk, ess_tail, mcse_mean, mean - nan for a cell whose draws are all
+ * equal or hold a non-finite value.  nsamples >= 4, nchains <= 64, nchains * nsamples <= 4096.  Synchronous.          */
+int btf_diag_eval(int device, int nchains, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* const* Ws,
+                  const double* const* Vs, btf_ctx* const* ctxs, int transform, double* out);
+
 /* ---- on-device sample collection (rng="device"; replaces the per-sample copies of
  * genlasso.py:51-65) ---------------------------------------------------------------------
  * btf_collect_begin allocates nsamples slots for W, V, Tau2 and the device-resident scalars;
