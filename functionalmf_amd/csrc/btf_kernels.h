@@ -663,16 +663,22 @@ __global__ __launch_bounds__(WAVES * WAVE) BTF_ACC_EU_ATTR(K, MODE, WAVES, FUSE)
   // MODE 2 (the stale cached weights of compat="reference"): every output that shares a source shares the source's Gram -
   // factor.py:349-357 reuses Xt / Lt for the rows >= K, :394-400 Q_likelihood until the NaN pattern changes - so the
   // K(K+1)/2 outer-product sums are accumulated only where an output IS a source (its own weights); a tile without any
-  // (all but the first at C4: every wave of a workgroup covers the tile's 128 outputs, so this is workgroup-uniform) runs
-  // the K-sum stream with the rescaled statistic, reduces one round instead of four and writes a quarter of the partials.
+  // (all but the first at C4) runs the K-sum stream with the rescaled statistic, reduces one round instead of four and
+  // writes a quarter of the partials.  gram_on is per wave: whether the wave accumulates the outer products and whether
+  // a summing thread (whose wave covers the same outputs) stores them.  The reduction's early exit needs a workgroup-
+  // uniform answer: with OPL == 2 every wave covers the tile's 128 outputs, so gram_on is one; with OPL == 1 the waves of
+  // the two halves may disagree (the first W tile with its rows 0..K-1 in half 0), so gram_any ORs them over the
+  // workgroup and the half without a source reduces (and stores) zeros nobody reads.
   // The consumers read a dependent output's Gram at its source's column (WSolveArgs.gsrc / VBandArgs.gsrc): the same
   // sums in the same order, accumulated once.
-  bool gram_on = true;
+  bool gram_on = true, gram_any = true;
   if constexpr (MODE == 2) {
     s0 = srcmap[col];
     if constexpr (OPL == 2) s1 = srcmap[col + 1];
     const bool own = s0 == (int)col || (OPL == 2 && s1 == (int)col + 1);
     gram_on = __builtin_amdgcn_readfirstlane(__any(own) ? 1 : 0) != 0;
+    if constexpr (OPL == 1) gram_any = __syncthreads_or(own ? 1 : 0) != 0;
+    else gram_any = gram_on;
   }
   // ... and how the source's weight of a row is fetched (wave-uniform choice, made once): 1 - every output of the wave has
   // the SAME source (the W half-sweep: row K-1 for all later rows): one scalar load per row; 2 - the lane's two outputs have
@@ -933,8 +939,8 @@ __global__ __launch_bounds__(WAVES * WAVE) BTF_ACC_EU_ATTR(K, MODE, WAVES, FUSE)
 #pragma unroll
   for (int g = 0; g < NV; g += ACC_RG) {
     // (MODE 2 without a source output in the tile: the Gram slots were never accumulated and nobody reads them here - rounds
-    //  that hold nothing but Gram values are skipped, uniformly)
-    if (MODE == 2 && !gram_on && g >= K) break;
+    //  that hold nothing but Gram values are skipped by the whole workgroup: gram_any, never the per-wave gram_on)
+    if (MODE == 2 && !gram_any && g >= K) break;
 #pragma unroll
     for (int v = 0; v < ACC_RG; ++v) {
       if (g + v < NV) {

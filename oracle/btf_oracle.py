@@ -236,12 +236,12 @@ def mvn_from_precision_spectral(Q, K, T, mu_part=None, z=None, force_psd=True, e
 # W half-sweep                       (factor.py:313-362)
 # --------------------------------------------------------------------------
 
-def w_step(st, Y, z=None, row0=0):
+def w_step(st, Y, z=None, row0=0, compat="reference"):
     """Row-by-row conjugate draw of W.  (row0: global index of the first row when
-    st["W"] / Y hold only a block of rows - used by the sharding tests.)  Reproduces quirk Q1: the design/factor
-    cache is refreshed only for rows < K or when the data holds any NaN
-    (factor.py:320, :349).  ``z``: optional flat array of the sum_i min(i+1,K)
-    normals, consumed in row order; else the legacy global RNG is used.
+    st["W"] / Y hold only a block of rows - used by the sharding tests.)  compat="reference" reproduces quirk Q1: the
+    design/factor cache is refreshed only for rows < K or when the data holds any NaN
+    (factor.py:320, :349); compat="exact": every row factors its own system.  ``z``: optional flat array of the
+    sum_i min(i+1,K) normals, consumed in row order; else the legacy global RNG is used.
     """
     W, V = st["W"], st["V"]
     N, K = W.shape
@@ -261,7 +261,7 @@ def w_step(st, Y, z=None, row0=0):
             c = cnt[i].reshape(-1)[keep] / nu2
         else:
             c = cnt[i].reshape(-1)[keep] / nu2[i].reshape(-1)[keep]
-        if row0 + i < K or any_nan or Xt is None:
+        if row0 + i < K or any_nan or Xt is None or compat == "exact":
             Vd = Vflat[keep][:, :d]
             Xt = (Vd * c[:, None]).T
             Q = Xt @ Vd + np.eye(d) / st["sigma2"]
@@ -534,8 +534,8 @@ def binomial_kappa(Ysucc, Ntrials, nu2):
     return (Ysucc - Ntrials / 2.0) * nu2
 
 
-def binomial_w_step(st, Ysucc, Ntrials, z=None):
-    return w_step(st, binomial_kappa(Ysucc, Ntrials, st["nu2"]), z=z)
+def binomial_w_step(st, Ysucc, Ntrials, z=None, compat="reference"):
+    return w_step(st, binomial_kappa(Ysucc, Ntrials, st["nu2"]), z=z, compat=compat)
 
 
 def binomial_v_step(st, Ysucc, Ntrials, Delta, **kw):

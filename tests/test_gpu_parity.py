@@ -2133,24 +2133,10 @@ def test_binomial_pseudo_data_bytes_and_fallback(ntrials):
     model._resample_W(data)
     model._resample_V(data)
     ost = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in dict(st, nu2=nu2).items()}
-    Yk = orc.binomial_kappa(Ys, Ntr, nu2)
-    # (compat="exact": every row / column with its own weights - the stale-weight quirks have their own fixtures)
-    W = ost["W"].copy()
-    Vf = ost["V"].reshape(-1, K)
-    zpos = 0
-    for i in range(N):
-        d = min(i + 1, K)
-        obs = ~np.isnan(Yk[i].reshape(-1))
-        c = np.where(obs, 1.0 / nu2[i].reshape(-1), 0.0)
-        y = np.where(obs, Yk[i].reshape(-1), 0.0)
-        Q = (Vf[:, :d] * c[:, None]).T @ Vf[:, :d] + np.eye(d) / ost["sigma2"]
-        m = (Vf[:, :d] * c[:, None]).T @ y
-        L = np.linalg.cholesky(Q)
-        W[i, :d] = np.linalg.solve(Q, m) + np.linalg.solve(L.T, zw[zpos:zpos + d])
-        zpos += d
-    assert relerr(model.W, W) < 1e-10
-    ost["W"] = W
-    orc.v_step(ost, Yk, orc.trend_penalty(T, tf), z=zv, compat="exact", perm=orc.perm_from_order(model.v_order(), K, T))
+    # (compat="exact": every row / column with its own weights - the stale-weight quirks: tests/test_gpu_weighted_shapes.py)
+    orc.binomial_w_step(ost, Ys, Ntr, z=zw, compat="exact")
+    assert relerr(model.W, ost["W"]) < 1e-10
+    orc.binomial_v_step(ost, Ys, Ntr, orc.trend_penalty(T, tf), z=zv, compat="exact", perm=orc.perm_from_order(model.v_order(), K, T))
     assert relerr(model.V, ost["V"]) < 1e-8
 
 

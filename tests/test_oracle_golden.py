@@ -99,6 +99,56 @@ def test_binomial_steps_given_omega(golden, tag):
         assert relerr(V, g["V_after_" + nm]) < 1e-10
 
 
+@pytest.mark.parametrize("nan", [False, True])
+def test_w_step_exact_is_the_own_weights_solve(nan):
+    """w_step(compat="exact"): every row its own normal equations, Q_i = V' C_i V + I / sigma2, m_i = V' C_i ybar_i,
+    W_i = Q_i^-1 m_i + L_i^-T z_i, C_i = cnt_i / nu2_i - against a direct dense solve; without NaN it must differ from
+    quirk Q1 (compat="reference") once the weights vary from cell to cell, with NaN the two coincide."""
+    rs = np.random.RandomState(31)
+    N, M, T, R, K = 9, 4, 5, 3, 3
+    Y = rs.normal(size=(N, M, T, R))
+    if nan:                                              # (any NaN, a missing replicate included, switches Q1 off)
+        Y[rs.rand(N, M, T, R) < 0.3] = np.nan
+        Y[2, 1, 3] = np.nan
+    nu2 = rs.gamma(2.0, 0.5, size=(N, M, T))
+    st = dict(W=rs.normal(size=(N, K)), V=rs.normal(size=(M, T, K)), sigma2=0.7, nu2=nu2)
+    z = rs.normal(size=sum(min(i + 1, K) for i in range(N)))
+    ex = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in st.items()}
+    W = orc.w_step(ex, Y, z=z, compat="exact")
+    cnt, ybar = orc.replicate_stats(Y)
+    Vf = st["V"].reshape(-1, K)
+    ref = st["W"].copy()
+    zpos = 0
+    for i in range(N):
+        d = min(i + 1, K)
+        obs = ~np.isnan(ybar[i].reshape(-1))
+        c = np.where(obs, cnt[i].reshape(-1) / nu2[i].reshape(-1), 0.0)
+        Q = (Vf[:, :d] * c[:, None]).T @ Vf[:, :d] + np.eye(d) / st["sigma2"]
+        m = (Vf[:, :d] * c[:, None]).T @ np.where(obs, ybar[i].reshape(-1), 0.0)
+        L = np.linalg.cholesky(Q)
+        ref[i, :d] = np.linalg.solve(Q, m) + np.linalg.solve(L.T, z[zpos:zpos + d])
+        zpos += d
+    assert relerr(W, ref) < 1e-12
+    rf = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in st.items()}
+    Wr = orc.w_step(rf, Y, z=z)
+    if nan:
+        assert relerr(Wr, ref) < 1e-12
+    else:
+        assert relerr(Wr[:K], ref[:K]) < 1e-12 and relerr(Wr, ref) > 1e-4
+
+
+def test_w_step_reference_keyword_keeps_quirk_q1(golden):
+    """compat="reference" spelled out is the default: g4_binomial_full (no NaN, rows >= K on row K-1's omega)."""
+    g = golden("g4_binomial_full.npz")
+    st = state_from(g, "s0_")
+    assert not np.isnan(g["Ysucc"]).any()
+    W = orc.binomial_w_step(st, g["Ysucc"], g["Ntrials"], z=g["z_W"], compat="reference")
+    assert relerr(W, g["W_after"]) < 1e-11
+    st = state_from(g, "s0_")
+    W = orc.binomial_w_step(st, g["Ysucc"], g["Ntrials"], z=g["z_W"], compat="exact")
+    assert relerr(W, g["W_after"]) > 1e-3
+
+
 def test_jitter_retry(golden):
     g = golden("g5_illcond.npz")
     N, M, T, R, K, tf = g["dims"]
