@@ -16,7 +16,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")   # override: A/B builds
 SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip"),
-           os.path.join(CSRC, "btf_gass_ep.hip"), os.path.join(CSRC, "btf_gamma_grid.hip"), os.path.join(CSRC, "btf_diag.hip")]
+           os.path.join(CSRC, "btf_gass_ep.hip"), os.path.join(CSRC, "btf_gamma_grid.hip"), os.path.join(CSRC, "btf_diag.hip"),
+           os.path.join(CSRC, "btf_predict.hip")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -29,6 +30,7 @@ PEER_DESC_BYTES = 256             # BTF_PEER_DESC_BYTES
 OPT_SAMPLER, OPT_NB_HISTOGRAMS, OPT_FUSE_GRAM, OPT_PG_EXACT, OPT_CURVE_COUNTS, OPT_SPLIT_ACCUM, OPT_FUSED_SWEEP, OPT_FUSED_STEP, OPT_FUSED_DATAFLOW = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ESS_HOST_LIKELIHOOD = -1          # BTF_ESS_HOST_LIKELIHOOD of include/btf.h
 CRIT_NOISE_PER_SAMPLE, CRIT_CURRENT = 1, 2   # BTF_CRIT_* flags of btf_crit_eval
+PRED_AUX_PER_SAMPLE, PRED_AUX_ROWS, PRED_AUX_COLS, PRED_AUX_DEPTH = 1, 2, 4, 8   # BTF_PRED_AUX_* flags of btf_predict_eval
 SAMPLERS = {"banded": 0, "spectral": 1, "chain": 2, "generic": 3, "banded_nopanel": 4}
 
 # every symbol include/btf.h declares: (name, restype, argtypes)
@@ -94,6 +96,9 @@ SIGNATURES = {
     "btf_collect_summary": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),
     "btf_crit_set_data": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
     "btf_crit_eval": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "btf_predict_batch": (C.c_int, [C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_uint64, _c_dp]),
+    "btf_predict_eval": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, C.c_int,
+                                   C.c_uint64, _c_dp, C.c_int, _c_ip, C.c_int] + [_c_dp] * 11),
     "btf_nmf_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp,
                                  C.POINTER(C.c_uint8), C.c_double]),
     "btf_nmf_run": (C.c_int, [C.c_void_p, _c_dp, _c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _c_ip, _c_dp,
@@ -193,6 +198,7 @@ def build(force=False, verbose=False, jobs=None):
     units = [(SOURCES[0], os.path.join(OBJ_DIR, tag + "_abi.o"), []), (SOURCES[1], os.path.join(OBJ_DIR, tag + "_crit.o"), [])]
     units += [(SOURCES[2], os.path.join(OBJ_DIR, tag + "_nmf.o"), []), (SOURCES[3], os.path.join(OBJ_DIR, tag + "_gass_ep.o"), [])]
     units += [(SOURCES[4], os.path.join(OBJ_DIR, tag + "_gamma_grid.o"), []), (SOURCES[5], os.path.join(OBJ_DIR, tag + "_diag.o"), [])]
+    units += [(SOURCES[6], os.path.join(OBJ_DIR, tag + "_predict.o"), [])]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

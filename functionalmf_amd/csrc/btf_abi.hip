@@ -13,6 +13,7 @@
 #include "btf_fused.h"
 #include "btf_diag.h"         // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
+#include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
 #include <hip/hip_ext.h>
@@ -3468,6 +3469,152 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
   CE(hipStreamSynchronize(c->stream));        // (not check_status: the sampler's status word is not this call's)
 #undef CE
 #undef CA
+  cleanup();
+  return BTF_OK;
+}
+
+// ---------------------------------------------------------- posterior predictive (btf_predict.h)
+int btf_predict_batch(int device, int family, int64_t n, const double* eta, const double* aux, uint64_t seed, double* out) {
+  if (family < 0 || family >= PRED_FAM_COUNT || n < 1 || !eta || !aux || !out) return fail(nullptr, BTF_EINVAL, "bad predict_batch arguments");
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  double *de = nullptr, *da = nullptr, *dout = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)de, (void*)da, (void*)dout}) if (p) (void)hipFree(p); };
+#define PB(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+  PB(hipMalloc((void**)&de, n * sizeof(double)));
+  PB(hipMalloc((void**)&da, n * sizeof(double)));
+  PB(hipMalloc((void**)&dout, n * sizeof(double)));
+  PB(hipMemcpy(de, eta, n * sizeof(double), hipMemcpyHostToDevice));
+  PB(hipMemcpy(da, aux, n * sizeof(double), hipMemcpyHostToDevice));
+  const dim3 grid((unsigned)((n + PRED_THREADS - 1) / PRED_THREADS)), block(PRED_THREADS);
+  switch (family) {
+    case 0: hipLaunchKernelGGL(pred_batch_kernel<0>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
+    case 1: hipLaunchKernelGGL(pred_batch_kernel<1>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
+    case 2: hipLaunchKernelGGL(pred_batch_kernel<2>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
+    case 3: hipLaunchKernelGGL(pred_batch_kernel<3>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
+    default: hipLaunchKernelGGL(pred_batch_kernel<4>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
+  }
+  PB(hipGetLastError());
+  PB(hipDeviceSynchronize());
+  PB(hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost));
+#undef PB
+  cleanup();
+  return BTF_OK;
+}
+
+int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                     const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps,
+                     int draws_per_sample, uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
+                     double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out, double* pit_hi_out,
+                     double* inside_out, double* nobs_out, double* rmse_out, double* mae_out, double* draws_out) {
+  if (!c || family < 0 || family >= PRED_FAM_COUNT || nsamples < 1 || draws_per_sample < 1 || (!Ws) != (!Vs) || nq < 0 ||
+      (nq > 0 && !q) || (q_out && nq < 1) || ncells < 0 || (ncells > 0 && (!cells || !draws_out)) || (Y && nreps < 1) ||
+      (aux_flags & ~(BTF_PRED_AUX_PER_SAMPLE | BTF_PRED_AUX_ROWS | BTF_PRED_AUX_COLS | BTF_PRED_AUX_DEPTH)))
+    return fail(c, BTF_EINVAL, "bad btf_predict_eval arguments");
+  if (!Y && (pit_lo_out || pit_hi_out || inside_out || nobs_out || rmse_out || mae_out))
+    return fail(c, BTF_EINVAL, "btf_predict_eval: pit / inside / nobs / rmse / mae compare with observations: pass Y");
+  if ((long long)nsamples * draws_per_sample > PRED_MAX_DRAWS)
+    return fail(c, BTF_EINVAL, "btf_predict_eval: nsamples * draws_per_sample = " + std::to_string((long long)nsamples * draws_per_sample) +
+                " exceeds 16384 (the draws of a cell are sorted in LDS)");
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_predict_eval needs an unsharded context");
+  if (!Ws && (!c->smp_W || nsamples > c->smp_n)) return fail(c, BTF_ESTATE, "btf_predict_eval: not that many collected samples");
+  const bool per_sample = (aux_flags & BTF_PRED_AUX_PER_SAMPLE) != 0;
+  const bool needs_par = family == PRED_FAM_GAUSSIAN || family == PRED_FAM_NEGBIN;
+  if (per_sample && !needs_par) return fail(c, BTF_EINVAL, "per-sample parameters are the Gaussian (variance) and Negative-Binomial (rate) families'");
+  if (per_sample && !aux_sample && (Ws || family != PRED_FAM_GAUSSIAN))
+    return fail(c, BTF_EINVAL, "per-sample parameters of uploaded states (and every Negative-Binomial rate): pass aux_sample");
+  if (!per_sample && needs_par && !(param > 0.0))
+    return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
+  for (int k = 0; k < nq; ++k)
+    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
+  const int S = nsamples, R = draws_per_sample, N = c->N, M = c->M, T = c->T, K = c->K, MT = M * T, n = S * R;
+  const size_t ncell = (size_t)N * MT;
+  if (ncell > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: more than 2^31 - 1 cells");
+  for (int k = 0; k < ncells; ++k)
+    if (cells[k] < 0 || (size_t)cells[k] >= ncell) return fail(c, BTF_EINVAL, "btf_predict_eval: cell index out of range");
+  HIPCHK(c, hipSetDevice(c->dev));
+  PredArgs a{};
+  a.aux_n0 = a.aux_n1 = a.aux_n2 = 1;
+  if (per_sample && family == PRED_FAM_NEGBIN) {
+    a.aux_n0 = (aux_flags & BTF_PRED_AUX_ROWS) ? N : 1; a.aux_n1 = (aux_flags & BTF_PRED_AUX_COLS) ? M : 1; a.aux_n2 = (aux_flags & BTF_PRED_AUX_DEPTH) ? T : 1;
+  }
+  const size_t naux = (size_t)a.aux_n0 * a.aux_n1 * a.aux_n2;
+  int P = 2;
+  while (P < n) P <<= 1;
+  const int wcells = std::max(1, std::min(16, (int)((64 * 1024) / ((size_t)P * sizeof(double)))));
+  const size_t lds = (size_t)wcells * P * sizeof(double);
+  const size_t nblk = (size_t)N * ((MT + wcells - 1) / wcells);
+  if (nblk > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: too many workgroups for one launch");
+  const int chunks = (int)((ncell + PRED_SCORE_CELLS - 1) / PRED_SCORE_CELLS);
+  const bool score = rmse_out || mae_out;
+  double *dW = nullptr, *dV = nullptr, *daux = nullptr, *dtr = nullptr, *dY = nullptr, *dq = nullptr, *dmean = nullptr, *dym = nullptr,
+         *dyv = nullptr, *dqo = nullptr, *dpl = nullptr, *dph = nullptr, *din = nullptr, *dno = nullptr, *ddr = nullptr, *dpart = nullptr,
+         *dsc = nullptr;
+  int* dlist = nullptr;
+  auto cleanup = [&]() {
+    for (double* p : {dW, dV, daux, dtr, dY, dq, dmean, dym, dyv, dqo, dpl, dph, din, dno, ddr, dpart, dsc}) if (p) (void)hipFree(p);
+    if (dlist) (void)hipFree(dlist);
+  };
+#define PE(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+#define PA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) { cleanup(); return rc__; } } while (0)
+#define PUP(d, h, n) do { PA(d, (n)); PE(hipMemcpyAsync(d, h, (size_t)(n) * sizeof(double), hipMemcpyHostToDevice, c->stream)); } while (0)
+  if (Ws) {
+    PUP(dW, Ws, (size_t)S * N * K); PUP(dV, Vs, (size_t)S * MT * K);
+    a.W = dW; a.V = dV;
+  } else {
+    a.W = c->smp_W; a.V = c->smp_V;
+  }
+  a.aux = nullptr; a.aux_stride = 1;
+  if (per_sample) {
+    if (aux_sample) { PUP(daux, aux_sample, (size_t)S * naux); a.aux = daux; a.aux_stride = (long long)naux; }
+    else { a.aux = c->smp_s + HYP_NU2; a.aux_stride = HYP_COUNT; }          // the collected nu2 of every kept state
+  }
+  if (trials) { PUP(dtr, trials, ncell); a.trials = dtr; }
+  if (Y) { PUP(dY, Y, ncell * (size_t)nreps); a.Y = dY; a.nreps = nreps; }
+  if (nq) { PUP(dq, q, (size_t)nq); a.q = dq; }
+  a.nq = nq;
+  if (ncells) {
+    PA(dlist, (size_t)ncells);
+    PE(hipMemcpyAsync(dlist, cells, (size_t)ncells * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    PA(ddr, (size_t)ncells * n);
+    a.list = dlist; a.nlist = ncells; a.draws = ddr;
+  }
+  if (mean_out) { PA(dmean, ncell); a.mean = dmean; }
+  if (ymean_out) { PA(dym, ncell); a.y_mean = dym; }
+  if (yvar_out) { PA(dyv, ncell); a.y_var = dyv; }
+  if (q_out) { PA(dqo, (size_t)nq * ncell); a.quant = dqo; }
+  if (pit_lo_out) { PA(dpl, ncell); a.pit_lo = dpl; }
+  if (pit_hi_out) { PA(dph, ncell); a.pit_hi = dph; }
+  if (inside_out) { PA(din, ncell); a.inside = din; }
+  if (nobs_out) { PA(dno, ncell); a.nobs = dno; }
+  if (score) { PA(dpart, (size_t)3 * S * chunks); PA(dsc, (size_t)2 * S); a.score_part = dpart; }
+  a.par = param; a.S = S; a.R = R; a.N = N; a.M = M; a.T = T; a.K = K; a.P = P; a.cells = wcells; a.seed = seed; a.chunks = chunks;
+#define PRED_LAUNCH(F)                                                                                                      \
+  case F: {                                                                                                                 \
+    PE(hipFuncSetAttribute((const void*)pred_kernel<F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
+    hipLaunchKernelGGL(pred_kernel<F>, dim3((unsigned)nblk), dim3(PRED_THREADS), lds, c->stream, a);                        \
+    PE(hipGetLastError());                                                                                                  \
+    if (score) {                                                                                                            \
+      hipLaunchKernelGGL(pred_score_kernel<F>, dim3(chunks, S), dim3(PRED_THREADS), 0, c->stream, a);                       \
+      PE(hipGetLastError());                                                                                                \
+    }                                                                                                                       \
+  } break;
+  switch (family) { PRED_LAUNCH(0) PRED_LAUNCH(1) PRED_LAUNCH(2) PRED_LAUNCH(3) PRED_LAUNCH(4) default: break; }
+#undef PRED_LAUNCH
+  if (score) {
+    hipLaunchKernelGGL(pred_score_total_kernel, dim3((S + 255) / 256), dim3(256), 0, c->stream, (const double*)dpart, S, chunks, dsc);
+    PE(hipGetLastError());
+  }
+#define PDN(h, d, n) do { if (h) PE(hipMemcpyAsync(h, d, (size_t)(n) * sizeof(double), hipMemcpyDeviceToHost, c->stream)); } while (0)
+  PDN(mean_out, dmean, ncell); PDN(ymean_out, dym, ncell); PDN(yvar_out, dyv, ncell); PDN(q_out, dqo, (size_t)nq * ncell);
+  PDN(pit_lo_out, dpl, ncell); PDN(pit_hi_out, dph, ncell); PDN(inside_out, din, ncell); PDN(nobs_out, dno, ncell);
+  PDN(rmse_out, dsc, S); PDN(mae_out, dsc + S, S);
+  if (ncells) PDN(draws_out, ddr, (size_t)ncells * n);
+  PE(hipStreamSynchronize(c->stream));        // (not check_status: the sampler's status word is not this call's)
+#undef PDN
+#undef PUP
+#undef PA
+#undef PE
   cleanup();
   return BTF_OK;
 }

@@ -793,6 +793,74 @@ class BayesianTensorFiltering(_BayesianModel):
             noise = np.asarray(results["nu2"], dtype=float).reshape(S)
         return Ws, Vs, noise
 
+    # ---- posterior predictive: replicated observations, bands, coverage, scores (functionalmf_amd/predictive.py) ----
+    def _pred_family(self):
+        """(family of btf_predict_eval, its fixed parameter, per-sample parameter?) of this model's likelihood."""
+        return self._crit_family()
+
+    def _pred_aux(self, results, nsamples):
+        """(per-sample parameter array or None, flags) for btf_predict_eval; results None: the collected samples."""
+        if results is None:
+            return None, _native.PRED_AUX_PER_SAMPLE         # the collected nu2 of every kept state
+        if "nu2" not in results or np.size(results["nu2"]) != nsamples:
+            raise ValueError("results: nu2 must hold one variance per sample, (S,1)")
+        return np.asarray(results["nu2"], dtype=float).reshape(nsamples), _native.PRED_AUX_PER_SAMPLE
+
+    def _pred_states(self, results):
+        from . import predictive as _pred
+        try:
+            Ws, Vs = results["W"], results["V"]
+        except (KeyError, TypeError):
+            raise ValueError("results must be a run_gibbs result dict with W (S,N,K) and V (S,M,T,K)")
+        return _pred.check_states(Ws, Vs, (self.nrows, self.ncols, self.ndepth), self.nembeds)
+
+    def posterior_predictive(self, results=None, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=None, trials=None,
+                             cells=None):
+        """Posterior predictive of the observations on the GPU (csrc/btf_predict.h): for every cell (i,j,t), kept sample s
+        and r < draws_per_sample a replicated observation y_rep ~ p(y | w_i^s . v_jt^s, theta_s), reduced on the device.
+        What flutrends/benchmark.py:60-75, :129-134 and politics/benchmark.py:147-172 compute on the host.
+
+        results: a run_gibbs result dict (W, V; Gaussian: nu2; Negative-Binomial: R, else the current rate), uploaded;
+            None: the samples the last device-collecting run_gibbs left on the device (no upload).
+        data: the observations to compare with; None: the data the model is bound to (nothing, if none is bound).  Another
+            tensor of the same shape (NaN elsewhere) scores held-out observations, as information_criteria(data=).
+        q: percentiles of the draws; coverage is that of the interval [q[0], q[-1]].
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        trials: (N,M,T) Binomial trial counts for the draws; None: the N of the (Y, N) data pair (1 for Bernoulli tensors).
+        cells: flat indices or (i,j,t) triples of cells whose raw draws come back as `draws` (ncells, S * draws_per_sample).
+
+        Returns a dict: mean = mean_s E[y | theta_s]; y_mean, y_var (ddof 1) of the draws; quantiles (len(q),N,M,T); with
+        data: pit_lo / pit_hi (fraction of draws < y / <= y, averaged over the cell's observed replicates), inside and nobs
+        (observed replicates inside the interval / observed), rmse and mae (S,) of y - E[y | theta_s] over all observed y,
+        coverage = inside.sum() / nobs.sum(); nominal = (q[-1] - q[0]) / 100, nsamples, ndraws.
+        S * draws_per_sample <= 16384; unsharded models; gamma_grid and Python-callable likelihoods are not supported."""
+        from . import predictive as _pred
+        family, param, per_sample = self._pred_family()
+        if self._plan.world > 1 or self._exchange.active:
+            raise NotImplementedError("posterior predictive: unsharded models only")
+        if results is None:
+            S = getattr(self, "_collected", 0)
+            if S < 1:
+                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first), and no results= given")
+            Ws = Vs = None
+        else:
+            Ws, Vs = self._pred_states(results)
+            S = Ws.shape[0]
+        S, R = _pred.check_draws(S, draws_per_sample)
+        aux, flags = self._pred_aux(results, S) if per_sample else (None, 0)
+        if data is None:
+            data = getattr(self, "_data_ref", None)
+        Y = data
+        if isinstance(data, (tuple, list)):               # Binomial (Y, N): successes of N trials
+            Y = data[0]
+            if trials is None:
+                trials = data[1]
+        if seed is None:
+            seed = self._next_seed()
+        return _pred.evaluate(self._ctx, (self.nrows, self.ncols, self.ndepth), self.nembeds, family, S, Ws, Vs, param=param,
+                              aux=aux, aux_flags=flags, trials=trials, Y=Y, q=q, draws_per_sample=R, seed=seed, cells=cells)
+
     def logprob(self, data, reduce="sum", **state):
         """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,
         nu2=); further keys (Tau2, lam2, sigma2, ...: what the reference's DIC passes) are ignored.  reduce="sum": a
@@ -1284,6 +1352,18 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
         raise NotImplementedError("model-selection criteria for the Negative-Binomial model: its lgamma(y + R) terms depend on "
                                   "the sampled rate R at every observation (not supported yet)")
 
+    def _pred_family(self):
+        return 4, None, True                  # Negative-Binomial, logit link; the rate R of every sample
+
+    def _pred_aux(self, results, nsamples):
+        """The rate tensor of every sample: results['R'] (S,) + rate shape, else the current R for all of them."""
+        from . import predictive as _pred
+        shape = (self.nrows, self.ncols, self.ndepth)
+        if results is not None and "R" in results:
+            return _pred.rate_layout(results["R"], nsamples, shape)
+        R = np.broadcast_to(np.asarray(self.R, dtype=float), self._rate_shape())
+        return _pred.rate_layout(np.broadcast_to(R, (nsamples,) + R.shape), nsamples, shape)
+
     def _rate_shape(self):
         return tuple(1 if i in self._shared else c for i, c in enumerate((self.nrows, self.ncols, self.ndepth)))
 
@@ -1483,6 +1563,14 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         if self._link == 5:
             raise NotImplementedError("model-selection criteria (WAIC / DIC) are not available for the gamma_grid likelihood")
         return self._link, (self.likelihood_param if self._link in (3, 4) else None), False
+
+    def _pred_family(self):
+        if self._callback:
+            raise NotImplementedError("posterior predictive needs a device sampler of the likelihood: a Python-callable "
+                                      "loglikelihood says nothing about how y is drawn")
+        if self._link == 5:
+            raise NotImplementedError("posterior predictive is not available for the gamma_grid likelihood")
+        return self._crit_family()
 
     def _bind_data(self, data):
         if self._callback:           # the function's `data` is its own business (any object): nothing goes to the device

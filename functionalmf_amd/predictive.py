@@ -1,0 +1,211 @@
+"""Posterior predictive of the observations: replicated draws, bands, coverage and scores.
+
+The data-sized work - y_rep ~ p(y | theta_s) for every cell (i,j,t), kept sample s and replicate r, and its reduction to
+moments, percentiles, PIT values and interval membership - is the HIP kernel of csrc/btf_predict.h (btf_predict_eval):
+the (S,N,M,T) draws never leave the device.  This module holds the host halves around it, in plain numpy (importable
+without a GPU): the family table, the mean function E[y | eta], the argument checks, and `evaluate`, the one caller of
+the C entry point that BayesianTensorFiltering.posterior_predictive and utils.posterior_predictive share.
+
+What the reference's benchmark applications do on the host (flutrends/benchmark.py:60-75, :129-134: Gaussian draws per
+kept sample, 2.5 / 97.5 percentiles per cell in a Python loop, coverage of the held-out years; politics/benchmark.py:
+147-172: per-sample RMSE / MAE of E[y | theta_s] with Mu = R p / (1 - p) for the Negative-Binomial model).
+"""
+import numpy as np
+
+FAMILY_POISSON_LOG, FAMILY_POISSON_IDENTITY, FAMILY_LOGIT, FAMILY_GAUSSIAN, FAMILY_NEGBIN = 0, 1, 2, 3, 4
+FAMILIES = {"poisson": FAMILY_POISSON_LOG, "poisson_log": FAMILY_POISSON_LOG, "poisson_identity": FAMILY_POISSON_IDENTITY,
+            "binomial": FAMILY_LOGIT, "bernoulli": FAMILY_LOGIT, "logit": FAMILY_LOGIT,
+            "gaussian": FAMILY_GAUSSIAN, "normal": FAMILY_GAUSSIAN,
+            "negative_binomial": FAMILY_NEGBIN, "negbin": FAMILY_NEGBIN}
+MAX_DRAWS = 16384           # PRED_MAX_DRAWS of csrc/btf_predict.h: S * draws_per_sample per cell (sorted in LDS)
+POISSON_SWITCH = 10.0       # PRED_POIS_SWITCH: inversion below, transformed rejection (PTRS) from here
+BINOMIAL_SWITCH = 10.0      # PRED_BINOM_SWITCH: inversion while n min(p, 1-p) is below, BTRS from here
+ARRAY_OUTPUTS = ("mean", "y_mean", "y_var", "quantiles", "pit_lo", "pit_hi", "inside", "nobs", "rmse", "mae", "draws")
+
+
+def family_code(family):
+    """The integer family of btf_predict_eval from a name or a code."""
+    if isinstance(family, str):
+        if family not in FAMILIES:
+            raise ValueError("unknown predictive family %r (one of %s)" % (family, sorted(FAMILIES)))
+        return FAMILIES[family]
+    code = int(family)
+    if not 0 <= code <= 4:
+        raise ValueError("unknown predictive family %r" % (family,))
+    return code
+
+
+def mean_function(family, eta, aux=None):
+    """E[y | eta, aux]: eta (Gaussian); exp(eta) (Poisson, log link); eta, nan where eta <= 0 (Poisson, identity link);
+    trials * ilogit(eta) (aux = trials, default 1); r * p / (1 - p) = r * exp(eta) (Negative-Binomial, aux = the rate r)."""
+    code = family_code(family)
+    eta = np.asarray(eta, dtype=float)
+    if code == FAMILY_GAUSSIAN:
+        return eta.copy()
+    if code == FAMILY_POISSON_LOG:
+        return np.exp(eta)
+    if code == FAMILY_POISSON_IDENTITY:
+        return np.where(eta > 0, eta, np.nan)
+    if code == FAMILY_LOGIT:
+        return (1.0 if aux is None else np.asarray(aux, dtype=float)) / (1.0 + np.exp(-eta))
+    if aux is None:
+        raise ValueError("the Negative-Binomial mean needs the rate r as aux")
+    return np.asarray(aux, dtype=float) * np.exp(eta)
+
+
+def check_q(q):
+    qs = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64)
+    if qs.ndim != 1 or not np.all((qs >= 0) & (qs <= 100)):
+        raise ValueError("percentiles q must lie in [0, 100]")
+    return qs
+
+
+def check_draws(nsamples, draws_per_sample):
+    nsamples, R = int(nsamples), int(draws_per_sample)
+    if nsamples < 1:
+        raise ValueError("posterior predictive: at least one sample")
+    if R < 1:
+        raise ValueError("draws_per_sample must be >= 1")
+    if nsamples * R > MAX_DRAWS:
+        raise ValueError("posterior predictive: nsamples * draws_per_sample = %d exceeds %d (the draws of a cell are sorted "
+                         "in LDS); thin the samples or lower draws_per_sample" % (nsamples * R, MAX_DRAWS))
+    return nsamples, R
+
+
+def check_states(Ws, Vs, shape, nembeds):
+    """(Ws, Vs) as contiguous float64 (S,N,K) / (S,M,T,K) arrays matching the model."""
+    N, M, T = shape
+    Ws, Vs = np.ascontiguousarray(Ws, dtype=np.float64), np.ascontiguousarray(Vs, dtype=np.float64)
+    S = Ws.shape[0] if Ws.ndim == 3 else -1
+    if S < 1 or Ws.shape != (S, N, nembeds) or Vs.shape != (S, M, T, nembeds):
+        raise ValueError("W %r / V %r do not match (S,%d,%d) / (S,%d,%d,%d)" % (Ws.shape, Vs.shape, N, nembeds, M, T, nembeds))
+    return Ws, Vs
+
+
+def check_cells(cells, shape):
+    """Flat int32 cell indices from flat indices or (i,j,t) triples."""
+    if cells is None:
+        return None
+    c = np.asarray(cells)
+    if c.size == 0:
+        return None
+    if c.ndim == 2 and c.shape[1] == 3:
+        if np.any(c < 0) or np.any(c >= np.asarray(shape)):
+            raise ValueError("cells: (i,j,t) out of range")
+        c = np.ravel_multi_index(c.T, shape)
+    if c.ndim != 1 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("cells must be flat integer cell indices or (i,j,t) triples")
+    if np.any(c < 0) or np.any(c >= int(np.prod(shape))):
+        raise ValueError("cells: index out of range")
+    return np.ascontiguousarray(c, dtype=np.int32)
+
+
+def check_observations(Y, shape):
+    """Observations as a contiguous (N,M,T,R) array (nan = missing), or None."""
+    if Y is None:
+        return None
+    Y = np.asarray(Y, dtype=float)
+    if Y.ndim not in (3, 4) or Y.shape[:3] != tuple(shape):
+        raise ValueError("data shape %r does not match the model's %r" % (Y.shape, tuple(shape)))
+    return np.ascontiguousarray(Y[..., None] if Y.ndim == 3 else Y, dtype=np.float64)
+
+
+def check_trials(trials, shape):
+    if trials is None:
+        return None
+    t = np.asarray(trials, dtype=float)
+    if t.shape != tuple(shape):
+        raise ValueError("trials shape %r does not match the model's %r" % (t.shape, tuple(shape)))
+    return np.ascontiguousarray(t, dtype=np.float64)
+
+
+def rate_layout(R, nsamples, shape):
+    """Per-sample Negative-Binomial rates as (array (S, prod(extent)), flags): R is (S,) + a shape that broadcasts against
+    (N,M,T) with every axis either full or 1 (the model's `rdims`), or (S,) / (S,1) for one shared rate."""
+    from . import _native
+    R = np.asarray(R, dtype=float)
+    if R.ndim == 0 or R.shape[0] != nsamples:
+        raise ValueError("R must hold one rate (tensor) per sample: leading dimension %d" % nsamples)
+    tail = R.shape[1:]
+    if int(np.prod(tail, dtype=np.int64)) == 1:
+        tail = (1, 1, 1)
+    if len(tail) != 3 or any(e not in (1, full) for e, full in zip(tail, shape)):
+        raise ValueError("R %r: every axis after the first must be 1 or the model's %r" % (R.shape, tuple(shape)))
+    flags = _native.PRED_AUX_PER_SAMPLE
+    for e, bit in zip(tail, (_native.PRED_AUX_ROWS, _native.PRED_AUX_COLS, _native.PRED_AUX_DEPTH)):
+        if e > 1:
+            flags |= bit
+    return np.ascontiguousarray(R.reshape(nsamples, -1), dtype=np.float64), flags
+
+
+def evaluate(ctx, shape, nembeds, family, nsamples, Ws=None, Vs=None, param=None, aux=None, aux_flags=0, trials=None, Y=None,
+             q=(2.5, 97.5), draws_per_sample=1, seed=0, cells=None):
+    """btf_predict_eval on `ctx` (a _native.Context).  Ws / Vs None: the first `nsamples` device-collected samples.
+    aux / aux_flags: per-sample parameters (Gaussian variances (S,); rates from rate_layout).  Returns the result dict."""
+    from . import _native
+    code = family_code(family)
+    N, M, T = shape
+    S, R = check_draws(nsamples, draws_per_sample)
+    qs = check_q(q)
+    if (Ws is None) != (Vs is None):
+        raise ValueError("pass both Ws and Vs, or neither")
+    if Ws is not None:
+        Ws, Vs = check_states(Ws, Vs, shape, nembeds)
+        if Ws.shape[0] != S:
+            raise ValueError("nsamples does not match Ws")
+    Y4 = check_observations(Y, shape)
+    trials = check_trials(trials, shape)
+    cl = check_cells(cells, shape)
+    if aux is not None:
+        aux = np.ascontiguousarray(aux, dtype=np.float64)
+        if aux.shape[0] != S:
+            raise ValueError("per-sample parameters: one per sample")
+    n = S * R
+    out = {"mean": np.zeros((N, M, T)), "y_mean": np.zeros((N, M, T)), "y_var": np.zeros((N, M, T)),
+           "quantiles": np.zeros((len(qs), N, M, T))}
+    have_y = Y4 is not None
+    for k in ("pit_lo", "pit_hi", "inside", "nobs"):
+        out[k] = np.zeros((N, M, T)) if have_y else None
+    for k in ("rmse", "mae"):
+        out[k] = np.zeros(S) if have_y else None
+    out["draws"] = np.zeros((len(cl), n)) if cl is not None else None
+    dp = _native.dptr
+    ctx.call("btf_predict_eval", code, float(param if param is not None else 0.0), S, dp(Ws), dp(Vs), dp(aux), int(aux_flags),
+             dp(trials), dp(Y4), Y4.shape[3] if have_y else 0, R, int(seed) & 0xFFFFFFFFFFFFFFFF, dp(qs), len(qs),
+             cl.ctypes.data_as(_native._c_ip) if cl is not None else None, len(cl) if cl is not None else 0,
+             dp(out["mean"]), dp(out["y_mean"]), dp(out["y_var"]), dp(out["quantiles"]) if len(qs) else None, dp(out["pit_lo"]),
+             dp(out["pit_hi"]), dp(out["inside"]), dp(out["nobs"]), dp(out["rmse"]), dp(out["mae"]), dp(out["draws"]))
+    out = {k: v for k, v in out.items() if v is not None}
+    if cl is not None:
+        out["cells"] = cl
+    out.update(summarise(out.get("inside"), out.get("nobs"), qs))
+    out["nsamples"], out["ndraws"] = S, n
+    return out
+
+
+def summarise(inside, nobs, qs):
+    """coverage = observed replicates inside [q[0], q[-1]] over observed replicates (cells with nan draws left out);
+    nominal = (q[-1] - q[0]) / 100."""
+    res = {"nominal": float(qs[-1] - qs[0]) / 100.0 if len(qs) >= 2 else float("nan"), "coverage": float("nan")}
+    if inside is not None and nobs is not None and len(qs) >= 2:
+        ok = np.isfinite(inside)
+        den = float(nobs[ok].sum())
+        if den > 0:
+            res["coverage"] = float(inside[ok].sum()) / den
+    return res
+
+
+def batch(family, eta, aux, seed=0, device=0):
+    """out[i] ~ family(eta[i], aux[i]) from the device samplers (btf_predict_batch); draw i uses global draw index i.
+    aux: trials (logit), variance (Gaussian), rate r (Negative-Binomial); ignored by the Poisson families."""
+    from . import _native
+    code = family_code(family)
+    eta = np.ascontiguousarray(np.atleast_1d(eta), dtype=np.float64).ravel()
+    aux = np.ascontiguousarray(np.broadcast_to(np.asarray(aux, dtype=np.float64), eta.shape)).ravel()
+    out = np.zeros(eta.size)
+    lib = _native.load()
+    rc = lib.btf_predict_batch(int(device), code, eta.size, _native.dptr(eta), _native.dptr(aux), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                               _native.dptr(out))
+    if rc != _native.BTF_OK:
+        raise _native.BTFError(rc, lib.btf_last_error(None).decode())
+    return out

@@ -102,6 +102,42 @@ def posterior_summary(Ws, Vs, q=(5, 95), transform=None, device=0):
     return mean, quant
 
 
+def posterior_predictive(Ws, Vs, family, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=0, param=None, nu2=None, R=None,
+                         trials=None, cells=None, device=0):
+    """Posterior predictive of the observations from samples on the host, without a model: the stateless form of
+    BayesianTensorFiltering.posterior_predictive (see there for the outputs), next to posterior_summary.
+
+    Ws (S,N,K), Vs (S,M,T,K); family: "gaussian", "poisson", "poisson_identity", "binomial" or "negative_binomial".
+    Gaussian: nu2 (S,) per-sample variances, or param = one variance; Negative-Binomial: R (S,) + a shape broadcasting
+    against (N,M,T), or param = one rate; Binomial: trials (N,M,T) (default 1).  data: (N,M,T) or (N,M,T,R) observations
+    with NaN = missing, or a Binomial (Y, N) pair.  Needs ndepth >= 2 (a context is opened for the call).  No CPU fallback."""
+    from . import _native, predictive
+    Ws, Vs = np.asarray(Ws), np.asarray(Vs)
+    if Ws.ndim != 3 or Vs.ndim != 4 or Ws.shape[0] != Vs.shape[0] or Ws.shape[2] != Vs.shape[3]:
+        raise ValueError("Ws must be (S, N, K) and Vs (S, M, T, K)")
+    code = predictive.family_code(family)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    predictive.check_draws(S, draws_per_sample)
+    aux, flags = None, 0
+    if code == predictive.FAMILY_GAUSSIAN and nu2 is not None:
+        aux, flags = np.asarray(nu2, dtype=float).reshape(S), _native.PRED_AUX_PER_SAMPLE
+    elif code == predictive.FAMILY_NEGBIN and R is not None:
+        aux, flags = predictive.rate_layout(R, S, shape)
+    elif code in (predictive.FAMILY_GAUSSIAN, predictive.FAMILY_NEGBIN) and param is None:
+        raise ValueError("the Gaussian family needs nu2= or param= (variance), the Negative-Binomial R= or param= (rate)")
+    Y = data
+    if isinstance(data, (tuple, list)):
+        Y = data[0]
+        trials = data[1] if trials is None else trials
+    ctx = _native.Context(N, shape[1], shape[2], K, 0, device=device)
+    try:
+        return predictive.evaluate(ctx, shape, K, code, S, Ws, Vs, param=param, aux=aux, aux_flags=flags, trials=trials, Y=Y, q=q,
+                                   draws_per_sample=draws_per_sample, seed=seed, cells=cells)
+    finally:
+        ctx.close()
+
+
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
 from .nmf import factor_pav, tensor_nmf  # noqa: E402,F401
 

@@ -629,6 +629,38 @@ int btf_crit_set_data(btf_ctx* ctx, int slot, const double* S1, const double* cn
 int btf_crit_eval(btf_ctx* ctx, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
                   const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out);
 
+/* ---- posterior predictive of the observations (flutrends/benchmark.py:60-75, :129-134; politics/benchmark.py:147-172) ----
+ * Replicated observations y_rep ~ p(y | theta_s) for every cell and kept sample, reduced on the device to moments, order
+ * statistics and comparisons with data (csrc/btf_predict.h); the (S,N,M,T) draws never leave the chip.  Touches none of
+ * the sampler's state: a chain continued after a predictive call walks the same path.  Unsharded contexts.
+ *
+ * btf_predict_batch (stateless, for validating the samplers): out[i] ~ family(eta[i], aux[i]); draw i uses global draw
+ *   index i.  Families as btf_crit_eval: 0 Poisson log, 1 Poisson identity (nan where eta <= 0), 2 logit: aux = trials,
+ *   3 Gaussian: aux = variance, 4 Negative-Binomial logit: aux = rate r (mean r p / (1 - p), p = ilogit(eta)).
+ * btf_predict_eval: states as btf_crit_eval - Ws (S,N,K), Vs (S,M,T,K) uploaded, or both NULL: the first nsamples
+ *   collected slots.  param: the Gaussian variance / the Negative-Binomial rate of every sample, unless aux_flags &
+ *   BTF_PRED_AUX_PER_SAMPLE: sample s has aux_sample[s] (Gaussian; NULL with collected states: the collected nu2) or the
+ *   rate tensor aux_sample[s][...] whose extent along rows / columns / depth is N / M / T where the BTF_PRED_AUX_ROWS /
+ *   _COLS / _DEPTH bit is set and 1 (shared) otherwise.  trials (N,M,T) or NULL (one trial): the logit family's counts; a
+ *   nan count gives nan draws.  Y (N,M,T,nreps) or NULL: observations, nan = missing.  Draw (s, r) of flat cell c has
+ *   global draw index (c S + s) draws_per_sample + r: the draws do not depend on the launch geometry, on `cells` or on
+ *   where the states come from.  nsamples * draws_per_sample <= 16384 (BTF_EINVAL beyond).
+ *   Outputs, each may be NULL: mean (N,M,T) = mean_s E[y | theta_s] (no draws involved); y_mean, y_var (ddof 1) of the n =
+ *   S * draws_per_sample draws; q_out (nq,N,M,T) their percentiles q (numpy's linear interpolation); with Y: pit_lo /
+ *   pit_hi = mean over the cell's observed replicates of the fraction of draws < y / <= y (nan without observations),
+ *   inside = observed replicates within [q_out[0], q_out[nq-1]] (nq >= 2, else nan), nobs = observed replicates,
+ *   rmse / mae (S,) of y - E[y | theta_s] over all observed y (nan without any); draws_out (ncells, n): the raw draws of
+ *   the listed flat cells, in draw order.  A cell with a nan draw has nan in every draw-based output.  No floating-point
+ *   atomics: two calls with the same seed return identical bits.  Synchronises.                                    */
+enum { BTF_PRED_AUX_PER_SAMPLE = 1, BTF_PRED_AUX_ROWS = 2, BTF_PRED_AUX_COLS = 4, BTF_PRED_AUX_DEPTH = 8 };
+int btf_predict_batch(int device, int family, int64_t n, const double* eta, const double* aux, uint64_t seed, double* out);
+int btf_predict_eval(btf_ctx* ctx, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                     const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps,
+                     int draws_per_sample, uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
+                     double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out,
+                     double* pit_hi_out, double* inside_out, double* nobs_out, double* rmse_out, double* mae_out,
+                     double* draws_out);
+
 /* ---- non-negative tensor factorisation (replaces functionalmf.utils.tensor_nmf, utils.py:276-419, without its
  * max_entry / row_features projections) and the factor PAV projection (factor_pav, utils.py:218-252) ------------------
  * Context-free: a btf_nmf handle holds its own statistics, factors and a small device state on a stream of its own; no
