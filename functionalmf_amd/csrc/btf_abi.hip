@@ -14,6 +14,7 @@
 #include "btf_diag.h"         // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
+#include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
 #include <hip/hip_ext.h>
@@ -3907,6 +3908,158 @@ int btf_posterior_summary(int device, int nsamples, int nrows, int ncols, int nd
 #undef PS
   cleanup();
   return BTF_OK;
+}
+
+// ---------------------------------------------------------------- posterior curve functionals (btf_functionals.h)
+namespace {
+
+struct FuncOut { double *mean, *var, *quant, *defined, *prob, *curves, *pw; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): validation, scratch, the launches chunk by chunk, the
+// downloads.  c may be null (the stateless form: default stream, launches not counted).
+int functionals_run(btf_ctx* c, hipStream_t st, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform,
+                    const int* which, int nwhich, const double* x, double level, double exceed, const double* q, int nq,
+                    const int* curves, int ncurves, const FuncOut& o) {
+  FuncArgs a = {};
+  a.W = dW; a.V = dV; a.level = level; a.exceed = exceed;
+  a.S = S; a.N = N; a.M = M; a.T = T; a.nslots = nwhich; a.nq = nq;
+  for (int f = 0; f < FUNC_COUNT; ++f) a.slot[f] = -1;
+  for (int k = 0; k < nwhich; ++k) { a.slot[which[k]] = k; a.code[k] = which[k]; }
+  int P = 2;
+  while (P < S) P <<= 1;
+  a.P = P;
+  a.cells = std::max(1, std::min(FUNC_SORT_CELLS, (int)(FUNC_SORT_LDS / ((size_t)P * sizeof(double)))));
+  const size_t lds = (size_t)a.cells * P * sizeof(double);
+  const size_t NM = (size_t)N * M, per_col = (size_t)nwhich * S * N * sizeof(double);
+  const int jc_max = (int)std::max<size_t>(1, std::min<size_t>(std::min(M, 65535), FUNC_SCRATCH_BYTES / per_col));   // (a grid's y extent)
+  FuncKernel sweep = func_sweep_fn(K, transform), sort = func_sort_fn();
+  if (!sweep) return fail(c, BTF_EINVAL, "posterior functionals: nembeds must be 1..10 and transform 0..2");
+  double *dx = nullptr, *dq = nullptr, *dvals = nullptr, *dmean = nullptr, *dvar = nullptr, *dquant = nullptr, *ddef = nullptr,
+         *dprob = nullptr, *dcur = nullptr, *dpw = nullptr;
+  int* dcv = nullptr;
+  auto cleanup = [&]() {
+    for (void* p : {(void*)dx, (void*)dq, (void*)dvals, (void*)dmean, (void*)dvar, (void*)dquant, (void*)ddef, (void*)dprob, (void*)dcur,
+                    (void*)dpw, (void*)dcv})
+      if (p) (void)hipFree(p);
+  };
+#define FN(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+  FN(hipMalloc((void**)&dx, (size_t)T * sizeof(double)));
+  FN(hipMalloc((void**)&dvals, per_col * jc_max));
+  FN(hipMemcpyAsync(dx, x, (size_t)T * sizeof(double), hipMemcpyHostToDevice, st));
+  if (o.mean) FN(hipMalloc((void**)&dmean, nwhich * NM * sizeof(double)));
+  if (o.var) FN(hipMalloc((void**)&dvar, nwhich * NM * sizeof(double)));
+  if (o.prob) FN(hipMalloc((void**)&dprob, nwhich * NM * sizeof(double)));
+  if (o.defined) FN(hipMalloc((void**)&ddef, NM * sizeof(double)));
+  if (nq) {
+    FN(hipMalloc((void**)&dq, (size_t)nq * sizeof(double)));
+    FN(hipMalloc((void**)&dquant, (size_t)nq * nwhich * NM * sizeof(double)));
+    FN(hipMemcpyAsync(dq, q, (size_t)nq * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  if (ncurves) {
+    FN(hipMalloc((void**)&dcv, (size_t)2 * ncurves * sizeof(int)));
+    FN(hipMalloc((void**)&dcur, (size_t)nwhich * ncurves * S * sizeof(double)));
+    FN(hipMemcpyAsync(dcv, curves, (size_t)2 * ncurves * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (o.pw) FN(hipMalloc((void**)&dpw, (size_t)nwhich * S * NM * sizeof(double)));
+  a.x = dx; a.q = dq; a.vals = dvals; a.mean = dmean; a.var = dvar; a.quant = dquant; a.defined = ddef; a.prob = dprob; a.pw = dpw;
+  FN(hipFuncSetAttribute((const void*)sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int rowblocks = (N + WAVE - 1) / WAVE;
+  const bool reduce = o.mean || o.var || o.prob || o.defined || nq;
+  for (int j0 = 0; j0 < M; j0 += jc_max) {
+    a.j0 = j0; a.jc = std::min(jc_max, M - j0);
+    // sample slices: enough workgroups to fill the chip when rows x columns alone do not (geometry only)
+    const int zs = std::max(1, std::min((S + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * a.jc - 1) / (rowblocks * a.jc)));
+    const dim3 gsweep(rowblocks, a.jc, zs), gsort((N + a.cells - 1) / a.cells, a.jc, nwhich);
+    if (c) {
+      { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, sweep, gsweep, dim3(FUNC_WAVES * WAVE), 0, a); }
+      if (ncurves) { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, func_gather_fn(), dim3(ncurves, nwhich), dim3(256), 0, a, (const int*)dcv, ncurves, dcur); }
+      if (reduce) { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, sort, gsort, dim3(256), lds, a); }
+    } else {
+      hipLaunchKernelGGL(sweep, gsweep, dim3(FUNC_WAVES * WAVE), 0, st, a);
+      if (ncurves) hipLaunchKernelGGL(func_gather_fn(), dim3(ncurves, nwhich), dim3(256), 0, st, a, (const int*)dcv, ncurves, dcur);
+      if (reduce) hipLaunchKernelGGL(sort, gsort, dim3(256), lds, st, a);
+    }
+    FN(hipGetLastError());
+  }
+  if (o.mean) FN(hipMemcpyAsync(o.mean, dmean, nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (o.var) FN(hipMemcpyAsync(o.var, dvar, nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (o.prob) FN(hipMemcpyAsync(o.prob, dprob, nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (o.defined) {
+    if (a.slot[FUNC_CROSSING] < 0) FN(hipMemsetAsync(ddef, 0, NM * sizeof(double), st));
+    FN(hipMemcpyAsync(o.defined, ddef, NM * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  if (nq) FN(hipMemcpyAsync(o.quant, dquant, (size_t)nq * nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (ncurves) FN(hipMemcpyAsync(o.curves, dcur, (size_t)nwhich * ncurves * S * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (o.pw) FN(hipMemcpyAsync(o.pw, dpw, (size_t)nwhich * S * NM * sizeof(double), hipMemcpyDeviceToHost, st));
+  FN(hipStreamSynchronize(st));
+#undef FN
+  cleanup();
+  return BTF_OK;
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int functionals_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, const int* which, int nwhich, const double* x,
+                      double level, const double* q, int nq, const int* curves, int ncurves, const FuncOut& o) {
+  if (S < 1 || N < 1 || M < 1 || K < 1 || K > MAX_K || transform < 0 || transform > 2 || !which || nwhich < 1 || nwhich > FUNC_COUNT ||
+      !x || nq < 0 || (nq > 0 && (!q || !o.quant)) || ncurves < 0 || (ncurves > 0 && (!curves || !o.curves)))
+    return fail(c, BTF_EINVAL, "bad posterior functionals arguments");
+  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior functionals: at most " + std::to_string(FUNC_MAX_S) + " samples (one curve's values are sorted in LDS)");
+  if (T < 2) return fail(c, BTF_EINVAL, "posterior functionals: a curve needs ndepth >= 2");
+  bool seen[FUNC_COUNT] = {false};
+  for (int k = 0; k < nwhich; ++k) {
+    if (which[k] < 0 || which[k] >= FUNC_COUNT || seen[which[k]]) return fail(c, BTF_EINVAL, "posterior functionals: functional codes must be distinct and in 0..6");
+    seen[which[k]] = true;
+  }
+  if (seen[FUNC_CROSSING] && !(level == level)) return fail(c, BTF_EINVAL, "posterior functionals: crossing needs a level");
+  for (int t = 1; t < T; ++t)
+    if (!(x[t] > x[t - 1])) return fail(c, BTF_EINVAL, "posterior functionals: x must be strictly increasing");
+  for (int k = 0; k < nq; ++k)
+    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
+  for (int k = 0; k < ncurves; ++k)
+    if (curves[2 * k] < 0 || curves[2 * k] >= N || curves[2 * k + 1] < 0 || curves[2 * k + 1] >= M)
+      return fail(c, BTF_EINVAL, "posterior functionals: curve index out of range");
+  return BTF_OK;
+}
+
+}  // namespace
+
+int btf_posterior_functionals(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                              int transform, const int* which, int nwhich, const double* x, double level, double exceed,
+                              const double* q, int nq, const int* curves, int ncurves, double* mean_out, double* var_out,
+                              double* q_out, double* defined_out, double* prob_out, double* curves_out, double* pointwise_out) {
+  const FuncOut o = {mean_out, var_out, q_out, defined_out, prob_out, curves_out, pointwise_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior functionals arguments");
+  int rc = functionals_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, q, nq, curves, ncurves, o);
+  if (rc) return rc;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  const size_t nW = (size_t)nsamples * nrows * nembeds, nV = (size_t)nsamples * ncols * ndepth * nembeds;
+  double *dW = nullptr, *dV = nullptr;
+  auto cleanup = [&]() { if (dW) (void)hipFree(dW); if (dV) (void)hipFree(dV); };
+#define FU(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+  FU(hipMalloc((void**)&dW, nW * sizeof(double)));
+  FU(hipMalloc((void**)&dV, nV * sizeof(double)));
+  FU(hipMemcpy(dW, Ws, nW * sizeof(double), hipMemcpyHostToDevice));
+  FU(hipMemcpy(dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice));
+#undef FU
+  rc = functionals_run(nullptr, 0, dW, dV, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, exceed, q, nq,
+                       curves, ncurves, o);
+  cleanup();
+  return rc;
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload)
+int btf_collect_functionals(btf_ctx* c, int nsamples, int transform, const int* which, int nwhich, const double* x, double level,
+                            double exceed, const double* q, int nq, const int* curves, int ncurves, double* mean_out, double* var_out,
+                            double* q_out, double* defined_out, double* prob_out, double* curves_out, double* pointwise_out) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior functionals arguments");
+  const FuncOut o = {mean_out, var_out, q_out, defined_out, prob_out, curves_out, pointwise_out};
+  int rc = functionals_check(c, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, q, nq, curves, ncurves, o);
+  if (rc) return rc;
+  if (!c->smp_W || !c->smp_V || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_functionals: not that many collected samples");
+  HIPCHK(c, hipSetDevice(c->dev));
+  return functionals_run(c, c->stream, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
+                         q, nq, curves, ncurves, o);
 }
 
 // ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)

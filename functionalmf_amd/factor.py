@@ -861,6 +861,33 @@ class BayesianTensorFiltering(_BayesianModel):
         return _pred.evaluate(self._ctx, (self.nrows, self.ncols, self.ndepth), self.nembeds, family, S, Ws, Vs, param=param,
                               aux=aux, aux_flags=flags, trials=trials, Y=Y, q=q, draws_per_sample=R, seed=seed, cells=cells)
 
+    # ---- posterior curve functionals: AUC, peak, level crossing (functionalmf_amd/functionals.py) ----
+    def posterior_functionals(self, results=None, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None,
+                              curves=None, pointwise=False):
+        """Per-curve functionals of f(w_i . v_j,:) over depth - area under the curve, maximum / minimum and where they lie,
+        total rise, the first crossing of a level - summarised over the kept samples on the GPU (csrc/btf_functionals.h).
+        What doseresponse/feature_importance.py:40 computes from the (S,N,M,T) tensor on the host.
+
+        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device (no upload).
+        The other arguments and the returned dict: functionalmf_amd.utils.posterior_functionals.  The sampler's state is not
+        touched: a chain continued after the call walks the same path.  Unsharded models."""
+        from . import functionals as _func
+        if self._plan.world > 1 or self._exchange.active:
+            raise NotImplementedError("posterior functionals: unsharded models only")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        if results is None:
+            S = getattr(self, "_collected", 0)
+            if S < 1:
+                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first), and no results= given")
+            Ws = Vs = None
+        else:
+            _func.check_args(which, q, transform, x, level, exceed, curves, 1, *shape)
+            Ws, Vs = self._pred_states(results)
+            S = Ws.shape[0]
+        return _func.evaluate(shape, self.nembeds, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed,
+                              curves=curves, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
+
     def logprob(self, data, reduce="sum", **state):
         """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,
         nu2=); further keys (Tau2, lam2, sigma2, ...: what the reference's DIC passes) are ignored.  reduce="sum": a

@@ -138,6 +138,34 @@ def posterior_predictive(Ws, Vs, family, data=None, q=(2.5, 97.5), draws_per_sam
         ctx.close()
 
 
+def posterior_functionals(Ws, Vs, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None, curves=None,
+                          pointwise=False, device=0):
+    """Per-curve functionals of f(w_s[i] . v_s[j,:]) over depth, summarised over the kept samples, on the GPU, without a
+    model: the stateless form of BayesianTensorFiltering.posterior_functionals, next to posterior_summary.
+
+    The reference application does this on the host (doseresponse/feature_importance.py:40):
+
+        np.trapz(np.einsum('znk,zmtk->znmt', Ws, Vs), dx=1/(T-1), axis=-1).mean(axis=0)     # == out["auc"]["mean"]
+
+    which: any of "auc", "max", "min", "argmax", "argmin", "rise", "crossing" (functionalmf_amd.functionals.curve_functionals
+    is their definition in numpy); x: (T,) strictly increasing depth coordinates, default np.linspace(0, 1, T); level: the
+    level of `crossing` (e.g. 0.5 with transform="ilogit": the IC50).  Returns {name: {"mean", "var" (N,M; ddof 1),
+    "quantiles" (len(q),N,M)}}; crossing adds "defined" (N,M), the share of samples in which the level is crossed - its mean
+    and var run over those, its percentiles count the others as +inf and are nan where they reach them; exceed=c adds
+    "prob_above" (share of samples with value > c); curves=[(i,j), ...] adds "curves" (ncurves,S), the raw values in
+    sample order; pointwise=True adds "pointwise" (S,N,M).  At most 8192 samples, ndepth >= 2.  There is no CPU fallback."""
+    from . import functionals, predictive
+    Ws, Vs = np.asarray(Ws), np.asarray(Vs)
+    if Ws.ndim != 3 or Vs.ndim != 4 or Ws.shape[0] != Vs.shape[0] or Ws.shape[2] != Vs.shape[3]:
+        raise ValueError("Ws must be (S, N, K) and Vs (S, M, T, K)")
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    functionals.check_args(which, q, transform, x, level, exceed, curves, S, N, shape[1], shape[2])   # before any conversion
+    Ws, Vs = predictive.check_states(Ws, Vs, shape, K)
+    return functionals.evaluate(shape, K, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed, curves=curves,
+                                pointwise=pointwise, Ws=Ws, Vs=Vs, device=device)
+
+
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
 from .nmf import factor_pav, tensor_nmf  # noqa: E402,F401
 

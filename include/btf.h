@@ -576,6 +576,30 @@ int btf_posterior_summary(int device, int nsamples, int nrows, int ncols, int nd
                           const double* Ws, const double* Vs, int transform, const double* q, int nq,
                           double* mean_out, double* q_out);
 
+/* ---- posterior curve functionals (csrc/btf_functionals.h; replaces doseresponse/feature_importance.py:40) ---------------
+ * Per kept sample s and curve (i,j), m_t = f(w_i^s . v_jt^s) over the depth coordinates x (T, strictly increasing) is
+ * reduced to one number per requested functional, and the S numbers of a curve to mean, variance (ddof 1; nan below two
+ * values), percentiles (numpy's linear rule), and the share above `exceed`.  Functional codes (which[], distinct):
+ *   0 auc: trapezoid rule  1 max  2 min  3 argmax  4 argmin: x at the first occurrence  5 rise: sum of the positive steps
+ *   6 crossing: where m first crosses `level` (linear interpolation; x[0] if m_0 == level; undefined when it never does).
+ * An undefined crossing is left out of mean / var / prob, counts as +inf in the percentiles (right-censored), and a
+ * percentile that touches a non-finite order statistic is nan; defined_out (N,M) = share of samples with a crossing.
+ * Outputs, each NULL or, with nw = nwhich in the order of which[]: mean_out, var_out, prob_out (nw,N,M); q_out (nw,nq,N,M);
+ * curves_out (nw,ncurves,S): the raw values of the curves[] = (i,j) pairs in sample order (nan = undefined);
+ * pointwise_out (nw,S,N,M).  transform as btf_posterior_summary.  ndepth >= 2, nsamples <= 8192 (BTF_EINVAL beyond).
+ * fp64, no floating-point atomics, every sum in a fixed order: two calls return identical bits, whatever the launch
+ * geometry and wherever the states come from.  btf_collect_functionals reads the first nsamples collected slots without
+ * an upload and touches none of the sampler's state; its launches are counted under BTF_K_CRITERIA.  Synchronous.      */
+int btf_posterior_functionals(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws,
+                              const double* Vs, int transform, const int* which, int nwhich, const double* x, double level,
+                              double exceed, const double* q, int nq, const int* curves, int ncurves, double* mean_out,
+                              double* var_out, double* q_out, double* defined_out, double* prob_out, double* curves_out,
+                              double* pointwise_out);
+int btf_collect_functionals(btf_ctx* ctx, int nsamples, int transform, const int* which, int nwhich, const double* x,
+                            double level, double exceed, const double* q, int nq, const int* curves, int ncurves,
+                            double* mean_out, double* var_out, double* q_out, double* defined_out, double* prob_out,
+                            double* curves_out, double* pointwise_out);
+
 /* ---- convergence diagnostics (csrc/btf_diag.h) ----------------------------------------------------------------------
  * Split R-hat (rank-normalised, max of bulk and folded), bulk ESS, tail ESS (min over the 5 % / 95 % indicators), MCSE of
  * the mean and the mean, per cell of f(W V') over nchains chains of nsamples draws (Vehtari et al. 2021; one chain: its
