@@ -15,6 +15,7 @@
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
+#include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
 #include <hip/hip_ext.h>
@@ -1058,7 +1059,8 @@ void btf_destroy(btf_ctx* c) {
 }
 
 const char* btf_last_error(const btf_ctx* c) { return c ? c->err.c_str() : g_err.c_str(); }
-int btf_fail_index(const btf_ctx* c) { return c ? c->fail_index : -1; }
+int fold_fail_index();   // (defined with the fold-in entry points)
+int btf_fail_index(const btf_ctx* c) { return c ? c->fail_index : fold_fail_index(); }
 
 int btf_set_shard(btf_ctx* c, int row0, int nrows_local, int col0, int ncols_local) {
   if (!c) return BTF_EINVAL;
@@ -4060,6 +4062,185 @@ int btf_collect_functionals(btf_ctx* c, int nsamples, int transform, const int* 
   HIPCHK(c, hipSetDevice(c->dev));
   return functionals_run(c, c->stream, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
                          q, nq, curves, ncurves, o);
+}
+
+// ---------------------------------------------------------------- folding new rows in (btf_fold_in.h)
+namespace {
+
+thread_local int g_fold_fail_index = -1;      // btf_fail_index(NULL): the failing (sample, row) of the last stateless call
+
+struct FoldIn {
+  int family, S, R, M, T, K;
+  const double *count, *ysum, *trials, *z;
+  unsigned long long seed;
+  int inner_sweeps;
+  long long sample0;
+  double *W_out, *Wmean_out;
+  int transform;
+  const double* q; int nq;
+  double *mean_out, *q_out;
+};
+
+// everything that can be refused without a device
+int fold_in_check(btf_ctx* c, const FoldIn& f) {
+  if (f.family < FOLD_GAUSSIAN || f.family > FOLD_BINOMIAL || f.S < 1 || f.R < 1 || f.M < 1 || f.T < 1 || f.K < 1 || f.K > MAX_K ||
+      !f.ysum || !f.W_out || f.sample0 < 0 || f.nq < 0 || (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2)
+    return fail(c, BTF_EINVAL, "bad fold_in arguments");
+  if (f.family == FOLD_GAUSSIAN && !f.count) return fail(c, BTF_EINVAL, "fold_in: the Gaussian family needs count");
+  if (f.family == FOLD_BINOMIAL && (!f.trials || f.z || f.inner_sweeps < 1))
+    return fail(c, BTF_EINVAL, "fold_in: the Binomial family needs trials and inner_sweeps >= 1, and takes no z");
+  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "fold_in: the summary stage takes at most 16384 samples");
+  if ((double)(f.sample0 + f.S) * f.R >= 2147483647.0 || (double)f.R * f.M * f.T >= 2147483647.0)
+    return fail(c, BTF_EINVAL, "fold_in: (sample0 + nsamples) * nrows_new and nrows_new * ncols * ndepth must stay below 2^31");
+  for (int k = 0; k < f.nq; ++k)
+    if (!(f.q[k] >= 0.0 && f.q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
+  const size_t n = (size_t)f.R * f.M * f.T;
+  const double* cw = f.family == FOLD_GAUSSIAN ? f.count : f.trials;
+  for (size_t e = 0; e < n; ++e) {
+    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(f.ysum[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, "fold_in: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
+    if (f.family == FOLD_BINOMIAL && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLD_MAX_TRIALS))
+      return fail(c, BTF_EINVAL, "fold_in: Binomial trial counts must be integers up to " + std::to_string(FOLD_MAX_TRIALS));
+  }
+  return BTF_OK;
+}
+
+// The launches on device states dV (S,M,T,K) and per-sample scalars on the device (noise may be null: 1).  c may be null
+// (the stateless form: default stream, launches not counted).  W stays on the device between the draw and the summary.
+int fold_in_run(btf_ctx* c, hipStream_t st, const double* dV, const double* dnoise, int nstride, const double* dsig, int sstride,
+                const FoldIn& f) {
+  const int S = f.S, R = f.R, MT = f.M * f.T, K = f.K;
+  FoldKernel kern = fold_in_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, "fold_in: nembeds must be 1..10 and family 0..1");
+  // row statistics in the kernel's [cell][row] layout; Binomial: kappa = successes - trials / 2
+  std::vector<double> hc((size_t)MT * R), hy((size_t)MT * R);
+  const double* cw = f.family == FOLD_GAUSSIAN ? f.count : f.trials;
+  for (int r = 0; r < R; ++r)
+    for (int jt = 0; jt < MT; ++jt) {
+      const double cv = cw[(size_t)r * MT + jt], yv = f.ysum[(size_t)r * MT + jt];
+      hc[(size_t)jt * R + r] = cv;
+      hy[(size_t)jt * R + r] = f.family == FOLD_BINOMIAL ? (cv > 0.0 ? yv - 0.5 * cv : 0.0) : (cv > 0.0 ? yv : 0.0);
+    }
+  const size_t nW = (size_t)S * R * K, cellsN = (size_t)R * MT;
+  double *dc = nullptr, *dy = nullptr, *dz = nullptr, *dW = nullptr, *dWm = nullptr, *dq = nullptr, *dm = nullptr, *dqo = nullptr;
+  int* dstat = nullptr;
+  auto cleanup = [&]() {
+    for (void* p : {(void*)dc, (void*)dy, (void*)dz, (void*)dW, (void*)dWm, (void*)dq, (void*)dm, (void*)dqo, (void*)dstat})
+      if (p) (void)hipFree(p);
+  };
+#define FI(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+  FI(hipMalloc((void**)&dc, cellsN * sizeof(double)));
+  FI(hipMalloc((void**)&dy, cellsN * sizeof(double)));
+  FI(hipMalloc((void**)&dW, nW * sizeof(double)));
+  FI(hipMalloc((void**)&dstat, 2 * sizeof(int)));
+  if (f.Wmean_out) FI(hipMalloc((void**)&dWm, nW * sizeof(double)));
+  if (f.z) FI(hipMalloc((void**)&dz, nW * sizeof(double)));
+  FI(hipMemcpyAsync(dc, hc.data(), cellsN * sizeof(double), hipMemcpyHostToDevice, st));
+  FI(hipMemcpyAsync(dy, hy.data(), cellsN * sizeof(double), hipMemcpyHostToDevice, st));
+  if (f.z) FI(hipMemcpyAsync(dz, f.z, nW * sizeof(double), hipMemcpyHostToDevice, st));
+  const int stat0[2] = {0, INT_MAX};
+  FI(hipMemcpyAsync(dstat, stat0, sizeof(stat0), hipMemcpyHostToDevice, st));
+  FoldArgs a = {};
+  a.V = dV; a.noise = dnoise; a.sigma2 = dsig; a.nstride = nstride; a.sstride = sstride;
+  a.cnt = dc; a.ysum = dy; a.z = dz; a.W = dW; a.Wmean = dWm; a.status = dstat;
+  a.seed = f.seed; a.sample0 = f.sample0; a.S = S; a.R = R; a.MT = MT; a.sweeps = f.inner_sweeps;
+  const dim3 grid(S, (R + WAVE - 1) / WAVE);
+  if (c) { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, kern, grid, dim3(FOLD_PARTS * WAVE), 0, a); }
+  else hipLaunchKernelGGL(kern, grid, dim3(FOLD_PARTS * WAVE), 0, st, a);
+  FI(hipGetLastError());
+  if (f.mean_out) {
+    // the summary stage: posterior_summary_kernel on the device-resident W (S,R,K) and V, as btf_posterior_summary launches it
+    FI(hipMalloc((void**)&dm, cellsN * sizeof(double)));
+    FI(hipMalloc((void**)&dq, (size_t)std::max(f.nq, 1) * sizeof(double)));
+    FI(hipMalloc((void**)&dqo, std::max<size_t>(1, (size_t)f.nq * cellsN) * sizeof(double)));
+    if (f.nq) FI(hipMemcpyAsync(dq, f.q, (size_t)f.nq * sizeof(double), hipMemcpyHostToDevice, st));
+    int P = 2;
+    while (P < S) P <<= 1;
+    const int cells = std::max(1, std::min(16, (int)((128 * 1024) / ((size_t)P * sizeof(double)))));
+    const size_t lds = (size_t)cells * P * sizeof(double);
+    const dim3 sgrid((MT + cells - 1) / cells, R);
+#define FI_LAUNCH(KT_)                                                                                           \
+  case KT_: {                                                                                                    \
+    FI(hipFuncSetAttribute((const void*)posterior_summary_kernel<KT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(posterior_summary_kernel<KT_>, sgrid, dim3(256), lds, st, (const double*)dW, dV, S, R, MT, P, cells, \
+                       f.transform, (const double*)dq, f.nq, dm, dqo);                                           \
+  } break;
+    switch (K) {
+      FI_LAUNCH(1) FI_LAUNCH(2) FI_LAUNCH(3) FI_LAUNCH(4) FI_LAUNCH(5) FI_LAUNCH(6) FI_LAUNCH(7) FI_LAUNCH(8) FI_LAUNCH(9) FI_LAUNCH(10)
+      default: break;
+    }
+#undef FI_LAUNCH
+    FI(hipGetLastError());
+    FI(hipMemcpyAsync(f.mean_out, dm, cellsN * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (f.nq) FI(hipMemcpyAsync(f.q_out, dqo, (size_t)f.nq * cellsN * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  int stat[2] = {0, INT_MAX};
+  FI(hipMemcpyAsync(stat, dstat, sizeof(stat), hipMemcpyDeviceToHost, st));
+  FI(hipMemcpyAsync(f.W_out, dW, nW * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (f.Wmean_out) FI(hipMemcpyAsync(f.Wmean_out, dWm, nW * sizeof(double), hipMemcpyDeviceToHost, st));
+  FI(hipStreamSynchronize(st));
+#undef FI
+  cleanup();
+  if (stat[0]) {
+    if (c) c->fail_index = stat[1];
+    g_fold_fail_index = stat[1];
+    return fail(c, BTF_ENOTPD, "fold_in: the precision of (sample, row) index " + std::to_string(stat[1]) +
+                                   " = sample * nrows_new + row is not positive definite (or nu2 / sigma2 / V not finite)");
+  }
+  return BTF_OK;
+}
+
+}  // namespace
+
+int fold_fail_index() { return g_fold_fail_index; }
+
+int btf_fold_in_rows(int device, int family, int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs,
+                     const double* noise, const double* sigma2, const double* count, const double* ysum, const double* trials,
+                     const double* z, unsigned long long seed, int inner_sweeps, long long sample0, double* W_out, double* Wmean_out,
+                     int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  const FoldIn f = {family, nsamples, nrows_new, ncols, ndepth, nembeds, count, ysum, trials, z, seed, inner_sweeps, sample0,
+                    W_out, Wmean_out, transform, q, nq, mean_out, q_out};
+  g_fold_fail_index = -1;
+  if (!Vs || !sigma2 || (family == FOLD_GAUSSIAN && !noise)) return fail(nullptr, BTF_EINVAL, "bad fold_in arguments");
+  int rc = fold_in_check(nullptr, f);
+  if (rc) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(sigma2[s] > 0.0 && sigma2[s] < INFINITY) || (family == FOLD_GAUSSIAN && !(noise[s] > 0.0 && noise[s] < INFINITY)))
+      return fail(nullptr, BTF_EINVAL, "fold_in: nu2 and sigma2 must be finite and positive");
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  const size_t nV = (size_t)nsamples * ncols * ndepth * nembeds;
+  double *dV = nullptr, *dn = nullptr, *ds = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)dV, (void*)dn, (void*)ds}) if (p) (void)hipFree(p); };
+#define FU(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+  FU(hipMalloc((void**)&dV, nV * sizeof(double)));
+  FU(hipMalloc((void**)&ds, (size_t)nsamples * sizeof(double)));
+  FU(hipMemcpy(dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice));
+  FU(hipMemcpy(ds, sigma2, (size_t)nsamples * sizeof(double), hipMemcpyHostToDevice));
+  if (family == FOLD_GAUSSIAN) {
+    FU(hipMalloc((void**)&dn, (size_t)nsamples * sizeof(double)));
+    FU(hipMemcpy(dn, noise, (size_t)nsamples * sizeof(double), hipMemcpyHostToDevice));
+  }
+#undef FU
+  rc = fold_in_run(nullptr, 0, dV, dn, 1, ds, 1, f);
+  cleanup();
+  return rc;
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload): V from the sample slots, nu2_s and
+// sigma2_s from the collected scalars
+int btf_collect_fold_in(btf_ctx* c, int family, int nsamples, int nrows_new, const double* count, const double* ysum,
+                        const double* trials, const double* z, unsigned long long seed, int inner_sweeps, long long sample0,
+                        double* W_out, double* Wmean_out, int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  if (!c) return fail(c, BTF_EINVAL, "bad fold_in arguments");
+  const FoldIn f = {family, nsamples, nrows_new, c->M, c->T, c->K, count, ysum, trials, z, seed, inner_sweeps, sample0,
+                    W_out, Wmean_out, transform, q, nq, mean_out, q_out};
+  int rc = fold_in_check(c, f);
+  if (rc) return rc;
+  if (!c->smp_V || !c->smp_s || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_fold_in: not that many collected samples");
+  HIPCHK(c, hipSetDevice(c->dev));
+  return fold_in_run(c, c->stream, c->smp_V, family == FOLD_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT,
+                     c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, f);
 }
 
 // ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)

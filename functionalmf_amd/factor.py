@@ -888,6 +888,66 @@ class BayesianTensorFiltering(_BayesianModel):
         return _func.evaluate(shape, self.nembeds, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed,
                               curves=curves, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
 
+    # ---- folding new rows in (functionalmf_amd/fold_in.py, csrc/btf_fold_in.h) ----
+    def _fold_family(self):
+        """Family name of fold_in_rows for this model's likelihood."""
+        raise NotImplementedError("%s: fold_in_rows needs a conjugate row conditional (Gaussian and Binomial models)" % type(self).__name__)
+
+    def fold_in_rows(self, Y_new, results=None, seed=None, z=None, summary=True, q=(5, 95), transform=None, inner_sweeps=None,
+                     trials=None):
+        """Embeddings and curves of rows the chain never saw (a new cell line with a handful of drugs tested, a new
+        season), with uncertainty, on the GPU (csrc/btf_fold_in.h).  Given V the rows of W are conditionally independent
+        with prior N(0, sigma2 I) (factor.py:333), so under kept sample s the new row has the conditional _resample_W
+        draws from (factor.py:333-362), and one draw per kept sample is a draw from p(w_new | y_new, training data).
+        Exact for the Gaussian model; the Binomial model runs `inner_sweeps` Polya-Gamma rounds per (sample, row) from
+        w = 0 (factor.py:437-460; default: functionalmf_amd.fold_in.DEFAULT_INNER_SWEEPS).
+
+        Y_new: (R,M,T) or (R,M,T,nreps), NaN = missing; Binomial: the (Y, N) pair, or Y with trials= (default 1), counts
+            up to 32.  A row with no observation at all is allowed: its draw is the prior's.
+        results: a run_gibbs result dict (V (S,M,T,K), sigma2 one value per sample, Gaussian nu2 likewise), uploaded; None:
+            the samples the last device-collecting run_gibbs left on the device - no upload of V, and nu2_s, sigma2_s are read
+            from the collected scalars.
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        z: optional (S,R,K) standard normals replacing the device generator (Gaussian only): w = Q^-1 b + L^-T z, Q = L L'.
+
+        Returns a dict: W (S,R,K) one draw per kept sample; W_mean (S,R,K) the conditional means Q_s^-1 b_s (Gaussian
+        only); with summary=True, mean (R,M,T) and quantiles (len(q),R,M,T) of f(w_new^s . v_jt^s) from the summary kernel
+        on the device-resident W and V (transform as posterior_summary; at most 16384 samples); nsamples.  out["W"] together
+        with results["V"] goes straight into utils.posterior_summary, utils.posterior_predictive and
+        utils.posterior_functionals.  The sampler's state is not touched: a chain continued after the call walks the same
+        path.  Unsharded models.  Folding in new COLUMNS is out of scope: it needs the horseshoe local scales of a column
+        nobody has sampled."""
+        from . import fold_in as _fold
+        family = self._fold_family()
+        if self._plan.world > 1 or self._exchange.active:
+            raise NotImplementedError("fold_in_rows: unsharded models only")
+        M, T, K = self.ncols, self.ndepth, self.nembeds
+        R, weights, sums = _fold.row_statistics(Y_new, family, M, T, trials=trials)
+        gauss = _fold.FAMILIES[family] == _fold.FAMILIES["gaussian"]
+        Vs = nu2 = sigma2 = None
+        if results is None:
+            S = getattr(self, "_collected", 0)
+            if S < 1:
+                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first), and no results= given")
+        else:
+            try:
+                Vs = np.asarray(results["V"])
+            except (KeyError, TypeError):
+                raise ValueError("results must be a run_gibbs result dict with V (S,M,T,K), sigma2 and (Gaussian) nu2")
+            S = Vs.shape[0] if Vs.ndim == 4 else -1
+            if S < 1 or Vs.shape != (S, M, T, K):
+                raise ValueError("results: V %r does not match the model's (S,%d,%d,%d)" % (Vs.shape, M, T, K))
+        _fold.check_args(family, S, R, K, z, summary, q, transform, inner_sweeps)
+        if results is not None:
+            sigma2 = _fold.check_scalars("results: sigma2", results.get("sigma2"), S)
+            nu2 = _fold.check_scalars("results: nu2", results.get("nu2"), S) if gauss else None
+            Vs = np.ascontiguousarray(Vs, dtype=np.float64)
+        if seed is None:
+            seed = self._next_seed() if z is None else 0
+        return _fold.evaluate(family, S, R, M, T, K, weights, sums, z=z, seed=seed, summary=summary, q=q, transform=transform,
+                              inner_sweeps=inner_sweeps, ctx=self._ctx, Vs=Vs, nu2=nu2, sigma2=sigma2, device=self._ctx.device)
+
     def logprob(self, data, reduce="sum", **state):
         """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,
         nu2=); further keys (Tau2, lam2, sigma2, ...: what the reference's DIC passes) are ignored.  reduce="sum": a
@@ -1083,6 +1143,9 @@ class GaussianBayesianTensorFiltering(BayesianTensorFiltering):
 
     def _crit_family(self):
         return _criteria.FAMILY_GAUSSIAN, None, True        # variance: the sampled nu2
+
+    def _fold_family(self):
+        return "gaussian"
 
     def _upload(self, Y):
         if Y.ndim not in (3, 4):
@@ -1325,6 +1388,9 @@ class BinomialBayesianTensorFiltering(GaussianBayesianTensorFiltering):
     def _crit_family(self):
         return _criteria.FAMILY_LOGIT, None, False         # y successes of n trials, logit link (factor.py:425-460)
 
+    def _fold_family(self):
+        return "binomial"
+
     def _set_noise(self):
         if getattr(self, "_omega_host_new", False) and np.ndim(self._nu2) == 3:
             with np.errstate(divide='ignore'):
@@ -1381,6 +1447,10 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
 
     def _pred_family(self):
         return 4, None, True                  # Negative-Binomial, logit link; the rate R of every sample
+
+    def _fold_family(self):
+        raise NotImplementedError("fold_in_rows for the Negative-Binomial model: the pseudo-trial counts y + R of a new row depend "
+                                  "on the sampled rate R (not supported yet)")
 
     def _pred_aux(self, results, nsamples):
         """The rate tensor of every sample: results['R'] (S,) + rate shape, else the current R for all of them."""

@@ -166,6 +166,32 @@ def posterior_functionals(Ws, Vs, which=("auc",), q=(5, 95), transform=None, x=N
                                 pointwise=pointwise, Ws=Ws, Vs=Vs, device=device)
 
 
+def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summary=True, q=(5, 95), transform=None,
+                 inner_sweeps=None, trials=None, first_sample=0, device=0):
+    """Embeddings of rows the chain never saw, one draw per kept sample, on the GPU, without a model: the stateless form of
+    BayesianTensorFiltering.fold_in_rows (see there for the outputs), next to posterior_summary.
+
+    Vs (S,M,T,K); family "gaussian" (nu2 and sigma2: one value per sample) or "binomial" (sigma2).  Y_new: (R,M,T) or
+    (R,M,T,nreps) with NaN = missing; Binomial: a (Y, N) pair of (R,M,T) arrays, or Y with trials= (default 1), counts up to
+    32.  z: optional (S,R,K) standard normals in the place of the device generator (Gaussian only): w = Q^-1 b + L^-T z.
+    first_sample: the index of Vs[0] among the kept samples - with it a call over a slice of the samples returns the bits
+    of the whole call.  out["W"] and Vs go straight into posterior_summary, posterior_predictive and posterior_functionals.
+    functionalmf_amd.fold_in.conditional is the definition in numpy.  There is no CPU fallback."""
+    from . import fold_in
+    Vs = np.asarray(Vs)
+    if Vs.ndim != 4 or Vs.shape[0] < 1:
+        raise ValueError("Vs must be (S, M, T, K)")
+    S, M, T, K = Vs.shape
+    code = fold_in.family_code(family)
+    R, weights, sums = fold_in.row_statistics(Y_new, family, M, T, trials=trials)
+    fold_in.check_args(family, S, R, K, z, summary, q, transform, inner_sweeps, first_sample)     # before any conversion
+    sigma2 = fold_in.check_scalars("sigma2", sigma2, S)
+    nu2 = fold_in.check_scalars("nu2", nu2, S) if code == fold_in.FAMILIES["gaussian"] else None
+    Vs = np.ascontiguousarray(Vs, dtype=np.float64)
+    return fold_in.evaluate(family, S, R, M, T, K, weights, sums, z=z, seed=seed, summary=summary, q=q, transform=transform,
+                            inner_sweeps=inner_sweeps, first_sample=first_sample, Vs=Vs, nu2=nu2, sigma2=sigma2, device=device)
+
+
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
 from .nmf import factor_pav, tensor_nmf  # noqa: E402,F401
 

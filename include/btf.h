@@ -600,6 +600,33 @@ int btf_collect_functionals(btf_ctx* ctx, int nsamples, int transform, const int
                             double* mean_out, double* var_out, double* q_out, double* defined_out, double* prob_out,
                             double* curves_out, double* pointwise_out);
 
+/* ---- folding new rows into a fitted posterior (csrc/btf_fold_in.h) ---------------------------------------------------
+ * Given V the rows of W are conditionally independent (factor.py:333) with prior N(0, sigma2 I), so a row that was not in
+ * the fitted tensor has, under kept sample s, the conditional _resample_W draws from (factor.py:333-362):
+ *   Q_s = sum_jt count_jt v_jt^s v_jt^s' / nu2_s + I / sigma2_s,  b_s = sum_jt ysum_jt v_jt^s / nu2_s,  Q_s = L L',
+ *   W_out[s][r] = Q_s^-1 b_s + L^-T z  (factor.py:357-362),  Wmean_out[s][r] = Q_s^-1 b_s  (NULL: not wanted).
+ * family 0 Gaussian: count / ysum (R,M,T) = observed replicates of the cell and their sum (0, 0: missing), noise = nu2 and
+ * sigma2 one value per sample; z (S,R,K) standard normals or NULL: Philox keyed (seed, sample0 + s, r).  family 1 Binomial
+ * (factor.py:437-460): trials / ysum (R,M,T) = trials and successes of the observed cells (integers up to 32; 0: missing),
+ * inner_sweeps >= 1 rounds per (s, r) from w = 0 of omega_jt ~ PG(trials_jt, w . v_jt) (exact sampler) and the draw with
+ * weights omega and kappa = ysum - trials / 2; z must be NULL, noise is ignored.  A row without observations draws from
+ * the prior.  sample0: the global index of sample 0 (generator keys only), so that a call over a slice of the samples
+ * returns the bits of the whole call.  mean_out (R,M,T) non-NULL adds the summary stage on the device-resident W_out and
+ * V: mean and percentiles q of f(w_r^s . v_jt^s) exactly as btf_posterior_summary (transform, q, nq, q_out (nq,R,M,T)
+ * as there; nsamples <= 16384 then).  fp64, no floating-point atomics, every sum in a fixed order: two calls return
+ * identical bits whatever the launch geometry and wherever the states come from.  A non-positive pivot: BTF_ENOTPD, and
+ * btf_fail_index (ctx, or NULL after the stateless call) = (sample0 + s) * nrows_new + r of the first such pair.
+ * btf_collect_fold_in reads V, nu2_s and sigma2_s of the first nsamples collected slots without an upload and touches none
+ * of the sampler's state; its launches are counted under BTF_K_CRITERIA.  Synchronous.                                  */
+int btf_fold_in_rows(int device, int family, int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs,
+                     const double* noise, const double* sigma2, const double* count, const double* ysum, const double* trials,
+                     const double* z, unsigned long long seed, int inner_sweeps, long long sample0, double* W_out,
+                     double* Wmean_out, int transform, const double* q, int nq, double* mean_out, double* q_out);
+int btf_collect_fold_in(btf_ctx* ctx, int family, int nsamples, int nrows_new, const double* count, const double* ysum,
+                        const double* trials, const double* z, unsigned long long seed, int inner_sweeps, long long sample0,
+                        double* W_out, double* Wmean_out, int transform, const double* q, int nq, double* mean_out,
+                        double* q_out);
+
 /* ---- convergence diagnostics (csrc/btf_diag.h) ----------------------------------------------------------------------
  * Split R-hat (rank-normalised, max of bulk and folded), bulk ESS, tail ESS (min over the 5 % / 95 % indicators), MCSE of
  * the mean and the mean, per cell of f(W V') over nchains chains of nsamples draws (Vehtari et al. 2021; one chain: its
