@@ -17,7 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")   # override: A/B builds
 SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip"),
            os.path.join(CSRC, "btf_gass_ep.hip"), os.path.join(CSRC, "btf_gamma_grid.hip"), os.path.join(CSRC, "btf_diag.hip"),
-           os.path.join(CSRC, "btf_predict.hip"), os.path.join(CSRC, "btf_functionals.hip"), os.path.join(CSRC, "btf_fold_in.hip")]
+           os.path.join(CSRC, "btf_predict.hip"), os.path.join(CSRC, "btf_functionals.hip"), os.path.join(CSRC, "btf_fold_in.hip"),
+           os.path.join(CSRC, "btf_loo.hip")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -104,6 +105,8 @@ SIGNATURES = {
     "btf_collect_summary": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),
     "btf_crit_set_data": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
     "btf_crit_eval": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "btf_crit_loo": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp,
+                               _c_dp]),
     "btf_predict_batch": (C.c_int, [C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_uint64, _c_dp]),
     "btf_predict_eval": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, C.c_int,
                                    C.c_uint64, _c_dp, C.c_int, _c_ip, C.c_int] + [_c_dp] * 11),
@@ -207,7 +210,7 @@ def build(force=False, verbose=False, jobs=None):
     units += [(SOURCES[2], os.path.join(OBJ_DIR, tag + "_nmf.o"), []), (SOURCES[3], os.path.join(OBJ_DIR, tag + "_gass_ep.o"), [])]
     units += [(SOURCES[4], os.path.join(OBJ_DIR, tag + "_gamma_grid.o"), []), (SOURCES[5], os.path.join(OBJ_DIR, tag + "_diag.o"), [])]
     units += [(SOURCES[6], os.path.join(OBJ_DIR, tag + "_predict.o"), []), (SOURCES[7], os.path.join(OBJ_DIR, tag + "_functionals.o"), [])]
-    units += [(SOURCES[8], os.path.join(OBJ_DIR, tag + "_fold_in.o"), [])]
+    units += [(SOURCES[8], os.path.join(OBJ_DIR, tag + "_fold_in.o"), []), (SOURCES[9], os.path.join(OBJ_DIR, tag + "_loo.o"), [])]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

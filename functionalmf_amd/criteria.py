@@ -13,6 +13,10 @@ csrc/btf_criteria.h (btf_crit_eval).  This module holds the two host halves arou
   combine()     the kernel's per-curve accumulators and per-sample totals -> the dictionary of
                 BayesianTensorFiltering.information_criteria (plain numpy over (N,M)).
 
+  psis_loo_host()  the written definition of the PSIS-LOO kernel (csrc/btf_loo.h, btf_crit_loo): plain numpy / scipy over a
+                (S,N,M) log-likelihood matrix; loo_combine() builds the dictionary of BayesianTensorFiltering.loo()
+                and compare() the paired elpd difference of two models scored on the same data.
+
 It deliberately does not read the sampler's accumulation layouts: those differ by model and data form.
 """
 import numpy as np
@@ -124,3 +128,152 @@ def from_loglik(L, observed, L_at_mean):
             "waic_se": 2.0 * np.sqrt(obs.sum() * np.var(elpd_i)), "dic": 2 * mean_dev - dev_mean, "p_dic": mean_dev - dev_mean,
             "mean_deviance": mean_dev, "deviance_at_mean": dev_mean, "n_curves": int(obs.sum()), "nsamples": S,
             "loglik_per_sample": tot, "curves": {"lppd": lppd, "p_waic": p_waic}}
+
+
+# ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-curve-out (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson,
+# Gelman, Yao, Gabry 2024).  psis_loo_host is the definition; the kernel of csrc/btf_loo.h implements the same steps. ----
+LOO_MAX_SAMPLES = 4096    # LOO_MAX_S of csrc/btf_loo.h (the bound of btf_diag_eval)
+LOO_MIN_TAIL = 5          # fewer tail samples: no Pareto fit, k = inf and the unsmoothed estimate
+
+
+def tail_length(S, r_eff=1.0):
+    """Mt = min(floor(0.2 S), ceil(3 sqrt(S / r_eff))): the number of largest importance ratios the Pareto fit uses."""
+    return int(min(S // 5, np.ceil(3.0 * np.sqrt(S / float(r_eff)))))
+
+
+def gpd_fit(x):
+    """Zhang and Stephens (2009) estimate of the generalised Pareto distribution of the ascending excesses x > 0, with
+    the weak prior of the PSIS paper on the shape.  Returns (k, sigma); (nan, nan) when no grid weight survives."""
+    x = np.asarray(x, dtype=float)
+    n = x.shape[0]
+    m = 30 + int(np.floor(np.sqrt(n)))
+    i = np.arange(1, m + 1, dtype=float)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        b = 1.0 / x[n - 1] + (1.0 - np.sqrt(m / (i - 0.5))) / (3.0 * x[int(np.floor(n / 4.0 + 0.5)) - 1])
+        k = np.log1p(-b[:, None] * x[None, :]).mean(axis=1)
+        l = n * (np.log(-b / k) - k - 1.0)
+        w = 1.0 / np.exp(l[None, :] - l[:, None]).sum(axis=1)
+        keep = w >= 10.0 * np.finfo(float).eps
+        if not keep.any():                                # no grid point survives (a nan in every l_i): no fit
+            return np.nan, np.nan
+        w, b = w[keep], b[keep]
+        w = w / w.sum()
+        bp = (w * b).sum()
+        kp = np.log1p(-bp * x).mean()
+        sigma = -kp / bp
+    return (n * kp + 5.0) / (n + 10.0), sigma
+
+
+def psis_curve(ll, r_eff=1.0):
+    """PSIS-LOO of one curve from its S log-likelihoods: (elpd_loo, pareto_k, normalised log weights (S,)).
+    A nan (or +inf) sample: all nan.  A -inf sample, an infinite importance ratio: elpd_loo = -inf, k = inf, weights nan."""
+    from scipy.special import logsumexp
+    ll = np.asarray(ll, dtype=float)
+    S = ll.shape[0]
+    if np.isnan(ll).any() or (ll == np.inf).any():
+        return np.nan, np.nan, np.full(S, np.nan)
+    if (ll == -np.inf).any():
+        return -np.inf, np.inf, np.full(S, np.nan)
+    lr = -ll
+    lr = lr - lr.max()
+    lw = lr.copy()
+    k = np.inf
+    Mt = tail_length(S, r_eff)
+    if Mt >= LOO_MIN_TAIL:
+        order = np.argsort(lr, kind="stable")             # ascending; ties in lr by ascending sample index
+        cut = max(lr[order[S - Mt - 1]], np.log(np.finfo(float).tiny))
+        tail = order[lr[order] > cut]                     # strictly above: ties with the cut-off stay outside
+        n = tail.shape[0]
+        if n >= LOO_MIN_TAIL:
+            ecut = np.exp(cut)
+            x = np.exp(lr[tail]) - ecut
+            if x[0] > 0.0:
+                kf, sigma = gpd_fit(x)
+                if np.isfinite(kf) and np.isfinite(sigma):
+                    k = kf
+                    p = (np.arange(1, n + 1) - 0.5) / n
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        q = -sigma * np.log1p(-p) if k == 0.0 else sigma * np.expm1(-k * np.log1p(-p)) / k
+                        lw[tail] = np.log(q + ecut)
+    lw = np.minimum(lw, 0.0)                              # truncate at the raw maximum
+    lw = lw - logsumexp(lw)
+    return float(logsumexp(lw + ll)), float(k), lw
+
+
+def psis_loo_host(L, observed, r_eff=1.0, log_weights=False):
+    """PSIS-LOO of every curve of a (S,N,M) log-likelihood matrix, curve by curve on the host (psis_curve).
+
+    observed: (N,M) bool; r_eff: a scalar or (N,M), the relative efficiency of the draws (1: independent).
+    Returns the dictionary of loo_combine (without `mean`)."""
+    from scipy.special import logsumexp
+    L = np.asarray(L, dtype=float)
+    S, N, M = L.shape
+    r = np.broadcast_to(np.asarray(r_eff, dtype=float), (N, M))
+    if not (np.isfinite(r).all() and (r > 0).all()):
+        raise ValueError("r_eff must be finite and > 0")
+    elpd, kk = np.zeros((N, M)), np.zeros((N, M))
+    lw = np.zeros((S, N, M)) if log_weights else None
+    for i in range(N):
+        for j in range(M):
+            elpd[i, j], kk[i, j], w = psis_curve(L[:, i, j], r[i, j])
+            if log_weights:
+                lw[:, i, j] = w
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lppd = logsumexp(L, axis=0) - np.log(S)
+    return loo_combine(elpd, kk, lppd, observed, S, log_weights=lw)
+
+
+def loo_combine(elpd_loo, pareto_k, lppd, observed, nsamples, mean=None, log_weights=None):
+    """The dictionary of BayesianTensorFiltering.loo() from the per-curve (N,M) arrays.  Curves without observations
+    count 0 (pareto_k: nan there) and are left out of n_curves; the totals follow numpy on -inf / nan curves."""
+    obs = np.asarray(observed, dtype=bool)
+    S = int(nsamples)
+    elpd = np.where(obs, np.asarray(elpd_loo, dtype=float), 0.0)
+    lppd = np.where(obs, np.asarray(lppd, dtype=float), 0.0)
+    k = np.where(obs, np.asarray(pareto_k, dtype=float), np.nan)
+    with np.errstate(invalid="ignore"):
+        p_loo = np.where(obs, lppd - elpd, 0.0)
+        n = int(obs.sum())
+        e = elpd[obs]
+        total = float(e.sum())
+        se = float(np.sqrt(n * np.var(e))) if n > 0 else 0.0
+        good_k = min(1.0 - 1.0 / np.log10(S), 0.7) if S > 1 else 0.0
+        n_bad = int((k[obs] > good_k).sum())
+    out = {"elpd_loo": total, "p_loo": float(p_loo[obs].sum()), "looic": -2.0 * total, "se": se, "n_curves": n, "nsamples": S,
+           "good_k": float(good_k), "n_bad": n_bad, "observed": obs.copy(),
+           "curves": {"elpd_loo": elpd, "p_loo": p_loo, "pareto_k": k, "lppd": lppd}}
+    if mean is not None:
+        out["mean"] = mean
+    if log_weights is not None:
+        out["log_weights"] = log_weights
+    return out
+
+
+def _curve_elpd(res):
+    c = res["curves"]
+    return np.asarray(c["elpd_loo"] if "elpd_loo" in c else c["lppd"] - c["p_waic"], dtype=float)
+
+
+def compare(a, b, observed=None):
+    """Paired comparison of two models scored on the same data: a, b are result dictionaries of loo() or
+    information_criteria() (per-curve elpd: curves["elpd_loo"], or curves["lppd"] - curves["p_waic"]).
+    elpd_diff = sum_ij (a_ij - b_ij) over the curves observed in both (positive: a predicts better) and
+    se_diff = sqrt(n var_ij(a_ij - b_ij)), the standard error of that sum.  observed: the (N,M) mask of the curves to
+    compare; None: the curves both results mark as observed."""
+    ea, eb = _curve_elpd(a), _curve_elpd(b)
+    if ea.shape != eb.shape:
+        raise ValueError("compare: the two results score different shapes, %r and %r" % (ea.shape, eb.shape))
+    both = (_curve_observed(a) & _curve_observed(b)) if observed is None else np.asarray(observed, dtype=bool)
+    d = (ea - eb)[both]
+    n = int(both.sum())
+    with np.errstate(invalid="ignore"):
+        return {"elpd_diff": float(d.sum()), "se_diff": float(np.sqrt(n * np.var(d))) if n > 0 else 0.0, "n_curves": n}
+
+
+def _curve_observed(res):
+    """The observed-curve mask of a result dictionary: loo() carries it as `observed`; information_criteria() carries none
+    and sets every per-curve array of an unobserved curve to exactly 0."""
+    if "observed" in res:
+        return np.asarray(res["observed"], dtype=bool)
+    c = res["curves"]
+    return ~np.logical_and.reduce([np.asarray(c[key], dtype=float) == 0.0 for key in ("lppd", "p_waic", "mean_ll", "ll_at_mean") if key in c])

@@ -13,6 +13,7 @@
 #include "btf_fused.h"
 #include "btf_diag.h"         // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
+#include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
@@ -3386,17 +3387,24 @@ int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt,
   return BTF_OK;
 }
 
-int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
-                  const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out) {
-  if (!c || slot < 0 || slot > 1 || family < 0 || family >= CRIT_FAM_COUNT || nsamples < 1 || !curve_out || !total_out ||
-      (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
-    return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
-  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, "btf_crit_eval: no statistics in this slot (btf_crit_set_data)");
-  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_crit_eval needs an unsharded context");
+namespace {
+// the device side of a criteria call: the uploaded states and crit_kernel's outputs, freed on destruction
+struct CritRun {
+  double *dW = nullptr, *dV = nullptr, *dn = nullptr, *dmu = nullptr, *dcurve = nullptr, *dpart = nullptr, *dtot = nullptr, *dpw = nullptr;
+  CritArgs a{};
+  ~CritRun() { for (double* p : {dW, dV, dn, dmu, dcurve, dpart, dtot, dpw}) if (p) (void)hipFree(p); }
+};
+
+// Checks the arguments that btf_crit_eval and btf_crit_loo share, uploads the states and queues crit_kernel (with
+// `reduce` also the plug-in and per-sample-total kernels) on the context's stream.  `who` names the caller in messages.
+int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+             const double* noise, int flags, bool pointwise, bool reduce, CritRun& r) {
+  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, who + ": no statistics in this slot (btf_crit_set_data)");
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, who + " needs an unsharded context");
   const bool current = (flags & BTF_CRIT_CURRENT) != 0, per_sample = (flags & BTF_CRIT_NOISE_PER_SAMPLE) != 0;
   if (current && (Ws || nsamples != 1 || !c->have_W || !c->have_V))
     return fail(c, BTF_EINVAL, "BTF_CRIT_CURRENT scores the context's own W, V: one sample, Ws = Vs = NULL");
-  if (!Ws && !current && (!c->smp_W || nsamples > c->smp_n)) return fail(c, BTF_ESTATE, "btf_crit_eval: not that many collected samples");
+  if (!Ws && !current && (!c->smp_W || nsamples > c->smp_n)) return fail(c, BTF_ESTATE, who + ": not that many collected samples");
   if (per_sample && family != CRIT_FAM_GAUSSIAN) return fail(c, BTF_EINVAL, "per-sample noise is the Gaussian family's");
   if (per_sample && !noise && (Ws || current)) return fail(c, BTF_EINVAL, "per-sample noise of uploaded / current states: pass `noise`");
   if (!per_sample && (family == CRIT_FAM_GAUSSIAN || family == CRIT_FAM_NEGBIN) && !(param > 0.0))
@@ -3406,17 +3414,14 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
   const dim3 grid((N + WAVE - 1) / WAVE, M);
   const int nwg = (int)(grid.x * grid.y);
   const size_t nW = (size_t)S * N * K, nV = (size_t)S * M * T * K, NM = (size_t)N * M;
-  double *dW = nullptr, *dV = nullptr, *dn = nullptr, *dmu = nullptr, *dcurve = nullptr, *dpart = nullptr, *dtot = nullptr, *dpw = nullptr;
-  auto cleanup = [&]() { for (double* p : {dW, dV, dn, dmu, dcurve, dpart, dtot, dpw}) if (p) (void)hipFree(p); };
-#define CE(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-#define CA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) { cleanup(); return rc__; } } while (0)
-  CritArgs a{};
+#define CA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) return rc__; } while (0)
+  CritArgs& a = r.a;
   a.S1 = c->crit_S1[slot]; a.cnt = c->crit_cnt[slot]; a.c0 = c->crit_c0[slot]; a.c1 = c->crit_c1[slot];
   if (Ws) {
-    CA(dW, nW); CA(dV, nV);
-    CE(hipMemcpyAsync(dW, Ws, nW * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    CE(hipMemcpyAsync(dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    a.W = dW; a.V = dV;
+    CA(r.dW, nW); CA(r.dV, nV);
+    HIPCHK(c, hipMemcpyAsync(r.dW, Ws, nW * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    a.W = r.dW; a.V = r.dV;
   } else if (current) {
     a.W = c->W; a.V = c->V;
   } else {
@@ -3425,17 +3430,18 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
   a.noise = nullptr; a.noise_stride = 1;
   if (per_sample) {
     if (noise) {
-      CA(dn, (size_t)S);
-      CE(hipMemcpyAsync(dn, noise, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      a.noise = dn;
+      CA(r.dn, (size_t)S);
+      HIPCHK(c, hipMemcpyAsync(r.dn, noise, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      a.noise = r.dn;
     } else {
       a.noise = c->smp_s + HYP_NU2; a.noise_stride = HYP_COUNT;       // the collected nu2 of every kept state
     }
   }
   a.par = param; a.S = S; a.N = N; a.M = M; a.T = T;
-  CA(dmu, (size_t)M * T * N); CA(dcurve, CRIT_OUT * NM); CA(dpart, (size_t)S * nwg); CA(dtot, (size_t)S);
-  if (pointwise_out) CA(dpw, (size_t)S * NM);
-  a.mu = dmu; a.curve = dcurve; a.tot_part = dpart; a.pw = dpw;
+  CA(r.dmu, (size_t)M * T * N); CA(r.dcurve, CRIT_OUT * NM); CA(r.dpart, (size_t)S * nwg); CA(r.dtot, (size_t)S);
+  if (pointwise) CA(r.dpw, (size_t)S * NM);
+#undef CA
+  a.mu = r.dmu; a.curve = r.dcurve; a.tot_part = r.dpart; a.pw = r.dpw;
 #define CRIT_FAMS(KT_)                                                                                   \
   switch (family) {                                                                                      \
     case 0: p.launch(crit_kernel<KT_, 0>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
@@ -3449,7 +3455,8 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
     K_SWITCH(K, CRIT_FAMS(KT));
   }
 #undef CRIT_FAMS
-  CE(hipGetLastError());
+  HIPCHK(c, hipGetLastError());
+  if (!reduce) return BTF_OK;
   {
     Prof p(c, BTF_K_CRITERIA);
     switch (family) {
@@ -3460,18 +3467,99 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
       default: p.launch(crit_plugin_kernel<4>, grid, dim3(WAVE), 0, a); break;
     }
   }
-  CE(hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   {
     Prof p(c, BTF_K_CRITERIA);
-    p.launch(crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)dpart, S, nwg, dtot);
+    p.launch(crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)r.dpart, S, nwg, r.dtot);
   }
-  CE(hipGetLastError());
-  CE(hipMemcpyAsync(curve_out, dcurve, CRIT_OUT * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  CE(hipMemcpyAsync(total_out, dtot, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (pointwise_out) CE(hipMemcpyAsync(pointwise_out, dpw, (size_t)S * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  CE(hipStreamSynchronize(c->stream));        // (not check_status: the sampler's status word is not this call's)
-#undef CE
-#undef CA
+  HIPCHK(c, hipGetLastError());
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                  const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out) {
+  if (!c || slot < 0 || slot > 1 || family < 0 || family >= CRIT_FAM_COUNT || nsamples < 1 || !curve_out || !total_out ||
+      (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
+    return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
+  CritRun r;
+  int rc = crit_run(c, "btf_crit_eval", slot, family, param, nsamples, Ws, Vs, noise, flags, pointwise_out != nullptr, true, r);
+  if (rc) return rc;
+  const size_t S = (size_t)nsamples, NM = (size_t)c->N * c->M;
+  HIPCHK(c, hipMemcpyAsync(curve_out, r.dcurve, CRIT_OUT * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(total_out, r.dtot, S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (pointwise_out) HIPCHK(c, hipMemcpyAsync(pointwise_out, r.dpw, S * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // (not check_status: the sampler's status word is not this call's)
+  return BTF_OK;
+}
+
+// ---------------------------------------------------------- PSIS-LOO (btf_loo.h)
+int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                 const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
+                 double* logw_out) {
+  if (!c || slot < 0 || slot > 1 || family < 0 || family >= CRIT_FAM_COUNT || nsamples < 1 || !loo_out ||
+      (flags & ~BTF_CRIT_NOISE_PER_SAMPLE) || (!Ws) != (!Vs) || transform < 0 || transform > 2)
+    return fail(c, BTF_EINVAL, "bad btf_crit_loo arguments");
+  if (nsamples > LOO_MAX_S)
+    return fail(c, BTF_EINVAL, "btf_crit_loo: " + std::to_string(nsamples) + " samples, at most " + std::to_string(LOO_MAX_S));
+  const int S = nsamples, N = c->N, M = c->M, T = c->T;
+  const size_t NM = (size_t)N * M;
+  // the tail length Mt = min(floor(0.2 S), ceil(3 sqrt(S / r_eff))) of every curve, on the host: IEEE sqrt and division
+  auto tail = [S](double re) { return (int)std::min((double)(S / 5), std::ceil(3.0 * std::sqrt((double)S / re))); };
+  std::vector<int> mt;
+  if (r_eff) {
+    mt.resize(NM);
+    for (size_t o = 0; o < NM; ++o) {
+      if (!(r_eff[o] > 0.0) || !std::isfinite(r_eff[o]))
+        return fail(c, BTF_EINVAL, "btf_crit_loo: r_eff must be finite and > 0 (curve " + std::to_string(o) + ")");
+      mt[o] = tail(r_eff[o]);
+    }
+  }
+  CritRun r;
+  int rc = crit_run(c, "btf_crit_loo", slot, family, param, nsamples, Ws, Vs, noise, flags, true, false, r);
+  if (rc) return rc;
+  int* dmt = nullptr; double* dloo = nullptr; double* dmean = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)dmt, (void*)dloo, (void*)dmean}) if (p) (void)hipFree(p); };
+#define LE(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+#define LA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) { cleanup(); return rc__; } } while (0)
+  LA(dloo, 2 * NM);
+  if (r_eff) {
+    LA(dmt, NM);
+    LE(hipMemcpyAsync(dmt, mt.data(), NM * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  LooArgs a{};
+  a.pw = r.dpw; a.mt = dmt; a.mt_all = tail(1.0); a.S = S; a.NM = (int)NM; a.out = dloo;
+  a.P = 64; while (a.P < S) a.P <<= 1;
+  a.per_xcd = (int)((NM + 7) / 8);
+  const size_t lds = (size_t)a.P * (2 * sizeof(double) + sizeof(unsigned short));
+  const bool keep_lw = mean_out || logw_out;
+  {
+    Prof p(c, BTF_K_CRITERIA);
+    if (keep_lw) {
+      LE(hipFuncSetAttribute((const void*)loo_psis_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      p.launch(loo_psis_kernel<1>, dim3(8 * a.per_xcd), dim3(WAVE), lds, a);
+    } else {
+      LE(hipFuncSetAttribute((const void*)loo_psis_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      p.launch(loo_psis_kernel<0>, dim3(8 * a.per_xcd), dim3(WAVE), lds, a);
+    }
+  }
+  LE(hipGetLastError());
+  if (mean_out) {
+    LA(dmean, NM * T);
+    LooMeanArgs ma{};
+    ma.lw = r.dpw; ma.W = r.a.W; ma.V = r.a.V; ma.S = S; ma.N = N; ma.M = M; ma.T = T; ma.transform = transform; ma.mean = dmean;
+    Prof p(c, BTF_K_CRITERIA);
+    K_SWITCH(c->K, p.launch(loo_mean_kernel<KT>, dim3((N + WAVE - 1) / WAVE, M), dim3(LOO_WAVES * WAVE), 0, ma));
+    LE(hipGetLastError());
+    LE(hipMemcpyAsync(mean_out, dmean, NM * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  // loo_out: elpd_loo, pareto_k, then crit_kernel's two accumulators of lppd (curve_out[0], [1] of btf_crit_eval)
+  LE(hipMemcpyAsync(loo_out, dloo, 2 * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  LE(hipMemcpyAsync(loo_out + 2 * NM, r.dcurve, 2 * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (logw_out) LE(hipMemcpyAsync(logw_out, r.dpw, (size_t)S * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  LE(hipStreamSynchronize(c->stream));
+#undef LE
+#undef LA
   cleanup();
   return BTF_OK;
 }

@@ -764,7 +764,8 @@ class BayesianTensorFiltering(_BayesianModel):
 
         Returns a dict with waic, elpd_waic, p_waic, lppd, waic_se, dic, p_dic, mean_deviance, deviance_at_mean,
         n_curves, nsamples, loglik_per_sample (S,) and curves = {lppd, p_waic, mean_ll, ll_at_mean} of (N,M) arrays;
-        pointwise=True adds loglik (S,N,M), the full matrix (for PSIS-LOO with outside tools; S*N*M doubles of host memory).
+        pointwise=True adds loglik (S,N,M), the full matrix (S*N*M doubles of host memory; PSIS-LOO from it stays on the
+        device: loo()).
         Device memory: the criteria statistics, 16 B per cell (functionalmf_amd/criteria.py), and 8 B per cell of scratch."""
         self._crit_check()
         if results is None:
@@ -776,6 +777,63 @@ class BayesianTensorFiltering(_BayesianModel):
             Ws, Vs, noise = self._crit_results(results)
             curve, totals, obs, pw = self._crit_eval(data, Ws.shape[0], Ws, Vs, noise, pointwise=pointwise)
         return _criteria.combine(curve, totals, obs, pw)
+
+    def loo(self, results=None, data=None, r_eff=None, mean=False, transform=None, log_weights=False):
+        """PSIS-LOO: Pareto-smoothed importance-sampling leave-one-curve-out (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson,
+        Gelman, Yao, Gabry 2024) on the GPU (csrc/btf_loo.h); functionalmf_amd.criteria.psis_curve is its written definition.
+
+        results, data: as information_criteria, with the same pointwise unit: the curve (i,j) = all observed y_ijtr over
+            depth and replicates; curves without observations count 0 and are left out.
+        r_eff: the relative efficiency of the draws, None (1), a scalar or (N,M); finite and > 0.  It sets the number of
+            largest importance ratios the Pareto fit uses, min(floor(0.2 S), ceil(3 sqrt(S / r_eff))).
+        mean: also return the leave-curve-out fitted curve, mean (N,M,T) = sum_s w_s(i,j) f(w_i^s . v_jt^s) with the smoothed
+            normalised weights - what the model predicts for (i,j) had it not seen that curve; transform: f, as
+            posterior_summary (None / "identity", "ilogit", "square").
+        log_weights: also return the normalised log weights (S,N,M) (S*N*M doubles of host memory).
+
+        Returns a dict: elpd_loo = sum_ij elpd_loo_ij, p_loo = sum (lppd_ij - elpd_loo_ij), looic = -2 elpd_loo,
+        se = sqrt(n_curves var_ij elpd_loo_ij), n_curves, nsamples, good_k = min(1 - 1 / log10(S), 0.7), n_bad = the curves
+        with pareto_k > good_k (their elpd_loo_ij is not to be trusted), observed (N,M) bool, curves = {elpd_loo, p_loo, pareto_k, lppd} of (N,M)
+        arrays (0 for unobserved curves; pareto_k: nan there).  pareto_k = inf: no Pareto fit (S < 25, or every ratio of
+        the curve equal) and the unsmoothed estimate.  A curve with a -inf sample (poisson_identity where w.v <= 0) has
+        elpd_loo = -inf and pareto_k = inf, one with a nan sample nan; both have nan log weights and mean.
+        S <= 4096.  Device memory for the call's duration: 8 S N M bytes (1.05 GB at (512,256,64), S = 1000) beside the
+        criteria statistics.  criteria.compare(a, b) gives the paired elpd difference of two models' results."""
+        family, param, per_sample = self._crit_check()
+        codes = {None: 0, "identity": 0, "ilogit": 1, "square": 2}
+        if transform not in codes:
+            raise ValueError("transform must be None, 'identity', 'ilogit' or 'square', not %r" % (transform,))
+        code = codes[transform]
+        N, M, T = self.nrows, self.ncols, self.ndepth
+        if r_eff is not None:
+            r_eff = np.asarray(r_eff, dtype=float)
+            if r_eff.shape not in ((), (N, M)):
+                raise ValueError("r_eff must be a scalar or a (%d,%d) array" % (N, M))
+            if not (np.all(np.isfinite(r_eff)) and np.all(r_eff > 0)):
+                raise ValueError("r_eff must be finite and > 0")
+            r_eff = _native.as_f64(np.broadcast_to(r_eff, (N, M)))
+        if results is None:
+            S = getattr(self, "_collected", 0)
+            if S < 1:
+                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first)")
+            Ws = Vs = noise = None
+        else:
+            Ws, Vs, noise = self._crit_results(results)
+            S = Ws.shape[0]
+            Ws, Vs = _native.as_f64(Ws), _native.as_f64(Vs)
+        if S > _criteria.LOO_MAX_SAMPLES:
+            raise ValueError("loo: %d samples, at most %d" % (S, _criteria.LOO_MAX_SAMPLES))
+        slot, obs = self._crit_slot(data, family, param)
+        out = np.zeros((4, N, M))
+        mean_out = np.zeros((N, M, T)) if mean else None
+        lw = np.zeros((S, N, M)) if log_weights else None
+        noise = _native.as_f64(np.reshape(noise, -1)) if (per_sample and noise is not None) else None
+        self._ctx.call("btf_crit_loo", slot, int(family), float(param if param is not None else 0.0), int(S), _native.dptr(Ws),
+                       _native.dptr(Vs), _native.dptr(noise), _native.CRIT_NOISE_PER_SAMPLE if per_sample else 0,
+                       _native.dptr(r_eff), code, _native.dptr(out), _native.dptr(mean_out), _native.dptr(lw))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lppd = out[3] + np.log(out[2]) - np.log(S)            # (as criteria.combine forms it: the same bits)
+        return _criteria.loo_combine(out[0], out[1], lppd, obs, S, mean=mean_out, log_weights=lw)
 
     def _crit_results(self, results):
         N, M, T, K = self.nrows, self.ncols, self.ndepth, self.nembeds

@@ -64,7 +64,7 @@ enum {
   BTF_K_EIG = 11,    /* eigen-system of the K x K Gram (spectral sampler)   */
   BTF_K_HYPER = 12,  /* device hyper-parameter draws: Tau2 chain, nu2/sigma2, lam2 */
   BTF_K_ESS = 13,    /* elliptical slice sampling: prior draws, proposals, likelihood passes, decisions */
-  BTF_K_CRITERIA = 14, /* model-selection criteria: per-curve log-likelihood over the kept samples (btf_crit_eval) */
+  BTF_K_CRITERIA = 14, /* model-selection criteria: per-curve log-likelihood over the kept samples (btf_crit_eval, btf_crit_loo) */
   BTF_K_COUNT = 15
 };
 
@@ -679,6 +679,26 @@ enum { BTF_CRIT_NOISE_PER_SAMPLE = 1, BTF_CRIT_CURRENT = 2 };
 int btf_crit_set_data(btf_ctx* ctx, int slot, const double* S1, const double* cnt, const double* curve_c0, const double* curve_c1);
 int btf_crit_eval(btf_ctx* ctx, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
                   const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out);
+
+/* ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-curve-out (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson,
+ * Gelman, Yao, Gabry 2024), csrc/btf_loo.h; the written definition is functionalmf_amd/criteria.py: psis_curve --------
+ * btf_crit_loo: slot, family, param, states, noise and flags as btf_crit_eval (without BTF_CRIT_CURRENT).  The pointwise
+ *   log-likelihoods ll_s(i,j) stay on the device: per curve the log importance ratios -ll are sorted, the largest
+ *   Mt = min(floor(0.2 S), ceil(3 sqrt(S / r_eff))) are replaced by the order statistics of the generalised Pareto
+ *   distribution fitted to them (Zhang and Stephens 2009), every log weight is truncated at the raw maximum and
+ *   elpd_loo = logsumexp_s(lw_s + ll_s) with normalised lw.  r_eff [N][M] (finite, > 0) or NULL: 1 for every curve.
+ *   loo_out [4][N][M]: elpd_loo; the Pareto shape k-hat (inf: no fit - fewer than 5 tail samples, that is S < 25, or
+ *   all ratios equal - and the unsmoothed estimate); then the two accumulators of lppd exactly as curve_out[0], [1] of
+ *   btf_crit_eval (max-shifted sum of exp(ll_s), max), so that the caller forms lppd as it does there, bit for bit.
+ *   A curve with a -inf sample: elpd_loo = -inf, k = inf; with a nan sample: nan; their log weights are nan.
+ *   mean_out (N,M,T) or NULL: the leave-curve-out fitted curve sum_s exp(lw_s(i,j)) f(w_i^s . v_jt^s), f = `transform`
+ *   as btf_posterior_summary (0 identity, 1 ilogit, 2 square); logw_out (S,N,M) or NULL: the normalised log weights.
+ *   nsamples <= 4096.  Device scratch for the call's duration: 8 S N M bytes (1.05 GB at (512,256,64), S = 1000), and
+ *   8 N M T with mean_out.  Touches none of the sampler's state.  No floating-point atomics: two calls return identical
+ *   bits.  Unsharded contexts.  Synchronises.                                                                        */
+int btf_crit_loo(btf_ctx* ctx, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                 const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
+                 double* logw_out);
 
 /* ---- posterior predictive of the observations (flutrends/benchmark.py:60-75, :129-134; politics/benchmark.py:147-172) ----
  * Replicated observations y_rep ~ p(y | theta_s) for every cell and kept sample, reduced on the device to moments, order
