@@ -19,6 +19,7 @@
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
+#include "btf_scratch.h"        // Scratch: the device buffers of one analysis / stateless call
 #include <hip/hip_ext.h>
 #include <unistd.h>
 
@@ -220,8 +221,9 @@ int fail(btf_ctx* c, int code, const std::string& msg) {
 }  // namespace
 
 namespace btf {
-// the error text of the context-free entry points of other compilation units (btf_nmf.hip)
+// the error text of the context-free entry points of other compilation units (btf_nmf.hip), and of Scratch (btf_scratch.h)
 int set_global_error(int code, const std::string& msg) { return fail(nullptr, code, msg); }
+int report_error(btf_ctx* c, int code, const std::string& msg) { return fail(c, code, msg); }
 }  // namespace btf
 
 namespace {
@@ -269,6 +271,36 @@ struct Prof {
     else hipLaunchKernelGGL(kernel, grid, block, (unsigned)lds, st, args...);
   }
 };
+
+// One launch of an analysis entry point on its scratch's stream: counted under kid when the call has a context, and not
+// made at all once an allocation or copy of the scratch has failed.
+template <typename F, typename... Args>
+void launch_counted(Scratch& s, int kid, F kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
+  if (!s.ctx()) return s.launch(kernel, grid, block, lds, args...);
+  if (s.rc()) return;
+  { Prof p(s.ctx(), kid); p.launch_on(s.stream(), kernel, grid, block, lds, args...); }
+  s.check(hipGetLastError(), "hipGetLastError (kernel launch)");
+}
+// dynamic LDS beyond the default 64 KiB has to be allowed per kernel
+template <typename F>
+void allow_lds(Scratch& s, F kernel, size_t lds) {
+  s.check(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute");
+}
+
+// LDS geometry of the kernels that sort the n values of a cell in a row of P doubles: P the power of two >= n (and >= 2),
+// as many cells per workgroup as `budget` bytes hold, at least one (a row over the budget still gets its workgroup) and at
+// most `cap`.
+struct SortGeom { int P, cells; size_t lds; };
+SortGeom sort_geom(int n, size_t budget, int cap) {
+  SortGeom g;
+  g.P = 2;
+  while (g.P < n) g.P <<= 1;
+  g.cells = std::max(1, std::min(cap, (int)(budget / ((size_t)g.P * sizeof(double)))));
+  g.lds = (size_t)g.cells * g.P * sizeof(double);
+  return g;
+}
+constexpr size_t SUMMARY_SORT_LDS = 128 * 1024, PRED_SORT_LDS = 64 * 1024;
+constexpr int SUMMARY_SORT_CELLS = 16, PRED_SORT_CELLS = 16;
 
 // Delta' diag(lambda) Delta stencil: for every (t,d), d = 0..tf+1, the Delta rows r that
 // touch both t and t+d with the coefficient product Delta[r,t]*Delta[r,t+d].
@@ -823,6 +855,17 @@ void launch_ess_ll(btf_ctx* c, int what, int mode, int link, int nbx) {
     case 10: { constexpr int KT = 10; CALL; } break;               \
     default: break;                                                \
   }
+// the same over the five likelihood families of the criteria and predictive kernels (CRIT_FAM_* / PRED_FAM_*), as FT
+#define FAM_SWITCH(F, CALL)                                        \
+  switch (F) {                                                     \
+    case 0: { constexpr int FT = 0; CALL; } break;                 \
+    case 1: { constexpr int FT = 1; CALL; } break;                 \
+    case 2: { constexpr int FT = 2; CALL; } break;                 \
+    case 3: { constexpr int FT = 3; CALL; } break;                 \
+    case 4: { constexpr int FT = 4; CALL; } break;                 \
+    default: break;                                                \
+  }
+static_assert(CRIT_FAM_COUNT == 5 && PRED_FAM_COUNT == 5, "FAM_SWITCH covers families 0..4");
 
 int check_status(btf_ctx* c) {
   int st[2] = {0, -1};
@@ -3323,45 +3366,59 @@ int btf_collect_end(btf_ctx* c, int nsamples, double* W, double* V, double* Tau2
   return check_status(c);
 }
 
+namespace {
+// posterior_summary_kernel on device states W (S,rows,K), V (S,MT,K), on the scratch's stream: the one place that launches it
+void launch_summary(Scratch& s, const double* W, const double* V, int S, int rows, int MT, int K, int transform, const double* dq,
+                    int nq, double* mean, double* quant) {
+  const SortGeom g = sort_geom(S, SUMMARY_SORT_LDS, SUMMARY_SORT_CELLS);
+  const dim3 grid((MT + g.cells - 1) / g.cells, rows);
+  K_SWITCH(K, {
+    const auto kern = posterior_summary_kernel<KT>;
+    allow_lds(s, kern, g.lds);
+    s.launch(kern, grid, dim3(256), g.lds, W, V, S, rows, MT, g.P, g.cells, transform, dq, nq, mean, quant);
+  });
+}
+
+// the summary of btf_posterior_summary, btf_collect_summary and fold-in's last stage: its buffers, the launch, the downloads
+void summary_stage(Scratch& s, const double* W, const double* V, int S, int rows, int MT, int K, int transform, const double* q,
+                   int nq, double* mean_out, double* q_out) {
+  const size_t n = (size_t)rows * MT;
+  double* dm = s.alloc<double>(n);
+  const double* dq = nq ? s.upload(q, (size_t)nq) : s.alloc<double>(1);
+  double* dqo = s.alloc<double>((size_t)nq * n);
+  launch_summary(s, W, V, S, rows, MT, K, transform, dq, nq, dm, dqo);
+  s.download(mean_out, dm, n);
+  if (nq) s.download(q_out, dqo, (size_t)nq * n);
+}
+
+// Which states an analysis call reads and where its per-sample noise lies: the uploaded Ws / Vs, else the context's
+// current W / V (`current`), else the collected ones; the uploaded `noise` (`per` values a sample), else the collected
+// nu2 of every kept state.  The callers have refused what they do not take.
+struct States { const double *W, *V, *noise; long long noise_stride; };
+States resolve_states(btf_ctx* c, Scratch& s, int S, const double* Ws, const double* Vs, bool current, bool per_sample,
+                      const double* noise, size_t per) {
+  States r = {c->smp_W, c->smp_V, nullptr, 1};
+  if (Ws) {
+    r.W = s.upload(Ws, (size_t)S * c->N * c->K);
+    r.V = s.upload(Vs, (size_t)S * c->M * c->T * c->K);
+  } else if (current) {
+    r.W = c->W; r.V = c->V;
+  }
+  if (per_sample && noise) { r.noise = s.upload(noise, (size_t)S * per); r.noise_stride = (long long)per; }
+  else if (per_sample) { r.noise = c->smp_s + HYP_NU2; r.noise_stride = HYP_COUNT; }
+  return r;
+}
+}  // namespace
+
 // posterior summaries straight from the collected samples (no upload); see btf_posterior_summary
 int btf_collect_summary(btf_ctx* c, int nsamples, int transform, const double* q, int nq, double* mean_out, double* q_out) {
   if (!c || nsamples < 1 || nsamples > c->smp_n || nsamples > 16384 || !mean_out || nq < 0 || (nq > 0 && (!q || !q_out)) ||
       transform < 0 || transform > 2)
     return fail(c, BTF_EINVAL, "bad collect_summary arguments");
   HIPCHK(c, hipSetDevice(c->dev));
-  const int MT = c->M * c->T;
-  const size_t cellsN = (size_t)c->N * MT;
-  double *dq = nullptr, *dm = nullptr, *dqo = nullptr;
-  int rc;
-  if ((rc = dev_alloc(c, &dm, cellsN))) return rc;
-  if ((rc = dev_alloc(c, &dq, (size_t)std::max(nq, 1)))) { (void)hipFree(dm); return rc; }
-  if ((rc = dev_alloc(c, &dqo, std::max<size_t>(1, (size_t)nq * cellsN)))) { (void)hipFree(dm); (void)hipFree(dq); return rc; }
-  auto cleanup = [&]() { (void)hipFree(dm); (void)hipFree(dq); (void)hipFree(dqo); };
-#define CS(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  if (nq) CS(hipMemcpyAsync(dq, q, (size_t)nq * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  int P = 2;
-  while (P < nsamples) P <<= 1;
-  const int cells = std::max(1, std::min(16, (int)((128 * 1024) / ((size_t)P * sizeof(double)))));
-  const size_t lds = (size_t)cells * P * sizeof(double);
-  dim3 grid((MT + cells - 1) / cells, c->N);
-#define CS_LAUNCH(KT_)                                                                                           \
-  case KT_: {                                                                                                    \
-    CS(hipFuncSetAttribute((const void*)posterior_summary_kernel<KT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(posterior_summary_kernel<KT_>, grid, dim3(256), lds, c->stream, (const double*)c->smp_W,  \
-                       (const double*)c->smp_V, nsamples, c->N, MT, P, cells, transform, (const double*)dq, nq, dm, dqo); \
-  } break;
-  switch (c->K) {
-    CS_LAUNCH(1) CS_LAUNCH(2) CS_LAUNCH(3) CS_LAUNCH(4) CS_LAUNCH(5) CS_LAUNCH(6) CS_LAUNCH(7) CS_LAUNCH(8) CS_LAUNCH(9) CS_LAUNCH(10)
-    default: break;
-  }
-#undef CS_LAUNCH
-  CS(hipGetLastError());
-  CS(hipMemcpyAsync(mean_out, dm, cellsN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (nq) CS(hipMemcpyAsync(q_out, dqo, (size_t)nq * cellsN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  CS(hipStreamSynchronize(c->stream));
-#undef CS
-  cleanup();
-  return BTF_OK;
+  Scratch s(c, c->stream);
+  summary_stage(s, c->smp_W, c->smp_V, nsamples, c->N, c->M * c->T, c->K, transform, q, nq, mean_out, q_out);
+  return s.finish();
 }
 
 // ---------------------------------------------------------- model-selection criteria (btf_criteria.h)
@@ -3388,11 +3445,12 @@ int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt,
 }
 
 namespace {
-// the device side of a criteria call: the uploaded states and crit_kernel's outputs, freed on destruction
+// the device side of a criteria call: its scratch (the uploaded states, crit_kernel's outputs) and the kernels' arguments
 struct CritRun {
-  double *dW = nullptr, *dV = nullptr, *dn = nullptr, *dmu = nullptr, *dcurve = nullptr, *dpart = nullptr, *dtot = nullptr, *dpw = nullptr;
+  Scratch s;
   CritArgs a{};
-  ~CritRun() { for (double* p : {dW, dV, dn, dmu, dcurve, dpart, dtot, dpw}) if (p) (void)hipFree(p); }
+  double* tot = nullptr;      // [S] per-sample totals (crit_total_kernel)
+  explicit CritRun(btf_ctx* c) : s(c, c->stream) {}
 };
 
 // Checks the arguments that btf_crit_eval and btf_crit_loo share, uploads the states and queues crit_kernel (with
@@ -3413,67 +3471,22 @@ int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double pa
   const int S = nsamples, N = c->N, M = c->M, T = c->T, K = c->K;
   const dim3 grid((N + WAVE - 1) / WAVE, M);
   const int nwg = (int)(grid.x * grid.y);
-  const size_t nW = (size_t)S * N * K, nV = (size_t)S * M * T * K, NM = (size_t)N * M;
-#define CA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) return rc__; } while (0)
+  const size_t NM = (size_t)N * M;
+  Scratch& s = r.s;
   CritArgs& a = r.a;
   a.S1 = c->crit_S1[slot]; a.cnt = c->crit_cnt[slot]; a.c0 = c->crit_c0[slot]; a.c1 = c->crit_c1[slot];
-  if (Ws) {
-    CA(r.dW, nW); CA(r.dV, nV);
-    HIPCHK(c, hipMemcpyAsync(r.dW, Ws, nW * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(r.dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    a.W = r.dW; a.V = r.dV;
-  } else if (current) {
-    a.W = c->W; a.V = c->V;
-  } else {
-    a.W = c->smp_W; a.V = c->smp_V;
-  }
-  a.noise = nullptr; a.noise_stride = 1;
-  if (per_sample) {
-    if (noise) {
-      CA(r.dn, (size_t)S);
-      HIPCHK(c, hipMemcpyAsync(r.dn, noise, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      a.noise = r.dn;
-    } else {
-      a.noise = c->smp_s + HYP_NU2; a.noise_stride = HYP_COUNT;       // the collected nu2 of every kept state
-    }
-  }
+  const States st = resolve_states(c, s, S, Ws, Vs, current, per_sample, noise, 1);
+  a.W = st.W; a.V = st.V; a.noise = st.noise; a.noise_stride = st.noise_stride;
   a.par = param; a.S = S; a.N = N; a.M = M; a.T = T;
-  CA(r.dmu, (size_t)M * T * N); CA(r.dcurve, CRIT_OUT * NM); CA(r.dpart, (size_t)S * nwg); CA(r.dtot, (size_t)S);
-  if (pointwise) CA(r.dpw, (size_t)S * NM);
-#undef CA
-  a.mu = r.dmu; a.curve = r.dcurve; a.tot_part = r.dpart; a.pw = r.dpw;
-#define CRIT_FAMS(KT_)                                                                                   \
-  switch (family) {                                                                                      \
-    case 0: p.launch(crit_kernel<KT_, 0>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
-    case 1: p.launch(crit_kernel<KT_, 1>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
-    case 2: p.launch(crit_kernel<KT_, 2>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
-    case 3: p.launch(crit_kernel<KT_, 3>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                   \
-    default: p.launch(crit_kernel<KT_, 4>, grid, dim3(CRIT_WAVES * WAVE), 0, a); break;                  \
+  a.mu = s.alloc<double>((size_t)M * T * N); a.curve = s.alloc<double>(CRIT_OUT * NM);
+  a.tot_part = s.alloc<double>((size_t)S * nwg); r.tot = s.alloc<double>((size_t)S);
+  if (pointwise) a.pw = s.alloc<double>((size_t)S * NM);
+  K_SWITCH(K, FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_kernel<KT, FT>, grid, dim3(CRIT_WAVES * WAVE), 0, a)));
+  if (reduce) {
+    FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_plugin_kernel<FT>, grid, dim3(WAVE), 0, a));
+    launch_counted(s, BTF_K_CRITERIA, crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.tot_part, S, nwg, r.tot);
   }
-  {
-    Prof p(c, BTF_K_CRITERIA);
-    K_SWITCH(K, CRIT_FAMS(KT));
-  }
-#undef CRIT_FAMS
-  HIPCHK(c, hipGetLastError());
-  if (!reduce) return BTF_OK;
-  {
-    Prof p(c, BTF_K_CRITERIA);
-    switch (family) {
-      case 0: p.launch(crit_plugin_kernel<0>, grid, dim3(WAVE), 0, a); break;
-      case 1: p.launch(crit_plugin_kernel<1>, grid, dim3(WAVE), 0, a); break;
-      case 2: p.launch(crit_plugin_kernel<2>, grid, dim3(WAVE), 0, a); break;
-      case 3: p.launch(crit_plugin_kernel<3>, grid, dim3(WAVE), 0, a); break;
-      default: p.launch(crit_plugin_kernel<4>, grid, dim3(WAVE), 0, a); break;
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  {
-    Prof p(c, BTF_K_CRITERIA);
-    p.launch(crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)r.dpart, S, nwg, r.dtot);
-  }
-  HIPCHK(c, hipGetLastError());
-  return BTF_OK;
+  return s.rc();
 }
 }  // namespace
 
@@ -3482,15 +3495,14 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
   if (!c || slot < 0 || slot > 1 || family < 0 || family >= CRIT_FAM_COUNT || nsamples < 1 || !curve_out || !total_out ||
       (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
     return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
-  CritRun r;
+  CritRun r(c);
   int rc = crit_run(c, "btf_crit_eval", slot, family, param, nsamples, Ws, Vs, noise, flags, pointwise_out != nullptr, true, r);
   if (rc) return rc;
   const size_t S = (size_t)nsamples, NM = (size_t)c->N * c->M;
-  HIPCHK(c, hipMemcpyAsync(curve_out, r.dcurve, CRIT_OUT * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(total_out, r.dtot, S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (pointwise_out) HIPCHK(c, hipMemcpyAsync(pointwise_out, r.dpw, S * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));        // (not check_status: the sampler's status word is not this call's)
-  return BTF_OK;
+  r.s.download(curve_out, r.a.curve, CRIT_OUT * NM);
+  r.s.download(total_out, r.tot, S);
+  r.s.download(pointwise_out, r.a.pw, S * NM);
+  return r.s.finish();        // (not check_status: the sampler's status word is not this call's)
 }
 
 // ---------------------------------------------------------- PSIS-LOO (btf_loo.h)
@@ -3515,53 +3527,31 @@ int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, c
       mt[o] = tail(r_eff[o]);
     }
   }
-  CritRun r;
+  CritRun r(c);
   int rc = crit_run(c, "btf_crit_loo", slot, family, param, nsamples, Ws, Vs, noise, flags, true, false, r);
   if (rc) return rc;
-  int* dmt = nullptr; double* dloo = nullptr; double* dmean = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)dmt, (void*)dloo, (void*)dmean}) if (p) (void)hipFree(p); };
-#define LE(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-#define LA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) { cleanup(); return rc__; } } while (0)
-  LA(dloo, 2 * NM);
-  if (r_eff) {
-    LA(dmt, NM);
-    LE(hipMemcpyAsync(dmt, mt.data(), NM * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
+  Scratch& s = r.s;
+  double* dloo = s.alloc<double>(2 * NM);
   LooArgs a{};
-  a.pw = r.dpw; a.mt = dmt; a.mt_all = tail(1.0); a.S = S; a.NM = (int)NM; a.out = dloo;
+  a.pw = r.a.pw; a.mt = r_eff ? s.upload(mt.data(), NM) : nullptr; a.mt_all = tail(1.0); a.S = S; a.NM = (int)NM; a.out = dloo;
   a.P = 64; while (a.P < S) a.P <<= 1;
   a.per_xcd = (int)((NM + 7) / 8);
   const size_t lds = (size_t)a.P * (2 * sizeof(double) + sizeof(unsigned short));
-  const bool keep_lw = mean_out || logw_out;
-  {
-    Prof p(c, BTF_K_CRITERIA);
-    if (keep_lw) {
-      LE(hipFuncSetAttribute((const void*)loo_psis_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      p.launch(loo_psis_kernel<1>, dim3(8 * a.per_xcd), dim3(WAVE), lds, a);
-    } else {
-      LE(hipFuncSetAttribute((const void*)loo_psis_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      p.launch(loo_psis_kernel<0>, dim3(8 * a.per_xcd), dim3(WAVE), lds, a);
-    }
-  }
-  LE(hipGetLastError());
+  void (*const psis)(LooArgs) = (mean_out || logw_out) ? loo_psis_kernel<1> : loo_psis_kernel<0>;      // <1> keeps the log weights
+  allow_lds(s, psis, lds);
+  launch_counted(s, BTF_K_CRITERIA, psis, dim3(8 * a.per_xcd), dim3(WAVE), lds, a);
   if (mean_out) {
-    LA(dmean, NM * T);
     LooMeanArgs ma{};
-    ma.lw = r.dpw; ma.W = r.a.W; ma.V = r.a.V; ma.S = S; ma.N = N; ma.M = M; ma.T = T; ma.transform = transform; ma.mean = dmean;
-    Prof p(c, BTF_K_CRITERIA);
-    K_SWITCH(c->K, p.launch(loo_mean_kernel<KT>, dim3((N + WAVE - 1) / WAVE, M), dim3(LOO_WAVES * WAVE), 0, ma));
-    LE(hipGetLastError());
-    LE(hipMemcpyAsync(mean_out, dmean, NM * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ma.lw = r.a.pw; ma.W = r.a.W; ma.V = r.a.V; ma.S = S; ma.N = N; ma.M = M; ma.T = T; ma.transform = transform;
+    ma.mean = s.alloc<double>(NM * T);
+    K_SWITCH(c->K, launch_counted(s, BTF_K_CRITERIA, loo_mean_kernel<KT>, dim3((N + WAVE - 1) / WAVE, M), dim3(LOO_WAVES * WAVE), 0, ma));
+    s.download(mean_out, ma.mean, NM * T);
   }
   // loo_out: elpd_loo, pareto_k, then crit_kernel's two accumulators of lppd (curve_out[0], [1] of btf_crit_eval)
-  LE(hipMemcpyAsync(loo_out, dloo, 2 * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  LE(hipMemcpyAsync(loo_out + 2 * NM, r.dcurve, 2 * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (logw_out) LE(hipMemcpyAsync(logw_out, r.dpw, (size_t)S * NM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  LE(hipStreamSynchronize(c->stream));
-#undef LE
-#undef LA
-  cleanup();
-  return BTF_OK;
+  s.download(loo_out, dloo, 2 * NM);
+  s.download(loo_out + 2 * NM, r.a.curve, 2 * NM);
+  s.download(logw_out, r.a.pw, (size_t)S * NM);
+  return s.finish();
 }
 
 // ---------------------------------------------------------- posterior predictive (btf_predict.h)
@@ -3569,28 +3559,13 @@ int btf_predict_batch(int device, int family, int64_t n, const double* eta, cons
   if (family < 0 || family >= PRED_FAM_COUNT || n < 1 || !eta || !aux || !out) return fail(nullptr, BTF_EINVAL, "bad predict_batch arguments");
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  double *de = nullptr, *da = nullptr, *dout = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)de, (void*)da, (void*)dout}) if (p) (void)hipFree(p); };
-#define PB(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  PB(hipMalloc((void**)&de, n * sizeof(double)));
-  PB(hipMalloc((void**)&da, n * sizeof(double)));
-  PB(hipMalloc((void**)&dout, n * sizeof(double)));
-  PB(hipMemcpy(de, eta, n * sizeof(double), hipMemcpyHostToDevice));
-  PB(hipMemcpy(da, aux, n * sizeof(double), hipMemcpyHostToDevice));
+  Scratch s(nullptr, nullptr);
+  const double *de = s.upload(eta, (size_t)n), *da = s.upload(aux, (size_t)n);
+  double* dout = s.alloc<double>((size_t)n);
   const dim3 grid((unsigned)((n + PRED_THREADS - 1) / PRED_THREADS)), block(PRED_THREADS);
-  switch (family) {
-    case 0: hipLaunchKernelGGL(pred_batch_kernel<0>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
-    case 1: hipLaunchKernelGGL(pred_batch_kernel<1>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
-    case 2: hipLaunchKernelGGL(pred_batch_kernel<2>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
-    case 3: hipLaunchKernelGGL(pred_batch_kernel<3>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
-    default: hipLaunchKernelGGL(pred_batch_kernel<4>, grid, block, 0, 0, (const double*)de, (const double*)da, (long long)n, (unsigned long long)seed, dout); break;
-  }
-  PB(hipGetLastError());
-  PB(hipDeviceSynchronize());
-  PB(hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost));
-#undef PB
-  cleanup();
-  return BTF_OK;
+  FAM_SWITCH(family, s.launch(pred_batch_kernel<FT>, grid, block, 0, de, da, (long long)n, (unsigned long long)seed, dout));
+  s.download(out, dout, (size_t)n);
+  return s.finish();
 }
 
 int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const double* Ws, const double* Vs,
@@ -3630,84 +3605,43 @@ int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const d
     a.aux_n0 = (aux_flags & BTF_PRED_AUX_ROWS) ? N : 1; a.aux_n1 = (aux_flags & BTF_PRED_AUX_COLS) ? M : 1; a.aux_n2 = (aux_flags & BTF_PRED_AUX_DEPTH) ? T : 1;
   }
   const size_t naux = (size_t)a.aux_n0 * a.aux_n1 * a.aux_n2;
-  int P = 2;
-  while (P < n) P <<= 1;
-  const int wcells = std::max(1, std::min(16, (int)((64 * 1024) / ((size_t)P * sizeof(double)))));
-  const size_t lds = (size_t)wcells * P * sizeof(double);
-  const size_t nblk = (size_t)N * ((MT + wcells - 1) / wcells);
+  const SortGeom g = sort_geom(n, PRED_SORT_LDS, PRED_SORT_CELLS);
+  const size_t nblk = (size_t)N * ((MT + g.cells - 1) / g.cells);
   if (nblk > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: too many workgroups for one launch");
   const int chunks = (int)((ncell + PRED_SCORE_CELLS - 1) / PRED_SCORE_CELLS);
   const bool score = rmse_out || mae_out;
-  double *dW = nullptr, *dV = nullptr, *daux = nullptr, *dtr = nullptr, *dY = nullptr, *dq = nullptr, *dmean = nullptr, *dym = nullptr,
-         *dyv = nullptr, *dqo = nullptr, *dpl = nullptr, *dph = nullptr, *din = nullptr, *dno = nullptr, *ddr = nullptr, *dpart = nullptr,
-         *dsc = nullptr;
-  int* dlist = nullptr;
-  auto cleanup = [&]() {
-    for (double* p : {dW, dV, daux, dtr, dY, dq, dmean, dym, dyv, dqo, dpl, dph, din, dno, ddr, dpart, dsc}) if (p) (void)hipFree(p);
-    if (dlist) (void)hipFree(dlist);
-  };
-#define PE(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-#define PA(p, n) do { int rc__ = dev_alloc(c, &(p), (n)); if (rc__) { cleanup(); return rc__; } } while (0)
-#define PUP(d, h, n) do { PA(d, (n)); PE(hipMemcpyAsync(d, h, (size_t)(n) * sizeof(double), hipMemcpyHostToDevice, c->stream)); } while (0)
-  if (Ws) {
-    PUP(dW, Ws, (size_t)S * N * K); PUP(dV, Vs, (size_t)S * MT * K);
-    a.W = dW; a.V = dV;
-  } else {
-    a.W = c->smp_W; a.V = c->smp_V;
-  }
-  a.aux = nullptr; a.aux_stride = 1;
-  if (per_sample) {
-    if (aux_sample) { PUP(daux, aux_sample, (size_t)S * naux); a.aux = daux; a.aux_stride = (long long)naux; }
-    else { a.aux = c->smp_s + HYP_NU2; a.aux_stride = HYP_COUNT; }          // the collected nu2 of every kept state
-  }
-  if (trials) { PUP(dtr, trials, ncell); a.trials = dtr; }
-  if (Y) { PUP(dY, Y, ncell * (size_t)nreps); a.Y = dY; a.nreps = nreps; }
-  if (nq) { PUP(dq, q, (size_t)nq); a.q = dq; }
+  Scratch s(c, c->stream);
+  const States st = resolve_states(c, s, S, Ws, Vs, false, per_sample, aux_sample, naux);
+  a.W = st.W; a.V = st.V; a.aux = st.noise; a.aux_stride = st.noise_stride;
+  if (trials) a.trials = s.upload(trials, ncell);
+  if (Y) { a.Y = s.upload(Y, ncell * (size_t)nreps); a.nreps = nreps; }
+  if (nq) a.q = s.upload(q, (size_t)nq);
   a.nq = nq;
-  if (ncells) {
-    PA(dlist, (size_t)ncells);
-    PE(hipMemcpyAsync(dlist, cells, (size_t)ncells * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    PA(ddr, (size_t)ncells * n);
-    a.list = dlist; a.nlist = ncells; a.draws = ddr;
-  }
-  if (mean_out) { PA(dmean, ncell); a.mean = dmean; }
-  if (ymean_out) { PA(dym, ncell); a.y_mean = dym; }
-  if (yvar_out) { PA(dyv, ncell); a.y_var = dyv; }
-  if (q_out) { PA(dqo, (size_t)nq * ncell); a.quant = dqo; }
-  if (pit_lo_out) { PA(dpl, ncell); a.pit_lo = dpl; }
-  if (pit_hi_out) { PA(dph, ncell); a.pit_hi = dph; }
-  if (inside_out) { PA(din, ncell); a.inside = din; }
-  if (nobs_out) { PA(dno, ncell); a.nobs = dno; }
-  if (score) { PA(dpart, (size_t)3 * S * chunks); PA(dsc, (size_t)2 * S); a.score_part = dpart; }
-  a.par = param; a.S = S; a.R = R; a.N = N; a.M = M; a.T = T; a.K = K; a.P = P; a.cells = wcells; a.seed = seed; a.chunks = chunks;
-#define PRED_LAUNCH(F)                                                                                                      \
-  case F: {                                                                                                                 \
-    PE(hipFuncSetAttribute((const void*)pred_kernel<F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
-    hipLaunchKernelGGL(pred_kernel<F>, dim3((unsigned)nblk), dim3(PRED_THREADS), lds, c->stream, a);                        \
-    PE(hipGetLastError());                                                                                                  \
-    if (score) {                                                                                                            \
-      hipLaunchKernelGGL(pred_score_kernel<F>, dim3(chunks, S), dim3(PRED_THREADS), 0, c->stream, a);                       \
-      PE(hipGetLastError());                                                                                                \
-    }                                                                                                                       \
-  } break;
-  switch (family) { PRED_LAUNCH(0) PRED_LAUNCH(1) PRED_LAUNCH(2) PRED_LAUNCH(3) PRED_LAUNCH(4) default: break; }
-#undef PRED_LAUNCH
-  if (score) {
-    hipLaunchKernelGGL(pred_score_total_kernel, dim3((S + 255) / 256), dim3(256), 0, c->stream, (const double*)dpart, S, chunks, dsc);
-    PE(hipGetLastError());
-  }
-#define PDN(h, d, n) do { if (h) PE(hipMemcpyAsync(h, d, (size_t)(n) * sizeof(double), hipMemcpyDeviceToHost, c->stream)); } while (0)
-  PDN(mean_out, dmean, ncell); PDN(ymean_out, dym, ncell); PDN(yvar_out, dyv, ncell); PDN(q_out, dqo, (size_t)nq * ncell);
-  PDN(pit_lo_out, dpl, ncell); PDN(pit_hi_out, dph, ncell); PDN(inside_out, din, ncell); PDN(nobs_out, dno, ncell);
-  PDN(rmse_out, dsc, S); PDN(mae_out, dsc + S, S);
-  if (ncells) PDN(draws_out, ddr, (size_t)ncells * n);
-  PE(hipStreamSynchronize(c->stream));        // (not check_status: the sampler's status word is not this call's)
-#undef PDN
-#undef PUP
-#undef PA
-#undef PE
-  cleanup();
-  return BTF_OK;
+  if (ncells) { a.list = s.upload(cells, (size_t)ncells); a.nlist = ncells; a.draws = s.alloc<double>((size_t)ncells * n); }
+  if (mean_out) a.mean = s.alloc<double>(ncell);
+  if (ymean_out) a.y_mean = s.alloc<double>(ncell);
+  if (yvar_out) a.y_var = s.alloc<double>(ncell);
+  if (q_out) a.quant = s.alloc<double>((size_t)nq * ncell);
+  if (pit_lo_out) a.pit_lo = s.alloc<double>(ncell);
+  if (pit_hi_out) a.pit_hi = s.alloc<double>(ncell);
+  if (inside_out) a.inside = s.alloc<double>(ncell);
+  if (nobs_out) a.nobs = s.alloc<double>(ncell);
+  double* dsc = nullptr;      // [rmse | mae] per sample
+  if (score) { a.score_part = s.alloc<double>((size_t)3 * S * chunks); dsc = s.alloc<double>((size_t)2 * S); }
+  a.par = param; a.S = S; a.R = R; a.N = N; a.M = M; a.T = T; a.K = K; a.P = g.P; a.cells = g.cells; a.seed = seed; a.chunks = chunks;
+  FAM_SWITCH(family, {
+    allow_lds(s, pred_kernel<FT>, g.lds);
+    s.launch(pred_kernel<FT>, dim3((unsigned)nblk), dim3(PRED_THREADS), g.lds, a);
+    if (score) s.launch(pred_score_kernel<FT>, dim3(chunks, S), dim3(PRED_THREADS), 0, a);
+  });
+  if (score) s.launch(pred_score_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.score_part, S, chunks, dsc);
+  s.download(mean_out, a.mean, ncell); s.download(ymean_out, a.y_mean, ncell); s.download(yvar_out, a.y_var, ncell);
+  s.download(q_out, a.quant, (size_t)nq * ncell);
+  s.download(pit_lo_out, a.pit_lo, ncell); s.download(pit_hi_out, a.pit_hi, ncell); s.download(inside_out, a.inside, ncell);
+  s.download(nobs_out, a.nobs, ncell);
+  if (score && !s.rc()) { s.download(rmse_out, dsc, (size_t)S); s.download(mae_out, dsc + S, (size_t)S); }
+  if (ncells) s.download(draws_out, a.draws, (size_t)ncells * n);
+  return s.finish();        // (not check_status: the sampler's status word is not this call's)
 }
 
 // ---------------------------------------------------------- device-resident scalars
@@ -3962,42 +3896,11 @@ int btf_posterior_summary(int device, int nsamples, int nrows, int ncols, int nd
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   const int MT = ncols * ndepth;
-  const size_t cellsN = (size_t)nrows * MT;
-  double *dW = nullptr, *dV = nullptr, *dq = nullptr, *dm = nullptr, *dqo = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)dW, (void*)dV, (void*)dq, (void*)dm, (void*)dqo}) if (p) (void)hipFree(p); };
-#define PS(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  const size_t nW = (size_t)nsamples * nrows * nembeds, nV = (size_t)nsamples * MT * nembeds;
-  PS(hipMalloc((void**)&dW, nW * sizeof(double)));
-  PS(hipMalloc((void**)&dV, nV * sizeof(double)));
-  PS(hipMalloc((void**)&dm, cellsN * sizeof(double)));
-  PS(hipMalloc((void**)&dq, (size_t)std::max(nq, 1) * sizeof(double)));
-  PS(hipMalloc((void**)&dqo, std::max<size_t>(1, (size_t)nq * cellsN) * sizeof(double)));
-  PS(hipMemcpy(dW, Ws, nW * sizeof(double), hipMemcpyHostToDevice));
-  PS(hipMemcpy(dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice));
-  if (nq) PS(hipMemcpy(dq, q, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
-  int P = 2;
-  while (P < nsamples) P <<= 1;
-  const int cells = std::max(1, std::min(16, (int)((128 * 1024) / ((size_t)P * sizeof(double)))));
-  const size_t lds = (size_t)cells * P * sizeof(double);
-  dim3 grid((MT + cells - 1) / cells, nrows);
-#define PS_LAUNCH(KT_)                                                                                           \
-  case KT_: {                                                                                                    \
-    PS(hipFuncSetAttribute((const void*)posterior_summary_kernel<KT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(posterior_summary_kernel<KT_>, grid, dim3(256), lds, 0, (const double*)dW, (const double*)dV, nsamples, \
-                       nrows, MT, P, cells, transform, (const double*)dq, nq, dm, dqo);                         \
-  } break;
-  switch (nembeds) {
-    PS_LAUNCH(1) PS_LAUNCH(2) PS_LAUNCH(3) PS_LAUNCH(4) PS_LAUNCH(5) PS_LAUNCH(6) PS_LAUNCH(7) PS_LAUNCH(8) PS_LAUNCH(9) PS_LAUNCH(10)
-    default: break;
-  }
-#undef PS_LAUNCH
-  PS(hipGetLastError());
-  PS(hipDeviceSynchronize());
-  PS(hipMemcpy(mean_out, dm, cellsN * sizeof(double), hipMemcpyDeviceToHost));
-  if (nq) PS(hipMemcpy(q_out, dqo, (size_t)nq * cellsN * sizeof(double), hipMemcpyDeviceToHost));
-#undef PS
-  cleanup();
-  return BTF_OK;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dV = s.upload(Vs, (size_t)nsamples * MT * nembeds);
+  summary_stage(s, dW, dV, nsamples, nrows, MT, nembeds, transform, q, nq, mean_out, q_out);
+  return s.finish();
 }
 
 // ---------------------------------------------------------------- posterior curve functionals (btf_functionals.h)
@@ -4005,9 +3908,9 @@ namespace {
 
 struct FuncOut { double *mean, *var, *quant, *defined, *prob, *curves, *pw; };
 
-// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): validation, scratch, the launches chunk by chunk, the
-// downloads.  c may be null (the stateless form: default stream, launches not counted).
-int functionals_run(btf_ctx* c, hipStream_t st, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform,
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): scratch, the launches chunk by chunk, the downloads.
+// The scratch's context may be null (the stateless form: default stream, launches not counted).
+int functionals_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform,
                     const int* which, int nwhich, const double* x, double level, double exceed, const double* q, int nq,
                     const int* curves, int ncurves, const FuncOut& o) {
   FuncArgs a = {};
@@ -4015,76 +3918,45 @@ int functionals_run(btf_ctx* c, hipStream_t st, const double* dW, const double* 
   a.S = S; a.N = N; a.M = M; a.T = T; a.nslots = nwhich; a.nq = nq;
   for (int f = 0; f < FUNC_COUNT; ++f) a.slot[f] = -1;
   for (int k = 0; k < nwhich; ++k) { a.slot[which[k]] = k; a.code[k] = which[k]; }
-  int P = 2;
-  while (P < S) P <<= 1;
-  a.P = P;
-  a.cells = std::max(1, std::min(FUNC_SORT_CELLS, (int)(FUNC_SORT_LDS / ((size_t)P * sizeof(double)))));
-  const size_t lds = (size_t)a.cells * P * sizeof(double);
-  const size_t NM = (size_t)N * M, per_col = (size_t)nwhich * S * N * sizeof(double);
-  const int jc_max = (int)std::max<size_t>(1, std::min<size_t>(std::min(M, 65535), FUNC_SCRATCH_BYTES / per_col));   // (a grid's y extent)
+  const SortGeom g = sort_geom(S, FUNC_SORT_LDS, FUNC_SORT_CELLS);
+  a.P = g.P; a.cells = g.cells;
+  const size_t NM = (size_t)N * M, per_col = (size_t)nwhich * S * N;      // doubles of scratch a column takes
+  const int jc_max = (int)std::max<size_t>(1, std::min<size_t>(std::min(M, 65535), FUNC_SCRATCH_BYTES / (per_col * sizeof(double))));   // (a grid's y extent)
   FuncKernel sweep = func_sweep_fn(K, transform), sort = func_sort_fn();
-  if (!sweep) return fail(c, BTF_EINVAL, "posterior functionals: nembeds must be 1..10 and transform 0..2");
-  double *dx = nullptr, *dq = nullptr, *dvals = nullptr, *dmean = nullptr, *dvar = nullptr, *dquant = nullptr, *ddef = nullptr,
-         *dprob = nullptr, *dcur = nullptr, *dpw = nullptr;
-  int* dcv = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)dx, (void*)dq, (void*)dvals, (void*)dmean, (void*)dvar, (void*)dquant, (void*)ddef, (void*)dprob, (void*)dcur,
-                    (void*)dpw, (void*)dcv})
-      if (p) (void)hipFree(p);
-  };
-#define FN(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  FN(hipMalloc((void**)&dx, (size_t)T * sizeof(double)));
-  FN(hipMalloc((void**)&dvals, per_col * jc_max));
-  FN(hipMemcpyAsync(dx, x, (size_t)T * sizeof(double), hipMemcpyHostToDevice, st));
-  if (o.mean) FN(hipMalloc((void**)&dmean, nwhich * NM * sizeof(double)));
-  if (o.var) FN(hipMalloc((void**)&dvar, nwhich * NM * sizeof(double)));
-  if (o.prob) FN(hipMalloc((void**)&dprob, nwhich * NM * sizeof(double)));
-  if (o.defined) FN(hipMalloc((void**)&ddef, NM * sizeof(double)));
-  if (nq) {
-    FN(hipMalloc((void**)&dq, (size_t)nq * sizeof(double)));
-    FN(hipMalloc((void**)&dquant, (size_t)nq * nwhich * NM * sizeof(double)));
-    FN(hipMemcpyAsync(dq, q, (size_t)nq * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-  if (ncurves) {
-    FN(hipMalloc((void**)&dcv, (size_t)2 * ncurves * sizeof(int)));
-    FN(hipMalloc((void**)&dcur, (size_t)nwhich * ncurves * S * sizeof(double)));
-    FN(hipMemcpyAsync(dcv, curves, (size_t)2 * ncurves * sizeof(int), hipMemcpyHostToDevice, st));
-  }
-  if (o.pw) FN(hipMalloc((void**)&dpw, (size_t)nwhich * S * NM * sizeof(double)));
-  a.x = dx; a.q = dq; a.vals = dvals; a.mean = dmean; a.var = dvar; a.quant = dquant; a.defined = ddef; a.prob = dprob; a.pw = dpw;
-  FN(hipFuncSetAttribute((const void*)sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (!sweep) return fail(s.ctx(), BTF_EINVAL, "posterior functionals: nembeds must be 1..10 and transform 0..2");
+  a.x = s.upload(x, (size_t)T);
+  a.vals = s.alloc<double>(per_col * jc_max);
+  if (o.mean) a.mean = s.alloc<double>(nwhich * NM);
+  if (o.var) a.var = s.alloc<double>(nwhich * NM);
+  if (o.prob) a.prob = s.alloc<double>(nwhich * NM);
+  if (o.defined) a.defined = s.alloc<double>(NM);
+  if (nq) { a.q = s.upload(q, (size_t)nq); a.quant = s.alloc<double>((size_t)nq * nwhich * NM); }
+  const int* dcv = nullptr;
+  double* dcur = nullptr;
+  if (ncurves) { dcv = s.upload(curves, (size_t)2 * ncurves); dcur = s.alloc<double>((size_t)nwhich * ncurves * S); }
+  if (o.pw) a.pw = s.alloc<double>((size_t)nwhich * S * NM);
+  allow_lds(s, sort, g.lds);
   const int rowblocks = (N + WAVE - 1) / WAVE;
   const bool reduce = o.mean || o.var || o.prob || o.defined || nq;
   for (int j0 = 0; j0 < M; j0 += jc_max) {
     a.j0 = j0; a.jc = std::min(jc_max, M - j0);
     // sample slices: enough workgroups to fill the chip when rows x columns alone do not (geometry only)
     const int zs = std::max(1, std::min((S + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * a.jc - 1) / (rowblocks * a.jc)));
-    const dim3 gsweep(rowblocks, a.jc, zs), gsort((N + a.cells - 1) / a.cells, a.jc, nwhich);
-    if (c) {
-      { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, sweep, gsweep, dim3(FUNC_WAVES * WAVE), 0, a); }
-      if (ncurves) { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, func_gather_fn(), dim3(ncurves, nwhich), dim3(256), 0, a, (const int*)dcv, ncurves, dcur); }
-      if (reduce) { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, sort, gsort, dim3(256), lds, a); }
-    } else {
-      hipLaunchKernelGGL(sweep, gsweep, dim3(FUNC_WAVES * WAVE), 0, st, a);
-      if (ncurves) hipLaunchKernelGGL(func_gather_fn(), dim3(ncurves, nwhich), dim3(256), 0, st, a, (const int*)dcv, ncurves, dcur);
-      if (reduce) hipLaunchKernelGGL(sort, gsort, dim3(256), lds, st, a);
-    }
-    FN(hipGetLastError());
+    launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, a.jc, zs), dim3(FUNC_WAVES * WAVE), 0, a);
+    if (ncurves) launch_counted(s, BTF_K_CRITERIA, func_gather_fn(), dim3(ncurves, nwhich), dim3(256), 0, a, dcv, ncurves, dcur);
+    if (reduce) launch_counted(s, BTF_K_CRITERIA, sort, dim3((N + a.cells - 1) / a.cells, a.jc, nwhich), dim3(256), g.lds, a);
   }
-  if (o.mean) FN(hipMemcpyAsync(o.mean, dmean, nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (o.var) FN(hipMemcpyAsync(o.var, dvar, nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (o.prob) FN(hipMemcpyAsync(o.prob, dprob, nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
+  s.download(o.mean, a.mean, nwhich * NM);
+  s.download(o.var, a.var, nwhich * NM);
+  s.download(o.prob, a.prob, nwhich * NM);
   if (o.defined) {
-    if (a.slot[FUNC_CROSSING] < 0) FN(hipMemsetAsync(ddef, 0, NM * sizeof(double), st));
-    FN(hipMemcpyAsync(o.defined, ddef, NM * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (a.slot[FUNC_CROSSING] < 0 && !s.rc()) s.check(hipMemsetAsync(a.defined, 0, NM * sizeof(double), s.stream()), "hipMemsetAsync");
+    s.download(o.defined, a.defined, NM);
   }
-  if (nq) FN(hipMemcpyAsync(o.quant, dquant, (size_t)nq * nwhich * NM * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ncurves) FN(hipMemcpyAsync(o.curves, dcur, (size_t)nwhich * ncurves * S * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (o.pw) FN(hipMemcpyAsync(o.pw, dpw, (size_t)nwhich * S * NM * sizeof(double), hipMemcpyDeviceToHost, st));
-  FN(hipStreamSynchronize(st));
-#undef FN
-  cleanup();
-  return BTF_OK;
+  if (nq) s.download(o.quant, a.quant, (size_t)nq * nwhich * NM);
+  if (ncurves) s.download(o.curves, dcur, (size_t)nwhich * ncurves * S);
+  s.download(o.pw, a.pw, (size_t)nwhich * S * NM);
+  return s.finish();
 }
 
 // argument checks shared by the two entry points; everything here runs before any device call
@@ -4123,19 +3995,11 @@ int btf_posterior_functionals(int device, int nsamples, int nrows, int ncols, in
   if (rc) return rc;
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  const size_t nW = (size_t)nsamples * nrows * nembeds, nV = (size_t)nsamples * ncols * ndepth * nembeds;
-  double *dW = nullptr, *dV = nullptr;
-  auto cleanup = [&]() { if (dW) (void)hipFree(dW); if (dV) (void)hipFree(dV); };
-#define FU(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  FU(hipMalloc((void**)&dW, nW * sizeof(double)));
-  FU(hipMalloc((void**)&dV, nV * sizeof(double)));
-  FU(hipMemcpy(dW, Ws, nW * sizeof(double), hipMemcpyHostToDevice));
-  FU(hipMemcpy(dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice));
-#undef FU
-  rc = functionals_run(nullptr, 0, dW, dV, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, exceed, q, nq,
-                       curves, ncurves, o);
-  cleanup();
-  return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
+  return functionals_run(s, dW, dV, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, exceed, q, nq,
+                         curves, ncurves, o);
 }
 
 // the same on the first nsamples collected states, read where they lie (no upload)
@@ -4148,7 +4012,8 @@ int btf_collect_functionals(btf_ctx* c, int nsamples, int transform, const int* 
   if (rc) return rc;
   if (!c->smp_W || !c->smp_V || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_functionals: not that many collected samples");
   HIPCHK(c, hipSetDevice(c->dev));
-  return functionals_run(c, c->stream, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
+  Scratch s(c, c->stream);
+  return functionals_run(s, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
                          q, nq, curves, ncurves, o);
 }
 
@@ -4193,10 +4058,11 @@ int fold_in_check(btf_ctx* c, const FoldIn& f) {
   return BTF_OK;
 }
 
-// The launches on device states dV (S,M,T,K) and per-sample scalars on the device (noise may be null: 1).  c may be null
-// (the stateless form: default stream, launches not counted).  W stays on the device between the draw and the summary.
-int fold_in_run(btf_ctx* c, hipStream_t st, const double* dV, const double* dnoise, int nstride, const double* dsig, int sstride,
-                const FoldIn& f) {
+// The launches on device states dV (S,M,T,K) and per-sample scalars on the device (noise may be null: 1).  The scratch's
+// context may be null (the stateless form: default stream, launches not counted).  W stays on the device between the draw
+// and the summary.
+int fold_in_run(Scratch& s, const double* dV, const double* dnoise, int nstride, const double* dsig, int sstride, const FoldIn& f) {
+  btf_ctx* c = s.ctx();
   const int S = f.S, R = f.R, MT = f.M * f.T, K = f.K;
   FoldKernel kern = fold_in_fn(K, f.family);
   if (!kern) return fail(c, BTF_EINVAL, "fold_in: nembeds must be 1..10 and family 0..1");
@@ -4210,65 +4076,23 @@ int fold_in_run(btf_ctx* c, hipStream_t st, const double* dV, const double* dnoi
       hy[(size_t)jt * R + r] = f.family == FOLD_BINOMIAL ? (cv > 0.0 ? yv - 0.5 * cv : 0.0) : (cv > 0.0 ? yv : 0.0);
     }
   const size_t nW = (size_t)S * R * K, cellsN = (size_t)R * MT;
-  double *dc = nullptr, *dy = nullptr, *dz = nullptr, *dW = nullptr, *dWm = nullptr, *dq = nullptr, *dm = nullptr, *dqo = nullptr;
-  int* dstat = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)dc, (void*)dy, (void*)dz, (void*)dW, (void*)dWm, (void*)dq, (void*)dm, (void*)dqo, (void*)dstat})
-      if (p) (void)hipFree(p);
-  };
-#define FI(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(c, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  FI(hipMalloc((void**)&dc, cellsN * sizeof(double)));
-  FI(hipMalloc((void**)&dy, cellsN * sizeof(double)));
-  FI(hipMalloc((void**)&dW, nW * sizeof(double)));
-  FI(hipMalloc((void**)&dstat, 2 * sizeof(int)));
-  if (f.Wmean_out) FI(hipMalloc((void**)&dWm, nW * sizeof(double)));
-  if (f.z) FI(hipMalloc((void**)&dz, nW * sizeof(double)));
-  FI(hipMemcpyAsync(dc, hc.data(), cellsN * sizeof(double), hipMemcpyHostToDevice, st));
-  FI(hipMemcpyAsync(dy, hy.data(), cellsN * sizeof(double), hipMemcpyHostToDevice, st));
-  if (f.z) FI(hipMemcpyAsync(dz, f.z, nW * sizeof(double), hipMemcpyHostToDevice, st));
   const int stat0[2] = {0, INT_MAX};
-  FI(hipMemcpyAsync(dstat, stat0, sizeof(stat0), hipMemcpyHostToDevice, st));
   FoldArgs a = {};
   a.V = dV; a.noise = dnoise; a.sigma2 = dsig; a.nstride = nstride; a.sstride = sstride;
-  a.cnt = dc; a.ysum = dy; a.z = dz; a.W = dW; a.Wmean = dWm; a.status = dstat;
+  a.cnt = s.upload(hc.data(), cellsN); a.ysum = s.upload(hy.data(), cellsN);
+  a.W = s.alloc<double>(nW); a.status = s.upload(stat0, 2);
+  if (f.Wmean_out) a.Wmean = s.alloc<double>(nW);
+  if (f.z) a.z = s.upload(f.z, nW);
   a.seed = f.seed; a.sample0 = f.sample0; a.S = S; a.R = R; a.MT = MT; a.sweeps = f.inner_sweeps;
-  const dim3 grid(S, (R + WAVE - 1) / WAVE);
-  if (c) { Prof p(c, BTF_K_CRITERIA); p.launch_on(st, kern, grid, dim3(FOLD_PARTS * WAVE), 0, a); }
-  else hipLaunchKernelGGL(kern, grid, dim3(FOLD_PARTS * WAVE), 0, st, a);
-  FI(hipGetLastError());
-  if (f.mean_out) {
-    // the summary stage: posterior_summary_kernel on the device-resident W (S,R,K) and V, as btf_posterior_summary launches it
-    FI(hipMalloc((void**)&dm, cellsN * sizeof(double)));
-    FI(hipMalloc((void**)&dq, (size_t)std::max(f.nq, 1) * sizeof(double)));
-    FI(hipMalloc((void**)&dqo, std::max<size_t>(1, (size_t)f.nq * cellsN) * sizeof(double)));
-    if (f.nq) FI(hipMemcpyAsync(dq, f.q, (size_t)f.nq * sizeof(double), hipMemcpyHostToDevice, st));
-    int P = 2;
-    while (P < S) P <<= 1;
-    const int cells = std::max(1, std::min(16, (int)((128 * 1024) / ((size_t)P * sizeof(double)))));
-    const size_t lds = (size_t)cells * P * sizeof(double);
-    const dim3 sgrid((MT + cells - 1) / cells, R);
-#define FI_LAUNCH(KT_)                                                                                           \
-  case KT_: {                                                                                                    \
-    FI(hipFuncSetAttribute((const void*)posterior_summary_kernel<KT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(posterior_summary_kernel<KT_>, sgrid, dim3(256), lds, st, (const double*)dW, dV, S, R, MT, P, cells, \
-                       f.transform, (const double*)dq, f.nq, dm, dqo);                                           \
-  } break;
-    switch (K) {
-      FI_LAUNCH(1) FI_LAUNCH(2) FI_LAUNCH(3) FI_LAUNCH(4) FI_LAUNCH(5) FI_LAUNCH(6) FI_LAUNCH(7) FI_LAUNCH(8) FI_LAUNCH(9) FI_LAUNCH(10)
-      default: break;
-    }
-#undef FI_LAUNCH
-    FI(hipGetLastError());
-    FI(hipMemcpyAsync(f.mean_out, dm, cellsN * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (f.nq) FI(hipMemcpyAsync(f.q_out, dqo, (size_t)f.nq * cellsN * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3(S, (R + WAVE - 1) / WAVE), dim3(FOLD_PARTS * WAVE), 0, a);
+  // the summary stage reads the device-resident W (S,R,K) and V
+  if (f.mean_out) summary_stage(s, a.W, dV, S, R, MT, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
   int stat[2] = {0, INT_MAX};
-  FI(hipMemcpyAsync(stat, dstat, sizeof(stat), hipMemcpyDeviceToHost, st));
-  FI(hipMemcpyAsync(f.W_out, dW, nW * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (f.Wmean_out) FI(hipMemcpyAsync(f.Wmean_out, dWm, nW * sizeof(double), hipMemcpyDeviceToHost, st));
-  FI(hipStreamSynchronize(st));
-#undef FI
-  cleanup();
+  s.download(stat, a.status, 2);
+  s.download(f.W_out, a.W, nW);
+  s.download(f.Wmean_out, a.Wmean, nW);
+  const int rc = s.finish();
+  if (rc) return rc;
   if (stat[0]) {
     if (c) c->fail_index = stat[1];
     g_fold_fail_index = stat[1];
@@ -4297,22 +4121,11 @@ int btf_fold_in_rows(int device, int family, int nsamples, int nrows_new, int nc
       return fail(nullptr, BTF_EINVAL, "fold_in: nu2 and sigma2 must be finite and positive");
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  const size_t nV = (size_t)nsamples * ncols * ndepth * nembeds;
-  double *dV = nullptr, *dn = nullptr, *ds = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)dV, (void*)dn, (void*)ds}) if (p) (void)hipFree(p); };
-#define FU(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  FU(hipMalloc((void**)&dV, nV * sizeof(double)));
-  FU(hipMalloc((void**)&ds, (size_t)nsamples * sizeof(double)));
-  FU(hipMemcpy(dV, Vs, nV * sizeof(double), hipMemcpyHostToDevice));
-  FU(hipMemcpy(ds, sigma2, (size_t)nsamples * sizeof(double), hipMemcpyHostToDevice));
-  if (family == FOLD_GAUSSIAN) {
-    FU(hipMalloc((void**)&dn, (size_t)nsamples * sizeof(double)));
-    FU(hipMemcpy(dn, noise, (size_t)nsamples * sizeof(double), hipMemcpyHostToDevice));
-  }
-#undef FU
-  rc = fold_in_run(nullptr, 0, dV, dn, 1, ds, 1, f);
-  cleanup();
-  return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
+  const double* ds = s.upload(sigma2, (size_t)nsamples);
+  const double* dn = family == FOLD_GAUSSIAN ? s.upload(noise, (size_t)nsamples) : nullptr;
+  return fold_in_run(s, dV, dn, 1, ds, 1, f);
 }
 
 // the same on the first nsamples collected states, read where they lie (no upload): V from the sample slots, nu2_s and
@@ -4327,7 +4140,8 @@ int btf_collect_fold_in(btf_ctx* c, int family, int nsamples, int nrows_new, con
   if (rc) return rc;
   if (!c->smp_V || !c->smp_s || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_fold_in: not that many collected samples");
   HIPCHK(c, hipSetDevice(c->dev));
-  return fold_in_run(c, c->stream, c->smp_V, family == FOLD_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT,
+  Scratch s(c, c->stream);
+  return fold_in_run(s, c->smp_V, family == FOLD_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT,
                      c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, f);
 }
 
@@ -4354,56 +4168,28 @@ int btf_diag_eval(int device, int nchains, int nsamples, int nrows, int ncols, i
   const int MT = ncols * ndepth;
   const size_t cells = (size_t)nrows * MT;
   const size_t nW = (size_t)nsamples * nrows * nembeds, nV = (size_t)nsamples * MT * nembeds;
-  std::vector<double*> up;                                 // uploaded chains
+  Scratch s(nullptr, nullptr);
   std::vector<const double*> pw(nchains), pv(nchains);
-  const double** dpw = nullptr; const double** dpv = nullptr;
-  double* dout = nullptr;
-  auto cleanup = [&]() {
-    for (double* p : up) (void)hipFree(p);
-    for (void* p : {(void*)dpw, (void*)dpv, (void*)dout}) if (p) (void)hipFree(p);
-  };
-#define DG(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
   for (int c = 0; c < nchains; ++c) {
     const btf_ctx* x = ctxs ? ctxs[c] : nullptr;
     if (x) {                                               // the collection copies may still be in flight on its stream
-      DG(hipStreamSynchronize(x->stream));
+      s.check(hipStreamSynchronize(x->stream), "hipStreamSynchronize");
       pw[c] = x->smp_W; pv[c] = x->smp_V;
     } else {
-      double *dW = nullptr, *dV = nullptr;
-      DG(hipMalloc((void**)&dW, nW * sizeof(double)));
-      up.push_back(dW);
-      DG(hipMalloc((void**)&dV, nV * sizeof(double)));
-      up.push_back(dV);
-      DG(hipMemcpy(dW, Ws[c], nW * sizeof(double), hipMemcpyHostToDevice));
-      DG(hipMemcpy(dV, Vs[c], nV * sizeof(double), hipMemcpyHostToDevice));
-      pw[c] = dW; pv[c] = dV;
+      pw[c] = s.upload(Ws[c], nW); pv[c] = s.upload(Vs[c], nV);
     }
   }
-  DG(hipMalloc((void**)&dpw, nchains * sizeof(double*)));
-  DG(hipMalloc((void**)&dpv, nchains * sizeof(double*)));
-  DG(hipMalloc((void**)&dout, DIAG_OUT * cells * sizeof(double)));
-  DG(hipMemcpy(dpw, pw.data(), nchains * sizeof(double*), hipMemcpyHostToDevice));
-  DG(hipMemcpy(dpv, pv.data(), nchains * sizeof(double*), hipMemcpyHostToDevice));
+  double* dout = s.alloc<double>(DIAG_OUT * cells);
   int P = 2;
   while (P < nchains * nsamples) P <<= 1;
-  DiagArgs a{dpw, dpv, nchains, nsamples, nrows, MT, P, transform, dout};
+  DiagArgs a{s.upload(pw.data(), (size_t)nchains), s.upload(pv.data(), (size_t)nchains), nchains, nsamples, nrows, MT, P, transform, dout};
   const size_t lds = (size_t)(nchains * nsamples + P) * sizeof(double);
-#define DG_LAUNCH(KT_)                                                                                             \
-  case KT_: {                                                                                                      \
-    DG(hipFuncSetAttribute((const void*)diag_kernel<KT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-    hipLaunchKernelGGL(diag_kernel<KT_>, dim3((unsigned)cells), dim3(DIAG_THREADS), lds, 0, a);                   \
-  } break;
-  switch (nembeds) {
-    DG_LAUNCH(1) DG_LAUNCH(2) DG_LAUNCH(3) DG_LAUNCH(4) DG_LAUNCH(5) DG_LAUNCH(6) DG_LAUNCH(7) DG_LAUNCH(8) DG_LAUNCH(9) DG_LAUNCH(10)
-    default: break;
-  }
-#undef DG_LAUNCH
-  DG(hipGetLastError());
-  DG(hipDeviceSynchronize());
-  DG(hipMemcpy(out, dout, DIAG_OUT * cells * sizeof(double), hipMemcpyDeviceToHost));
-#undef DG
-  cleanup();
-  return BTF_OK;
+  K_SWITCH(nembeds, {
+    allow_lds(s, diag_kernel<KT>, lds);
+    s.launch(diag_kernel<KT>, dim3((unsigned)cells), dim3(DIAG_THREADS), lds, a);
+  });
+  s.download(out, dout, DIAG_OUT * cells);
+  return s.finish();
 }
 
 int btf_pg_batch(int device, int64_t n, const double* b, const double* psi, uint64_t seed, double* out) {
@@ -4414,31 +4200,20 @@ int btf_pg_batch_mode(int device, int64_t n, const double* b, const double* psi,
   if (n < 1 || !b || !psi || !out || mode < 0 || mode > PG_MODE_REF_F64 + 1) return fail(nullptr, BTF_EINVAL, "bad pg_batch arguments");
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  double *db = nullptr, *dp = nullptr, *dout = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)db, (void*)dp, (void*)dout}) if (p) (void)hipFree(p); };
-#define PB(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  PB(hipMalloc((void**)&db, n * sizeof(double)));
-  PB(hipMalloc((void**)&dp, n * sizeof(double)));
-  PB(hipMalloc((void**)&dout, n * sizeof(double)));
-  PB(hipMemcpy(db, b, n * sizeof(double), hipMemcpyHostToDevice));
-  PB(hipMemcpy(dp, psi, n * sizeof(double), hipMemcpyHostToDevice));
+  Scratch s(nullptr, nullptr);
+  double *db = s.upload(b, (size_t)n), *dp = s.upload(psi, (size_t)n), *dout = s.alloc<double>((size_t)n);
   const bool allf64 = mode == PG_MODE_REF_F64 + 1;      // 4: PG_MODE_EXACT_ALL with every trip of the flat sampler repeated in f64
   if (allf64) mode = PG_MODE_EXACT_ALL;
   const bool flat = mode == PG_MODE_DEFAULT || mode == PG_MODE_EXACT_ALL;
   if (flat) {      // the integer counts the mode gives to the flat exact sampler
     constexpr int CPL = 4;
     const dim3 grid((unsigned)((n + 256 * CPL - 1) / (256 * CPL)));
-    if (allf64) hipLaunchKernelGGL((pgx_batch_kernel<CPL, true>), grid, dim3(256), pgx_rows_lds(CPL), 0, db, dp, dout, (long long)n, (unsigned long long)seed, mode);
-    else hipLaunchKernelGGL((pgx_batch_kernel<CPL, false>), grid, dim3(256), pgx_rows_lds(CPL), 0, db, dp, dout, (long long)n, (unsigned long long)seed, mode);
-    PB(hipGetLastError());
+    if (allf64) s.launch(pgx_batch_kernel<CPL, true>, grid, dim3(256), pgx_rows_lds(CPL), db, dp, dout, (long long)n, (unsigned long long)seed, mode);
+    else s.launch(pgx_batch_kernel<CPL, false>, grid, dim3(256), pgx_rows_lds(CPL), db, dp, dout, (long long)n, (unsigned long long)seed, mode);
   }
-  hipLaunchKernelGGL(pg_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, db, dp, dout, (long long)n, seed, mode, flat ? 1 : 0);
-  PB(hipGetLastError());
-  PB(hipDeviceSynchronize());
-  PB(hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost));
-  cleanup();
-#undef PB
-  return BTF_OK;
+  s.launch(pg_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, db, dp, dout, (long long)n, seed, mode, flat ? 1 : 0);
+  s.download(out, dout, (size_t)n);
+  return s.finish();
 }
 
 int btf_sym_eig(int device, int K, int nparts, const double* parts, double* out, const double* warm_from) {
@@ -4446,26 +4221,18 @@ int btf_sym_eig(int device, int K, int nparts, const double* parts, double* out,
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   const size_t np = (size_t)nparts * tri(K), no = (size_t)K + K * K + 2;
-  double *dp = nullptr, *dout = nullptr;
-  auto cleanup = [&]() { if (dp) (void)hipFree(dp); if (dout) (void)hipFree(dout); };
-#define SE(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  SE(hipMalloc((void**)&dp, np * sizeof(double)));
-  SE(hipMalloc((void**)&dout, no * sizeof(double)));
-  SE(hipMemset(dout, 0, no * sizeof(double)));
-  if (warm_from) {      // a previous solution to refine: eigenvalues, vectors, (sweeps), then the "valid" word
-    std::vector<double> w(no, 0.0);
+  // the solution slot: zeros, or a previous solution to refine: eigenvalues, vectors, (sweeps), then the "valid" word
+  std::vector<double> w(no, 0.0);
+  if (warm_from) {
     std::memcpy(w.data(), warm_from, ((size_t)K + K * K) * sizeof(double));
     w[(size_t)K + K * K + 1] = 1.0;
-    SE(hipMemcpy(dout, w.data(), no * sizeof(double), hipMemcpyHostToDevice));
   }
-  SE(hipMemcpy(dp, parts, np * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(gram_eig_kernel, dim3(1), dim3(WAVE), 0, 0, (const double*)dp, nparts, K, dout, warm_from ? 1 : 0);
-  SE(hipGetLastError());
-  SE(hipDeviceSynchronize());
-  SE(hipMemcpy(out, dout, ((size_t)K + K * K + 1) * sizeof(double), hipMemcpyDeviceToHost));
-#undef SE
-  cleanup();
-  return BTF_OK;
+  Scratch s(nullptr, nullptr);
+  double* dout = s.upload(w.data(), no);
+  const double* dp = s.upload(parts, np);
+  s.launch(gram_eig_kernel, dim3(1), dim3(WAVE), 0, dp, nparts, K, dout, warm_from ? 1 : 0);
+  s.download(out, dout, (size_t)K + K * K + 1);
+  return s.finish();
 }
 
 // Measurement aid (bench.py roofline.read_ceiling_GBs): the rate of a plain streaming read - one 16-byte load
@@ -4482,27 +4249,28 @@ int btf_read_probe(int device, size_t bytes, int reps, double* gb_per_s) {
   if (bytes < 1024 || reps < 1 || !gb_per_s) return fail(nullptr, BTF_EINVAL, "bad read_probe arguments");
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  double2* x = nullptr; double* out = nullptr;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  auto cleanup = [&]() { if (x) (void)hipFree(x); if (out) (void)hipFree(out); if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); };
-#define RP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
   const size_t n2 = bytes / sizeof(double2);
-  RP(hipMalloc((void**)&x, n2 * sizeof(double2)));
-  RP(hipMalloc((void**)&out, sizeof(double)));
-  RP(hipMemset(x, 0, n2 * sizeof(double2)));
-  RP(hipEventCreate(&t0));
-  RP(hipEventCreate(&t1));
-  hipLaunchKernelGGL(read_probe_kernel, dim3(512), dim3(1024), 0, 0, (const double2*)x, n2, out);      // warm-up
-  RP(hipDeviceSynchronize());
-  RP(hipEventRecord(t0, 0));
+  Scratch s(nullptr, nullptr);
+  double2* x = s.alloc<double2>(n2);
+  double* out = s.alloc<double>(1);
+  struct Events {
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    ~Events() { if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
+  } ev;
+  if (!s.rc()) s.check(hipMemsetAsync(x, 0, n2 * sizeof(double2), nullptr), "hipMemsetAsync");
+  s.check(hipEventCreate(&ev.t0), "hipEventCreate");
+  s.check(hipEventCreate(&ev.t1), "hipEventCreate");
+  s.launch(read_probe_kernel, dim3(512), dim3(1024), 0, (const double2*)x, n2, out);      // warm-up
+  if (s.finish()) return s.rc();
+  // the timed launches go out back to back, checked once behind the loop
+  s.check(hipEventRecord(ev.t0, nullptr), "hipEventRecord");
   for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(read_probe_kernel, dim3(512), dim3(1024), 0, 0, (const double2*)x, n2, out);
-  RP(hipEventRecord(t1, 0));
-  RP(hipEventSynchronize(t1));
+  s.check(hipGetLastError(), "hipGetLastError (read_probe_kernel)");
+  s.check(hipEventRecord(ev.t1, nullptr), "hipEventRecord");
+  s.check(hipEventSynchronize(ev.t1), "hipEventSynchronize");
   float ms = 0.f;
-  RP(hipEventElapsedTime(&ms, t0, t1));
-#undef RP
+  if (!s.check(hipEventElapsedTime(&ms, ev.t0, ev.t1), "hipEventElapsedTime")) return s.rc();
   *gb_per_s = (double)n2 * sizeof(double2) * reps / (ms * 1e-3) / 1e9;
-  cleanup();
   return BTF_OK;
 }
 
@@ -4516,40 +4284,26 @@ int btf_sync(btf_ctx* c) {
 int btf_mvn_banded(int device, int batch, int n, int bw, const double* band, const double* mu_part, const double* z,
                    uint64_t seed, double eps0, int attempts, double* x_out, int32_t* tries_out) {
   if (batch < 1 || n < 1 || bw < 0 || bw > 63 || !band || !x_out) return fail(nullptr, BTF_EINVAL, "bad mvn arguments");
-  btf_ctx* c = nullptr;
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   const int R1 = bw + 1;
   const size_t nb = (size_t)batch * n * R1, nv = (size_t)batch * n;
-  double *dband = nullptr, *dmu = nullptr, *dz = nullptr, *dx = nullptr, *dwork = nullptr;
-  int *dtries = nullptr, *dstatus = nullptr;
-  int rc = BTF_OK;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)dband, (void*)dmu, (void*)dz, (void*)dx, (void*)dwork, (void*)dtries, (void*)dstatus})
-      if (p) (void)hipFree(p);
-  };
-#define MV(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  MV(hipMalloc((void**)&dband, nb * sizeof(double)));
-  MV(hipMemcpy(dband, band, nb * sizeof(double), hipMemcpyHostToDevice));
-  if (mu_part) { MV(hipMalloc((void**)&dmu, nv * sizeof(double))); MV(hipMemcpy(dmu, mu_part, nv * sizeof(double), hipMemcpyHostToDevice)); }
-  if (z) { MV(hipMalloc((void**)&dz, nv * sizeof(double))); MV(hipMemcpy(dz, z, nv * sizeof(double), hipMemcpyHostToDevice)); }
-  MV(hipMalloc((void**)&dx, nv * sizeof(double)));
-  MV(hipMalloc((void**)&dwork, (nb + 2 * nv) * sizeof(double)));
-  MV(hipMalloc((void**)&dtries, batch * sizeof(int)));
-  MV(hipMalloc((void**)&dstatus, 2 * sizeof(int)));
-  MV(hipMemset(dstatus, 0, 2 * sizeof(int)));
+  const int st0[2] = {0, 0};
+  Scratch s(nullptr, nullptr);
+  const double* dband = s.upload(band, nb);
+  const double* dmu = mu_part ? s.upload(mu_part, nv) : nullptr;
+  const double* dz = z ? s.upload(z, nv) : nullptr;
+  double *dx = s.alloc<double>(nv), *dwork = s.alloc<double>(nb + 2 * nv);
+  int *dtries = s.alloc<int>((size_t)batch), *dstatus = s.upload(st0, 2);
   MvnArgs a{dband, dmu, dz, dx, dwork, n, bw, seed, eps0, attempts < 0 ? 0 : attempts, dtries, dstatus};
   const size_t lds = ((size_t)(bw * (bw + 1) / 2 + 3) / 4 + 1) * sizeof(double);
-  hipLaunchKernelGGL(mvn_banded_kernel, dim3(batch), dim3(WAVE), lds, 0, a);
-  MV(hipGetLastError());
-  MV(hipDeviceSynchronize());
-  int st[2];
-  MV(hipMemcpy(st, dstatus, sizeof(st), hipMemcpyDeviceToHost));
-  MV(hipMemcpy(x_out, dx, nv * sizeof(double), hipMemcpyDeviceToHost));
-  if (tries_out) MV(hipMemcpy(tries_out, dtries, batch * sizeof(int), hipMemcpyDeviceToHost));
-  cleanup();
-#undef MV
-  (void)c; (void)rc;
+  s.launch(mvn_banded_kernel, dim3(batch), dim3(WAVE), lds, a);
+  int st[2] = {0, 0};
+  s.download(st, dstatus, 2);
+  s.download(x_out, dx, nv);
+  s.download(tries_out, dtries, (size_t)batch);
+  const int rc = s.finish();
+  if (rc) return rc;
   if (st[0]) return fail(nullptr, BTF_ENOTPD, "precision not positive definite in batch item " + std::to_string(st[1]));
   return BTF_OK;
 }
@@ -4561,33 +4315,22 @@ int btf_mvn_dense(int device, int batch, int n, const double* A, int form, const
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   const size_t nm = (size_t)batch * n * n, nv = (size_t)batch * n;
-  double *dA = nullptr, *dmu = nullptr, *dmp = nullptr, *dz = nullptr, *dx = nullptr, *dwork = nullptr;
-  int *dtries = nullptr, *dstatus = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)dA, (void*)dmu, (void*)dmp, (void*)dz, (void*)dx, (void*)dwork, (void*)dtries, (void*)dstatus})
-      if (p) (void)hipFree(p);
-  };
-#define MD(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(nullptr, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  MD(hipMalloc((void**)&dA, nm * sizeof(double)));
-  MD(hipMemcpy(dA, A, nm * sizeof(double), hipMemcpyHostToDevice));
-  if (mu) { MD(hipMalloc((void**)&dmu, nv * sizeof(double))); MD(hipMemcpy(dmu, mu, nv * sizeof(double), hipMemcpyHostToDevice)); }
-  if (mu_part) { MD(hipMalloc((void**)&dmp, nv * sizeof(double))); MD(hipMemcpy(dmp, mu_part, nv * sizeof(double), hipMemcpyHostToDevice)); }
-  if (z) { MD(hipMalloc((void**)&dz, nv * sizeof(double))); MD(hipMemcpy(dz, z, nv * sizeof(double), hipMemcpyHostToDevice)); }
-  MD(hipMalloc((void**)&dx, nv * sizeof(double)));
-  MD(hipMalloc((void**)&dwork, nm * sizeof(double)));
-  MD(hipMalloc((void**)&dtries, batch * sizeof(int)));
-  MD(hipMalloc((void**)&dstatus, 2 * sizeof(int)));
-  MD(hipMemset(dstatus, 0, 2 * sizeof(int)));
+  const int st0[2] = {0, 0};
+  Scratch s(nullptr, nullptr);
+  const double* dA = s.upload(A, nm);
+  const double* dmu = mu ? s.upload(mu, nv) : nullptr;
+  const double* dmp = mu_part ? s.upload(mu_part, nv) : nullptr;
+  const double* dz = z ? s.upload(z, nv) : nullptr;
+  double *dx = s.alloc<double>(nv), *dwork = s.alloc<double>(nm);
+  int *dtries = s.alloc<int>((size_t)batch), *dstatus = s.upload(st0, 2);
   MvnDenseArgs a{dA, dmu, dmp, dz, dx, dwork, n, form, (unsigned long long)seed, eps0, attempts < 0 ? 0 : attempts, dtries, dstatus};
-  hipLaunchKernelGGL(mvn_dense_kernel, dim3(batch), dim3(MVD_THREADS), 2 * (size_t)n * sizeof(double), 0, a);
-  MD(hipGetLastError());
-  MD(hipDeviceSynchronize());
-  int st[2];
-  MD(hipMemcpy(st, dstatus, sizeof(st), hipMemcpyDeviceToHost));
-  MD(hipMemcpy(x_out, dx, nv * sizeof(double), hipMemcpyDeviceToHost));
-  if (tries_out) MD(hipMemcpy(tries_out, dtries, batch * sizeof(int), hipMemcpyDeviceToHost));
-  cleanup();
-#undef MD
+  s.launch(mvn_dense_kernel, dim3(batch), dim3(MVD_THREADS), 2 * (size_t)n * sizeof(double), a);
+  int st[2] = {0, 0};
+  s.download(st, dstatus, 2);
+  s.download(x_out, dx, nv);
+  s.download(tries_out, dtries, (size_t)batch);
+  const int rc = s.finish();
+  if (rc) return rc;
   if (st[0]) return fail(nullptr, BTF_ENOTPD, "matrix not positive definite in batch item " + std::to_string(st[1]));
   return BTF_OK;
 }
@@ -5166,6 +4909,22 @@ int btf_host_selftest(void) {
     ST_CHECK(64 * ((4096 + rv - 1) / rv) + 1 <= 256);
     ST_CHECK(pick_rpb(16384, 4, 0, false, 256, 0) == 512 && pick_rpb(512, 128, 0, false, 256, 1) == 512);   // C3: untouched
     ST_CHECK(pick_rpb(65536, 4, 0, false, 0, 0) == 1024);                                                       // unknown chip: the old rule
+  }
+  // sort geometry of the summary, predictive and functionals kernels: the row is the power of two that holds the values,
+  // the cells of a workgroup stay within the cap and - unless one row alone is larger - within the LDS budget
+  {
+    const int Ss[] = {1, 2, 3, 4, 63, 64, 65, 1000, 8191, 8192, 8193, 16384};
+    const struct { size_t budget; int cap; } uses[] = {{SUMMARY_SORT_LDS, SUMMARY_SORT_CELLS}, {PRED_SORT_LDS, PRED_SORT_CELLS},
+                                                      {(size_t)FUNC_SORT_LDS, FUNC_SORT_CELLS}};
+    for (int S : Ss)
+      for (const auto& u : uses) {
+        const SortGeom g = sort_geom(S, u.budget, u.cap);
+        const int lo = std::max(S, 2);
+        ST_CHECK((g.P & (g.P - 1)) == 0 && g.P >= lo && g.P < 2 * lo);
+        ST_CHECK(g.cells >= 1 && g.cells <= u.cap);
+        ST_CHECK(g.lds == 8 * (size_t)g.cells * g.P && g.lds <= std::max(u.budget, 8 * (size_t)g.P));
+        if (u.budget == SUMMARY_SORT_LDS) ST_CHECK(g.lds <= 128 * 1024);
+      }
   }
   // which Polya-Gamma sampler takes a count
   ST_CHECK(pg_class_of(0.0, PG_MODE_DEFAULT) == PG_CLASS_NONE && pg_class_of(4.0, PG_MODE_DEFAULT) == PG_CLASS_FLAT);

@@ -2,6 +2,7 @@
 // include/btf.h, one compilation unit of their own.  gfx950 only.
 #include "../../include/btf.h"
 #include "btf_nmf.h"
+#include "btf_scratch.h"      // Scratch: the device buffers of btf_nmf_pav
 
 #include <algorithm>
 #include <cmath>
@@ -224,21 +225,15 @@ int btf_nmf_pav(int device, int nrows, int ncols, int ndepth, int nembeds, const
     return fail(BTF_EINVAL, "bad btf_nmf_pav arguments");
   if (!pav_fits(ndepth, nembeds)) return fail(BTF_EINVAL, "btf_nmf_pav: ndepth * nembeds too large for the PAV kernel");
   NMFCHK(hipSetDevice(device));
-  double *dW = nullptr, *dV = nullptr;
   const size_t nW = (size_t)nrows * nembeds, nV = (size_t)ncols * ndepth * nembeds;
-  auto cleanup = [&]() { if (dW) (void)hipFree(dW); if (dV) (void)hipFree(dV); };
-#define PAVCHK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return fail(BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-  PAVCHK(hipMalloc((void**)&dW, nW * sizeof(double)));
-  PAVCHK(hipMalloc((void**)&dV, nV * sizeof(double)));
-  PAVCHK(hipMemcpy(dW, W, nW * sizeof(double), hipMemcpyHostToDevice));
-  PAVCHK(hipMemcpy(dV, V, nV * sizeof(double), hipMemcpyHostToDevice));
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(W, nW);
+  double* dV = s.upload(V, nV);
+  if (s.rc()) return s.rc();
   launch_pav(nembeds, dim3(ncols), (size_t)ndepth * nembeds * sizeof(double) + (size_t)ndepth * sizeof(int), 0, dW, dV, nrows, ndepth);
-  PAVCHK(hipGetLastError());
-  PAVCHK(hipDeviceSynchronize());
-  PAVCHK(hipMemcpy(V, dV, nV * sizeof(double), hipMemcpyDeviceToHost));
-#undef PAVCHK
-  cleanup();
-  return BTF_OK;
+  s.check(hipGetLastError(), "hipGetLastError (nmf_pav_kernel)");
+  s.download(V, dV, nV);
+  return s.finish();
 }
 
 }  // extern "C"
