@@ -1,0 +1,384 @@
+"""The Python front end of the posterior analysis features: summary, diagnostics, criteria / PSIS-LOO, predictive,
+functionals and fold-in.
+
+Two halves.  The argument checks every feature shares, as plain functions (importable without a GPU): the transform table,
+the percentile check, the (S,N,K) / (S,M,T,K) shape check and the per-sample scalar check - the stateless forms in utils.py
+and the feature modules (predictive.py, functionals.py, fold_in.py, diagnostics.py) use them too.  And `PosteriorAnalysis`,
+the mixin BayesianTensorFiltering inherits its analysis methods from: each method refuses what it cannot do in a fixed order
+(`_unsharded`, the family hook of the model, its own arguments), resolves its samples in one place (`_samples`: the
+device-collected ones, or an uploaded run_gibbs result dict) and hands over to the `evaluate` of its feature module, the one
+caller of the C entry point.  The hooks that differ by likelihood (_crit_family, _pred_family, _pred_aux, _fold_family)
+stay with the models in factor.py.
+"""
+import numpy as np
+
+from . import _native
+from . import criteria as _criteria
+
+TRANSFORMS = {None: 0, "identity": 0, "ilogit": 1, "square": 2}      # f of f(w_i . v_jt): the code of the kernels
+
+
+class TransformError(ValueError, KeyError):
+    """An unknown transform.  Also a KeyError, what posterior_summary's table lookup raised before the check was shared."""
+    __str__ = ValueError.__str__            # (KeyError prints the repr of its argument)
+
+
+def transform_code(transform):
+    if not isinstance(transform, (str, type(None))) or transform not in TRANSFORMS:
+        raise TransformError("transform must be None, 'identity', 'ilogit' or 'square', not %r" % (transform,))
+    return TRANSFORMS[transform]
+
+
+def check_q(q, allow_none=False):
+    """Percentiles as a contiguous float64 1-D array; None (where allowed): none."""
+    if q is None and allow_none:
+        return np.zeros(0)
+    qs = _native.as_f64(np.atleast_1d(q))
+    if qs.ndim != 1 or not np.all((qs >= 0) & (qs <= 100)):
+        raise ValueError("percentiles q must lie in [0, 100]")
+    return qs
+
+
+def check_states(Ws, Vs, shape=None, nembeds=None, what=""):
+    """(Ws, Vs) as contiguous float64 (S,N,K) / (S,M,T,K) arrays.  shape=None: they only have to agree with each other
+    (the stateless forms); shape (N,M,T) and nembeds: they match the model and hold at least one sample.  Ws=None: Vs alone
+    (fold_in_rows: at least one sample either way)."""
+    Vs = _native.as_f64(Vs)
+    S = Vs.shape[0] if Vs.ndim == 4 else -1
+    if Ws is not None:
+        Ws = _native.as_f64(Ws)
+    if shape is None:
+        N, M, T, K = ("N", "M", "T", "K")
+        ok = Vs.ndim == 4 and (S >= 1 if Ws is None else Ws.ndim == 3 and Ws.shape[::2] == Vs.shape[::3])
+    else:
+        (N, M, T), K = shape, nembeds
+        ok = S >= 1 and Vs.shape == (S, M, T, K) and (Ws is None or Ws.shape == (S, N, K))
+    if not ok:
+        want_V = "(S,%s,%s,%s)" % (M, T, K)
+        if Ws is None:
+            raise ValueError("%sVs must be %s, got %r" % (what, want_V, Vs.shape))
+        raise ValueError("%sWs must be (S,%s,%s) and Vs %s, got %r / %r" % (what, N, K, want_V, Ws.shape, Vs.shape))
+    return Ws, Vs
+
+
+def check_scalars(name, v, S, positive=True):
+    """One value per sample (nu2, sigma2) as a contiguous (S,) array; positive: each finite and > 0."""
+    if v is None:
+        raise ValueError("%s: one value per sample is needed" % name)
+    a = np.asarray(v, dtype=float)
+    if a.size != S:
+        raise ValueError("%s must hold one value per sample (%d), got shape %r" % (name, S, a.shape))
+    a = np.ascontiguousarray(a.reshape(S))
+    if positive and not (np.all(np.isfinite(a)) and np.all(a > 0)):
+        raise ValueError("%s must be finite and positive" % name)
+    return a
+
+
+def summary(call, shape, q, transform):
+    """(mean (N,M,T), quantiles (len(q),N,M,T)) of f(W V') from a summary entry point: call(code, q, nq, mean, quantiles)
+    runs it with whatever precedes those five arguments (btf_collect_summary, btf_posterior_summary)."""
+    code = transform_code(transform)
+    qs = _native.as_f64(np.atleast_1d(q))
+    mean = np.zeros(tuple(shape))
+    quant = np.zeros((len(qs),) + mean.shape)
+    call(code, _native.dptr(qs), len(qs), _native.dptr(mean), _native.dptr(quant))
+    return mean, quant
+
+
+class PosteriorAnalysis:
+    """The analysis methods of BayesianTensorFiltering (functionalmf_amd/factor.py), over the samples a device-collecting
+    run_gibbs kept (`_collected` of them) or a run_gibbs result dict."""
+
+    def _unsharded(self, what):
+        if self._plan.world > 1 or self._exchange.active:
+            raise NotImplementedError("%s: unsharded models only" % what)
+
+    def _samples(self, results, need=("W", "V")):
+        """(S, Ws, Vs) of an analysis call.  results None: the S samples the last device-collecting run_gibbs kept, and
+        Ws = Vs = None (they are read where they lie); otherwise the dict's states, checked against the model, as contiguous
+        float64 arrays to upload (Ws None unless "W" is needed)."""
+        if results is None:
+            S = getattr(self, "_collected", 0)
+            if S < 1:
+                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first), and no results given")
+            return S, None, None
+        try:
+            Ws, Vs = results["W"] if "W" in need else None, results["V"]
+        except (KeyError, TypeError):
+            raise ValueError("results must be a run_gibbs result dict with %sV (S,M,T,K)" % ("W (S,N,K) and " if "W" in need else ""))
+        Ws, Vs = check_states(Ws, Vs, (self.nrows, self.ncols, self.ndepth), self.nembeds, what="results: ")
+        return Vs.shape[0], Ws, Vs
+
+    def posterior_summary(self, q=(5, 95), transform=None):
+        """Mean and percentiles of f(W V') over the samples the last device-collecting run_gibbs kept,
+        computed where they lie (btf_collect_summary); see functionalmf_amd.utils.posterior_summary."""
+        self._unsharded("posterior_summary")
+        S = self._samples(None)[0]
+        return summary(lambda *tail: self._ctx.call("btf_collect_summary", int(S), *tail), (self.nrows, self.ncols, self.ndepth),
+                       q, transform)
+
+    def convergence_diagnostics(self, *others, transform=None):
+        """Split R-hat, bulk / tail ESS and MCSE per cell of f(W V') over this model's device-collected samples and
+        those of `others` (models or run_gibbs result dicts): functionalmf_amd.diagnostics.convergence([self, *others])."""
+        from . import diagnostics
+        return diagnostics.convergence([self] + list(others), transform=transform)
+
+    # ---- model selection: per-curve log-likelihood, WAIC, DIC, PSIS-LOO (functionalmf_amd/criteria.py, csrc/btf_criteria.h) ----
+    def _crit_drop(self, slot):
+        keys = getattr(self, "_crit_keys", None)
+        if keys is not None and keys[slot] is not None:
+            self._ctx.call("btf_crit_set_data", slot, None, None, None, None)
+            keys[slot] = None
+
+    def _crit_slot(self, data, family, param):
+        """Upload the criteria statistics of `data` once (cached by identity, shape and fingerprint, as set_data
+        recognises the bound data); returns (slot, observed-curve mask).  Slot 0 holds the bound data, 1 held-out data."""
+        from .factor import _fingerprint
+        if data is None:
+            data = getattr(self, "_data_ref", None)
+            if data is None:
+                raise ValueError("no data bound to the model: pass data=")
+        arrays = data if isinstance(data, (tuple, list)) else (data,)
+        key = (family, param) + tuple((id(a), np.shape(a), _fingerprint(a)) for a in arrays)
+        if getattr(self, "_crit_keys", None) is None:
+            self._crit_keys, self._crit_obs, self._crit_refs = [None, None], [None, None], [None, None]
+        for slot in (0, 1):
+            if self._crit_keys[slot] == key:
+                return slot, self._crit_obs[slot]
+        bound = getattr(self, "_data_ref", None)
+        bound = bound if isinstance(bound, (tuple, list)) else (bound,)
+        slot = 0 if len(bound) == len(arrays) and all(a is b for a, b in zip(arrays, bound)) else 1
+        S1, cnt, c0, c1, obs = _criteria.statistics(family, data, (self.nrows, self.ncols, self.ndepth), param)
+        self._ctx.call("btf_crit_set_data", slot, _native.dptr(S1), _native.dptr(cnt), _native.dptr(c0), _native.dptr(c1))
+        self._crit_keys[slot], self._crit_obs[slot], self._crit_refs[slot] = key, obs, data     # (refs: ids stay unique)
+        return slot, obs
+
+    def _crit_check(self):
+        """Refusals before any work: sharded contexts, likelihoods without a device form."""
+        self._unsharded("model-selection criteria")
+        return self._crit_family()
+
+    def _crit_noise(self, results, S):
+        """The per-sample noise variances of a result dict (None: the collected ones, or a likelihood without)."""
+        if results is None or not self._crit_family()[2]:
+            return None
+        return check_scalars("results: nu2", results.get("nu2"), S, positive=False)
+
+    def _crit_head(self, data, nsamples, Ws=None, Vs=None, noise=None, current=False):
+        """The arguments btf_crit_eval and btf_crit_loo share - slot, family, parameter, samples, noise, flags - and the
+        observed-curve mask of the slot."""
+        family, param, per_sample = self._crit_check()
+        slot, obs = self._crit_slot(data, family, param)
+        flags = (_native.CRIT_NOISE_PER_SAMPLE if per_sample else 0) | (_native.CRIT_CURRENT if current else 0)
+        noise = _native.as_f64(np.reshape(noise, -1)) if (per_sample and noise is not None) else None
+        Ws = None if Ws is None else _native.as_f64(Ws)
+        Vs = None if Vs is None else _native.as_f64(Vs)
+        return (slot, int(family), float(param if param is not None else 0.0), int(nsamples), _native.dptr(Ws), _native.dptr(Vs),
+                _native.dptr(noise), flags), obs
+
+    def _crit_eval(self, data, nsamples, Ws=None, Vs=None, noise=None, current=False, pointwise=False):
+        head, obs = self._crit_head(data, nsamples, Ws, Vs, noise, current)
+        curve, totals, pw = _criteria.evaluate(self._ctx, head, (self.nrows, self.ncols), pointwise)
+        return curve, totals, obs, pw
+
+    def information_criteria(self, results=None, data=None, pointwise=False):
+        """WAIC and DIC of the posterior samples, from the per-curve log-likelihood (csrc/btf_criteria.h; replaces the
+        scoring of _BayesianModel.select_hyperparams_DIC, genlasso.py:69-136, and doseresponse/select_btf.py:9-23).
+
+        results: a run_gibbs result dict (W (S,N,K), V (S,M,T,K); Gaussian: nu2 (S,1)), uploaded; None: the samples the
+            last device-collecting run_gibbs left on the device (no upload).
+        data: the observations to score; None: the data the model is bound to.  Another tensor of the same shape scores
+            held-out observations (NaN everywhere else): `lppd` is then their log pointwise predictive density.
+
+        The pointwise unit is the curve (i,j): ll_s(i,j) = the normalised log-likelihood of all observed y_ijtr of the
+        curve under sample s.  Curves without observations count 0 and are left out of n_curves.
+            lppd_ij = logsumexp_s ll_s(i,j) - log S        p_waic_ij = var_s ll_s(i,j) (ddof 1; 0 when S = 1)
+            elpd_waic = sum (lppd_ij - p_waic_ij),  waic = -2 elpd_waic,  waic_se = 2 sqrt(n_curves var_ij(lppd - p_waic))
+            mean_deviance = -2 mean_s sum_ij ll_s,   deviance_at_mean = -2 sum_ij ll(Mu-bar, theta-bar)
+            p_dic = mean_deviance - deviance_at_mean,   dic = mean_deviance + p_dic
+        Mu-bar_ijt = mean_s w_i^s . v_jt^s is the posterior mean of the product, NOT W-bar V-bar': W and V are identified
+        only up to rotation and sign between samples, so their means are meaningless (doseresponse/select_btf.py plugs in
+        the mean of W V' too).  theta-bar: the mean sampled nu2 (Gaussian), the fixed likelihood_param otherwise.
+        A -inf sample (poisson_identity where w.v <= 0) follows scipy.special.logsumexp / np.var: that curve's p_waic is nan.
+
+        Returns a dict with waic, elpd_waic, p_waic, lppd, waic_se, dic, p_dic, mean_deviance, deviance_at_mean,
+        n_curves, nsamples, loglik_per_sample (S,) and curves = {lppd, p_waic, mean_ll, ll_at_mean} of (N,M) arrays;
+        pointwise=True adds loglik (S,N,M), the full matrix (S*N*M doubles of host memory; PSIS-LOO from it stays on the
+        device: loo()).
+        Device memory: the criteria statistics, 16 B per cell (functionalmf_amd/criteria.py), and 8 B per cell of scratch."""
+        self._crit_check()
+        S, Ws, Vs = self._samples(results)
+        curve, totals, obs, pw = self._crit_eval(data, S, Ws, Vs, self._crit_noise(results, S), pointwise=pointwise)
+        return _criteria.combine(curve, totals, obs, pw)
+
+    def loo(self, results=None, data=None, r_eff=None, mean=False, transform=None, log_weights=False):
+        """PSIS-LOO: Pareto-smoothed importance-sampling leave-one-curve-out (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson,
+        Gelman, Yao, Gabry 2024) on the GPU (csrc/btf_loo.h); functionalmf_amd.criteria.psis_curve is its written definition.
+
+        results, data: as information_criteria, with the same pointwise unit: the curve (i,j) = all observed y_ijtr over
+            depth and replicates; curves without observations count 0 and are left out.
+        r_eff: the relative efficiency of the draws, None (1), a scalar or (N,M); finite and > 0.  It sets the number of
+            largest importance ratios the Pareto fit uses, min(floor(0.2 S), ceil(3 sqrt(S / r_eff))).
+        mean: also return the leave-curve-out fitted curve, mean (N,M,T) = sum_s w_s(i,j) f(w_i^s . v_jt^s) with the smoothed
+            normalised weights - what the model predicts for (i,j) had it not seen that curve; transform: f, as
+            posterior_summary (None / "identity", "ilogit", "square").
+        log_weights: also return the normalised log weights (S,N,M) (S*N*M doubles of host memory).
+
+        Returns a dict: elpd_loo = sum_ij elpd_loo_ij, p_loo = sum (lppd_ij - elpd_loo_ij), looic = -2 elpd_loo,
+        se = sqrt(n_curves var_ij elpd_loo_ij), n_curves, nsamples, good_k = min(1 - 1 / log10(S), 0.7), n_bad = the curves
+        with pareto_k > good_k (their elpd_loo_ij is not to be trusted), observed (N,M) bool, curves = {elpd_loo, p_loo, pareto_k, lppd} of (N,M)
+        arrays (0 for unobserved curves; pareto_k: nan there).  pareto_k = inf: no Pareto fit (S < 25, or every ratio of
+        the curve equal) and the unsmoothed estimate.  A curve with a -inf sample (poisson_identity where w.v <= 0) has
+        elpd_loo = -inf and pareto_k = inf, one with a nan sample nan; both have nan log weights and mean.
+        S <= 4096.  Device memory for the call's duration: 8 S N M bytes (1.05 GB at (512,256,64), S = 1000) beside the
+        criteria statistics.  criteria.compare(a, b) gives the paired elpd difference of two models' results."""
+        self._crit_check()
+        code = transform_code(transform)
+        shape = (self.nrows, self.ncols, self.ndepth)
+        if r_eff is not None:
+            r_eff = np.asarray(r_eff, dtype=float)
+            if r_eff.shape not in ((), shape[:2]):
+                raise ValueError("r_eff must be a scalar or a (%d,%d) array" % shape[:2])
+            if not (np.all(np.isfinite(r_eff)) and np.all(r_eff > 0)):
+                raise ValueError("r_eff must be finite and > 0")
+            r_eff = _native.as_f64(np.broadcast_to(r_eff, shape[:2]))
+        S, Ws, Vs = self._samples(results)
+        noise = self._crit_noise(results, S)
+        if S > _criteria.LOO_MAX_SAMPLES:
+            raise ValueError("loo: %d samples, at most %d" % (S, _criteria.LOO_MAX_SAMPLES))
+        head, obs = self._crit_head(data, S, Ws, Vs, noise)
+        return _criteria.loo_evaluate(self._ctx, head, shape, obs, r_eff=r_eff, transform=code, mean=mean, log_weights=log_weights)
+
+    # ---- posterior predictive: replicated observations, bands, coverage, scores (functionalmf_amd/predictive.py) ----
+    def posterior_predictive(self, results=None, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=None, trials=None,
+                             cells=None):
+        """Posterior predictive of the observations on the GPU (csrc/btf_predict.h): for every cell (i,j,t), kept sample s
+        and r < draws_per_sample a replicated observation y_rep ~ p(y | w_i^s . v_jt^s, theta_s), reduced on the device.
+        What flutrends/benchmark.py:60-75, :129-134 and politics/benchmark.py:147-172 compute on the host.
+
+        results: a run_gibbs result dict (W, V; Gaussian: nu2; Negative-Binomial: R, else the current rate), uploaded;
+            None: the samples the last device-collecting run_gibbs left on the device (no upload).
+        data: the observations to compare with; None: the data the model is bound to (nothing, if none is bound).  Another
+            tensor of the same shape (NaN elsewhere) scores held-out observations, as information_criteria(data=).
+        q: percentiles of the draws; coverage is that of the interval [q[0], q[-1]].
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        trials: (N,M,T) Binomial trial counts for the draws; None: the N of the (Y, N) data pair (1 for Bernoulli tensors).
+        cells: flat indices or (i,j,t) triples of cells whose raw draws come back as `draws` (ncells, S * draws_per_sample).
+
+        Returns a dict: mean = mean_s E[y | theta_s]; y_mean, y_var (ddof 1) of the draws; quantiles (len(q),N,M,T); with
+        data: pit_lo / pit_hi (fraction of draws < y / <= y, averaged over the cell's observed replicates), inside and nobs
+        (observed replicates inside the interval / observed), rmse and mae (S,) of y - E[y | theta_s] over all observed y,
+        coverage = inside.sum() / nobs.sum(); nominal = (q[-1] - q[0]) / 100, nsamples, ndraws.
+        S * draws_per_sample <= 16384; unsharded models; gamma_grid and Python-callable likelihoods are not supported."""
+        from . import predictive as _pred
+        family, param, per_sample = self._pred_family()
+        self._unsharded("posterior predictive")
+        S, Ws, Vs = self._samples(results)
+        S, R = _pred.check_draws(S, draws_per_sample)
+        aux, flags = self._pred_aux(results, S) if per_sample else (None, 0)
+        if data is None:
+            data = getattr(self, "_data_ref", None)
+        Y = data
+        if isinstance(data, (tuple, list)):               # Binomial (Y, N): successes of N trials
+            Y = data[0]
+            if trials is None:
+                trials = data[1]
+        if seed is None:
+            seed = self._next_seed()
+        return _pred.evaluate(self._ctx, (self.nrows, self.ncols, self.ndepth), self.nembeds, family, S, Ws, Vs, param=param,
+                              aux=aux, aux_flags=flags, trials=trials, Y=Y, q=q, draws_per_sample=R, seed=seed, cells=cells)
+
+    # ---- posterior curve functionals: AUC, peak, level crossing (functionalmf_amd/functionals.py) ----
+    def posterior_functionals(self, results=None, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None,
+                              curves=None, pointwise=False):
+        """Per-curve functionals of f(w_i . v_j,:) over depth - area under the curve, maximum / minimum and where they lie,
+        total rise, the first crossing of a level - summarised over the kept samples on the GPU (csrc/btf_functionals.h).
+        What doseresponse/feature_importance.py:40 computes from the (S,N,M,T) tensor on the host.
+
+        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device (no upload).
+        The other arguments and the returned dict: functionalmf_amd.utils.posterior_functionals.  The sampler's state is not
+        touched: a chain continued after the call walks the same path.  Unsharded models."""
+        from . import functionals as _func
+        self._unsharded("posterior functionals")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        if results is not None:                            # a bad argument is reported before a malformed results
+            _func.check_args(which, q, transform, x, level, exceed, curves, 1, *shape)
+        S, Ws, Vs = self._samples(results)
+        return _func.evaluate(shape, self.nembeds, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed,
+                              curves=curves, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
+
+    # ---- folding new rows in (functionalmf_amd/fold_in.py, csrc/btf_fold_in.h) ----
+    def fold_in_rows(self, Y_new, results=None, seed=None, z=None, summary=True, q=(5, 95), transform=None, inner_sweeps=None,
+                     trials=None):
+        """Embeddings and curves of rows the chain never saw (a new cell line with a handful of drugs tested, a new
+        season), with uncertainty, on the GPU (csrc/btf_fold_in.h).  Given V the rows of W are conditionally independent
+        with prior N(0, sigma2 I) (factor.py:333), so under kept sample s the new row has the conditional _resample_W
+        draws from (factor.py:333-362), and one draw per kept sample is a draw from p(w_new | y_new, training data).
+        Exact for the Gaussian model; the Binomial model runs `inner_sweeps` Polya-Gamma rounds per (sample, row) from
+        w = 0 (factor.py:437-460; default: functionalmf_amd.fold_in.DEFAULT_INNER_SWEEPS).
+
+        Y_new: (R,M,T) or (R,M,T,nreps), NaN = missing; Binomial: the (Y, N) pair, or Y with trials= (default 1), counts
+            up to 32.  A row with no observation at all is allowed: its draw is the prior's.
+        results: a run_gibbs result dict (V (S,M,T,K), sigma2 one value per sample, Gaussian nu2 likewise), uploaded; None:
+            the samples the last device-collecting run_gibbs left on the device - no upload of V, and nu2_s, sigma2_s are read
+            from the collected scalars.
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        z: optional (S,R,K) standard normals replacing the device generator (Gaussian only): w = Q^-1 b + L^-T z, Q = L L'.
+
+        Returns a dict: W (S,R,K) one draw per kept sample; W_mean (S,R,K) the conditional means Q_s^-1 b_s (Gaussian
+        only); with summary=True, mean (R,M,T) and quantiles (len(q),R,M,T) of f(w_new^s . v_jt^s) from the summary kernel
+        on the device-resident W and V (transform as posterior_summary; at most 16384 samples); nsamples.  out["W"] together
+        with results["V"] goes straight into utils.posterior_summary, utils.posterior_predictive and
+        utils.posterior_functionals.  The sampler's state is not touched: a chain continued after the call walks the same
+        path.  Unsharded models.  Folding in new COLUMNS is out of scope: it needs the horseshoe local scales of a column
+        nobody has sampled."""
+        from . import fold_in as _fold
+        family = self._fold_family()
+        self._unsharded("fold_in_rows")
+        M, T, K = self.ncols, self.ndepth, self.nembeds
+        R, weights, sums = _fold.row_statistics(Y_new, family, M, T, trials=trials)
+        S, _, Vs = self._samples(results, need=("V",))
+        _fold.check_args(family, S, R, K, z, summary, q, transform, inner_sweeps)
+        nu2 = sigma2 = None
+        if results is not None:
+            sigma2 = check_scalars("results: sigma2", results.get("sigma2"), S)
+            if _fold.FAMILIES[family] == _fold.FAMILIES["gaussian"]:
+                nu2 = check_scalars("results: nu2", results.get("nu2"), S)
+        if seed is None:
+            seed = self._next_seed() if z is None else 0
+        return _fold.evaluate(family, S, R, M, T, K, weights, sums, z=z, seed=seed, summary=summary, q=q, transform=transform,
+                              inner_sweeps=inner_sweeps, ctx=self._ctx, Vs=Vs, nu2=nu2, sigma2=sigma2, device=self._ctx.device)
+
+    def logprob(self, data, reduce="sum", **state):
+        """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,
+        nu2=); further keys (Tau2, lam2, sigma2, ...: what the reference's DIC passes) are ignored.  reduce="sum": a
+        float; "curve": the (N,M) per-curve values (0 for curves without observations).  The criteria kernel with one sample.
+        Deviation: the reference (factor.py:262-264, :610-612, :1002-1005) returns an elementwise array built from an
+        undefined name, with sigma2 where the noise variance nu2 belongs."""
+        from .factor import _scalar
+        if reduce not in ("sum", "curve"):
+            raise ValueError("reduce must be 'sum' or 'curve'")
+        per_sample = self._crit_check()[2]
+        W, V = state.get("W"), state.get("V")
+        noise = None
+        if per_sample:
+            noise = np.array([_scalar(state["nu2"] if state.get("nu2") is not None else self.nu2)])
+        if W is None and V is None and not (self._W_host_new or self._V_host_new):
+            curve, totals, obs, _ = self._crit_eval(data, 1, noise=noise, current=True)       # the device's own W, V
+        else:
+            if W is None:
+                self._pull_W()
+                W = self._W
+            if V is None:
+                self._pull_V()
+                V = self._V
+            W, V = np.asarray(W, dtype=float), np.asarray(V, dtype=float)
+            if W.shape != (self.nrows, self.nembeds) or V.shape != (self.ncols, self.ndepth, self.nembeds):
+                raise ValueError("W %r / V %r do not match the model" % (W.shape, V.shape))
+            curve, totals, obs, _ = self._crit_eval(data, 1, W[None], V[None], noise)
+        if reduce == "sum":
+            return float(totals[0])
+        return np.where(obs, curve[2], 0.0)

@@ -260,6 +260,17 @@ def load():
     return lib
 
 
+def check(rc, lib, handle=None, fail_index=True):
+    """Raise what the return code of an entry point stands for, with the text the library keeps for `handle` (a context,
+    or None: the stateless entry points).  fail_index=False: the entry point records no failing system (index -1)."""
+    if rc == BTF_OK:
+        return
+    msg = lib.btf_last_error(handle).decode()
+    if rc == BTF_ENOTPD:
+        raise NotPositiveDefiniteError(rc, msg, lib.btf_fail_index(handle) if fail_index else -1)
+    raise BTFError(rc, msg)
+
+
 def dptr(a):
     return a.ctypes.data_as(_c_dp) if a is not None else None
 
@@ -274,10 +285,8 @@ class Context:
     def __init__(self, nrows, ncols, ndepth, nembeds, tf_order, device=0, stream=None):
         self.lib = load()
         self.h = _ctx()
-        rc = self.lib.btf_create(C.byref(self.h), nrows, ncols, ndepth, nembeds, tf_order, device,
-                                 C.c_void_p(stream) if stream else None)
-        if rc != BTF_OK:
-            raise BTFError(rc, self.lib.btf_last_error(None).decode())
+        check(self.lib.btf_create(C.byref(self.h), nrows, ncols, ndepth, nembeds, tf_order, device,
+                                  C.c_void_p(stream) if stream else None), self.lib)
         self.dims = (nrows, ncols, ndepth, nembeds, tf_order)
         self.device = device
         self.stream_handle = self.lib.btf_stream(self.h)      # hipStream_t the step functions enqueue on
@@ -294,12 +303,7 @@ class Context:
             pass
 
     def check(self, rc):
-        if rc == BTF_OK:
-            return
-        msg = self.lib.btf_last_error(self.h).decode()
-        if rc == BTF_ENOTPD:
-            raise NotPositiveDefiniteError(rc, msg, self.lib.btf_fail_index(self.h))
-        raise BTFError(rc, msg)
+        check(rc, self.lib, self.h)
 
     def call(self, name, *args):
         self.check(getattr(self.lib, name)(self.h, *args))

@@ -110,6 +110,19 @@ def combine(curve, totals, observed, loglik=None):
     return out
 
 
+def evaluate(ctx, head, shape, pointwise=False):
+    """btf_crit_eval on `ctx` (a _native.Context).  head: the arguments it shares with btf_crit_loo - slot, family, parameter,
+    nsamples, Ws, Vs, noise, flags (PosteriorAnalysis._crit_head); shape (N,M).  Returns (curve (5,N,M), totals (S,),
+    pointwise (S,N,M) or None): what combine() takes."""
+    from . import _native
+    S = head[3]
+    curve = np.zeros((CURVE_OUTPUTS,) + tuple(shape))
+    totals = np.zeros(S)
+    pw = np.zeros((S,) + tuple(shape)) if pointwise else None
+    ctx.call("btf_crit_eval", *head, _native.dptr(curve), _native.dptr(totals), _native.dptr(pw))
+    return curve, totals, pw
+
+
 def from_loglik(L, observed, L_at_mean):
     """The criteria dictionary straight from a (S, N, M) log-likelihood matrix and the (N, M) plug-in log-likelihood,
     by scipy / numpy (the definition combine() implements; used to check it)."""
@@ -247,6 +260,21 @@ def loo_combine(elpd_loo, pareto_k, lppd, observed, nsamples, mean=None, log_wei
     if log_weights is not None:
         out["log_weights"] = log_weights
     return out
+
+
+def loo_evaluate(ctx, head, shape, observed, r_eff=None, transform=0, mean=False, log_weights=False):
+    """btf_crit_loo on `ctx` (a _native.Context) and the dictionary of BayesianTensorFiltering.loo().  head: as evaluate();
+    shape (N,M,T); r_eff: None or a contiguous (N,M) array; transform: the code of the leave-curve-out mean."""
+    from . import _native
+    N, M, T = shape
+    S = head[3]
+    out = np.zeros((4, N, M))
+    mean_out = np.zeros((N, M, T)) if mean else None
+    lw = np.zeros((S, N, M)) if log_weights else None
+    ctx.call("btf_crit_loo", *head, _native.dptr(r_eff), int(transform), _native.dptr(out), _native.dptr(mean_out), _native.dptr(lw))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lppd = out[3] + np.log(out[2]) - np.log(S)            # (as combine forms it: the same bits)
+    return loo_combine(out[0], out[1], lppd, observed, S, mean=mean_out, log_weights=lw)
 
 
 def _curve_elpd(res):

@@ -20,11 +20,12 @@ import ctypes as C
 
 import numpy as np
 
+from ._analysis import check_states, transform_code
+
 MIN_DRAWS = 4                 # draws per chain
 MAX_CHAINS = 64               # DIAG_MAX_CHAINS of csrc/btf_diag.h
 MAX_POOLED_DRAWS = 4096       # DIAG_MAX_DRAWS: chains x draws per cell (the kernel keeps a cell's draws in LDS)
 RHAT_THRESHOLD = 1.01
-TRANSFORMS = {None: 0, "identity": 0, "ilogit": 1, "square": 2}
 OUTPUTS = ("rhat", "ess_bulk", "ess_tail", "mcse_mean", "mean")
 _SCALAR_COLUMNS = {"nu2": 0, "sigma2": 1, "lam2": 2}     # of the collected scalars (btf_collect_end)
 
@@ -118,36 +119,33 @@ def _is_model(obj):
 def _describe(chain):
     """(kind, S, (N, M, T, K), device, payload) of one chain; model refusals here, before any device call."""
     if isinstance(chain, dict):
-        try:
-            W, V = np.asarray(chain["W"], dtype=float), np.asarray(chain["V"], dtype=float)
-        except KeyError:
+        if "W" not in chain or "V" not in chain:
             raise ValueError("a result dict needs W (S,N,K) and V (S,M,T,K)")
-        if W.ndim != 3 or V.ndim != 4 or W.shape[0] != V.shape[0] or W.shape[2] != V.shape[3]:
-            raise ValueError("a result dict needs W (S,N,K) and V (S,M,T,K); got %r / %r" % (W.shape, V.shape))
+        W, V = check_states(chain["W"], chain["V"], what="a result dict: ")
         return "dict", W.shape[0], (W.shape[1], V.shape[1], V.shape[2], W.shape[2]), None, (W, V)
     if _is_model(chain):
-        if chain._plan.world > 1 or chain._exchange.active:
-            raise NotImplementedError("convergence diagnostics: unsharded models only")
-        n = getattr(chain, "_collected", 0)
-        if n < 1:
-            raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first)")
+        chain._unsharded("convergence diagnostics")
+        n = chain._samples(None)[0]
         return "model", n, (chain.nrows, chain.ncols, chain.ndepth, chain.nembeds), chain.device, chain
     raise ValueError("a chain is a run_gibbs result dict or a model whose last run_gibbs collected on the device")
 
 
-def _scalar_series(kind, payload, S, name):
-    if kind == "dict":
-        if name not in payload:
-            return None
-        v = np.asarray(payload[name], dtype=float)
-        return v.reshape(S) if v.size == S else None
-    col = _SCALAR_COLUMNS.get(name)
-    if col is None:
-        return None
+def _scalar_table(chain, S):
+    """{name: one value per draw} of a chain: a result dict is its own table; a model's collected scalars come in one
+    download."""
+    if isinstance(chain, dict):
+        return chain
     from . import _native
     sc = np.zeros((S, 8))
-    payload._ctx.call("btf_collect_end", int(S), None, None, None, _native.dptr(sc))
-    return sc[:, col].copy()
+    chain._ctx.call("btf_collect_end", int(S), None, None, None, _native.dptr(sc))
+    return {name: sc[:, col].copy() for name, col in _SCALAR_COLUMNS.items()}
+
+
+def _scalar_series(table, S, name):
+    if name not in table:
+        return None
+    v = np.asarray(table[name], dtype=float)
+    return v.reshape(S) if v.size == S else None
 
 
 def convergence(chains, transform=None, scalars=("nu2", "sigma2", "lam2")):
@@ -170,8 +168,7 @@ def convergence(chains, transform=None, scalars=("nu2", "sigma2", "lam2")):
     min_ess_bulk, min_ess_tail (nan-aware); nchains; ndraws: S per chain; scalars: {name: {rhat, ess_bulk, ess_tail,
     mcse_mean}}}.  Raises ValueError (bad transform, shapes or sizes, chains on different devices) before any device call,
     RuntimeError for a model without device-collected samples, NotImplementedError for a sharded model."""
-    if not isinstance(transform, (str, type(None))) or transform not in TRANSFORMS:
-        raise ValueError("transform must be None, 'identity', 'ilogit' or 'square'")
+    tcode = transform_code(transform)
     if isinstance(chains, dict) or _is_model(chains):
         chains = [chains]
     chains = list(chains)
@@ -201,19 +198,16 @@ def convergence(chains, transform=None, scalars=("nu2", "sigma2", "lam2")):
 
     from . import _native
     lib = _native.load()
-    keep, wp, vp = [], (_native._c_dp * nch)(), (_native._c_dp * nch)()
+    wp, vp = (_native._c_dp * nch)(), (_native._c_dp * nch)()             # (desc keeps the uploaded arrays alive)
     ctxs = (C.c_void_p * nch)()
     for c, (kind, _, _, _, payload) in enumerate(desc):
         if kind == "model":
             ctxs[c] = payload._ctx.h
         else:
-            W, V = (_native.as_f64(a) for a in payload)
-            keep += [W, V]
+            W, V = payload
             wp[c], vp[c] = _native.dptr(W), _native.dptr(V)
     out = np.zeros((len(OUTPUTS), N, M, T))
-    rc = lib.btf_diag_eval(int(device), nch, int(S), N, M, T, K, wp, vp, ctxs, TRANSFORMS[transform], _native.dptr(out))
-    if rc != _native.BTF_OK:
-        raise _native.BTFError(rc, lib.btf_last_error(None).decode())
+    _native.check(lib.btf_diag_eval(int(device), nch, int(S), N, M, T, K, wp, vp, ctxs, tcode, _native.dptr(out)), lib)
     res = dict(zip(OUTPUTS, out))
     rhat = res["rhat"]
     with np.errstate(invalid="ignore"):
@@ -224,8 +218,9 @@ def convergence(chains, transform=None, scalars=("nu2", "sigma2", "lam2")):
         res["min_" + k] = float(np.nanmin(a)) if np.any(~np.isnan(a)) else float("nan")
     res["nchains"], res["ndraws"] = nch, int(S)
     res["scalars"] = {}
+    tables = [_scalar_table(c, S) for c in chains] if scalars else []
     for name in scalars or ():
-        series = [_scalar_series(d[0], chains[i] if d[0] == "dict" else d[4], S, name) for i, d in enumerate(desc)]
+        series = [_scalar_series(t, S, name) for t in tables]
         if all(s is not None for s in series):
             res["scalars"][name] = chain_diagnostics(np.stack(series))
     return res

@@ -40,6 +40,7 @@ import numpy as np
 from . import _native
 from . import criteria as _criteria
 from . import likelihoods as _likelihoods
+from ._analysis import PosteriorAnalysis, check_scalars
 from .genlasso import _BayesianModel, ConjugateInverseGammaPrior
 from .utils import bayes_grid_penalty, sample_horseshoe_plus, sample_horseshoe
 from .parallel import ShardPlan, Exchange
@@ -103,7 +104,7 @@ def stale_col_sources(missing):
     return src
 
 
-class BayesianTensorFiltering(_BayesianModel):
+class BayesianTensorFiltering(PosteriorAnalysis, _BayesianModel):
     def __init__(self, nrows, ncols, ndepth,
                  nembeds=5, tf_order=2,
                  sigma2_init=None, sigma2_true=None,
@@ -668,190 +669,11 @@ class BayesianTensorFiltering(_BayesianModel):
     def _sweeps_on_device(self):
         return False
 
-    def posterior_summary(self, q=(5, 95), transform=None):
-        """Mean and percentiles of f(W V') over the samples the last device-collecting run_gibbs kept,
-        computed where they lie (btf_collect_summary); see functionalmf_amd.utils.posterior_summary."""
-        n = getattr(self, "_collected", 0)
-        if n < 1:
-            raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first)")
-        code = {None: 0, "identity": 0, "ilogit": 1, "square": 2}[transform]
-        qs = _native.as_f64(np.atleast_1d(q))
-        mean = np.zeros((self.nrows, self.ncols, self.ndepth))
-        quant = np.zeros((len(qs),) + mean.shape)
-        self._ctx.call("btf_collect_summary", int(n), code, _native.dptr(qs), len(qs), _native.dptr(mean), _native.dptr(quant))
-        return mean, quant
-
-    def convergence_diagnostics(self, *others, transform=None):
-        """Split R-hat, bulk / tail ESS and MCSE per cell of f(W V') over this model's device-collected samples and
-        those of `others` (models or run_gibbs result dicts): functionalmf_amd.diagnostics.convergence([self, *others])."""
-        from . import diagnostics
-        return diagnostics.convergence([self] + list(others), transform=transform)
-
-    # ---- model selection: per-curve log-likelihood, WAIC, DIC (functionalmf_amd/criteria.py, csrc/btf_criteria.h) ----
+    # ---- what the analysis front (functionalmf_amd/_analysis.py: PosteriorAnalysis) asks of a model's likelihood ----
     def _crit_family(self):
         """(family of btf_crit_eval, its parameter, per-sample noise?) of this model's likelihood."""
         raise NotImplementedError("%s: no device log-likelihood for the model-selection criteria" % type(self).__name__)
 
-    def _crit_drop(self, slot):
-        keys = getattr(self, "_crit_keys", None)
-        if keys is not None and keys[slot] is not None:
-            self._ctx.call("btf_crit_set_data", slot, None, None, None, None)
-            keys[slot] = None
-
-    def _crit_slot(self, data, family, param):
-        """Upload the criteria statistics of `data` once (cached by identity, shape and fingerprint, as set_data
-        recognises the bound data); returns (slot, observed-curve mask).  Slot 0 holds the bound data, 1 held-out data."""
-        if data is None:
-            data = getattr(self, "_data_ref", None)
-            if data is None:
-                raise ValueError("no data bound to the model: pass data=")
-        arrays = data if isinstance(data, (tuple, list)) else (data,)
-        key = (family, param) + tuple((id(a), np.shape(a), _fingerprint(a)) for a in arrays)
-        if getattr(self, "_crit_keys", None) is None:
-            self._crit_keys, self._crit_obs, self._crit_refs = [None, None], [None, None], [None, None]
-        for slot in (0, 1):
-            if self._crit_keys[slot] == key:
-                return slot, self._crit_obs[slot]
-        bound = getattr(self, "_data_ref", None)
-        bound = bound if isinstance(bound, (tuple, list)) else (bound,)
-        slot = 0 if len(bound) == len(arrays) and all(a is b for a, b in zip(arrays, bound)) else 1
-        S1, cnt, c0, c1, obs = _criteria.statistics(family, data, (self.nrows, self.ncols, self.ndepth), param)
-        self._ctx.call("btf_crit_set_data", slot, _native.dptr(S1), _native.dptr(cnt), _native.dptr(c0), _native.dptr(c1))
-        self._crit_keys[slot], self._crit_obs[slot], self._crit_refs[slot] = key, obs, data     # (refs: ids stay unique)
-        return slot, obs
-
-    def _crit_check(self):
-        """Refusals before any work: sharded contexts, likelihoods without a device form."""
-        if self._plan.world > 1 or self._exchange.active:
-            raise NotImplementedError("model-selection criteria: unsharded models only")
-        return self._crit_family()
-
-    def _crit_eval(self, data, nsamples, Ws=None, Vs=None, noise=None, current=False, pointwise=False):
-        family, param, per_sample = self._crit_check()
-        slot, obs = self._crit_slot(data, family, param)
-        N, M = self.nrows, self.ncols
-        curve = np.zeros((_criteria.CURVE_OUTPUTS, N, M))
-        totals = np.zeros(nsamples)
-        pw = np.zeros((nsamples, N, M)) if pointwise else None
-        flags = (_native.CRIT_NOISE_PER_SAMPLE if per_sample else 0) | (_native.CRIT_CURRENT if current else 0)
-        noise = _native.as_f64(np.reshape(noise, -1)) if (per_sample and noise is not None) else None
-        Ws = None if Ws is None else _native.as_f64(Ws)
-        Vs = None if Vs is None else _native.as_f64(Vs)
-        self._ctx.call("btf_crit_eval", slot, int(family), float(param if param is not None else 0.0), int(nsamples),
-                       _native.dptr(Ws), _native.dptr(Vs), _native.dptr(noise), flags, _native.dptr(curve),
-                       _native.dptr(totals), _native.dptr(pw))
-        return curve, totals, obs, pw
-
-    def information_criteria(self, results=None, data=None, pointwise=False):
-        """WAIC and DIC of the posterior samples, from the per-curve log-likelihood (csrc/btf_criteria.h; replaces the
-        scoring of _BayesianModel.select_hyperparams_DIC, genlasso.py:69-136, and doseresponse/select_btf.py:9-23).
-
-        results: a run_gibbs result dict (W (S,N,K), V (S,M,T,K); Gaussian: nu2 (S,1)), uploaded; None: the samples the
-            last device-collecting run_gibbs left on the device (no upload).
-        data: the observations to score; None: the data the model is bound to.  Another tensor of the same shape scores
-            held-out observations (NaN everywhere else): `lppd` is then their log pointwise predictive density.
-
-        The pointwise unit is the curve (i,j): ll_s(i,j) = the normalised log-likelihood of all observed y_ijtr of the
-        curve under sample s.  Curves without observations count 0 and are left out of n_curves.
-            lppd_ij = logsumexp_s ll_s(i,j) - log S        p_waic_ij = var_s ll_s(i,j) (ddof 1; 0 when S = 1)
-            elpd_waic = sum (lppd_ij - p_waic_ij),  waic = -2 elpd_waic,  waic_se = 2 sqrt(n_curves var_ij(lppd - p_waic))
-            mean_deviance = -2 mean_s sum_ij ll_s,   deviance_at_mean = -2 sum_ij ll(Mu-bar, theta-bar)
-            p_dic = mean_deviance - deviance_at_mean,   dic = mean_deviance + p_dic
-        Mu-bar_ijt = mean_s w_i^s . v_jt^s is the posterior mean of the product, NOT W-bar V-bar': W and V are identified
-        only up to rotation and sign between samples, so their means are meaningless (doseresponse/select_btf.py plugs in
-        the mean of W V' too).  theta-bar: the mean sampled nu2 (Gaussian), the fixed likelihood_param otherwise.
-        A -inf sample (poisson_identity where w.v <= 0) follows scipy.special.logsumexp / np.var: that curve's p_waic is nan.
-
-        Returns a dict with waic, elpd_waic, p_waic, lppd, waic_se, dic, p_dic, mean_deviance, deviance_at_mean,
-        n_curves, nsamples, loglik_per_sample (S,) and curves = {lppd, p_waic, mean_ll, ll_at_mean} of (N,M) arrays;
-        pointwise=True adds loglik (S,N,M), the full matrix (S*N*M doubles of host memory; PSIS-LOO from it stays on the
-        device: loo()).
-        Device memory: the criteria statistics, 16 B per cell (functionalmf_amd/criteria.py), and 8 B per cell of scratch."""
-        self._crit_check()
-        if results is None:
-            n = getattr(self, "_collected", 0)
-            if n < 1:
-                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first)")
-            curve, totals, obs, pw = self._crit_eval(data, n, pointwise=pointwise)
-        else:
-            Ws, Vs, noise = self._crit_results(results)
-            curve, totals, obs, pw = self._crit_eval(data, Ws.shape[0], Ws, Vs, noise, pointwise=pointwise)
-        return _criteria.combine(curve, totals, obs, pw)
-
-    def loo(self, results=None, data=None, r_eff=None, mean=False, transform=None, log_weights=False):
-        """PSIS-LOO: Pareto-smoothed importance-sampling leave-one-curve-out (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson,
-        Gelman, Yao, Gabry 2024) on the GPU (csrc/btf_loo.h); functionalmf_amd.criteria.psis_curve is its written definition.
-
-        results, data: as information_criteria, with the same pointwise unit: the curve (i,j) = all observed y_ijtr over
-            depth and replicates; curves without observations count 0 and are left out.
-        r_eff: the relative efficiency of the draws, None (1), a scalar or (N,M); finite and > 0.  It sets the number of
-            largest importance ratios the Pareto fit uses, min(floor(0.2 S), ceil(3 sqrt(S / r_eff))).
-        mean: also return the leave-curve-out fitted curve, mean (N,M,T) = sum_s w_s(i,j) f(w_i^s . v_jt^s) with the smoothed
-            normalised weights - what the model predicts for (i,j) had it not seen that curve; transform: f, as
-            posterior_summary (None / "identity", "ilogit", "square").
-        log_weights: also return the normalised log weights (S,N,M) (S*N*M doubles of host memory).
-
-        Returns a dict: elpd_loo = sum_ij elpd_loo_ij, p_loo = sum (lppd_ij - elpd_loo_ij), looic = -2 elpd_loo,
-        se = sqrt(n_curves var_ij elpd_loo_ij), n_curves, nsamples, good_k = min(1 - 1 / log10(S), 0.7), n_bad = the curves
-        with pareto_k > good_k (their elpd_loo_ij is not to be trusted), observed (N,M) bool, curves = {elpd_loo, p_loo, pareto_k, lppd} of (N,M)
-        arrays (0 for unobserved curves; pareto_k: nan there).  pareto_k = inf: no Pareto fit (S < 25, or every ratio of
-        the curve equal) and the unsmoothed estimate.  A curve with a -inf sample (poisson_identity where w.v <= 0) has
-        elpd_loo = -inf and pareto_k = inf, one with a nan sample nan; both have nan log weights and mean.
-        S <= 4096.  Device memory for the call's duration: 8 S N M bytes (1.05 GB at (512,256,64), S = 1000) beside the
-        criteria statistics.  criteria.compare(a, b) gives the paired elpd difference of two models' results."""
-        family, param, per_sample = self._crit_check()
-        codes = {None: 0, "identity": 0, "ilogit": 1, "square": 2}
-        if transform not in codes:
-            raise ValueError("transform must be None, 'identity', 'ilogit' or 'square', not %r" % (transform,))
-        code = codes[transform]
-        N, M, T = self.nrows, self.ncols, self.ndepth
-        if r_eff is not None:
-            r_eff = np.asarray(r_eff, dtype=float)
-            if r_eff.shape not in ((), (N, M)):
-                raise ValueError("r_eff must be a scalar or a (%d,%d) array" % (N, M))
-            if not (np.all(np.isfinite(r_eff)) and np.all(r_eff > 0)):
-                raise ValueError("r_eff must be finite and > 0")
-            r_eff = _native.as_f64(np.broadcast_to(r_eff, (N, M)))
-        if results is None:
-            S = getattr(self, "_collected", 0)
-            if S < 1:
-                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first)")
-            Ws = Vs = noise = None
-        else:
-            Ws, Vs, noise = self._crit_results(results)
-            S = Ws.shape[0]
-            Ws, Vs = _native.as_f64(Ws), _native.as_f64(Vs)
-        if S > _criteria.LOO_MAX_SAMPLES:
-            raise ValueError("loo: %d samples, at most %d" % (S, _criteria.LOO_MAX_SAMPLES))
-        slot, obs = self._crit_slot(data, family, param)
-        out = np.zeros((4, N, M))
-        mean_out = np.zeros((N, M, T)) if mean else None
-        lw = np.zeros((S, N, M)) if log_weights else None
-        noise = _native.as_f64(np.reshape(noise, -1)) if (per_sample and noise is not None) else None
-        self._ctx.call("btf_crit_loo", slot, int(family), float(param if param is not None else 0.0), int(S), _native.dptr(Ws),
-                       _native.dptr(Vs), _native.dptr(noise), _native.CRIT_NOISE_PER_SAMPLE if per_sample else 0,
-                       _native.dptr(r_eff), code, _native.dptr(out), _native.dptr(mean_out), _native.dptr(lw))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            lppd = out[3] + np.log(out[2]) - np.log(S)            # (as criteria.combine forms it: the same bits)
-        return _criteria.loo_combine(out[0], out[1], lppd, obs, S, mean=mean_out, log_weights=lw)
-
-    def _crit_results(self, results):
-        N, M, T, K = self.nrows, self.ncols, self.ndepth, self.nembeds
-        try:
-            Ws, Vs = np.asarray(results["W"], dtype=float), np.asarray(results["V"], dtype=float)
-        except (KeyError, TypeError):
-            raise ValueError("results must be a run_gibbs result dict with W (S,N,K) and V (S,M,T,K)")
-        S = Ws.shape[0] if Ws.ndim == 3 else -1
-        if Ws.shape != (S, N, K) or Vs.shape != (S, M, T, K) or S < 1:
-            raise ValueError("results: W %r / V %r do not match the model's (S,%d,%d) / (S,%d,%d,%d)" % (Ws.shape, Vs.shape, N, K, M, T, K))
-        noise = None
-        if self._crit_family()[2]:
-            if "nu2" not in results or np.size(results["nu2"]) != S:
-                raise ValueError("results: nu2 must hold one variance per sample, (S,1)")
-            noise = np.asarray(results["nu2"], dtype=float).reshape(S)
-        return Ws, Vs, noise
-
-    # ---- posterior predictive: replicated observations, bands, coverage, scores (functionalmf_amd/predictive.py) ----
     def _pred_family(self):
         """(family of btf_predict_eval, its fixed parameter, per-sample parameter?) of this model's likelihood."""
         return self._crit_family()
@@ -860,181 +682,11 @@ class BayesianTensorFiltering(_BayesianModel):
         """(per-sample parameter array or None, flags) for btf_predict_eval; results None: the collected samples."""
         if results is None:
             return None, _native.PRED_AUX_PER_SAMPLE         # the collected nu2 of every kept state
-        if "nu2" not in results or np.size(results["nu2"]) != nsamples:
-            raise ValueError("results: nu2 must hold one variance per sample, (S,1)")
-        return np.asarray(results["nu2"], dtype=float).reshape(nsamples), _native.PRED_AUX_PER_SAMPLE
+        return check_scalars("results: nu2", results.get("nu2"), nsamples, positive=False), _native.PRED_AUX_PER_SAMPLE
 
-    def _pred_states(self, results):
-        from . import predictive as _pred
-        try:
-            Ws, Vs = results["W"], results["V"]
-        except (KeyError, TypeError):
-            raise ValueError("results must be a run_gibbs result dict with W (S,N,K) and V (S,M,T,K)")
-        return _pred.check_states(Ws, Vs, (self.nrows, self.ncols, self.ndepth), self.nembeds)
-
-    def posterior_predictive(self, results=None, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=None, trials=None,
-                             cells=None):
-        """Posterior predictive of the observations on the GPU (csrc/btf_predict.h): for every cell (i,j,t), kept sample s
-        and r < draws_per_sample a replicated observation y_rep ~ p(y | w_i^s . v_jt^s, theta_s), reduced on the device.
-        What flutrends/benchmark.py:60-75, :129-134 and politics/benchmark.py:147-172 compute on the host.
-
-        results: a run_gibbs result dict (W, V; Gaussian: nu2; Negative-Binomial: R, else the current rate), uploaded;
-            None: the samples the last device-collecting run_gibbs left on the device (no upload).
-        data: the observations to compare with; None: the data the model is bound to (nothing, if none is bound).  Another
-            tensor of the same shape (NaN elsewhere) scores held-out observations, as information_criteria(data=).
-        q: percentiles of the draws; coverage is that of the interval [q[0], q[-1]].
-        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
-            an integer leaves the model untouched, and two calls with it return identical bits.
-        trials: (N,M,T) Binomial trial counts for the draws; None: the N of the (Y, N) data pair (1 for Bernoulli tensors).
-        cells: flat indices or (i,j,t) triples of cells whose raw draws come back as `draws` (ncells, S * draws_per_sample).
-
-        Returns a dict: mean = mean_s E[y | theta_s]; y_mean, y_var (ddof 1) of the draws; quantiles (len(q),N,M,T); with
-        data: pit_lo / pit_hi (fraction of draws < y / <= y, averaged over the cell's observed replicates), inside and nobs
-        (observed replicates inside the interval / observed), rmse and mae (S,) of y - E[y | theta_s] over all observed y,
-        coverage = inside.sum() / nobs.sum(); nominal = (q[-1] - q[0]) / 100, nsamples, ndraws.
-        S * draws_per_sample <= 16384; unsharded models; gamma_grid and Python-callable likelihoods are not supported."""
-        from . import predictive as _pred
-        family, param, per_sample = self._pred_family()
-        if self._plan.world > 1 or self._exchange.active:
-            raise NotImplementedError("posterior predictive: unsharded models only")
-        if results is None:
-            S = getattr(self, "_collected", 0)
-            if S < 1:
-                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first), and no results= given")
-            Ws = Vs = None
-        else:
-            Ws, Vs = self._pred_states(results)
-            S = Ws.shape[0]
-        S, R = _pred.check_draws(S, draws_per_sample)
-        aux, flags = self._pred_aux(results, S) if per_sample else (None, 0)
-        if data is None:
-            data = getattr(self, "_data_ref", None)
-        Y = data
-        if isinstance(data, (tuple, list)):               # Binomial (Y, N): successes of N trials
-            Y = data[0]
-            if trials is None:
-                trials = data[1]
-        if seed is None:
-            seed = self._next_seed()
-        return _pred.evaluate(self._ctx, (self.nrows, self.ncols, self.ndepth), self.nembeds, family, S, Ws, Vs, param=param,
-                              aux=aux, aux_flags=flags, trials=trials, Y=Y, q=q, draws_per_sample=R, seed=seed, cells=cells)
-
-    # ---- posterior curve functionals: AUC, peak, level crossing (functionalmf_amd/functionals.py) ----
-    def posterior_functionals(self, results=None, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None,
-                              curves=None, pointwise=False):
-        """Per-curve functionals of f(w_i . v_j,:) over depth - area under the curve, maximum / minimum and where they lie,
-        total rise, the first crossing of a level - summarised over the kept samples on the GPU (csrc/btf_functionals.h).
-        What doseresponse/feature_importance.py:40 computes from the (S,N,M,T) tensor on the host.
-
-        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
-            the device (no upload).
-        The other arguments and the returned dict: functionalmf_amd.utils.posterior_functionals.  The sampler's state is not
-        touched: a chain continued after the call walks the same path.  Unsharded models."""
-        from . import functionals as _func
-        if self._plan.world > 1 or self._exchange.active:
-            raise NotImplementedError("posterior functionals: unsharded models only")
-        shape = (self.nrows, self.ncols, self.ndepth)
-        if results is None:
-            S = getattr(self, "_collected", 0)
-            if S < 1:
-                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first), and no results= given")
-            Ws = Vs = None
-        else:
-            _func.check_args(which, q, transform, x, level, exceed, curves, 1, *shape)
-            Ws, Vs = self._pred_states(results)
-            S = Ws.shape[0]
-        return _func.evaluate(shape, self.nembeds, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed,
-                              curves=curves, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
-
-    # ---- folding new rows in (functionalmf_amd/fold_in.py, csrc/btf_fold_in.h) ----
     def _fold_family(self):
         """Family name of fold_in_rows for this model's likelihood."""
         raise NotImplementedError("%s: fold_in_rows needs a conjugate row conditional (Gaussian and Binomial models)" % type(self).__name__)
-
-    def fold_in_rows(self, Y_new, results=None, seed=None, z=None, summary=True, q=(5, 95), transform=None, inner_sweeps=None,
-                     trials=None):
-        """Embeddings and curves of rows the chain never saw (a new cell line with a handful of drugs tested, a new
-        season), with uncertainty, on the GPU (csrc/btf_fold_in.h).  Given V the rows of W are conditionally independent
-        with prior N(0, sigma2 I) (factor.py:333), so under kept sample s the new row has the conditional _resample_W
-        draws from (factor.py:333-362), and one draw per kept sample is a draw from p(w_new | y_new, training data).
-        Exact for the Gaussian model; the Binomial model runs `inner_sweeps` Polya-Gamma rounds per (sample, row) from
-        w = 0 (factor.py:437-460; default: functionalmf_amd.fold_in.DEFAULT_INNER_SWEEPS).
-
-        Y_new: (R,M,T) or (R,M,T,nreps), NaN = missing; Binomial: the (Y, N) pair, or Y with trials= (default 1), counts
-            up to 32.  A row with no observation at all is allowed: its draw is the prior's.
-        results: a run_gibbs result dict (V (S,M,T,K), sigma2 one value per sample, Gaussian nu2 likewise), uploaded; None:
-            the samples the last device-collecting run_gibbs left on the device - no upload of V, and nu2_s, sigma2_s are read
-            from the collected scalars.
-        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
-            an integer leaves the model untouched, and two calls with it return identical bits.
-        z: optional (S,R,K) standard normals replacing the device generator (Gaussian only): w = Q^-1 b + L^-T z, Q = L L'.
-
-        Returns a dict: W (S,R,K) one draw per kept sample; W_mean (S,R,K) the conditional means Q_s^-1 b_s (Gaussian
-        only); with summary=True, mean (R,M,T) and quantiles (len(q),R,M,T) of f(w_new^s . v_jt^s) from the summary kernel
-        on the device-resident W and V (transform as posterior_summary; at most 16384 samples); nsamples.  out["W"] together
-        with results["V"] goes straight into utils.posterior_summary, utils.posterior_predictive and
-        utils.posterior_functionals.  The sampler's state is not touched: a chain continued after the call walks the same
-        path.  Unsharded models.  Folding in new COLUMNS is out of scope: it needs the horseshoe local scales of a column
-        nobody has sampled."""
-        from . import fold_in as _fold
-        family = self._fold_family()
-        if self._plan.world > 1 or self._exchange.active:
-            raise NotImplementedError("fold_in_rows: unsharded models only")
-        M, T, K = self.ncols, self.ndepth, self.nembeds
-        R, weights, sums = _fold.row_statistics(Y_new, family, M, T, trials=trials)
-        gauss = _fold.FAMILIES[family] == _fold.FAMILIES["gaussian"]
-        Vs = nu2 = sigma2 = None
-        if results is None:
-            S = getattr(self, "_collected", 0)
-            if S < 1:
-                raise RuntimeError("no samples collected on the device (run_gibbs with rng='device' first), and no results= given")
-        else:
-            try:
-                Vs = np.asarray(results["V"])
-            except (KeyError, TypeError):
-                raise ValueError("results must be a run_gibbs result dict with V (S,M,T,K), sigma2 and (Gaussian) nu2")
-            S = Vs.shape[0] if Vs.ndim == 4 else -1
-            if S < 1 or Vs.shape != (S, M, T, K):
-                raise ValueError("results: V %r does not match the model's (S,%d,%d,%d)" % (Vs.shape, M, T, K))
-        _fold.check_args(family, S, R, K, z, summary, q, transform, inner_sweeps)
-        if results is not None:
-            sigma2 = _fold.check_scalars("results: sigma2", results.get("sigma2"), S)
-            nu2 = _fold.check_scalars("results: nu2", results.get("nu2"), S) if gauss else None
-            Vs = np.ascontiguousarray(Vs, dtype=np.float64)
-        if seed is None:
-            seed = self._next_seed() if z is None else 0
-        return _fold.evaluate(family, S, R, M, T, K, weights, sums, z=z, seed=seed, summary=summary, q=q, transform=transform,
-                              inner_sweeps=inner_sweeps, ctx=self._ctx, Vs=Vs, nu2=nu2, sigma2=sigma2, device=self._ctx.device)
-
-    def logprob(self, data, reduce="sum", **state):
-        """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,
-        nu2=); further keys (Tau2, lam2, sigma2, ...: what the reference's DIC passes) are ignored.  reduce="sum": a
-        float; "curve": the (N,M) per-curve values (0 for curves without observations).  The criteria kernel with one sample.
-        Deviation: the reference (factor.py:262-264, :610-612, :1002-1005) returns an elementwise array built from an
-        undefined name, with sigma2 where the noise variance nu2 belongs."""
-        if reduce not in ("sum", "curve"):
-            raise ValueError("reduce must be 'sum' or 'curve'")
-        per_sample = self._crit_check()[2]
-        W, V = state.get("W"), state.get("V")
-        noise = None
-        if per_sample:
-            noise = np.array([_scalar(state["nu2"] if state.get("nu2") is not None else self.nu2)])
-        if W is None and V is None and not (self._W_host_new or self._V_host_new):
-            curve, totals, obs, _ = self._crit_eval(data, 1, noise=noise, current=True)       # the device's own W, V
-        else:
-            if W is None:
-                self._pull_W()
-                W = self._W
-            if V is None:
-                self._pull_V()
-                V = self._V
-            W, V = np.asarray(W, dtype=float), np.asarray(V, dtype=float)
-            if W.shape != (self.nrows, self.nembeds) or V.shape != (self.ncols, self.ndepth, self.nembeds):
-                raise ValueError("W %r / V %r do not match the model" % (W.shape, V.shape))
-            curve, totals, obs, _ = self._crit_eval(data, 1, W[None], V[None], noise)
-        if reduce == "sum":
-            return float(totals[0])
-        return np.where(obs, curve[2], 0.0)
 
     # ---- the two half-sweeps (device) ----------------------------------------------
     def _w_normals(self):

@@ -37,11 +37,7 @@ def sample_banded_batch(band, mu_part=None, z=None, seed=0, device=0,
                             C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(force_psd_eps),
                             int(force_psd_attempts) if force_psd else 0, _native.dptr(x),
                             tries.ctypes.data_as(_native._c_ip))
-    if rc != _native.BTF_OK:
-        msg = lib.btf_last_error(None).decode()
-        if rc == _native.BTF_ENOTPD:
-            raise _native.NotPositiveDefiniteError(rc, msg)
-        raise _native.BTFError(rc, msg)
+    _native.check(rc, lib, fail_index=False)
     return x, tries
 
 
@@ -115,11 +111,7 @@ def sample_dense_batch(A, precision=False, chol_factor=False, mu=None, mu_part=N
     rc = lib.btf_mvn_dense(device, B, n, _native.dptr(A), form, _native.dptr(mu), _native.dptr(mp), _native.dptr(zz),
                            C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(force_psd_eps),
                            int(force_psd_attempts) if force_psd else 0, _native.dptr(x), tries.ctypes.data_as(_native._c_ip))
-    if rc != _native.BTF_OK:
-        msg = lib.btf_last_error(None).decode()
-        if rc == _native.BTF_ENOTPD:
-            raise _native.NotPositiveDefiniteError(rc, msg)
-        raise _native.BTFError(rc, msg)
+    _native.check(rc, lib, fail_index=False)
     return x, tries
 
 

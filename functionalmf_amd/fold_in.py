@@ -16,8 +16,9 @@ btf_collect_fold_in); this module holds the host halves in plain numpy (importab
 """
 import numpy as np
 
+from ._analysis import check_q, transform_code
+
 FAMILIES = {"gaussian": 0, "binomial": 1}
-TRANSFORMS = {None: 0, "identity": 0, "ilogit": 1, "square": 2}
 MAX_SUMMARY_SAMPLES = 16384      # the limit of posterior_summary_kernel (one cell's values are sorted in LDS)
 MAX_TRIALS = 32                  # FOLD_MAX_TRIALS of csrc/btf_fold_in.h: the counts pg_exact=None draws exactly
 # rounds of the Binomial inner chain per (sample, row): the smallest count after which the largest |z| of the mean against
@@ -94,19 +95,6 @@ def row_statistics(Y_new, family, M, T, trials=None):
     return Y.shape[0], np.ascontiguousarray(n), np.ascontiguousarray(y)
 
 
-def check_scalars(name, v, S):
-    """One finite positive value per sample, as a contiguous (S,) array."""
-    if v is None:
-        raise ValueError("%s: one value per sample is needed" % name)
-    a = np.asarray(v, dtype=float)
-    if a.size != S:
-        raise ValueError("%s must hold one value per sample (%d), got shape %r" % (name, S, a.shape))
-    a = np.ascontiguousarray(a.reshape(S))
-    if not np.all(np.isfinite(a)) or not np.all(a > 0):
-        raise ValueError("%s must be finite and positive" % name)
-    return a
-
-
 def check_args(family, S, R, K, z=None, summary=True, q=(5, 95), transform=None, inner_sweeps=None, first_sample=0):
     """Validate and normalise; raises ValueError before any device call.  Returns (family code, z or None, qs, transform
     code, inner_sweeps)."""
@@ -115,16 +103,13 @@ def check_args(family, S, R, K, z=None, summary=True, q=(5, 95), transform=None,
         raise ValueError("fold_in_rows: at least one sample")
     if not 1 <= int(K) <= 10:
         raise ValueError("fold_in_rows: nembeds must be 1..10")
-    if transform not in TRANSFORMS:
-        raise ValueError("transform must be None, 'identity', 'ilogit' or 'square'")
+    tcode = transform_code(transform)
     if summary and int(S) > MAX_SUMMARY_SAMPLES:
         raise ValueError("fold_in_rows: %d samples exceed the %d of the summary kernel; thin the samples or pass summary=False"
                          % (S, MAX_SUMMARY_SAMPLES))
     if int(first_sample) < 0 or (int(first_sample) + int(S)) * int(R) >= 2 ** 31:
         raise ValueError("fold_in_rows: first_sample must be >= 0 and (first_sample + S) * R below 2^31")
-    qs = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64) if (summary and q is not None) else np.zeros(0)
-    if qs.ndim != 1 or not np.all((qs >= 0) & (qs <= 100)):
-        raise ValueError("percentiles q must lie in [0, 100]")
+    qs = check_q(q, allow_none=True) if summary else np.zeros(0)
     if z is not None:
         if code != FAMILIES["gaussian"]:
             raise ValueError("z replaces the device generator for the Gaussian model only (the Binomial chain also draws Polya-Gamma variates)")
@@ -137,7 +122,7 @@ def check_args(family, S, R, K, z=None, summary=True, q=(5, 95), transform=None,
         inner_sweeps = DEFAULT_INNER_SWEEPS
     if int(inner_sweeps) != inner_sweeps or int(inner_sweeps) < 1:
         raise ValueError("inner_sweeps must be a positive integer")
-    return code, z, qs, TRANSFORMS[transform], int(inner_sweeps)
+    return code, z, qs, tcode, int(inner_sweeps)
 
 
 def evaluate(family, S, R, M, T, K, weights, sums, z=None, seed=0, summary=True, q=(5, 95), transform=None, inner_sweeps=None,
@@ -160,11 +145,8 @@ def evaluate(family, S, R, M, T, K, weights, sums, z=None, seed=0, summary=True,
         ctx.call("btf_collect_fold_in", code, int(S), int(R), *tail)
     else:
         lib = _native.load()
-        rc = lib.btf_fold_in_rows(int(device), code, int(S), int(R), int(M), int(T), int(K), d(Vs), d(nu2), d(sigma2), *tail)
-        if rc == _native.BTF_ENOTPD:
-            raise _native.NotPositiveDefiniteError(rc, lib.btf_last_error(None).decode(), lib.btf_fail_index(None))
-        if rc != _native.BTF_OK:
-            raise _native.BTFError(rc, lib.btf_last_error(None).decode())
+        _native.check(lib.btf_fold_in_rows(int(device), code, int(S), int(R), int(M), int(T), int(K), d(Vs), d(nu2), d(sigma2), *tail),
+                      lib)
     out = {"W": W, "nsamples": int(S)}
     if gauss:
         out["W_mean"] = Wm

@@ -18,9 +18,10 @@ For one sampled curve m (T,) over depth coordinates x (T, strictly increasing; d
 """
 import numpy as np
 
+from ._analysis import check_q, transform_code
+
 NAMES = ("auc", "max", "min", "argmax", "argmin", "rise", "crossing")      # index = the code of csrc/btf_functionals.h
 CODES = {n: k for k, n in enumerate(NAMES)}
-TRANSFORMS = {None: 0, "identity": 0, "ilogit": 1, "square": 2}
 MAX_SAMPLES = 8192          # FUNC_MAX_S of csrc/btf_functionals.h: the S values of a curve are sorted in 64 KiB of LDS
 
 _trapezoid = getattr(np, "trapezoid", None) or np.trapz
@@ -79,8 +80,7 @@ def check_args(which, q, transform, x, level, exceed, curves, S, N, M, T):
             raise ValueError("unknown functional %r (one of %s)" % (n, NAMES))
     if len(set(names)) != len(names):
         raise ValueError("which names a functional twice")
-    if transform not in TRANSFORMS:
-        raise ValueError("transform must be None, 'identity', 'ilogit' or 'square'")
+    tcode = transform_code(transform)
     if int(T) < 2:
         raise ValueError("posterior functionals need ndepth >= 2 (a curve over depth)")
     if int(S) < 1:
@@ -88,9 +88,7 @@ def check_args(which, q, transform, x, level, exceed, curves, S, N, M, T):
     if int(S) > MAX_SAMPLES:
         raise ValueError("posterior functionals: %d samples exceed %d (the values of a curve are sorted in LDS); thin the samples"
                          % (S, MAX_SAMPLES))
-    qs = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64) if q is not None else np.zeros(0)
-    if qs.ndim != 1 or not np.all((qs >= 0) & (qs <= 100)):
-        raise ValueError("percentiles q must lie in [0, 100]")
+    qs = check_q(q, allow_none=True)
     xs = default_x(T) if x is None else np.ascontiguousarray(x, dtype=np.float64)
     if xs.shape != (int(T),):
         raise ValueError("x must hold ndepth = %d depth coordinates, got shape %r" % (T, xs.shape))
@@ -108,7 +106,7 @@ def check_args(which, q, transform, x, level, exceed, curves, S, N, M, T):
             raise ValueError("curves must be (i, j) pairs inside (%d, %d)" % (N, M))
         if not len(cv):
             cv = None
-    return names, np.array([CODES[n] for n in names], dtype=np.int32), TRANSFORMS[transform], qs, xs, lev, exc, cv
+    return names, np.array([CODES[n] for n in names], dtype=np.int32), tcode, qs, xs, lev, exc, cv
 
 
 def evaluate(shape, K, S, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None, curves=None,
@@ -136,9 +134,7 @@ def evaluate(shape, K, S, which=("auc",), q=(5, 95), transform=None, x=None, lev
         ctx.call("btf_collect_functionals", int(S), *tail)
     else:
         lib = _native.load()
-        rc = lib.btf_posterior_functionals(int(device), int(S), N, M, T, K, d(Ws), d(Vs), *tail)
-        if rc != _native.BTF_OK:
-            raise _native.BTFError(rc, lib.btf_last_error(None).decode())
+        _native.check(lib.btf_posterior_functionals(int(device), int(S), N, M, T, K, d(Ws), d(Vs), *tail), lib)
     out = {}
     for k, n in enumerate(names):
         r = {"mean": mean[k], "var": var[k], "quantiles": quant[k] if nq else np.zeros((0, N, M))}

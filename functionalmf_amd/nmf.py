@@ -15,11 +15,6 @@ from . import _native
 MAX_NEMBEDS = 10
 
 
-def _check(rc, lib):
-    if rc != _native.BTF_OK:
-        raise _native.BTFError(rc, lib.btf_last_error(None).decode())
-
-
 def _as_Y4(Y):
     Y = np.asarray(Y, dtype=np.float64)
     if Y.ndim == 3:
@@ -61,8 +56,8 @@ class NMFData:
         self.h = C.c_void_p()
         N, M, T, R = Y.shape
         cp = counts.ctypes.data_as(C.POINTER(C.c_uint8)) if counts is not None else None
-        _check(self.lib.btf_nmf_create(C.byref(self.h), int(device), N, M, T, R, self.nembeds, _native.dptr(S), cp, ssw),
-               self.lib)
+        _native.check(self.lib.btf_nmf_create(C.byref(self.h), int(device), N, M, T, R, self.nembeds, _native.dptr(S), cp, ssw),
+                      self.lib)
 
     def close(self):
         if getattr(self, "h", None):
@@ -83,9 +78,9 @@ class NMFData:
         steps = C.c_int32(0)
         hist = np.zeros(max(int(max_steps), 1))
         ms = np.zeros(1)
-        _check(self.lib.btf_nmf_run(self.h, _native.dptr(W), _native.dptr(V), int(bool(fit_W)), int(bool(fit_V)),
-                                    int(bool(monotone)), int(max_steps), float(tol), int(bool(verbose)), C.byref(steps),
-                                    _native.dptr(hist), _native.dptr(ms) if timing else None), self.lib)
+        _native.check(self.lib.btf_nmf_run(self.h, _native.dptr(W), _native.dptr(V), int(bool(fit_W)), int(bool(fit_V)),
+                                           int(bool(monotone)), int(max_steps), float(tol), int(bool(verbose)), C.byref(steps),
+                                           _native.dptr(hist), _native.dptr(ms) if timing else None), self.lib)
         info = {"steps": int(steps.value), "rmse": hist[:steps.value].copy()}
         if timing:
             info["device_ms"] = float(ms[0])
@@ -153,7 +148,7 @@ def factor_pav(W, V, in_place=False, device=0):
     V3 = out.reshape((1,) + out.shape) if out.ndim == 2 else out
     M, T = V3.shape[:2]
     lib = _native.load()
-    _check(lib.btf_nmf_pav(int(device), W.shape[0], M, T, K, _native.dptr(Wc), _native.dptr(V3)), lib)
+    _native.check(lib.btf_nmf_pav(int(device), W.shape[0], M, T, K, _native.dptr(Wc), _native.dptr(V3)), lib)
     if in_place:
         if not isinstance(V, np.ndarray):
             raise ValueError("in_place=True needs V to be a numpy array")

@@ -150,9 +150,7 @@ class Exchange:
         nb = _native.COMM_ID_BYTES
         ident = (C.c_ubyte * nb)()
         if self.plan.rank == 0:
-            rc = self.ctx.lib.btf_comm_unique_id(ident, nb)
-            if rc != _native.BTF_OK:
-                raise _native.BTFError(rc, self.ctx.lib.btf_last_error(None).decode())
+            _native.check(self.ctx.lib.btf_comm_unique_id(ident, nb), self.ctx.lib)
         on_gpu = dist.get_backend(self.group) == "nccl"
         t = torch.tensor(list(ident), dtype=torch.uint8, device=torch.device("cuda", self.ctx.device) if on_gpu else "cpu")
         src = dist.get_global_rank(self.group, 0) if self.group is not None else 0

@@ -12,6 +12,8 @@ kept sample, 2.5 / 97.5 percentiles per cell in a Python loop, coverage of the h
 """
 import numpy as np
 
+from ._analysis import check_q, check_states  # noqa: F401  (the shared checks, under the names this module had for them)
+
 FAMILY_POISSON_LOG, FAMILY_POISSON_IDENTITY, FAMILY_LOGIT, FAMILY_GAUSSIAN, FAMILY_NEGBIN = 0, 1, 2, 3, 4
 FAMILIES = {"poisson": FAMILY_POISSON_LOG, "poisson_log": FAMILY_POISSON_LOG, "poisson_identity": FAMILY_POISSON_IDENTITY,
             "binomial": FAMILY_LOGIT, "bernoulli": FAMILY_LOGIT, "logit": FAMILY_LOGIT,
@@ -53,13 +55,6 @@ def mean_function(family, eta, aux=None):
     return np.asarray(aux, dtype=float) * np.exp(eta)
 
 
-def check_q(q):
-    qs = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64)
-    if qs.ndim != 1 or not np.all((qs >= 0) & (qs <= 100)):
-        raise ValueError("percentiles q must lie in [0, 100]")
-    return qs
-
-
 def check_draws(nsamples, draws_per_sample):
     nsamples, R = int(nsamples), int(draws_per_sample)
     if nsamples < 1:
@@ -70,16 +65,6 @@ def check_draws(nsamples, draws_per_sample):
         raise ValueError("posterior predictive: nsamples * draws_per_sample = %d exceeds %d (the draws of a cell are sorted "
                          "in LDS); thin the samples or lower draws_per_sample" % (nsamples * R, MAX_DRAWS))
     return nsamples, R
-
-
-def check_states(Ws, Vs, shape, nembeds):
-    """(Ws, Vs) as contiguous float64 (S,N,K) / (S,M,T,K) arrays matching the model."""
-    N, M, T = shape
-    Ws, Vs = np.ascontiguousarray(Ws, dtype=np.float64), np.ascontiguousarray(Vs, dtype=np.float64)
-    S = Ws.shape[0] if Ws.ndim == 3 else -1
-    if S < 1 or Ws.shape != (S, N, nembeds) or Vs.shape != (S, M, T, nembeds):
-        raise ValueError("W %r / V %r do not match (S,%d,%d) / (S,%d,%d,%d)" % (Ws.shape, Vs.shape, N, nembeds, M, T, nembeds))
-    return Ws, Vs
 
 
 def check_cells(cells, shape):
@@ -204,8 +189,6 @@ def batch(family, eta, aux, seed=0, device=0):
     aux = np.ascontiguousarray(np.broadcast_to(np.asarray(aux, dtype=np.float64), eta.shape)).ravel()
     out = np.zeros(eta.size)
     lib = _native.load()
-    rc = lib.btf_predict_batch(int(device), code, eta.size, _native.dptr(eta), _native.dptr(aux), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                               _native.dptr(out))
-    if rc != _native.BTF_OK:
-        raise _native.BTFError(rc, lib.btf_last_error(None).decode())
+    _native.check(lib.btf_predict_batch(int(device), code, eta.size, _native.dptr(eta), _native.dptr(aux),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, _native.dptr(out)), lib)
     return out

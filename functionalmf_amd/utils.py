@@ -84,22 +84,15 @@ def posterior_summary(Ws, Vs, q=(5, 95), transform=None, device=0):
     LDS).  `transform`: None, "ilogit" (the Binomial examples) or "square".  Returns (mean, quantiles)
     with shapes (N, M, T) and (len(q), N, M, T); percentiles use numpy's default linear interpolation.
     There is no CPU fallback."""
-    from . import _native
-    Ws, Vs = _native.as_f64(Ws), _native.as_f64(Vs)
-    if Ws.ndim != 3 or Vs.ndim != 4 or Ws.shape[0] != Vs.shape[0] or Ws.shape[2] != Vs.shape[3]:
-        raise ValueError("Ws must be (S, N, K) and Vs (S, M, T, K)")
-    code = {None: 0, "identity": 0, "ilogit": 1, "square": 2}[transform]
+    from . import _analysis, _native
+    Ws, Vs = _analysis.check_states(Ws, Vs)
     S, N, K = Ws.shape
     M, T = Vs.shape[1:3]
-    qs = _native.as_f64(np.atleast_1d(q))
-    mean = np.zeros((N, M, T))
-    quant = np.zeros((len(qs), N, M, T))
-    lib = _native.load()
-    rc = lib.btf_posterior_summary(int(device), S, N, M, T, K, _native.dptr(Ws), _native.dptr(Vs), code,
-                                   _native.dptr(qs), len(qs), _native.dptr(mean), _native.dptr(quant))
-    if rc != _native.BTF_OK:
-        raise _native.BTFError(rc, lib.btf_last_error(None).decode())
-    return mean, quant
+
+    def call(*tail):
+        lib = _native.load()
+        _native.check(lib.btf_posterior_summary(int(device), S, N, M, T, K, _native.dptr(Ws), _native.dptr(Vs), *tail), lib)
+    return _analysis.summary(call, (N, M, T), q, transform)
 
 
 def posterior_predictive(Ws, Vs, family, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=0, param=None, nu2=None, R=None,
@@ -111,10 +104,8 @@ def posterior_predictive(Ws, Vs, family, data=None, q=(2.5, 97.5), draws_per_sam
     Gaussian: nu2 (S,) per-sample variances, or param = one variance; Negative-Binomial: R (S,) + a shape broadcasting
     against (N,M,T), or param = one rate; Binomial: trials (N,M,T) (default 1).  data: (N,M,T) or (N,M,T,R) observations
     with NaN = missing, or a Binomial (Y, N) pair.  Needs ndepth >= 2 (a context is opened for the call).  No CPU fallback."""
-    from . import _native, predictive
-    Ws, Vs = np.asarray(Ws), np.asarray(Vs)
-    if Ws.ndim != 3 or Vs.ndim != 4 or Ws.shape[0] != Vs.shape[0] or Ws.shape[2] != Vs.shape[3]:
-        raise ValueError("Ws must be (S, N, K) and Vs (S, M, T, K)")
+    from . import _analysis, _native, predictive
+    Ws, Vs = _analysis.check_states(Ws, Vs)
     code = predictive.family_code(family)
     S, N, K = Ws.shape
     shape = (N,) + Vs.shape[1:3]
@@ -154,14 +145,10 @@ def posterior_functionals(Ws, Vs, which=("auc",), q=(5, 95), transform=None, x=N
     and var run over those, its percentiles count the others as +inf and are nan where they reach them; exceed=c adds
     "prob_above" (share of samples with value > c); curves=[(i,j), ...] adds "curves" (ncurves,S), the raw values in
     sample order; pointwise=True adds "pointwise" (S,N,M).  At most 8192 samples, ndepth >= 2.  There is no CPU fallback."""
-    from . import functionals, predictive
-    Ws, Vs = np.asarray(Ws), np.asarray(Vs)
-    if Ws.ndim != 3 or Vs.ndim != 4 or Ws.shape[0] != Vs.shape[0] or Ws.shape[2] != Vs.shape[3]:
-        raise ValueError("Ws must be (S, N, K) and Vs (S, M, T, K)")
+    from . import _analysis, functionals
+    Ws, Vs = _analysis.check_states(Ws, Vs)
     S, N, K = Ws.shape
     shape = (N,) + Vs.shape[1:3]
-    functionals.check_args(which, q, transform, x, level, exceed, curves, S, N, shape[1], shape[2])   # before any conversion
-    Ws, Vs = predictive.check_states(Ws, Vs, shape, K)
     return functionals.evaluate(shape, K, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed, curves=curves,
                                 pointwise=pointwise, Ws=Ws, Vs=Vs, device=device)
 
@@ -177,17 +164,14 @@ def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summa
     first_sample: the index of Vs[0] among the kept samples - with it a call over a slice of the samples returns the bits
     of the whole call.  out["W"] and Vs go straight into posterior_summary, posterior_predictive and posterior_functionals.
     functionalmf_amd.fold_in.conditional is the definition in numpy.  There is no CPU fallback."""
-    from . import fold_in
-    Vs = np.asarray(Vs)
-    if Vs.ndim != 4 or Vs.shape[0] < 1:
-        raise ValueError("Vs must be (S, M, T, K)")
+    from . import _analysis, fold_in
+    Vs = _analysis.check_states(None, Vs)[1]
     S, M, T, K = Vs.shape
     code = fold_in.family_code(family)
     R, weights, sums = fold_in.row_statistics(Y_new, family, M, T, trials=trials)
-    fold_in.check_args(family, S, R, K, z, summary, q, transform, inner_sweeps, first_sample)     # before any conversion
-    sigma2 = fold_in.check_scalars("sigma2", sigma2, S)
-    nu2 = fold_in.check_scalars("nu2", nu2, S) if code == fold_in.FAMILIES["gaussian"] else None
-    Vs = np.ascontiguousarray(Vs, dtype=np.float64)
+    fold_in.check_args(family, S, R, K, z, summary, q, transform, inner_sweeps, first_sample)
+    sigma2 = _analysis.check_scalars("sigma2", sigma2, S)
+    nu2 = _analysis.check_scalars("nu2", nu2, S) if code == fold_in.FAMILIES["gaussian"] else None
     return fold_in.evaluate(family, S, R, M, T, K, weights, sums, z=z, seed=seed, summary=summary, q=q, transform=transform,
                             inner_sweeps=inner_sweeps, first_sample=first_sample, Vs=Vs, nu2=nu2, sigma2=sigma2, device=device)
 

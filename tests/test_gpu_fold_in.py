@@ -347,3 +347,40 @@ def test_full_size_c3():
     for err, cond in checks:
         assert cond < COND_MAX
         assert err < W_TOL
+
+
+def _arrays(out, prefix=""):
+    """Every array of a returned value (a tuple or a dict, nested) as (path, array) pairs."""
+    if isinstance(out, dict):
+        return [p for k in sorted(out) for p in _arrays(out[k], "%s%s." % (prefix, k))]
+    if isinstance(out, (tuple, list)):
+        return [p for i, v in enumerate(out) for p in _arrays(v, "%s%d." % (prefix, i))]
+    return [(prefix, out)] if isinstance(out, np.ndarray) else []
+
+
+def test_collected_and_uploaded_samples_agree_in_every_analysis_call():
+    """9. Every analysis method resolves its samples in one place (PosteriorAnalysis._samples): each of them, called on the
+    device-collected samples and on the same run's result dict uploaded, returns the same bits in every array."""
+    N, M, T, K = 5, 3, 6, 2
+    rs = np.random.RandomState(4)
+    Y = np.einsum("nk,mtk->nmt", rs.normal(size=(N, K)), 0.4 * np.cumsum(rs.normal(size=(M, T, K)), axis=1)) \
+        + rs.normal(0, 0.5, size=(N, M, T))
+    Y_new = Y[:2].copy()
+    Y_new[1, 1:] = np.nan
+    np.random.seed(3)
+    model = GaussianBayesianTensorFiltering(N, M, T, nembeds=K, rng="device", device_seed=2)
+    res = model.run_gibbs(Y, nburn=2, nsamples=8, verbose=False)
+    calls = {
+        "posterior_summary": lambda r: model.posterior_summary() if r is None else utils.posterior_summary(r["W"], r["V"]),
+        "information_criteria": lambda r: model.information_criteria(r, pointwise=True),
+        "loo": lambda r: model.loo(r, mean=True, log_weights=True),
+        "posterior_predictive": lambda r: model.posterior_predictive(r, seed=1),
+        "posterior_functionals": lambda r: model.posterior_functionals(r, which=("auc", "max", "crossing"), level=0.0, pointwise=True),
+        "fold_in_rows": lambda r: model.fold_in_rows(Y_new, results=r, seed=1),
+    }
+    collected = {name: call(None) for name, call in calls.items()}
+    for name, call in calls.items():
+        a, b = _arrays(collected[name]), _arrays(call(res))
+        assert len(a) >= 2 and [p for p, _ in a] == [p for p, _ in b], name
+        for (path, x), (_, y) in zip(a, b):
+            assert x.shape == y.shape and np.array_equal(x, y, equal_nan=True), (name, path)
