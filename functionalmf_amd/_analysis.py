@@ -1,5 +1,5 @@
 """The Python front end of the posterior analysis features: summary, diagnostics, criteria / PSIS-LOO, predictive,
-functionals and fold-in.
+functionals, ranking and fold-in.
 
 Two halves.  The argument checks every feature shares, as plain functions (importable without a GPU): the transform table,
 the percentile check, the (S,N,K) / (S,M,T,K) shape check and the per-sample scalar check - the stateless forms in utils.py
@@ -308,6 +308,26 @@ class PosteriorAnalysis:
         S, Ws, Vs = self._samples(results)
         return _func.evaluate(shape, self.nembeds, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed,
                               curves=curves, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
+
+    # ---- posterior ranking: which column is best for a row, with what probability (functionalmf_amd/ranking.py) ----
+    def posterior_ranking(self, which="auc", along="cols", order="ascending", top=(1, 5), transform=None, x=None, level=None,
+                          pairs=None, pointwise=False, results=None):
+        """The rank of every curve within its row (along="cols": the columns of a row are ranked) or its column
+        (along="rows") by one functional of posterior_functionals, per kept sample, summarised over the samples on the GPU
+        (csrc/btf_ranking.h): expected rank, its variance and the probability of being among the best k.  A property of the
+        joint posterior across curves, which the per-curve summaries of posterior_functionals cannot give.
+
+        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device (no upload).
+        The other arguments and the returned dict: functionalmf_amd.utils.posterior_ranking.  The sampler's state is not
+        touched: a chain continued after the call walks the same path.  Unsharded models."""
+        from . import ranking as _rank
+        self._unsharded("posterior ranking")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        _rank.check_args(which, along, order, top, transform, x, level, pairs, 1, *shape)
+        S, Ws, Vs = self._samples(results)
+        return _rank.evaluate(shape, self.nembeds, S, which=which, along=along, order=order, top=top, transform=transform, x=x,
+                              level=level, pairs=pairs, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
 
     # ---- folding new rows in (functionalmf_amd/fold_in.py, csrc/btf_fold_in.h) ----
     def fold_in_rows(self, Y_new, results=None, seed=None, z=None, summary=True, q=(5, 95), transform=None, inner_sweeps=None,

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")
 SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip"),
            os.path.join(CSRC, "btf_gass_ep.hip"), os.path.join(CSRC, "btf_gamma_grid.hip"), os.path.join(CSRC, "btf_diag.hip"),
            os.path.join(CSRC, "btf_predict.hip"), os.path.join(CSRC, "btf_functionals.hip"), os.path.join(CSRC, "btf_fold_in.hip"),
-           os.path.join(CSRC, "btf_loo.hip")]
+           os.path.join(CSRC, "btf_loo.hip"), os.path.join(CSRC, "btf_ranking.hip")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -92,6 +92,10 @@ SIGNATURES = {
                                             C.c_int, _c_ip, C.c_int] + [_c_dp] * 7),
     "btf_collect_functionals": (C.c_int, [_ctx, C.c_int, C.c_int, _c_ip, C.c_int, _c_dp, C.c_double, C.c_double, _c_dp, C.c_int, _c_ip,
                                           C.c_int] + [_c_dp] * 7),
+    "btf_posterior_ranking": (C.c_int, [C.c_int] * 6 + [_c_dp, _c_dp, C.c_int, C.c_int, _c_dp, C.c_double, C.c_int, C.c_int, _c_ip, C.c_int,
+                                        _c_ip, C.c_int, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_dp, C.c_longlong]),
+    "btf_collect_ranking": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _c_dp, C.c_double, C.c_int, C.c_int, _c_ip, C.c_int, _c_ip, C.c_int,
+                                      _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_dp, C.c_longlong]),
     "btf_fold_in_rows": (C.c_int, [C.c_int] * 7 + [_c_dp] * 7 + [C.c_uint64, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int,
                                    _c_dp, _c_dp]),
     "btf_collect_fold_in": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [_c_dp] * 4 + [C.c_uint64, C.c_int, C.c_int64, _c_dp, _c_dp,
@@ -211,6 +215,7 @@ def build(force=False, verbose=False, jobs=None):
     units += [(SOURCES[4], os.path.join(OBJ_DIR, tag + "_gamma_grid.o"), []), (SOURCES[5], os.path.join(OBJ_DIR, tag + "_diag.o"), [])]
     units += [(SOURCES[6], os.path.join(OBJ_DIR, tag + "_predict.o"), []), (SOURCES[7], os.path.join(OBJ_DIR, tag + "_functionals.o"), [])]
     units += [(SOURCES[8], os.path.join(OBJ_DIR, tag + "_fold_in.o"), []), (SOURCES[9], os.path.join(OBJ_DIR, tag + "_loo.o"), [])]
+    units += [(SOURCES[10], os.path.join(OBJ_DIR, tag + "_ranking.o"), [])]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

@@ -16,6 +16,7 @@
 #include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
+#include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
@@ -4015,6 +4016,144 @@ int btf_collect_functionals(btf_ctx* c, int nsamples, int transform, const int* 
   Scratch s(c, c->stream);
   return functionals_run(s, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
                          q, nq, curves, ncurves, o);
+}
+
+// ---------------------------------------------------------------- posterior ranking (btf_ranking.h)
+namespace {
+
+struct RankOut { double *expected, *var, *ptop; int* ranks; double *prob_less, *prob_defined; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): per chunk of samples the functionals' sweep into the
+// scratch, the gather and count of the pairs, the rank kernel; then the finish kernel and the downloads.  scratch_bytes
+// caps the chunk's scratch (0: FUNC_SCRATCH_BYTES; one sample is the least a chunk holds).
+int ranking_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform, int which,
+                const double* x, double level, int along, int descending, const int* top, int ntop, const int* pairs, int npairs,
+                const RankOut& o, long long scratch_bytes) {
+  FuncKernel sweep = func_sweep_fn(K, transform);
+  if (!sweep) return fail(s.ctx(), BTF_EINVAL, "posterior ranking: nembeds must be 1..10 and transform 0..2");
+  const size_t NM = (size_t)N * M, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
+  const int sc_max = (int)std::max<size_t>(1, std::min<size_t>(S, cap / (NM * sizeof(double))));
+  FuncArgs f = {};
+  f.level = level; f.exceed = std::nan(""); f.N = N; f.M = M; f.T = T; f.nslots = 1;
+  for (int k = 0; k < FUNC_COUNT; ++k) f.slot[k] = -1;
+  f.slot[which] = 0; f.code[0] = which;
+  f.x = s.upload(x, (size_t)T);
+  double* vals = s.alloc<double>(NM * sc_max);
+  RankArgs r = {};
+  r.vals = vals; r.S = S; r.N = N; r.M = M; r.along = along; r.ntop = ntop; r.P = npairs;
+  for (int k = 0; k < ntop; ++k) r.top[k] = std::min(top[k], RANK_MAX_L + 1);      // (a rank never exceeds RANK_MAX_L)
+  r.L = along ? N : M;
+  while ((1 << r.lshift) < r.L) ++r.lshift;
+  r.Lp = 1 << r.lshift;
+  const int ngroups = along ? M : N;
+  r.G = std::max(1, std::min(ngroups, std::min(RANK_MAX_L / r.Lp, RANK_MAX_GROUPS)));
+  const size_t lds = rank_lds_bytes(r.G, r.Lp);
+  const int tiles = (ngroups + r.G - 1) / r.G;
+  r.A = s.alloc<unsigned long long>(NM);
+  r.B = s.alloc<unsigned long long>(NM);
+  r.C = s.alloc<unsigned int>((size_t)ntop * NM);
+  if (o.ranks) r.ranks = s.alloc<int>((size_t)S * NM);
+  r.expected = s.alloc<double>(NM); r.var = s.alloc<double>(NM); r.ptop = s.alloc<double>((size_t)ntop * NM);
+  const int* dpairs = nullptr;
+  double* dpv = nullptr;
+  if (npairs) {
+    dpairs = s.upload(pairs, (size_t)4 * npairs);             // (i,j,i2,j2) rows = 2 npairs (i,j) curves for the gather
+    dpv = s.alloc<double>((size_t)2 * npairs * sc_max);
+    r.pvals = dpv;
+    r.pless = s.alloc<unsigned int>(npairs); r.pdef = s.alloc<unsigned int>(npairs);
+    r.prob_less = s.alloc<double>(npairs); r.prob_defined = s.alloc<double>(npairs);
+  }
+  auto zero = [&](void* p, size_t bytes) { if (!s.rc()) s.check(hipMemsetAsync(p, 0, bytes, s.stream()), "hipMemsetAsync"); };
+  zero(r.A, NM * sizeof(unsigned long long)); zero(r.B, NM * sizeof(unsigned long long)); zero(r.C, (size_t)ntop * NM * sizeof(unsigned int));
+  if (npairs) { zero(r.pless, npairs * sizeof(unsigned int)); zero(r.pdef, npairs * sizeof(unsigned int)); }
+  RankKernel rank = rank_fn(descending != 0);
+  const int rowblocks = (N + WAVE - 1) / WAVE, JMAX = 65535;   // (a grid's y extent)
+  for (int s0 = 0; s0 < S; s0 += sc_max) {
+    const int sc = std::min(sc_max, S - s0);
+    f.W = dW + (size_t)s0 * N * K; f.V = dV + (size_t)s0 * M * T * K; f.S = sc;
+    for (int j0 = 0; j0 < M; j0 += JMAX) {                     // vals[column][sample of the chunk][row]
+      f.j0 = j0; f.jc = std::min(JMAX, M - j0); f.vals = vals + (size_t)j0 * sc * N;
+      const int zs = std::max(1, std::min((sc + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * f.jc - 1) / (rowblocks * f.jc)));
+      launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, f.jc, zs), dim3(FUNC_WAVES * WAVE), 0, f);
+    }
+    r.s0 = s0; r.sc = sc;
+    if (npairs) {
+      f.j0 = 0; f.jc = M; f.vals = vals;
+      launch_counted(s, BTF_K_CRITERIA, func_gather_fn(), dim3(2 * npairs, 1), dim3(256), 0, f, dpairs, 2 * npairs, dpv);
+      launch_counted(s, BTF_K_CRITERIA, rank_pairs_fn(), dim3(npairs), dim3(256), 0, r);
+    }
+    // sample slices: enough workgroups for two per CU when the tiles alone are fewer (geometry only)
+    const int ys = std::max(1, std::min(sc, (1024 + tiles - 1) / tiles));
+    launch_counted(s, BTF_K_CRITERIA, rank, dim3(tiles, ys), dim3(RANK_THREADS), lds, r);
+  }
+  launch_counted(s, BTF_K_CRITERIA, rank_finish_fn(), dim3((unsigned)((NM + npairs + 255) / 256)), dim3(256), 0, r);
+  s.download(o.expected, r.expected, NM);
+  s.download(o.var, r.var, NM);
+  s.download(o.ptop, r.ptop, (size_t)ntop * NM);
+  s.download(o.ranks, r.ranks, (size_t)S * NM);
+  if (npairs) { s.download(o.prob_less, r.prob_less, (size_t)npairs); s.download(o.prob_defined, r.prob_defined, (size_t)npairs); }
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int ranking_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, int which, const double* x, double level, int along,
+                  int descending, const int* top, int ntop, const int* pairs, int npairs, const RankOut& o, long long scratch_bytes) {
+  if (S < 1 || N < 1 || M < 1 || K < 1 || K > MAX_K || transform < 0 || transform > 2 || which < 0 || which >= FUNC_COUNT || !x ||
+      along < 0 || along > 1 || descending < 0 || descending > 1 || !top || ntop < 1 || ntop > RANK_MAX_TOP || npairs < 0 ||
+      (npairs > 0 && (!pairs || !o.prob_less || !o.prob_defined)) || scratch_bytes < 0)
+    return fail(c, BTF_EINVAL, "bad posterior ranking arguments");
+  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior ranking: at most " + std::to_string(FUNC_MAX_S) + " samples");
+  if ((along ? N : M) > RANK_MAX_L)
+    return fail(c, BTF_EINVAL, "posterior ranking: at most " + std::to_string(RANK_MAX_L) + " members in a group (it is sorted in LDS)");
+  if (T < 2) return fail(c, BTF_EINVAL, "posterior ranking: a curve needs ndepth >= 2");
+  if (which == FUNC_CROSSING && !(level == level)) return fail(c, BTF_EINVAL, "posterior ranking: crossing needs a level");
+  for (int t = 1; t < T; ++t)
+    if (!(x[t] > x[t - 1])) return fail(c, BTF_EINVAL, "posterior ranking: x must be strictly increasing");
+  for (int k = 0; k < ntop; ++k) {
+    if (top[k] < 1) return fail(c, BTF_EINVAL, "posterior ranking: top must hold integers >= 1");
+    for (int l = 0; l < k; ++l)
+      if (top[l] == top[k]) return fail(c, BTF_EINVAL, "posterior ranking: top must hold distinct integers");
+  }
+  for (int k = 0; k < 2 * npairs; ++k)
+    if (pairs[2 * k] < 0 || pairs[2 * k] >= N || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= M)
+      return fail(c, BTF_EINVAL, "posterior ranking: pair index out of range");
+  return BTF_OK;
+}
+
+}  // namespace
+
+int btf_posterior_ranking(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                          int transform, int which, const double* x, double level, int along, int descending, const int* top, int ntop,
+                          const int* pairs, int npairs, double* expected_out, double* var_out, double* ptop_out, int* ranks_out,
+                          double* prob_less_out, double* prob_defined_out, long long scratch_bytes) {
+  const RankOut o = {expected_out, var_out, ptop_out, ranks_out, prob_less_out, prob_defined_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior ranking arguments");
+  int rc = ranking_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, which, x, level, along, descending, top, ntop,
+                         pairs, npairs, o, scratch_bytes);
+  if (rc) return rc;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
+  return ranking_run(s, dW, dV, nsamples, nrows, ncols, ndepth, nembeds, transform, which, x, level, along, descending, top, ntop,
+                     pairs, npairs, o, scratch_bytes);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload)
+int btf_collect_ranking(btf_ctx* c, int nsamples, int transform, int which, const double* x, double level, int along, int descending,
+                        const int* top, int ntop, const int* pairs, int npairs, double* expected_out, double* var_out,
+                        double* ptop_out, int* ranks_out, double* prob_less_out, double* prob_defined_out, long long scratch_bytes) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior ranking arguments");
+  const RankOut o = {expected_out, var_out, ptop_out, ranks_out, prob_less_out, prob_defined_out};
+  int rc = ranking_check(c, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop, pairs, npairs,
+                         o, scratch_bytes);
+  if (rc) return rc;
+  if (!c->smp_W || !c->smp_V || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_ranking: not that many collected samples");
+  HIPCHK(c, hipSetDevice(c->dev));
+  Scratch s(c, c->stream);
+  return ranking_run(s, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop,
+                     pairs, npairs, o, scratch_bytes);
 }
 
 // ---------------------------------------------------------------- folding new rows in (btf_fold_in.h)

@@ -153,6 +153,36 @@ def posterior_functionals(Ws, Vs, which=("auc",), q=(5, 95), transform=None, x=N
                                 pointwise=pointwise, Ws=Ws, Vs=Vs, device=device)
 
 
+def posterior_ranking(Ws, Vs, which="auc", along="cols", order="ascending", top=(1, 5), transform=None, x=None, level=None,
+                      pairs=None, pointwise=False, device=0, _scratch_bytes=0):
+    """Which column is best for a row (or which row for a column), and with what probability, on the GPU, without a model:
+    the stateless form of BayesianTensorFiltering.posterior_ranking, next to posterior_functionals.
+
+    On the host this takes the (S,N,M) array of posterior_functionals(pointwise=True) and an argsort per group:
+
+        f = posterior_functionals(Ws, Vs, which=("auc",), pointwise=True)["auc"]["pointwise"]
+        (f.argsort(-1, kind="stable").argsort(-1) == 0).mean(0)                             # == out["p_top"][0], top=(1,)
+
+    which: ONE of "auc", "max", "min", "argmax", "argmin", "rise", "crossing"; transform, x, level: as posterior_functionals.
+    along="cols" ranks the M columns within each row, along="rows" the N rows within each column; order="ascending" gives
+    rank 1 to the smallest value, "descending" to the largest.  Ties go to the smaller index; an undefined value (a crossing
+    that never happens) ranks after every defined one in both orders.  top: 1 to 8 distinct integers k >= 1.
+    functionalmf_amd.ranking.ranks / summarize are the definition in numpy; the device agrees with them exactly.
+
+    Returns a dict: expected_rank and rank_var (N,M; ddof 1, 0 for a single sample) of the rank over the samples,
+    p_top (len(top),N,M) = the share of samples with rank <= k, and top, along, order, which, nsamples.  pointwise=True adds
+    ranks (S,N,M) int32.  pairs: a (P,4) integer array of curve pairs (i, j, i2, j2) anywhere in the tensor adds prob_less (P,)
+    = the share of samples with f(i,j) < f(i2,j2) and prob_defined, the share in which both values are defined (a sample
+    with an undefined value counts for neither).  At most 8192 samples and 4096 members in a group, ndepth >= 2.  There is
+    no CPU fallback."""
+    from . import _analysis, ranking
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    return ranking.evaluate(shape, K, S, which=which, along=along, order=order, top=top, transform=transform, x=x, level=level,
+                            pairs=pairs, pointwise=pointwise, Ws=Ws, Vs=Vs, device=device, _scratch_bytes=_scratch_bytes)
+
+
 def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summary=True, q=(5, 95), transform=None,
                  inner_sweeps=None, trials=None, first_sample=0, device=0):
     """Embeddings of rows the chain never saw, one draw per kept sample, on the GPU, without a model: the stateless form of

@@ -600,6 +600,32 @@ int btf_collect_functionals(btf_ctx* ctx, int nsamples, int transform, const int
                             double* mean_out, double* var_out, double* q_out, double* defined_out, double* prob_out,
                             double* curves_out, double* pointwise_out);
 
+/* ---- posterior ranking (csrc/btf_ranking.h) ----------------------------------------------------------------------------
+ * The rank of every curve within its row (along 0: the ncols columns of a row are one group) or its column (along 1: the
+ * nrows rows of a column), per kept sample, by the value of ONE functional `which` (the codes above; x, level, transform as
+ * btf_posterior_functionals): rank = 1 + the number of members of the group before it in the order (value, index),
+ * ascending or (descending 1) descending in the value; ties go to the smaller index, an undefined value (nan) ranks after
+ * every defined one in both orders.  Over the samples, per curve, all in integers: A = sum r, B = sum r^2,
+ * C_k = #{s : r <= top[k]} (top: ntop = 1..8 distinct integers >= 1), then one fp64 division each:
+ *   expected_out (N,M) = A / S;  var_out (N,M) = (S B - A A) / (S (S - 1)), 0 when S = 1;  ptop_out (ntop,N,M) = C_k / S.
+ * ranks_out (S,N,M) int32 or NULL: the ranks themselves.  pairs: npairs (i,j,i2,j2) rows, curves anywhere in the tensor:
+ * prob_less_out (npairs) = #{s : f_s(i,j) < f_s(i2,j2)} / S and prob_defined_out = #{s : both defined} / S (a sample with an
+ * undefined value counts for neither).  The values are those of btf_posterior_functionals bit for bit, and everything
+ * after them is integer: two calls return identical bits whatever the geometry.  Groups of at most 4096 members and
+ * nsamples <= 8192 (BTF_EINVAL beyond), ndepth >= 2.  scratch_bytes: the cap of the staging buffer, which holds whole
+ * samples (0: the default of the functionals; at least one sample is staged).  btf_collect_ranking reads the first nsamples
+ * collected slots without an upload and touches none of the sampler's state; its launches are counted under
+ * BTF_K_CRITERIA.  Synchronous.                                                                                          */
+int btf_posterior_ranking(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws,
+                          const double* Vs, int transform, int which, const double* x, double level, int along, int descending,
+                          const int* top, int ntop, const int* pairs, int npairs, double* expected_out, double* var_out,
+                          double* ptop_out, int* ranks_out, double* prob_less_out, double* prob_defined_out,
+                          long long scratch_bytes);
+int btf_collect_ranking(btf_ctx* ctx, int nsamples, int transform, int which, const double* x, double level, int along,
+                        int descending, const int* top, int ntop, const int* pairs, int npairs, double* expected_out,
+                        double* var_out, double* ptop_out, int* ranks_out, double* prob_less_out, double* prob_defined_out,
+                        long long scratch_bytes);
+
 /* ---- folding new rows into a fitted posterior (csrc/btf_fold_in.h) ---------------------------------------------------
  * Given V the rows of W are conditionally independent (factor.py:333) with prior N(0, sigma2 I), so a row that was not in
  * the fitted tensor has, under kept sample s, the conditional _resample_W draws from (factor.py:333-362):
