@@ -118,6 +118,10 @@ SIGNATURES = {
                                  C.POINTER(C.c_uint8), C.c_double]),
     "btf_nmf_run": (C.c_int, [C.c_void_p, _c_dp, _c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _c_ip, _c_dp,
                               _c_dp]),
+    "btf_nmf_set_bounds": (C.c_int, [C.c_void_p, C.c_double]),
+    "btf_nmf_set_row_features": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.POINTER(C.c_uint8)]),
+    "btf_nmf_run_bounded": (C.c_int, [C.c_void_p, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                      _c_ip, _c_dp, _c_dp, C.POINTER(C.c_uint8), _c_ip]),
     "btf_nmf_destroy": (None, [C.c_void_p]),
     "btf_nmf_pav": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp]),
     "btf_sync": (C.c_int, [_ctx]),

@@ -1,5 +1,6 @@
 """Non-negative tensor factorisation and the factor PAV projection on the GPU: the chain initialisers of the reference's
-examples (functionalmf.utils.tensor_nmf, utils.py:276-419, and factor_pav, utils.py:218-252).
+examples (functionalmf.utils.tensor_nmf, utils.py:276-420, and factor_pav, utils.py:218-252).  tensor_nmf is the plain
+factorisation; bounded_tensor_nmf adds the reference's max_entry projection and its row_features.
 
 The host draws the starting point (numpy's legacy stream, in the reference's order) and builds compact statistics of the
 data once: per cell the sum of the observed replicates and their count, plus the within-cell sum of squares.  Every ALS
@@ -54,6 +55,7 @@ class NMFData:
         self.complete = counts is None
         self.lib = _native.load()
         self.h = C.c_void_p()
+        self._bounded = False
         N, M, T, R = Y.shape
         cp = counts.ctypes.data_as(C.POINTER(C.c_uint8)) if counts is not None else None
         _native.check(self.lib.btf_nmf_create(C.byref(self.h), int(device), N, M, T, R, self.nembeds, _native.dptr(S), cp, ssw),
@@ -70,21 +72,82 @@ class NMFData:
         except Exception:
             pass
 
-    def run(self, W, V, max_steps=30, monotone=False, tol=1e-4, verbose=False, fit_W=True, fit_V=True, timing=False):
+    def run(self, W, V, max_steps=30, monotone=False, tol=1e-4, verbose=False, fit_W=True, fit_V=True, timing=False,
+            max_entry=None, row_features=None, R=None):
         """ALS from (W, V); returns (W, V, info) with new arrays.  info: steps, rmse (one per step run) and, with
-        timing=True, device_ms (device time of the queued steps)."""
+        timing=True, device_ms (device time of the queued steps).  max_entry: every fitted row, cell and feature row whose
+        entries exceed it is projected (see bounded_tensor_nmf).  row_features X (N, F), nan = missing, with the
+        starting R (F, K): info["R"] is the fitted R.  With either, info also holds projected_rows (N,), projected_cells
+        (M, T) and projected_features (F,), the systems projected in the last step run, and projected (per step: their
+        number)."""
         W = np.array(W, dtype=np.float64, order="C", copy=True)
         V = np.array(V, dtype=np.float64, order="C", copy=True)
+        N, M, T = self.shape[:3]
+        if max_entry is not None and not (np.isfinite(max_entry) and max_entry > 0):
+            raise ValueError("max_entry must be positive and finite, got %r" % (max_entry,))
+        if (row_features is None) != (R is None):
+            raise ValueError("row_features and R come together")
         steps = C.c_int32(0)
         hist = np.zeros(max(int(max_steps), 1))
         ms = np.zeros(1)
-        _native.check(self.lib.btf_nmf_run(self.h, _native.dptr(W), _native.dptr(V), int(bool(fit_W)), int(bool(fit_V)),
-                                           int(bool(monotone)), int(max_steps), float(tol), int(bool(verbose)), C.byref(steps),
-                                           _native.dptr(hist), _native.dptr(ms) if timing else None), self.lib)
+        if max_entry is None and row_features is None:
+            if self._bounded:                               # a handle that ran bounded before: back to the plain state
+                self._set(0.0, None)
+            _native.check(self.lib.btf_nmf_run(self.h, _native.dptr(W), _native.dptr(V), int(bool(fit_W)), int(bool(fit_V)),
+                                               int(bool(monotone)), int(max_steps), float(tol), int(bool(verbose)),
+                                               C.byref(steps), _native.dptr(hist), _native.dptr(ms) if timing else None),
+                          self.lib)
+            flags = nproj = None
+        else:
+            F = 0
+            if row_features is not None:
+                X = _check_features(row_features, N)
+                F = X.shape[1]
+                R = np.array(R, dtype=np.float64, order="C", copy=True)
+                if R.shape != (F, self.nembeds):
+                    raise ValueError("R must be (%d, %d), got %s" % (F, self.nembeds, R.shape))
+            self._set(0.0 if max_entry is None else float(max_entry), X if F else None)
+            flags = np.zeros(N + M * T + F, dtype=np.uint8)
+            nproj = np.zeros(max(int(max_steps), 1), dtype=np.int32)
+            _native.check(self.lib.btf_nmf_run_bounded(
+                self.h, _native.dptr(W), _native.dptr(V), _native.dptr(R) if F else None, int(bool(fit_W)), int(bool(fit_V)),
+                int(bool(monotone)), int(max_steps), float(tol), int(bool(verbose)), C.byref(steps), _native.dptr(hist),
+                _native.dptr(ms) if timing else None, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                nproj.ctypes.data_as(C.POINTER(C.c_int32))), self.lib)
         info = {"steps": int(steps.value), "rmse": hist[:steps.value].copy()}
         if timing:
             info["device_ms"] = float(ms[0])
+        if flags is not None:
+            info["projected_rows"] = flags[:N].astype(bool)
+            info["projected_cells"] = flags[N:N + M * T].astype(bool).reshape(M, T)
+            info["projected_features"] = flags[N + M * T:].astype(bool)
+            info["projected"] = nproj[:steps.value].copy()
+            if row_features is not None:
+                info["R"] = R
         return W, V, info
+
+    def _set(self, max_entry, X):
+        """Bounds and features of the handle for the next run (btf_nmf_set_bounds / btf_nmf_set_row_features)."""
+        _native.check(self.lib.btf_nmf_set_bounds(self.h, max_entry), self.lib)
+        if X is None:
+            _native.check(self.lib.btf_nmf_set_row_features(self.h, 0, None, None), self.lib)
+        else:
+            obs = ~np.isnan(X)
+            SX = np.ascontiguousarray(np.where(obs, X, 0.0))
+            op = None if bool(obs.all()) else np.ascontiguousarray(obs, dtype=np.uint8)
+            _native.check(self.lib.btf_nmf_set_row_features(self.h, X.shape[1], _native.dptr(SX),
+                                                            op.ctypes.data_as(C.POINTER(C.c_uint8)) if op is not None else None),
+                          self.lib)
+        self._bounded = max_entry > 0 or X is not None
+
+
+def _check_features(row_features, N):
+    X = np.asarray(row_features, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != N or X.shape[1] < 1:
+        raise ValueError("row_features must be (%d, F) with F >= 1, got %s" % (N, X.shape))
+    if np.isinf(X).any():
+        raise ValueError("row_features must be finite or nan (missing)")
+    return X
 
 
 def _check_nembeds(nembeds):
@@ -100,11 +163,19 @@ def tensor_nmf(Y, nembeds, max_steps=30, monotone=False, tol=1e-4, verbose=False
     functionalmf.utils.tensor_nmf (utils.py:276-419): the same starting point under np.random.seed, the same steps and
     stopping rule.  Returns (W, V) float64 of shapes (N, K) and (M, T, K), or (W, V, info) with return_info=True: info
     holds `steps` (ALS steps run) and `rmse` (per step: sqrt of the residual sum of squares).  Given W / V are not
-    modified.  `max_entry` and `row_features` (SLSQP projections in the reference) raise NotImplementedError."""
+    modified.  `max_entry` and `row_features` raise NotImplementedError here: bounded_tensor_nmf takes them."""
     if max_entry is not None:
-        raise NotImplementedError("tensor_nmf: max_entry (the reference's SLSQP projection) is not supported on the GPU")
+        raise NotImplementedError("tensor_nmf: max_entry (the reference's SLSQP projection) is bounded_tensor_nmf's")
     if row_features is not None:
-        raise NotImplementedError("tensor_nmf: row_features (side information) is not supported on the GPU")
+        raise NotImplementedError("tensor_nmf: row_features (side information) is bounded_tensor_nmf's")
+    W, V, info = _als(Y, nembeds, None, None, None, max_steps, monotone, tol, verbose, W, V, fit_W, fit_V, device)
+    if return_info:
+        return W, V, info
+    return W, V
+
+
+def _als(Y, nembeds, max_entry, row_features, R, max_steps, monotone, tol, verbose, W, V, fit_W, fit_V, device):
+    """The argument checks, the reference's starting point and the run shared by tensor_nmf and bounded_tensor_nmf."""
     K = _check_nembeds(nembeds)
     Yarr = np.asarray(Y)
     if Yarr.ndim not in (3, 4) or min(Yarr.shape) < 1:
@@ -116,22 +187,51 @@ def tensor_nmf(Y, nembeds, max_steps=30, monotone=False, tol=1e-4, verbose=False
         raise ValueError("W must be (%d, %d), got %s" % (N, K, np.shape(W)))
     if V is not None and np.shape(V) != (M, T, K):
         raise ValueError("V must be (%d, %d, %d), got %s" % (M, T, K, np.shape(V)))
-    # the reference's starting point, from the legacy global stream in its order (utils.py:283-292)
+    if max_entry is not None and not (np.isfinite(max_entry) and max_entry > 0):
+        raise ValueError("max_entry must be positive and finite, got %r" % (max_entry,))
+    X = None
+    if row_features is not None:
+        X = _check_features(row_features, N)
+        if R is not None and np.shape(R) != (X.shape[1], K):
+            raise ValueError("R must be (%d, %d), got %s" % (X.shape[1], K, np.shape(R)))
+    elif R is not None:
+        raise ValueError("R given without row_features")
+    # the reference's starting point, from the legacy global stream in its order (utils.py:283-295)
     if W is None:
         W = np.random.gamma(1, 1, size=(N, K))
         if N > 1:
             W[np.triu_indices(K, k=1)] = 0
     if V is None:
         V = np.random.gamma(1, 1, size=(M, T, K))
+    if X is not None and R is None:
+        R = np.random.gamma(1, 1, size=(X.shape[1], K))
     data = NMFData(Yarr, K, device=device)
     try:
-        W, V, info = data.run(W, V, max_steps=int(max_steps), monotone=monotone, tol=tol, verbose=verbose, fit_W=fit_W,
-                              fit_V=fit_V)
+        return data.run(W, V, max_steps=int(max_steps), monotone=monotone, tol=tol, verbose=verbose, fit_W=fit_W,
+                        fit_V=fit_V, max_entry=max_entry, row_features=X, R=R)
     finally:
         data.close()
-    if return_info:
-        return W, V, info
-    return W, V
+
+
+def bounded_tensor_nmf(Y, nembeds, max_entry=None, row_features=None, R=None, max_steps=30, monotone=False, tol=1e-4,
+                       verbose=False, W=None, V=None, fit_W=True, fit_V=True, device=0, return_info=False):
+    """tensor_nmf with the reference's `max_entry` and `row_features` (utils.py:294-295, 326-347, 369-377, 384-407).
+
+    max_entry: after its NNLS solve every row of W (leading d = min(K, i+1) entries) and every cell V[j,t] whose fitted
+    entries W V' exceed max_entry is replaced by the least-squares solution under 0 <= W V' <= max_entry over all cells
+    (rows) and x >= 1e-6: SLSQP in the reference, an exact dual active-set solve on the device here, so the two agree to
+    SLSQP's stopping slack.  With monotone=True and data in [0, 1] the result starts a [0,1] + monotone constrained chain.
+
+    row_features X (N, F), nan = missing: side information per row.  R (F, K) is drawn after W and V from the legacy
+    stream (or given, to restart from a state); the observed X[i] join row i's system with R as their design rows, and
+    after the V step every R[f] = max(NNLS(W[obs], X[obs, f]), 1e-3), projected like a cell; a feature nobody observed
+    keeps its value.  The rmse and the stopping rule use Y only.
+
+    Returns (W, V), or (W, V, R) with row_features, with info appended when return_info=True (NMFData.run lists its
+    keys).  Without max_entry and row_features the result is tensor_nmf's, bit for bit."""
+    W, V, info = _als(Y, nembeds, max_entry, row_features, R, max_steps, monotone, tol, verbose, W, V, fit_W, fit_V, device)
+    out = (W, V) if row_features is None else (W, V, info.pop("R"))
+    return out + (info,) if return_info else out
 
 
 def factor_pav(W, V, in_place=False, device=0):

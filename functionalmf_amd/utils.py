@@ -207,7 +207,7 @@ def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summa
 
 
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
-from .nmf import factor_pav, tensor_nmf  # noqa: E402,F401
+from .nmf import bounded_tensor_nmf, factor_pav, tensor_nmf  # noqa: E402,F401
 
 
 def ep_from_mf(Y, W, V, mode='max', multiplier=2):

@@ -758,8 +758,8 @@ int btf_predict_eval(btf_ctx* ctx, int family, double param, int nsamples, const
                      double* pit_hi_out, double* inside_out, double* nobs_out, double* rmse_out, double* mae_out,
                      double* draws_out);
 
-/* ---- non-negative tensor factorisation (replaces functionalmf.utils.tensor_nmf, utils.py:276-419, without its
- * max_entry / row_features projections) and the factor PAV projection (factor_pav, utils.py:218-252) ------------------
+/* ---- non-negative tensor factorisation (replaces functionalmf.utils.tensor_nmf, utils.py:276-420, its max_entry
+ * projection and row_features included) and the factor PAV projection (factor_pav, utils.py:218-252) ------------------
  * Context-free: a btf_nmf handle holds its own statistics, factors and a small device state on a stream of its own; no
  * btf_ctx is touched (csrc/btf_nmf.h).
  * btf_nmf_create: uploads the statistics of Y (N,M,T,R): S [N][M*T] = sum of the observed replicates per cell, counts
@@ -773,12 +773,32 @@ int btf_predict_eval(btf_ctx* ctx, int family, double param, int nsamples, const
  *   rmse of each step run; steps_out: the number run; device_ms (or NULL): device time of the queued steps.  verbose
  *   synchronises per step and prints "Step n" / "delta: x".  A Lawson-Hanson NNLS that reaches its cap of 3 x unknowns
  *   (scipy's default) returns BTF_EINVAL.  No floating-point atomics: two identical runs return identical bits.
+ * btf_nmf_set_bounds: max_entry > 0 for the later runs of this handle (0: none, the default).  After its NNLS solve a row
+ *   i (leading d entries), a cell (j,t) or a feature row R[f] whose fitted entries exceed max_entry, max_q c_q.x >
+ *   max_entry over the shared rows c_q (all M*T vectors V[j,t,:d] for a row, all N rows of W otherwise), is replaced by
+ *   the minimiser of 1/2 |b - A x|^2 subject to 0 <= c_q.x <= max_entry for every q and x >= 1e-6 (utils.py:338-347,
+ *   369-377, 398-407: SLSQP there, an exact dual active-set method on the normal equations here, one wave per system).
+ *   A projection that reaches its cap of 50 (K + 1) steps, has no feasible point or a singular A'A returns BTF_EINVAL.
+ * btf_nmf_set_row_features: X [N][nfeatures] with 0 where missing, observed [N][nfeatures] bytes or NULL when nothing
+ *   is missing; nfeatures = 0 removes them.  With features every observed x_if joins row i's system as the design row
+ *   R[f] (its bound constraints stay those of V), and after the V step and PAV every R[f] = max(NNLS(W[obs], X[obs,f]),
+ *   1e-3) with the same projection against W; a feature nobody observed keeps its value.  rmse and the stopping rule
+ *   use Y only.  Synchronises.
+ * btf_nmf_run_bounded: btf_nmf_run with R (nfeatures,K) read and overwritten (NULL exactly when no features are set;
+ *   btf_nmf_run refuses a handle with features).  projected_out (or NULL) [N + M*T + nfeatures] bytes: 1 for every row,
+ *   cell and feature projected in the last step run; nprojected_out (or NULL) [max_steps]: the systems projected per
+ *   step.  Without bounds and features it queues the kernels of btf_nmf_run and returns the same bits.
  * btf_nmf_pav: factor_pav of every column of V (M,T,K) against W (N,K), in place; T (8 K + 4) <= 65536.  Synchronises. */
 typedef struct btf_nmf btf_nmf;
 int btf_nmf_create(btf_nmf** out, int device, int nrows, int ncols, int ndepth, int nreps, int nembeds, const double* S,
                    const unsigned char* counts, double ssw);
 int btf_nmf_run(btf_nmf* h, double* W, double* V, int fit_W, int fit_V, int monotone, int max_steps, double tol, int verbose,
                 int* steps_out, double* rmse_out, double* device_ms);
+int btf_nmf_set_bounds(btf_nmf* h, double max_entry);
+int btf_nmf_set_row_features(btf_nmf* h, int nfeatures, const double* X, const unsigned char* observed);
+int btf_nmf_run_bounded(btf_nmf* h, double* W, double* V, double* R, int fit_W, int fit_V, int monotone, int max_steps,
+                        double tol, int verbose, int* steps_out, double* rmse_out, double* device_ms,
+                        unsigned char* projected_out, int* nprojected_out);
 void btf_nmf_destroy(btf_nmf* h);
 int btf_nmf_pav(int device, int nrows, int ncols, int ndepth, int nembeds, const double* W, double* V);
 
