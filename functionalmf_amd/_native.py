@@ -150,6 +150,9 @@ SIGNATURES = {
     "btf_gass_select": (C.c_int, [_ctx, C.c_int, C.c_uint64, _c_ip]),
     "btf_gass_run": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int]),
     "btf_gass_set_ep": (C.c_int, [_ctx, _c_dp, _c_dp]),
+    "btf_gass_set_row_features": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_uint8), _c_dp]),
+    "btf_gass_set_U": (C.c_int, [_ctx, _c_dp]),
+    "btf_gass_get_U": (C.c_int, [_ctx, _c_dp]),
     "btf_mvn_dense": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, C.c_uint64, C.c_double, C.c_int,
                                 _c_dp, _c_ip]),
     "btf_get_likelihood_form": (C.c_int, [_ctx, _c_ip]),

@@ -9,6 +9,7 @@
 #include "btf_spectral.h"
 #include "btf_gass.h"
 #include "btf_gass_ep.h"
+#include "btf_gass_features.h"
 #include "btf_gamma_grid.h"    // the gamma-grid likelihood (instances in btf_gamma_grid.hip)
 #include "btf_fused.h"
 #include "btf_diag.h"         // convergence diagnostics (instances in btf_diag.hip)
@@ -93,6 +94,14 @@ struct btf_ctx {
   double* gs_thetas = nullptr; int* gs_ntheta = nullptr; double* gs_ll = nullptr; double* gs_llp = nullptr; size_t gs_llp_elems = 0; double* gs_hh = nullptr; double* gs_cur = nullptr;
   int* gs_nacc = nullptr; double* gs_u = nullptr;
   int gs_chains = 0, gs_what = -1, gs_link = 0;
+  // binary row features (btf_gass_set_row_features, btf_gass_features.h): the codes in both orientations, U, the user's
+  // row constraints on the host (gs_rc holds them followed by the 2F derived rows), the rows' side term of the current
+  // state, and the feature chains' own grids / candidates / likelihoods (what = 2)
+  int ft_F = 0; unsigned char* ft_rows = nullptr; unsigned char* ft_cols = nullptr; double* ft_U = nullptr;
+  std::vector<double> gs_rc_host; double* ft_side = nullptr;
+  double* ft_X0 = nullptr; double* ft_Nu = nullptr; double* ft_z = nullptr; unsigned char* ft_mask = nullptr; int* ft_info = nullptr;
+  double* ft_thetas = nullptr; int* ft_ntheta = nullptr; double* ft_ll = nullptr; double* ft_hh = nullptr; double* ft_cur = nullptr;
+  double* ft_part = nullptr; int* ft_nacc = nullptr; double* ft_u = nullptr; double* ft_theta = nullptr; int* ft_keep = nullptr;
   // EP-centred GASS (btf_gass_set_ep): per-cell (Mu, p) in the row and the column layout, per-chain constants, the centre
   // and the current state's correction of the last begin, the twisted envelope of the column systems
   double2* ep_rows = nullptr; double2* ep_cols = nullptr; double* ep_crow = nullptr; double* ep_ccol = nullptr;
@@ -1081,7 +1090,9 @@ void btf_destroy(btf_ctx* c) {
                   c->gpart, c->zbuf, c->bsum, c->gband, c->status, c->tries, c->st_ptr, c->st_row, c->st_coef,
                   c->srcmap_w, c->srcmap_v, c->pband, c->pimg, c->dbg, c->gpart_w, c->gpart_v, c->gsum_v, c->eig, c->cv_cptr, c->cv_crow, c->cv_cdef, c->cv_rptr, c->cv_rcol, c->cv_rdef, c->eig_cols, c->cv_dcols, c->A8_wT, c->A8_v, c->gs_cons, c->gs_cc, c->gs_rc, c->gs_av, c->gs_mask, c->gs_info, c->gs_thetas, c->gs_ntheta, c->gs_ll, c->gs_llp, c->gs_hh, c->gs_cur, c->gs_nacc, c->gs_u, c->st_drow, c->st_dcoef, c->essX0, c->essNu, c->ess_st, c->ess_theta, c->ess_done, c->ess_part, c->Ta, c->Tb, c->Tc, c->lsum, c->dr_ptr, c->dr_col, c->dr_val, c->sse_cols, c->vs_rec, c->vc_scratch, c->gs_cptr, c->gs_cidx, c->gs_cval,
                   c->ep_rows, c->ep_cols, c->ep_crow, c->ep_ccol, c->ep_mu, c->ep_corr, c->ep_pband, c->ep_envg, c->ep_f, c->ep_off,
-                  c->gg_tab, c->gg_Lw, c->gg_Lv};
+                  c->gg_tab, c->gg_Lw, c->gg_Lv,
+                  c->ft_rows, c->ft_cols, c->ft_U, c->ft_side, c->ft_X0, c->ft_Nu, c->ft_z, c->ft_mask, c->ft_info, c->ft_thetas,
+                  c->ft_ntheta, c->ft_ll, c->ft_hh, c->ft_cur, c->ft_part, c->ft_nacc, c->ft_u, c->ft_theta, c->ft_keep};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->pin_lsum) (void)hipHostFree(c->pin_lsum);
@@ -2409,7 +2420,52 @@ int gass_check(btf_ctx* c, int what, int link) {
   if (!c->gs_cons) return fail(c, BTF_ESTATE, "btf_gass_set_constraints first");
   return BTF_OK;
 }
+// the buffers of a set of chains: rows / columns share the gs_* scratch, the feature chains (what = 2) have their own
+struct GassBufs {
+  unsigned char* mask; int* info; double* thetas; int* ntheta; double* ll; double* hh; double* cur; int* nacc;
+  double* X0; double* Nu; double* X; int per; double* theta; int* keep;
+};
+GassBufs gass_bufs(btf_ctx* c, int what) {
+  if (what == 2)
+    return {c->ft_mask, c->ft_info, c->ft_thetas, c->ft_ntheta, c->ft_ll, c->ft_hh, c->ft_cur, c->ft_nacc,
+            c->ft_X0, c->ft_Nu, c->ft_U, c->K, c->ft_theta, c->ft_keep};
+  return {c->gs_mask, c->gs_info, c->gs_thetas, c->gs_ntheta, c->gs_ll, c->gs_hh, c->gs_cur, c->gs_nacc,
+          c->essX0, c->essNu, what == 0 ? c->W : c->V, what == 0 ? c->K : c->T * c->K, c->ess_theta, c->ess_done};
+}
+// gs_rc: the user's fixed row constraints, then room for the 2F rows derived from U (gass_feat_rc_kernel)
+int gass_rc_alloc(btf_ctx* c) {
+  if (c->gs_rc) { (void)hipFree(c->gs_rc); c->gs_rc = nullptr; }
+  const size_t rows = (size_t)c->gs_nrc + 2 * (size_t)c->ft_F, w = (size_t)c->K + 1;
+  if (rows == 0) return BTF_OK;
+  int rc;
+  if ((rc = dev_alloc(c, &c->gs_rc, rows * w))) return rc;
+  if (c->gs_nrc > 0)
+    HIPCHK(c, hipMemcpy(c->gs_rc, c->gs_rc_host.data(), (size_t)c->gs_nrc * w * sizeof(double), hipMemcpyHostToDevice));
+  return BTF_OK;
+}
+// the Bernoulli side term (btf_gass_features.h): rows - of every candidate, added to gs_ll, or (current) of the state
+// into ft_side; features - the whole ll of every candidate, or of the state into ft_part
+void gass_bern_launch(btf_ctx* c, int what, bool current) {
+  GassBernArgs a{};
+  a.K = c->K;
+  if (what == 0) {
+    a.X0 = c->essX0; a.Nu = c->essNu; a.Mu = c->gs_ep ? c->ep_mu : nullptr; a.Fx = c->ft_U; a.codes = c->ft_rows;
+    a.nchains = c->N; a.ncell = c->ft_F; a.thetas = c->gs_thetas; a.ntheta = c->gs_ntheta; a.ll = c->gs_ll;
+    a.cur = current ? c->ft_side : nullptr;
+  } else {
+    a.X0 = c->ft_X0; a.Nu = c->ft_Nu; a.Fx = c->W; a.codes = c->ft_cols;
+    a.nchains = c->ft_F; a.ncell = c->N; a.thetas = c->ft_thetas; a.ntheta = c->ft_ntheta; a.ll = c->ft_ll;
+    a.cur = current ? c->ft_part : nullptr;
+  }
+  Prof p(c, BTF_K_ESS);
+  p.launch(gass_bern_eval_fn(what == 0, what == 0 && c->gs_ep), dim3(a.nchains), dim3(GASS_THREADS), 0, a);
+}
 int gass_eval_launch(btf_ctx* c, int what, int link) {
+  if (what == 2) {
+    gass_bern_launch(c, 2, false);
+    HIPCHK(c, hipGetLastError());
+    return BTF_OK;
+  }
   GassEvalArgs a{};
   a.X0 = c->essX0; a.Nu = c->essNu; a.N = c->N; a.M = c->M; a.T = c->T; a.K = c->K; a.Rc = (double)c->R;
   a.thetas = c->gs_thetas; a.ntheta = c->gs_ntheta;
@@ -2461,7 +2517,39 @@ int gass_eval_launch(btf_ctx* c, int what, int link) {
   if (nsplit > 1)
     hipLaunchKernelGGL(gass_ll_sum_kernel, dim3((nch * GASS_MAXC + 255) / 256), dim3(256), 0, c->stream, (const double*)c->gs_llp, nsplit,
                        (const int*)c->gs_ntheta, nch, c->gs_ll);
+  if (what == 0 && c->ft_F > 0) gass_bern_launch(c, 0, false);
   HIPCHK(c, hipGetLastError());
+  return BTF_OK;
+}
+// the feature chains' begin: x0 = U, v = z (or Philox), the valid grid over the 2N rows (w_i, 0), (-w_i, -1), the slice
+int gass_feat_begin(btf_ctx* c, const double* z, const double* u, uint64_t seed, int pick_ngrid) {
+  if (c->ft_F < 1) return fail(c, BTF_ESTATE, "btf_gass_set_row_features first");
+  if (!c->have_W) return fail(c, BTF_ESTATE, "the feature chains need W");
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "generalized analytic slice sampling needs an unsharded context");
+  HIPCHK(c, hipSetDevice(c->dev));
+  const int F = c->ft_F, K = c->K;
+  if (z) HIPCHK(c, hipMemcpyAsync(c->ft_z, z, (size_t)F * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (u) HIPCHK(c, hipMemcpyAsync(c->ft_u, u, (size_t)F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (z || u) HIPCHK(c, hipStreamSynchronize(c->stream));
+  const unsigned long long dseed = seed * 0x9E3779B97F4A7C15ULL + 0x6A09E667F3BCC909ULL;
+  GassFeatArgs a{};
+  a.U = c->ft_U; a.W = c->W; a.z = z ? c->ft_z : nullptr; a.N = c->N; a.F = F; a.K = K;
+  a.X0 = c->ft_X0; a.Nu = c->ft_Nu; a.vmask = c->ft_mask; a.info = c->ft_info;
+  a.pick = pick_ngrid > 0 ? 1 : 0; a.ngrid = pick_ngrid; a.thetas = c->ft_thetas; a.ntheta = c->ft_ntheta;
+  a.seed = seed; a.pseed = dseed;
+  {
+    Prof p(c, BTF_K_ESS);
+    p.launch(gass_feat_analyse_fn(), dim3(F), dim3(GASS_THREADS), 0, a);
+  }
+  c->gs_ep = false;
+  gass_bern_launch(c, 2, true);
+  {
+    Prof p(c, BTF_K_ESS);
+    p.launch(gass_slice_kernel, dim3((F + 255) / 256), dim3(256), 0, (const double*)c->ft_part, 1, F, (const double*)(u ? c->ft_u : nullptr),
+             dseed, c->ft_hh, c->ft_cur);
+  }
+  HIPCHK(c, hipGetLastError());
+  c->gs_chains = F; c->gs_what = 2; c->gs_link = 0;
   return BTF_OK;
 }
 // EP-centred begin: X0 <- state - mu, Nu <- L'^-1 z, ep_mu <- mu, ep_corr <- the current state's correction (btf_gass_ep.h)
@@ -2558,13 +2646,79 @@ int btf_gass_set_constraints(btf_ctx* c, const double* cons, int J, const double
   }
   HIPCHK(c, hipMemcpy(c->gs_cc, cc.data(), cc.size() * sizeof(double), hipMemcpyHostToDevice));
   if ((rc = dev_alloc(c, &c->gs_av, (size_t)c->M * J * K))) return rc;
-  if (c->gs_rc) { (void)hipFree(c->gs_rc); c->gs_rc = nullptr; }
-  if (nrc > 0) {
-    if ((rc = dev_alloc(c, &c->gs_rc, (size_t)nrc * (K + 1)))) return rc;
-    HIPCHK(c, hipMemcpy(c->gs_rc, row_cons, (size_t)nrc * (K + 1) * sizeof(double), hipMemcpyHostToDevice));
-  }
+  c->gs_rc_host.assign(row_cons, row_cons + (nrc > 0 ? (size_t)nrc * (K + 1) : 0));
   c->gs_J = J; c->gs_nrc = nrc;
+  return gass_rc_alloc(c);
+}
+
+int btf_gass_set_row_features(btf_ctx* c, int F, const uint8_t* codes, const double* U) {
+  if (!c) return BTF_EINVAL;
+  if (F < 0 || (F > 0 && (!codes || !U))) return fail(c, BTF_EINVAL, "btf_gass_set_row_features: codes [N][F] and U [F][K], or F = 0");
+  HIPCHK(c, hipSetDevice(c->dev));
+  int rc;
+  if (F == 0) {
+    if (c->ft_F == 0) return BTF_OK;
+    c->ft_F = 0;
+    if (c->gs_what == 2) { c->gs_what = -1; c->gs_chains = 0; }
+    return gass_rc_alloc(c);
+  }
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "row features need an unsharded context");
+  if (c->K < 1 || c->K > EIG_MAXK) return fail(c, BTF_EINVAL, "btf_gass_set_row_features: nembeds must be in 1..10");
+  const int N = c->N, K = c->K;
+  const size_t nf = (size_t)N * F;
+  std::vector<unsigned char> tr(nf);
+  for (int i = 0; i < N; ++i)
+    for (int f = 0; f < F; ++f) {
+      const unsigned char v = codes[(size_t)i * F + f];
+      if (v > 2) return fail(c, BTF_EINVAL, "btf_gass_set_row_features: codes are 0, 1 or 2 (missing)");
+      tr[(size_t)f * N + i] = v;
+    }
+  for (size_t e = 0; e < (size_t)F * K; ++e)
+    if (!std::isfinite(U[e])) return fail(c, BTF_EINVAL, "btf_gass_set_row_features: U must be finite");
+  HIPCHK(c, hipStreamSynchronize(c->stream));             // (a queued update may still read the buffers replaced below)
+  const size_t nf_ = (size_t)F;
+  if ((rc = dev_alloc(c, &c->ft_rows, nf))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_cols, nf))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_U, nf_ * K))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_side, (size_t)N))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_X0, nf_ * K))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_Nu, nf_ * K))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_z, nf_ * K))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_mask, nf_ * GASS_GRID))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_info, nf_ * 2))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_thetas, nf_ * GASS_MAXC))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_ntheta, nf_))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_ll, nf_ * GASS_MAXC))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_hh, nf_))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_cur, nf_))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_part, nf_))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_nacc, nf_))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_u, nf_))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_theta, nf_))) return rc;
+  if ((rc = dev_alloc(c, &c->ft_keep, nf_))) return rc;
+  HIPCHK(c, hipMemcpy(c->ft_rows, codes, nf, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ft_cols, tr.data(), nf, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ft_U, U, nf_ * K * sizeof(double), hipMemcpyHostToDevice));
+  c->ft_F = F;
+  if (c->gs_what == 2) { c->gs_what = -1; c->gs_chains = 0; }
+  return gass_rc_alloc(c);
+}
+
+int btf_gass_set_U(btf_ctx* c, const double* U) {
+  if (!c || !U) return BTF_EINVAL;
+  if (c->ft_F < 1) return fail(c, BTF_ESTATE, "btf_gass_set_row_features first");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipMemcpyAsync(c->ft_U, U, (size_t)c->ft_F * c->K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return BTF_OK;
+}
+
+int btf_gass_get_U(btf_ctx* c, double* U) {
+  if (!c || !U) return BTF_EINVAL;
+  if (c->ft_F < 1) return fail(c, BTF_ESTATE, "btf_gass_set_row_features first");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipMemcpyAsync(U, c->ft_U, (size_t)c->ft_F * c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return check_status(c);
 }
 
 int btf_gass_set_ep(btf_ctx* c, const double* mu, const double* sigma) {
@@ -2633,6 +2787,10 @@ int btf_gass_begin(btf_ctx* c, int what, int link, const double* z, const double
                    int pick_ngrid) {
   if (!c) return BTF_EINVAL;
   int rc;
+  if (what == 2) {          // the feature chains: no curve likelihood, no curve constraints
+    if (pick_ngrid < 0 || pick_ngrid > GASS_MAXC) return fail(c, BTF_EINVAL, "at most 128 candidates per chain");
+    return gass_feat_begin(c, z, u, seed, pick_ngrid);
+  }
   if ((rc = gass_check(c, what, link))) return rc;
   if (pick_ngrid < 0 || pick_ngrid > GASS_MAXC) return fail(c, BTF_EINVAL, "at most 128 candidates per chain");
   HIPCHK(c, hipSetDevice(c->dev));
@@ -2664,10 +2822,22 @@ int btf_gass_begin(btf_ctx* c, int what, int link, const double* z, const double
     Prof p(c, BTF_K_ESS);
     p.launch(gass_ep_fix_fn(), dim3((nch + 255) / 256), dim3(256), 0, (const double*)c->ep_corr, nch, c->gs_cur, c->gs_hh);
   }
+  const bool feat = what == 0 && c->ft_F > 0;
+  if (feat) {       // the rows' side term of the current state joins cur_ll and the slice height; the 2F rows derived from U
+    c->gs_ep = ep;
+    gass_bern_launch(c, 0, true);
+    {
+      Prof p(c, BTF_K_ESS);
+      p.launch(gass_ep_fix_fn(), dim3((nch + 255) / 256), dim3(256), 0, (const double*)c->ft_side, nch, c->gs_cur, c->gs_hh);
+    }
+    Prof p(c, BTF_K_ESS);
+    p.launch(gass_feat_rc_fn(), dim3((2 * c->ft_F * (c->K + 1) + 255) / 256), dim3(256), 0, (const double*)c->ft_U, c->ft_F, c->K,
+             c->gs_rc + (size_t)c->gs_nrc * (c->K + 1));
+  }
   GassArgs a{};
   a.X0 = c->essX0; a.Nu = c->essNu; a.Cons = c->gs_cons; a.Cc = c->gs_cc; a.J = c->gs_J;
   if (c->gs_cnnz > 0) { a.cs_ptr = c->gs_cptr; a.cs_idx = c->gs_cidx; a.cs_val = c->gs_cval; a.cs_nnz = c->gs_cnnz; }
-  a.AV = c->gs_av; a.Rc = c->gs_rc; a.nrc = what == 0 ? c->gs_nrc : 0; a.W = c->W;
+  a.AV = c->gs_av; a.Rc = c->gs_rc; a.nrc = what == 0 ? c->gs_nrc + (feat ? 2 * c->ft_F : 0) : 0; a.W = c->W;
   a.N = c->N; a.M = c->M; a.T = c->T; a.K = c->K;
   a.vmask = c->gs_mask; a.info = c->gs_info; a.pick = pick_ngrid > 0 ? 1 : 0; a.ngrid = pick_ngrid;
   a.thetas = c->gs_thetas; a.ntheta = c->gs_ntheta; a.seed = dseed;
@@ -2703,10 +2873,11 @@ int btf_gass_grid(btf_ctx* c, int what, int32_t* info, uint8_t* mask, double* sl
   if (c->gs_what != what || c->gs_chains < 1) return fail(c, BTF_ESTATE, "btf_gass_grid follows btf_gass_begin of the same factor");
   HIPCHK(c, hipSetDevice(c->dev));
   const size_t nch = (size_t)c->gs_chains;
-  HIPCHK(c, hipMemcpyAsync(info, c->gs_info, nch * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (mask) HIPCHK(c, hipMemcpyAsync(mask, c->gs_mask, nch * GASS_GRID, hipMemcpyDeviceToHost, c->stream));
-  if (slice) HIPCHK(c, hipMemcpyAsync(slice, c->gs_hh, nch * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (cur_ll) HIPCHK(c, hipMemcpyAsync(cur_ll, c->gs_cur, nch * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  const GassBufs b = gass_bufs(c, what);
+  HIPCHK(c, hipMemcpyAsync(info, b.info, nch * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (mask) HIPCHK(c, hipMemcpyAsync(mask, b.mask, nch * GASS_GRID, hipMemcpyDeviceToHost, c->stream));
+  if (slice) HIPCHK(c, hipMemcpyAsync(slice, b.hh, nch * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (cur_ll) HIPCHK(c, hipMemcpyAsync(cur_ll, b.cur, nch * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   return check_status(c);
 }
 
@@ -2715,17 +2886,18 @@ int btf_gass_eval(btf_ctx* c, int what, const double* thetas, const int32_t* nth
   if (c->gs_what != what || c->gs_chains < 1) return fail(c, BTF_ESTATE, "btf_gass_eval follows btf_gass_begin of the same factor");
   HIPCHK(c, hipSetDevice(c->dev));
   const size_t nch = (size_t)c->gs_chains;
+  const GassBufs b = gass_bufs(c, what);
   if (thetas) {
     if (!ntheta) return fail(c, BTF_EINVAL, "candidate counts missing");
     for (size_t q = 0; q < nch; ++q) if (ntheta[q] < 0 || ntheta[q] > GASS_MAXC) return fail(c, BTF_EINVAL, "at most 128 candidates per chain");
-    HIPCHK(c, hipMemcpyAsync(c->gs_thetas, thetas, nch * GASS_MAXC * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->gs_ntheta, ntheta, nch * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.thetas, thetas, nch * GASS_MAXC * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.ntheta, ntheta, nch * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   int rc;
   if ((rc = gass_eval_launch(c, what, c->gs_link))) return rc;
   if (ll_out) {
-    HIPCHK(c, hipMemcpyAsync(ll_out, c->gs_ll, nch * GASS_MAXC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ll_out, b.ll, nch * GASS_MAXC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return check_status(c);
   }
   return BTF_OK;
@@ -2736,10 +2908,11 @@ int btf_gass_commit(btf_ctx* c, int what, const double* theta, const int32_t* ke
   if (c->gs_what != what || c->gs_chains < 1) return fail(c, BTF_ESTATE, "btf_gass_commit follows btf_gass_begin of the same factor");
   HIPCHK(c, hipSetDevice(c->dev));
   const size_t nch = (size_t)c->gs_chains;
-  HIPCHK(c, hipMemcpyAsync(c->ess_theta, theta, nch * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->ess_done, keep, nch * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  const GassBufs b = gass_bufs(c, what);
+  HIPCHK(c, hipMemcpyAsync(b.theta, theta, nch * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b.keep, keep, nch * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const int per = what == 0 ? c->K : c->T * c->K;
+  const int per = b.per;
   const long long n = (long long)nch * per;
   {
     Prof p(c, BTF_K_ESS);
@@ -2747,10 +2920,11 @@ int btf_gass_commit(btf_ctx* c, int what, const double* theta, const int32_t* ke
       p.launch(gass_ep_commit_fn(), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)c->essX0, (const double*)c->essNu,
                (const double*)c->ep_mu, what == 0 ? c->W : c->V, n, per, (const double*)c->ess_theta, (const int*)c->ess_done);
     else
-      p.launch(ess_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)c->essX0, (const double*)c->essNu,
-               what == 0 ? c->W : c->V, n, per, (const double*)c->ess_theta, (const int*)c->ess_done, 0);
+      p.launch(ess_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)b.X0, (const double*)b.Nu,
+               b.X, n, per, (const double*)b.theta, (const int*)b.keep, 0);
   }
   HIPCHK(c, hipGetLastError());
+  if (what == 2) return BTF_OK;
   if (what == 0) c->ngp_w = 0; else c->ngp_v = 0;
   c->w_part_valid = false; c->w_local_done = c->v_local_done = false; c->sse_cols_valid = false; c->nb_L_valid = false;
   return BTF_OK;
@@ -2760,19 +2934,20 @@ int btf_gass_select(btf_ctx* c, int what, uint64_t seed, int32_t* naccept_out) {
   if (!c) return BTF_EINVAL;
   if (c->gs_what != what || c->gs_chains < 1) return fail(c, BTF_ESTATE, "btf_gass_select follows btf_gass_begin of the same factor");
   HIPCHK(c, hipSetDevice(c->dev));
-  const int nch = c->gs_chains, per = what == 0 ? c->K : c->T * c->K;
+  const int nch = c->gs_chains;
+  const GassBufs b = gass_bufs(c, what);
   {
     Prof p(c, BTF_K_ESS);
-    p.launch(gass_select_kernel, dim3(nch), dim3(GASS_THREADS), 0, (const double*)c->gs_ll, (const int*)c->gs_ntheta, (const double*)c->gs_thetas,
-             (const double*)c->gs_hh, (const double*)c->essX0, (const double*)c->essNu, what == 0 ? c->W : c->V, per,
-             (unsigned long long)(seed * 0x9E3779B97F4A7C15ULL + 0xBB67AE8584CAA73BULL), c->gs_nacc, (double*)nullptr,
+    p.launch(gass_select_kernel, dim3(nch), dim3(GASS_THREADS), 0, (const double*)b.ll, (const int*)b.ntheta, (const double*)b.thetas,
+             (const double*)b.hh, (const double*)b.X0, (const double*)b.Nu, b.X, b.per,
+             (unsigned long long)(seed * 0x9E3779B97F4A7C15ULL + 0xBB67AE8584CAA73BULL), b.nacc, (double*)nullptr,
              (const double*)(c->gs_ep ? c->ep_mu : nullptr));
   }
   HIPCHK(c, hipGetLastError());
-  if (what == 0) c->ngp_w = 0; else c->ngp_v = 0;
-  c->w_part_valid = false; c->w_local_done = c->v_local_done = false; c->sse_cols_valid = false; c->nb_L_valid = false;
+  if (what == 0) c->ngp_w = 0; else if (what == 1) c->ngp_v = 0;
+  if (what != 2) { c->w_part_valid = false; c->w_local_done = c->v_local_done = false; c->sse_cols_valid = false; c->nb_L_valid = false; }
   if (naccept_out) {
-    HIPCHK(c, hipMemcpyAsync(naccept_out, c->gs_nacc, (size_t)nch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(naccept_out, b.nacc, (size_t)nch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     return check_status(c);
   }
   return BTF_OK;

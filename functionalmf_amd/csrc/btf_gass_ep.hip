@@ -1,7 +1,9 @@
-// EP-centred GASS proposals (btf_gass_ep.h): the kernels, one compilation unit of their own.  btf_abi.hip launches them
-// through the function pointers below (counted under BTF_K_ESS).  gfx950 only.
+// EP-centred GASS proposals (btf_gass_ep.h) and the binary row features of the constrained model
+// (btf_gass_features.h): the kernels, one compilation unit of their own.  btf_abi.hip launches them through the
+// function pointers below (counted under BTF_K_ESS).  gfx950 only.
 #define BTF_GASS_EP_UNIT
 #include "btf_gass_ep.h"
+#include "btf_gass_features.h"
 
 namespace btf {
 
@@ -27,5 +29,12 @@ GassEpKernel gass_ep_cols_fn(int K) {
 
 GassEpFixKernel gass_ep_fix_fn() { return gass_ep_fix_kernel; }
 GassEpCommitKernel gass_ep_commit_fn() { return gass_ep_commit_kernel; }
+
+GassFeatRcKernel gass_feat_rc_fn() { return gass_feat_rc_kernel; }
+GassFeatKernel gass_feat_analyse_fn() { return gass_feat_analyse_kernel; }
+GassBernKernel gass_bern_eval_fn(bool rows, bool ep) {
+  if (rows) return ep ? gass_bern_eval_kernel<true, true> : gass_bern_eval_kernel<true, false>;
+  return gass_bern_eval_kernel<false, false>;      // (the feature chains' prior is N(0, I): no EP centre)
+}
 
 }  // namespace btf

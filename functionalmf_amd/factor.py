@@ -1556,10 +1556,30 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
     rng="host": per row / column the slice height, the proposal normals, the grid subsample and the selection are drawn
     from `chain_rngs(what)[c]` (default: RandomState objects seeded from the global legacy generator) in the reference's
     order - with the same streams the update reproduces the reference's worker functions (tests/golden/g10_gass.npz).
-    rng="device": everything on the GPU (btf_gass_run), nothing read back."""
+    rng="device": everything on the GPU (btf_gass_run), nothing read back.
+
+    row_features: optional (nrows, F) array of 0, 1 or nan (missing) - the binary row features of the dose-response
+    application (doseresponse/fit.py:40-50, :102-145); feature_embeddings: the (F, nembeds) start of U (the third
+    return value of `bounded_tensor_nmf(..., row_features=X)`), required with it.  Every row update of W then adds
+    sum_f x_if log(w_i . u_f) + (1 - x_if) log(1 - w_i . u_f) to the likelihood (missing pairs add nothing) and keeps
+    0 <= w_i . u_f <= 1 through 2F constraints derived from the current U behind `Row_constraints`; with
+    sample_features=True (default) `resample()` also updates every u_f after V (`_resample_U`): prior N(0, I), the
+    constraints 0 <= W u_f <= 1, the same term over the rows - all F chains in one set of launches; rng="host": one
+    RandomState per feature from `chain_rngs(2)`, draws in the order of gass.py.  sample_features=False: U stays fixed.
+    `U` is read and assigned like W; it is part of run_gibbs' results and of checkpoint() / restore()."""
 
     def __init__(self, nrows, ncols, ndepth, loglikelihood, Constraints, ep_approx=None, nthreads=3, gass_ngrid=100,
-                 Row_constraints=None, multiprocessing=True, sharedprefix=None, worker_init=None, **kwargs):
+                 Row_constraints=None, multiprocessing=True, sharedprefix=None, worker_init=None,
+                 row_features=None, feature_embeddings=None, sample_features=True, **kwargs):
+        if row_features is None:
+            if feature_embeddings is not None:
+                raise ValueError("feature_embeddings was given without row_features")
+            feat = None
+        else:
+            feat = self._check_features(row_features, feature_embeddings, nrows, kwargs.get("nembeds", 5))
+            W0 = kwargs.get("W_true") if kwargs.get("W_true") is not None else kwargs.get("W_init")
+            if W0 is not None:
+                self._check_feature_start(np.asarray(W0, dtype=float), feat[1])
         if ep_approx is not None:
             if not isinstance(ep_approx, (tuple, list)) or len(ep_approx) != 2:
                 raise ValueError("ep_approx must be a pair (Mu_ep, Sigma_ep)")
@@ -1590,6 +1610,81 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
         self.gass_info = {}
         self._Mu_ep, self._Sigma_ep = ep
         self._ep_dirty = ep[0] is not None
+        self._X_codes, self._U = (None, None) if feat is None else feat
+        self.row_features = None if feat is None else np.array(row_features, dtype=float)
+        self.nfeatures = 0 if feat is None else int(self._X_codes.shape[1])
+        self.sample_U = feat is not None and bool(sample_features)
+        self._feat_set = self._feat_checked = False
+        self._U_host_new, self._U_dev_new = feat is not None, False
+
+    @staticmethod
+    def _check_features(row_features, feature_embeddings, nrows, nembeds):
+        """(codes uint8 (nrows, F): 0, 1, 2 = missing; U float64 (F, nembeds)) or ValueError."""
+        X = np.asarray(row_features, dtype=float)
+        if X.ndim != 2 or X.shape[0] != nrows or X.shape[1] < 1:
+            raise ValueError("row_features must be (nrows, F) with F >= 1, got %r" % (X.shape,))
+        miss = np.isnan(X)
+        if not np.all(miss | (X == 0) | (X == 1)):
+            raise ValueError("row_features must hold 0, 1 or nan (missing)")
+        if feature_embeddings is None:
+            raise ValueError("row_features needs feature_embeddings: the (F, nembeds) start of U")
+        U = np.array(feature_embeddings, dtype=np.float64, order="C")
+        if U.shape != (X.shape[1], nembeds):
+            raise ValueError("feature_embeddings must be (F, nembeds) = (%d, %d), got %r" % (X.shape[1], nembeds, U.shape))
+        if not np.all(np.isfinite(U)):
+            raise ValueError("feature_embeddings must be finite")
+        if not 1 <= int(nembeds) <= 10:
+            raise ValueError("row_features needs nembeds in 1..10")
+        return np.ascontiguousarray(np.where(miss, 2, X).astype(np.uint8)), U
+
+    @staticmethod
+    def _check_feature_start(W, U):
+        """0 <= W U' <= 1 (gass.py:35 asserts 'Invalid starting point' here); the worst (row, feature) pair otherwise."""
+        P = W @ U.T
+        viol = np.maximum(-P, P - 1.0)
+        if np.any(viol > 0) or np.any(np.isnan(P)):
+            i, f = np.unravel_index(np.argmax(np.where(np.isnan(viol), np.inf, viol)), viol.shape)
+            raise ValueError("invalid starting point: w_%d . u_%d = %r is outside [0, 1] (row %d, feature %d is the worst pair)"
+                             % (i, f, float(P[i, f]), i, f))
+
+    @property
+    def U(self):
+        if self._U is None:
+            return None
+        if self._U_dev_new:
+            self._ctx.call("btf_gass_get_U", _native.dptr(self._U))
+            self._U_dev_new = False
+        self._U_host_new = True                 # (may be written through the returned array)
+        return self._U
+
+    @U.setter
+    def U(self, value):
+        if self._X_codes is None:
+            raise ValueError("the model was built without row_features")
+        value = np.array(value, dtype=np.float64, order="C")
+        if value.shape != (self.nfeatures, self.nembeds):
+            raise ValueError("U must be (F, nembeds) = (%d, %d)" % (self.nfeatures, self.nembeds))
+        self._U = value
+        self._U_host_new, self._U_dev_new = True, False
+        self._feat_checked = False
+
+    def _push_features(self):
+        if self._X_codes is None:
+            return
+        import ctypes
+        if self._U_host_new or not self._feat_set:
+            self._U = _native.as_f64(self._U)
+        if not self._feat_set:
+            self._ctx.call("btf_gass_set_row_features", int(self.nfeatures),
+                           self._X_codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _native.dptr(self._U))
+            self._feat_set = True
+        elif self._U_host_new:
+            self._ctx.call("btf_gass_set_U", _native.dptr(self._U))
+        self._U_host_new = False
+        if not self._feat_checked:              # the first update (and the first after U was assigned)
+            self._pull_W()
+            self._check_feature_start(self._W, self._U)
+            self._feat_checked = True
 
     @staticmethod
     def _check_ep(Mu_ep, Sigma_ep, shape):
@@ -1658,8 +1753,10 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
 
     def _gass_step(self, what, data):
         import ctypes
-        self._bind_data(data)
+        if what != 2:
+            self._bind_data(data)
         self._push_state()
+        self._push_features()
         if not self._cons_set:
             rc = self.Row_constraints
             self._ctx.call("btf_gass_set_constraints", _native.dptr(self._cons), int(self._cons.shape[0]),
@@ -1672,7 +1769,7 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
             self._ctx.call("btf_gass_run", what, self._link, self._next_seed(), self.gass_ngrid, eps, att)
         else:
             N, M, T, K = self.nrows, self.ncols, self.ndepth, self.nembeds
-            nch = N if what == 0 else M
+            nch = (N, M, self.nfeatures)[what]
             rngs = self.chain_rngs(what) if self.chain_rngs is not None else \
                 [np.random.RandomState(np.random.randint(0, 2 ** 31 - 1)) for _ in range(nch)]
             # gass.py:21-24 per chain: the slice uniform, then the proposal normals
@@ -1685,11 +1782,16 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
                     u[i] = rngs[i].random_sample()
                     z[off:off + d] = rngs[i].normal(size=d)
                     off += d
-            else:
+            elif what == 1:
                 z = np.empty((M, K * T))
                 for j in range(M):
                     u[j] = rngs[j].random_sample()
                     z[j] = rngs[j].normal(size=K * T)
+            else:                                   # identity covariance: the proposal is the normals themselves
+                z = np.empty((nch, K))
+                for f in range(nch):
+                    u[f] = rngs[f].random_sample()
+                    z[f] = rngs[f].normal(size=K)
             self._keep_z = (z, u)
             self._ctx.call("btf_gass_begin", what, self._link, _native.dptr(z), _native.dptr(u), self._next_seed(), eps, att, 0)
             info = np.zeros((nch, 2), dtype=np.int32)
@@ -1719,6 +1821,9 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
                     keep[c] = 0
             self._ctx.call("btf_gass_commit", what, _native.dptr(theta), keep.ctypes.data_as(_native._c_ip))
             self.gass_info = {"valid": info[:, 0].copy(), "unrestricted": info[:, 1].copy(), "candidates": nth, "accepted": acc}
+        if what == 2:
+            self._U_dev_new = True
+            return
         self._ess_ready = True
         if what == 0:
             self._W_dev_new = True
@@ -1732,3 +1837,30 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
 
     def _resample_V(self, data):
         self._gass_step(1, data)
+
+    def _resample_U(self, data=None):
+        """One GASS update of every feature embedding u_f given W (doseresponse/fit.py:113-130), all F chains together."""
+        if self._X_codes is None:
+            raise ValueError("the model was built without row_features")
+        self._gass_step(2, data)
+
+    def resample(self, data, **kwargs):
+        super().resample(data, **kwargs)
+        if self.sample_U:
+            self._resample_U(data)
+
+    def _inferred_variables(self, var_map):
+        super()._inferred_variables(var_map)
+        if self._X_codes is not None:
+            var_map['U'] = np.copy(self.U)
+
+    def _extra_state(self):
+        st = super()._extra_state()
+        if self._X_codes is not None:
+            st["U"] = np.array(self.U, dtype=float)
+        return st
+
+    def _set_extra_state(self, st):
+        super()._set_extra_state(st)
+        if self._X_codes is not None and "U" in st:
+            self.U = np.array(st["U"], dtype=float)

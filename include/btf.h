@@ -564,6 +564,21 @@ int btf_gass_run(btf_ctx* ctx, int what, int link, uint64_t seed, int ngrid, dou
  * ll - sum_cells log N(tau; Mu_ep, Sigma_ep) over every cell of the chain; commit and select write
  * x0 cos + v sin + mu.  The kernels are counted under BTF_K_ESS. */
 int btf_gass_set_ep(btf_ctx* ctx, const double* mu, const double* sigma);
+/* btf_gass_set_row_features: binary row features of the constrained model (doseresponse/fit.py:40-50, :102-145).  codes
+ * [N][F]: 0, 1 or 2 (missing); U [F][K]: the feature embeddings (finite).  F = 0 clears.  While set,
+ *   - the row chains (what = 0) add  sum_f x_if log(w_i . u_f) + (1 - x_if) log(1 - w_i . u_f)  (missing pairs and pairs
+ *     outside [0, 1] add nothing) to cur_ll, the slice and every candidate's ll, for every likelihood family and with
+ *     or without btf_gass_set_ep, and their constraints gain the 2F rows (u_f, 0), (-u_f, -1) behind row_cons, rebuilt
+ *     from the current U at every btf_gass_begin;
+ *   - what = 2 is accepted by btf_gass_begin / grid / eval / commit / select / run: one chain per feature, x0 = u_f,
+ *     v = z ([F][K], or NULL: Philox), prior N(0, I_K), constraints 0 <= w_i . u <= 1 for every row, likelihood the same
+ *     term summed over the rows; u, info, mask, slice, cur_ll, thetas, ll_out, theta, keep are indexed by feature; link,
+ *     eps0 and attempts are ignored.  Without features what = 2 returns BTF_ESTATE.
+ * btf_gass_set_U / btf_gass_get_U: U [F][K] (BTF_ESTATE without features).  Unsharded contexts, nembeds <= 10.  The
+ * kernels are counted under BTF_K_ESS. */
+int btf_gass_set_row_features(btf_ctx* ctx, int F, const uint8_t* codes, const double* U);
+int btf_gass_set_U(btf_ctx* ctx, const double* U);
+int btf_gass_get_U(btf_ctx* ctx, double* U);
 
 /* ---- posterior summaries (stateless) --------------------------------
  * Mean and percentiles over the kept samples of f(w_s[i] . v_s[j,t]) for every cell: what the
