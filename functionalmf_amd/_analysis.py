@@ -1,5 +1,5 @@
 """The Python front end of the posterior analysis features: summary, diagnostics, criteria / PSIS-LOO, predictive,
-functionals, ranking and fold-in.
+functionals, ranking, feature association and fold-in.
 
 Two halves.  The argument checks every feature shares, as plain functions (importable without a GPU): the transform table,
 the percentile check, the (S,N,K) / (S,M,T,K) shape check and the per-sample scalar check - the stateless forms in utils.py
@@ -328,6 +328,35 @@ class PosteriorAnalysis:
         S, Ws, Vs = self._samples(results)
         return _rank.evaluate(shape, self.nembeds, S, which=which, along=along, order=order, top=top, transform=transform, x=x,
                               level=level, pairs=pairs, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
+
+    # ---- posterior feature association: which biomarker goes with which drug (functionalmf_amd/association.py) ----
+    def posterior_feature_association(self, U=None, results=None, which="auc", stats=("r",), q=(5, 95), transform=None, x=None,
+                                      level=None, pairs=None, of_means=True):
+        """The association across the rows between every row feature's probability w_i . u_f and one functional of
+        posterior_functionals of every column's curves - correlation and regression slope per kept sample, summarised over
+        the samples on the GPU (csrc/btf_assoc.h) - and the plug-in table doseresponse/feature_importance.py:39-54 computes
+        from posterior means.
+
+        U: the sampled feature embeddings (S,F,nembeds), one per kept sample; None: results["U"] (run_gibbs returns it for a
+            model with row_features= and sample_features=True; it stays on the host, so it is uploaded either way).
+        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device (no upload).
+        The other arguments and the returned dict: functionalmf_amd.utils.posterior_feature_association.  The sampler's
+        state is not touched: a chain continued after the call walks the same path.  Unsharded models."""
+        from . import association as _assoc
+        self._unsharded("posterior feature association")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        if U is None and results is not None:
+            try:
+                U = results["U"] if "U" in results else None
+            except TypeError:
+                raise ValueError("results must be a run_gibbs result dict")
+        U = _assoc.check_features(U, K=self.nembeds)
+        _assoc.check_args(which, stats, q, transform, x, level, pairs, 1, shape[1], shape[2], U.shape[1])
+        S, Ws, Vs = self._samples(results)
+        U = _assoc.check_features(U, S, self.nembeds)        # one embedding per kept sample
+        return _assoc.evaluate(shape, self.nembeds, S, U, which=which, stats=stats, q=q, transform=transform, x=x, level=level,
+                               pairs=pairs, of_means=of_means, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
 
     # ---- folding new rows in (functionalmf_amd/fold_in.py, csrc/btf_fold_in.h) ----
     def fold_in_rows(self, Y_new, results=None, seed=None, z=None, summary=True, q=(5, 95), transform=None, inner_sweeps=None,

@@ -19,6 +19,8 @@ SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.h
            os.path.join(CSRC, "btf_gass_ep.hip"), os.path.join(CSRC, "btf_gamma_grid.hip"), os.path.join(CSRC, "btf_diag.hip"),
            os.path.join(CSRC, "btf_predict.hip"), os.path.join(CSRC, "btf_functionals.hip"), os.path.join(CSRC, "btf_fold_in.hip"),
            os.path.join(CSRC, "btf_loo.hip"), os.path.join(CSRC, "btf_ranking.hip")]
+# compilation units added since: SOURCES keeps its eleven entries (build() addresses them by index); (source, object suffix)
+MORE_SOURCES = [(os.path.join(CSRC, "btf_assoc.hip"), "_assoc.o")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -96,6 +98,10 @@ SIGNATURES = {
                                         _c_ip, C.c_int, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_dp, C.c_longlong]),
     "btf_collect_ranking": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _c_dp, C.c_double, C.c_int, C.c_int, _c_ip, C.c_int, _c_ip, C.c_int,
                                       _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_dp, C.c_longlong]),
+    "btf_posterior_association": (C.c_int, [C.c_int] * 7 + [_c_dp, _c_dp, _c_dp, C.c_int, C.c_int, _c_dp, C.c_double, _c_ip, C.c_int, _c_dp,
+                                            C.c_int, _c_ip, C.c_int] + [_c_dp] * 10 + [C.c_longlong]),
+    "btf_collect_association": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, C.c_int, _c_dp, C.c_double, _c_ip, C.c_int, _c_dp, C.c_int,
+                                          _c_ip, C.c_int] + [_c_dp] * 10 + [C.c_longlong]),
     "btf_fold_in_rows": (C.c_int, [C.c_int] * 7 + [_c_dp] * 7 + [C.c_uint64, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int,
                                    _c_dp, _c_dp]),
     "btf_collect_fold_in": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [_c_dp] * 4 + [C.c_uint64, C.c_int, C.c_int64, _c_dp, _c_dp,
@@ -204,7 +210,7 @@ OBJ_DIR = os.path.join(ROOT, "build", "obj")          # git- and gpurun-ignored
 def build(force=False, verbose=False, jobs=None):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU): the C-ABI unit and the
     parts of btf_instances.hip (the large kernel families, one compilation each) in parallel, then one link."""
-    deps = SOURCES + [INST_SOURCE] + HEADERS
+    deps = SOURCES + [src for src, _ in MORE_SOURCES] + [INST_SOURCE] + HEADERS
     if not force and os.path.exists(LIB_PATH) and \
             os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(p) for p in deps):
         return LIB_PATH
@@ -223,6 +229,7 @@ def build(force=False, verbose=False, jobs=None):
     units += [(SOURCES[6], os.path.join(OBJ_DIR, tag + "_predict.o"), []), (SOURCES[7], os.path.join(OBJ_DIR, tag + "_functionals.o"), [])]
     units += [(SOURCES[8], os.path.join(OBJ_DIR, tag + "_fold_in.o"), []), (SOURCES[9], os.path.join(OBJ_DIR, tag + "_loo.o"), [])]
     units += [(SOURCES[10], os.path.join(OBJ_DIR, tag + "_ranking.o"), [])]
+    units += [(src, os.path.join(OBJ_DIR, tag + suffix), []) for src, suffix in MORE_SOURCES]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 

@@ -18,6 +18,7 @@
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
 #include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
+#include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
@@ -4329,6 +4330,151 @@ int btf_collect_ranking(btf_ctx* c, int nsamples, int transform, int which, cons
   Scratch s(c, c->stream);
   return ranking_run(s, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop,
                      pairs, npairs, o, scratch_bytes);
+}
+
+// ---------------------------------------------------------------- posterior feature association (btf_assoc.h)
+namespace {
+
+struct AssocOut { double *mean, *var, *quant, *prob, *defined, *nmean, *values, *of_means, *sdx, *sdy; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K), dU (S,F,K): per chunk of samples the functionals' sweep
+// into the scratch, the moments of every (sample, column) and the running curve means; then the reduction over the samples
+// per (feature, column), the raw values of the requested pairs, the plug-in table, and the downloads.  scratch_bytes caps
+// the chunk's scratch (0: FUNC_SCRATCH_BYTES; one sample is the least a chunk holds).
+int assoc_run(Scratch& s, const double* dW, const double* dV, const double* dU, int S, int N, int M, int T, int K, int F, int transform,
+              int which, const double* x, double level, const int* stats, int nstats, const double* q, int nq, const int* pairs,
+              int npairs, const AssocOut& o, long long scratch_bytes) {
+  FuncKernel sweep = func_sweep_fn(K, transform);
+  AssocKernel moments = assoc_moments_fn(K), reduce = assoc_reduce_fn(K);
+  if (!sweep || !moments || !reduce) return fail(s.ctx(), BTF_EINVAL, "posterior association: nembeds must be 1..10 and transform 0..2");
+  const size_t NM = (size_t)N * M, FM = (size_t)F * M, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
+  const int sc_max = (int)std::max<size_t>(1, std::min<size_t>(S, cap / (NM * sizeof(double))));
+  FuncArgs f = {};
+  f.level = level; f.exceed = std::nan(""); f.N = N; f.M = M; f.T = T; f.nslots = 1;
+  for (int k = 0; k < FUNC_COUNT; ++k) f.slot[k] = -1;
+  f.slot[which] = 0; f.code[0] = which;
+  f.x = s.upload(x, (size_t)T);
+  double* vals = s.alloc<double>(NM * sc_max);
+  AssocArgs a = {};
+  a.vals = vals; a.W = dW; a.U = dU; a.S = S; a.N = N; a.M = M; a.F = F;
+  a.mom = s.alloc<double>((size_t)S * M * assoc_nmom(K));
+  a.nst = nstats;
+  for (int k = 0; k < nstats; ++k) a.st[k] = stats[k];
+  const SortGeom g = sort_geom(S, ASSOC_SORT_LDS, ASSOC_ROWS);      // rows of P doubles; a pair takes one per statistic
+  a.P = g.P;
+  while ((1 << a.pshift) < a.P) ++a.pshift;
+  a.cells = std::max(1, std::min(g.cells / nstats, F));
+  const size_t lds = (size_t)a.cells * nstats * a.P * sizeof(double);
+  a.nq = nq;
+  if (nq) { a.q = s.upload(q, (size_t)nq); a.quant = s.alloc<double>((size_t)nstats * nq * FM); }
+  a.mean = s.alloc<double>(nstats * FM); a.var = s.alloc<double>(nstats * FM); a.prob = s.alloc<double>(nstats * FM);
+  a.defined = s.alloc<double>(FM); a.nmean = s.alloc<double>(M);
+  if (npairs) { a.npairs = npairs; a.pairs = s.upload(pairs, (size_t)2 * npairs); a.values = s.alloc<double>((size_t)nstats * npairs * S); }
+  const bool plug = o.of_means != nullptr;
+  auto zero = [&](void* p, size_t bytes) { if (!s.rc()) s.check(hipMemsetAsync(p, 0, bytes, s.stream()), "hipMemsetAsync"); };
+  if (plug) {
+    a.pbar = s.alloc<double>((size_t)F * N); a.gbar = s.alloc<double>(NM); a.gcnt = s.alloc<int>(NM);
+    a.om = s.alloc<double>(ASSOC_OM * FM); a.sdx = s.alloc<double>(F); a.sdy = s.alloc<double>(M);
+    zero(a.gbar, NM * sizeof(double)); zero(a.gcnt, NM * sizeof(int));
+  }
+  allow_lds(s, reduce, lds);
+  const int rowblocks = (N + WAVE - 1) / WAVE, JMAX = 65535;   // (a grid's y extent)
+  const unsigned rb = (unsigned)((N + ASSOC_THREADS - 1) / ASSOC_THREADS);
+  for (int s0 = 0; s0 < S; s0 += sc_max) {
+    const int sc = std::min(sc_max, S - s0);
+    f.W = dW + (size_t)s0 * N * K; f.V = dV + (size_t)s0 * M * T * K; f.S = sc;
+    for (int j0 = 0; j0 < M; j0 += JMAX) {                     // vals[column][sample of the chunk][row]
+      f.j0 = j0; f.jc = std::min(JMAX, M - j0); f.vals = vals + (size_t)j0 * sc * N;
+      const int zs = std::max(1, std::min((sc + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * f.jc - 1) / (rowblocks * f.jc)));
+      launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, f.jc, zs), dim3(FUNC_WAVES * WAVE), 0, f);
+    }
+    a.s0 = s0; a.sc = sc;
+    launch_counted(s, BTF_K_CRITERIA, moments, dim3(M, sc), dim3(WAVE), 0, a);
+    if (plug) launch_counted(s, BTF_K_CRITERIA, assoc_gbar_fn(), dim3(rb * M), dim3(ASSOC_THREADS), 0, a);
+  }
+  const unsigned ftiles = (unsigned)((F + a.cells - 1) / a.cells);
+  launch_counted(s, BTF_K_CRITERIA, reduce, dim3(ftiles * M), dim3(ASSOC_THREADS), lds, a);
+  if (npairs) launch_counted(s, BTF_K_CRITERIA, assoc_values_fn(K), dim3(npairs), dim3(ASSOC_THREADS), 0, a);
+  if (plug) {
+    launch_counted(s, BTF_K_CRITERIA, assoc_pbar_fn(K), dim3(rb * ((F + ASSOC_FT - 1) / ASSOC_FT)), dim3(ASSOC_THREADS), 0, a);
+    launch_counted(s, BTF_K_CRITERIA, assoc_gbar_finish_fn(), dim3((unsigned)((NM + ASSOC_THREADS - 1) / ASSOC_THREADS)), dim3(ASSOC_THREADS), 0, a);
+    launch_counted(s, BTF_K_CRITERIA, assoc_cross_fn(), dim3((unsigned)F * ((M + 3) / 4)), dim3(ASSOC_THREADS), 0, a);
+  }
+  s.download(o.mean, a.mean, nstats * FM);
+  s.download(o.var, a.var, nstats * FM);
+  s.download(o.prob, a.prob, nstats * FM);
+  if (nq) s.download(o.quant, a.quant, (size_t)nstats * nq * FM);
+  s.download(o.defined, a.defined, FM);
+  s.download(o.nmean, a.nmean, (size_t)M);
+  if (npairs) s.download(o.values, a.values, (size_t)nstats * npairs * S);
+  if (plug) { s.download(o.of_means, a.om, ASSOC_OM * FM); s.download(o.sdx, a.sdx, (size_t)F); s.download(o.sdy, a.sdy, (size_t)M); }
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int assoc_check(btf_ctx* c, int S, int N, int M, int T, int K, int F, const double* Us, int transform, int which, const double* x,
+                double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs, const AssocOut& o,
+                long long scratch_bytes) {
+  if (S < 1 || N < 1 || M < 1 || F < 1 || K < 1 || K > MAX_K || !Us || transform < 0 || transform > 2 || which < 0 || which >= FUNC_COUNT ||
+      !x || !stats || nstats < 1 || nstats > ASSOC_NSTATS || nq < 0 || (nq > 0 && (!q || !o.quant)) || npairs < 0 ||
+      (npairs > 0 && (!pairs || !o.values)) || (o.of_means && (!o.sdx || !o.sdy)) || scratch_bytes < 0)
+    return fail(c, BTF_EINVAL, "bad posterior association arguments");
+  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior association: at most " + std::to_string(FUNC_MAX_S) + " samples (the values of a pair are sorted in LDS)");
+  if ((long long)F * M > 0x7fffffffLL || (long long)N * M > 0x7fffffffLL * (long long)ASSOC_THREADS)
+    return fail(c, BTF_EINVAL, "posterior association: too many (feature, column) pairs or curves for one launch");
+  if (T < 2) return fail(c, BTF_EINVAL, "posterior association: a curve needs ndepth >= 2");
+  if (which == FUNC_CROSSING && !(level == level)) return fail(c, BTF_EINVAL, "posterior association: crossing needs a level");
+  for (int t = 1; t < T; ++t)
+    if (!(x[t] > x[t - 1])) return fail(c, BTF_EINVAL, "posterior association: x must be strictly increasing");
+  for (int k = 0; k < nstats; ++k)
+    if (stats[k] < 0 || stats[k] >= ASSOC_NSTATS || (k > 0 && stats[k] == stats[0]))
+      return fail(c, BTF_EINVAL, "posterior association: statistic codes must be distinct and in 0..1");
+  for (int k = 0; k < nq; ++k)
+    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
+  for (int k = 0; k < npairs; ++k)
+    if (pairs[2 * k] < 0 || pairs[2 * k] >= F || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= M)
+      return fail(c, BTF_EINVAL, "posterior association: pair index out of range");
+  return BTF_OK;
+}
+
+}  // namespace
+
+int btf_posterior_association(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, int nfeatures, const double* Ws,
+                              const double* Vs, const double* Us, int transform, int which, const double* x, double level,
+                              const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs, double* mean_out,
+                              double* var_out, double* q_out, double* prob_out, double* defined_out, double* nmean_out,
+                              double* values_out, double* of_means_out, double* sdx_out, double* sdy_out, long long scratch_bytes) {
+  const AssocOut o = {mean_out, var_out, q_out, prob_out, defined_out, nmean_out, values_out, of_means_out, sdx_out, sdy_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior association arguments");
+  int rc = assoc_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, nfeatures, Us, transform, which, x, level, stats, nstats, q, nq,
+                       pairs, npairs, o, scratch_bytes);
+  if (rc) return rc;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
+  const double* dU = s.upload(Us, (size_t)nsamples * nfeatures * nembeds);
+  return assoc_run(s, dW, dV, dU, nsamples, nrows, ncols, ndepth, nembeds, nfeatures, transform, which, x, level, stats, nstats, q, nq,
+                   pairs, npairs, o, scratch_bytes);
+}
+
+// the same on the first nsamples collected states, read where they lie; only Us (the host keeps U) is uploaded
+int btf_collect_association(btf_ctx* c, int nsamples, int nfeatures, const double* Us, int transform, int which, const double* x,
+                            double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs,
+                            double* mean_out, double* var_out, double* q_out, double* prob_out, double* defined_out, double* nmean_out,
+                            double* values_out, double* of_means_out, double* sdx_out, double* sdy_out, long long scratch_bytes) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior association arguments");
+  const AssocOut o = {mean_out, var_out, q_out, prob_out, defined_out, nmean_out, values_out, of_means_out, sdx_out, sdy_out};
+  int rc = assoc_check(c, nsamples, c->N, c->M, c->T, c->K, nfeatures, Us, transform, which, x, level, stats, nstats, q, nq, pairs, npairs,
+                       o, scratch_bytes);
+  if (rc) return rc;
+  if (!c->smp_W || !c->smp_V || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_association: not that many collected samples");
+  HIPCHK(c, hipSetDevice(c->dev));
+  Scratch s(c, c->stream);
+  const double* dU = s.upload(Us, (size_t)nsamples * nfeatures * c->K);
+  return assoc_run(s, c->smp_W, c->smp_V, dU, nsamples, c->N, c->M, c->T, c->K, nfeatures, transform, which, x, level, stats, nstats, q, nq,
+                   pairs, npairs, o, scratch_bytes);
 }
 
 // ---------------------------------------------------------------- folding new rows in (btf_fold_in.h)

@@ -183,6 +183,37 @@ def posterior_ranking(Ws, Vs, which="auc", along="cols", order="ascending", top=
                             pairs=pairs, pointwise=pointwise, Ws=Ws, Vs=Vs, device=device, _scratch_bytes=_scratch_bytes)
 
 
+def posterior_feature_association(Ws, Vs, Us, which="auc", stats=("r",), q=(5, 95), transform=None, x=None, level=None, pairs=None,
+                                  of_means=True, device=0, _scratch_bytes=0):
+    """Which row feature (biomarker) goes with which column's curve functional (drug sensitivity), with uncertainty, on the
+    GPU, without a model: the stateless form of BayesianTensorFiltering.posterior_feature_association.  What
+    doseresponse/feature_importance.py:39-54 computes on posterior means only.
+
+    Ws (S,N,K), Vs (S,M,T,K) and Us (S,F,K), the sampled feature embeddings (run_gibbs returns "U" for a model with
+    row_features= and sample_features=True).  For kept sample s, feature f and column j: y_i = the functional `which` of curve
+    (i,j) - ONE of "auc", "max", "min", "argmax", "argmin", "rise", "crossing"; transform, x, level as posterior_functionals,
+    whose pointwise values these are bit for bit - is regressed over the rows i on x_i = w_i^s . u_f^s:
+        r = Sxy / sqrt(Sxx Syy),   slope = Sxy / Sxx     (centred sums over the rows with a defined y_i; n of them)
+    A row whose `crossing` is undefined is left out of that column's regression in that sample; the triple is defined when
+    n >= 3, Sxx > 0 and Syy > 0.  functionalmf_amd.association.statistics / summarize are the definition in numpy.
+
+    Returns a dict: for every name of stats (a subset of ("r", "slope")) a dict of mean, var (ddof 1; 0 with one defined
+    sample), quantiles (len(q),F,M) by np.nanpercentile's rule and prob_positive, each (F,M) over the DEFINED samples (nan
+    when there is none); defined (F,M) = defined samples / S; n_mean (M,) = the mean of n over the samples; which, stats,
+    nsamples.  pairs: a (P,2) integer array of (feature, column) adds values (P,S) to every statistic, the raw per-sample
+    values with nan where undefined.  of_means=True adds the plug-in table of the reference: of_means = {r, slope, intercept,
+    stderr, n (F,M); sd_x (F,), sd_y (M,)} of the regression of the posterior-mean functional on the posterior-mean feature
+    probability mean_s W_s U_s' - scipy.stats.linregress's numbers and the two ddof-0 standard deviations
+    feature_importance.py:50 filters on; the p-value follows from r and n.
+    At most 8192 samples, ndepth >= 2.  There is no CPU fallback."""
+    from . import _analysis, association
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    return association.evaluate(shape, K, S, Us, which=which, stats=stats, q=q, transform=transform, x=x, level=level, pairs=pairs,
+                                of_means=of_means, Ws=Ws, Vs=Vs, device=device, _scratch_bytes=_scratch_bytes)
+
+
 def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summary=True, q=(5, 95), transform=None,
                  inner_sweeps=None, trials=None, first_sample=0, device=0):
     """Embeddings of rows the chain never saw, one draw per kept sample, on the GPU, without a model: the stateless form of

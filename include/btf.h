@@ -641,6 +641,39 @@ int btf_collect_ranking(btf_ctx* ctx, int nsamples, int transform, int which, co
                         double* var_out, double* ptop_out, int* ranks_out, double* prob_less_out, double* prob_defined_out,
                         long long scratch_bytes);
 
+/* ---- posterior feature association (csrc/btf_assoc.h) -------------------------------------------------------------------
+ * The association between a row feature's probability and ONE curve functional across the rows, per kept sample: what
+ * doseresponse/feature_importance.py:39-54 computes on posterior means only.  For kept sample s, feature f (Us (S,F,K):
+ * the feature embeddings u_f^s) and column j, with y_i = the functional `which` of curve (i,j) (codes, x, level, transform
+ * as btf_posterior_functionals; the same values bit for bit), x_i = w_i^s . u_f^s, I = {i : y_i defined}, n = |I| and the
+ * centred sums Sxx, Syy, Sxy over I:   r = Sxy / sqrt(Sxx Syy),  slope = Sxy / Sxx,  defined iff n >= 3, Sxx > 0, Syy > 0.
+ * x is linear in w, so the sums follow from per-(sample, column) moments of W (3 + 2K + K(K+1)/2 doubles each, kept on the
+ * device for the call) and the (S,F,M,N) product is never formed.  stats: nstats = 1..2 distinct codes, 0 r, 1 slope.
+ * Outputs over the DEFINED samples, each NULL or, with ns = nstats in the order of stats[]: mean_out, var_out (ddof 1; 0 with
+ * one defined sample), prob_out = share of defined samples with a value > 0 (ns,F,M), nan where no sample is defined;
+ * q_out (ns,nq,F,M): numpy's linear percentiles of the defined samples; defined_out (F,M) = defined samples / S;
+ * nmean_out (M) = mean_s n; values_out (ns,npairs,S): the raw statistics of the pairs[] = (f,j) rows, nan where undefined.
+ * of_means_out (5,F,M) or NULL: the plug-in table r, slope, intercept, stderr = sqrt((1 - r^2) Syy / Sxx / (n - 2)), n of the
+ * regression of gbar(:,j) = mean over the defined samples of y on Pbar(:,f) = mean_s W_s U_s' over the rows with a defined
+ * gbar (scipy.stats.linregress's numbers), with sdx_out (F) and sdy_out (M), the ddof-0 standard deviations of Pbar(:,f)
+ * over all rows and of gbar(:,j) over its defined rows.
+ * fp64, no floating-point atomics, every sum in a fixed order: two calls return identical bits, whatever scratch_bytes
+ * (the cap of the staging buffer, which holds whole samples; 0: the default of the functionals).  nsamples <= 8192
+ * (BTF_EINVAL beyond), ndepth >= 2.  btf_collect_association reads W and V from the first nsamples collected slots without
+ * an upload (Us alone is uploaded) and touches none of the sampler's state; its launches are counted under
+ * BTF_K_CRITERIA.  Synchronous.                                                                                          */
+int btf_posterior_association(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, int nfeatures,
+                              const double* Ws, const double* Vs, const double* Us, int transform, int which, const double* x,
+                              double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs,
+                              double* mean_out, double* var_out, double* q_out, double* prob_out, double* defined_out,
+                              double* nmean_out, double* values_out, double* of_means_out, double* sdx_out, double* sdy_out,
+                              long long scratch_bytes);
+int btf_collect_association(btf_ctx* ctx, int nsamples, int nfeatures, const double* Us, int transform, int which, const double* x,
+                            double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs,
+                            double* mean_out, double* var_out, double* q_out, double* prob_out, double* defined_out,
+                            double* nmean_out, double* values_out, double* of_means_out, double* sdx_out, double* sdy_out,
+                            long long scratch_bytes);
+
 /* ---- folding new rows into a fitted posterior (csrc/btf_fold_in.h) ---------------------------------------------------
  * Given V the rows of W are conditionally independent (factor.py:333) with prior N(0, sigma2 I), so a row that was not in
  * the fitted tensor has, under kept sample s, the conditional _resample_W draws from (factor.py:333-362):
