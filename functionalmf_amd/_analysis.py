@@ -1,5 +1,5 @@
 """The Python front end of the posterior analysis features: summary, diagnostics, criteria / PSIS-LOO, predictive,
-functionals, ranking, feature association and fold-in.
+functionals, ranking, feature association, monotone projection and fold-in.
 
 Two halves.  The argument checks every feature shares, as plain functions (importable without a GPU): the transform table,
 the percentile check, the (S,N,K) / (S,M,T,K) shape check and the per-sample scalar check - the stateless forms in utils.py
@@ -357,6 +357,33 @@ class PosteriorAnalysis:
         U = _assoc.check_features(U, S, self.nembeds)        # one embedding per kept sample
         return _assoc.evaluate(shape, self.nembeds, S, U, which=which, stats=stats, q=q, transform=transform, x=x, level=level,
                                pairs=pairs, of_means=of_means, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
+
+    # ---- monotone projection of the posterior: factor_pav of every kept sample (functionalmf_amd/monotone.py) ----
+    def posterior_monotone(self, results=None, q=(5, 95), transform=None, increasing=False, return_V=False, in_place=False):
+        """Project every kept sample to monotone curves on the GPU (csrc/btf_monotone.h): V'_s[j] = factor_pav(W_s, V_s[j])
+        for every sample and column in one launch, and the mean and percentiles of f(W_s V'_s) from the summary kernel on the
+        projected states where they lie.  What doseresponse/fit.py:365-374 does on the host, sample by sample.
+
+        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device (no upload).
+        q, transform: as posterior_summary; q=None: no summary.  increasing: no curve may decrease (-factor_pav(W, -V)).
+        return_V: also return the projected samples V (S,M,T,K); dict(W=res["W"], V=out["V"]) is a results= for every
+            other analysis call.
+        in_place: (results=None only; ValueError otherwise) overwrite the device-collected V samples with their
+            projection, without a second copy of them.  Every later analysis call on the collected samples -
+            posterior_summary, posterior_functionals, posterior_ranking, posterior_feature_association,
+            information_criteria, loo - then sees the projected posterior: the btf_mono route of select_btf.py.  THIS
+            CANNOT BE UNDONE: the unprojected samples on the device are gone (the host dict run_gibbs returned is not
+            touched, and the next collecting run_gibbs starts a fresh, unprojected set).
+
+        The returned dict: functionalmf_amd.utils.posterior_monotone.  The sampler's state is not touched: a chain continued
+        after the call walks the same path.  Works for every model class (it needs only W and V).  Unsharded models."""
+        from . import monotone as _mono
+        self._unsharded("posterior monotone")
+        _mono.check_args(q, transform, increasing, return_V, in_place, self.ndepth, self.nembeds, uploaded=results is not None)
+        S, Ws, Vs = self._samples(results)
+        return _mono.evaluate((self.nrows, self.ncols, self.ndepth), self.nembeds, S, q=q, transform=transform,
+                              increasing=increasing, return_V=return_V, in_place=in_place, ctx=self._ctx, Ws=Ws, Vs=Vs)
 
     # ---- folding new rows in (functionalmf_amd/fold_in.py, csrc/btf_fold_in.h) ----
     def fold_in_rows(self, Y_new, results=None, seed=None, z=None, summary=True, q=(5, 95), transform=None, inner_sweeps=None,

@@ -20,7 +20,7 @@ SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.h
            os.path.join(CSRC, "btf_predict.hip"), os.path.join(CSRC, "btf_functionals.hip"), os.path.join(CSRC, "btf_fold_in.hip"),
            os.path.join(CSRC, "btf_loo.hip"), os.path.join(CSRC, "btf_ranking.hip")]
 # compilation units added since: SOURCES keeps its eleven entries (build() addresses them by index); (source, object suffix)
-MORE_SOURCES = [(os.path.join(CSRC, "btf_assoc.hip"), "_assoc.o")]
+MORE_SOURCES = [(os.path.join(CSRC, "btf_assoc.hip"), "_assoc.o"), (os.path.join(CSRC, "btf_monotone.hip"), "_monotone.o")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -102,6 +102,8 @@ SIGNATURES = {
                                             C.c_int, _c_ip, C.c_int] + [_c_dp] * 10 + [C.c_longlong]),
     "btf_collect_association": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, C.c_int, _c_dp, C.c_double, _c_ip, C.c_int, _c_dp, C.c_int,
                                           _c_ip, C.c_int] + [_c_dp] * 10 + [C.c_longlong]),
+    "btf_posterior_monotone": (C.c_int, [C.c_int] * 6 + [_c_dp, _c_dp, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_ip, _c_dp, _c_dp]),
+    "btf_collect_monotone": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, C.c_int, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_ip, _c_dp, _c_dp]),
     "btf_fold_in_rows": (C.c_int, [C.c_int] * 7 + [_c_dp] * 7 + [C.c_uint64, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int,
                                    _c_dp, _c_dp]),
     "btf_collect_fold_in": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [_c_dp] * 4 + [C.c_uint64, C.c_int, C.c_int64, _c_dp, _c_dp,

@@ -19,6 +19,7 @@
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
 #include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
 #include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
+#include "btf_monotone.h"       // monotone projection of the posterior (kernel in btf_monotone.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
@@ -4475,6 +4476,82 @@ int btf_collect_association(btf_ctx* c, int nsamples, int nfeatures, const doubl
   const double* dU = s.upload(Us, (size_t)nsamples * nfeatures * c->K);
   return assoc_run(s, c->smp_W, c->smp_V, dU, nsamples, c->N, c->M, c->T, c->K, nfeatures, transform, which, x, level, stats, nstats, q, nq,
                    pairs, npairs, o, scratch_bytes);
+}
+
+// ---------------------------------------------------------------- monotone projection of the posterior (btf_monotone.h)
+namespace {
+
+// The projection of the device states dW (S,N,K), dVin (S,M,T,K) into dVout (dVin itself: in place), the summary of the
+// projected states where they lie, and the downloads.  Null outputs are skipped; mean_out null: no summary.
+int mono_run(Scratch& s, const double* dW, const double* dVin, double* dVout, int S, int N, int M, int T, int K, int increasing,
+             int transform, const double* q, int nq, double* V_out, int* pools_out, double* mean_out, double* q_out) {
+  MonoKernel project = mono_project_fn(K);
+  if (!project) return fail(s.ctx(), BTF_EINVAL, "posterior monotone: nembeds must be 1..10");
+  const size_t nW = (size_t)N * K, nV = (size_t)M * T * K, YMAX = 65535;   // (a grid's y extent)
+  int* dpools = s.alloc<int>((size_t)S * M);
+  MonoArgs a = {};
+  a.N = N; a.M = M; a.T = T; a.increasing = increasing ? 1 : 0;
+  for (size_t s0 = 0; s0 < (size_t)S; s0 += YMAX) {
+    const unsigned sc = (unsigned)std::min<size_t>(YMAX, (size_t)S - s0);
+    a.W = dW + s0 * nW; a.Vin = dVin + s0 * nV; a.Vout = dVout + s0 * nV; a.pools = dpools + s0 * M;
+    launch_counted(s, BTF_K_CRITERIA, project, dim3((unsigned)M, sc), dim3(MONO_THREADS), mono_lds(T, K), a);
+  }
+  if (mean_out) summary_stage(s, dW, dVout, S, N, M * T, K, transform, q, nq, mean_out, q_out);
+  s.download(V_out, (const double*)dVout, (size_t)S * nV);
+  s.download(pools_out, (const int*)dpools, (size_t)S * M);
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int mono_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, const double* q, int nq, const double* mean_out,
+               const double* q_out) {
+  if (S < 1 || N < 1 || M < 1 || T < 1 || K < 1 || K > MAX_K || nq < 0 || (nq > 0 && (!q || !q_out || !mean_out)) ||
+      (mean_out && (transform < 0 || transform > 2)))
+    return fail(c, BTF_EINVAL, "bad posterior monotone arguments");
+  if (mean_out && S > 16384) return fail(c, BTF_EINVAL, "posterior monotone: at most 16384 samples with a summary (its values are sorted in LDS)");
+  if (!mono_fits(T, K))
+    return fail(c, BTF_EINVAL, "posterior monotone: ndepth * nembeds too large for the PAV kernels (pav_fits: 8 T K + 4 T <= 65536 bytes of LDS)");
+  if ((long long)M * T > 0x7fffffffLL) return fail(c, BTF_EINVAL, "posterior monotone: too many cells for one launch");
+  for (int k = 0; k < nq; ++k)
+    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
+  return BTF_OK;
+}
+
+}  // namespace
+
+int btf_posterior_monotone(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                           int increasing, int transform, const double* q, int nq, double* V_out, int* pools_out, double* mean_out,
+                           double* q_out) {
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior monotone arguments");
+  int rc = mono_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, q, nq, mean_out, q_out);
+  if (rc) return rc;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);       // the scratch's own copy: projected where it lies
+  return mono_run(s, dW, dV, dV, nsamples, nrows, ncols, ndepth, nembeds, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
+}
+
+// the same on the first nsamples collected states, read where they lie (Ws = Vs = NULL), or on uploaded states on the
+// context's device and stream; in_place overwrites the collected V samples and needs no second copy of them
+int btf_collect_monotone(btf_ctx* c, int nsamples, const double* Ws, const double* Vs, int increasing, int in_place, int transform,
+                         const double* q, int nq, double* V_out, int* pools_out, double* mean_out, double* q_out) {
+  if (!c || (Ws == nullptr) != (Vs == nullptr)) return fail(c, BTF_EINVAL, "bad posterior monotone arguments");
+  int rc = mono_check(c, nsamples, c->N, c->M, c->T, c->K, transform, q, nq, mean_out, q_out);
+  if (rc) return rc;
+  if (in_place && Ws) return fail(c, BTF_EINVAL, "btf_collect_monotone: in_place projects the collected samples, not uploaded states");
+  if (!Ws && (!c->smp_W || !c->smp_V || nsamples > c->smp_n)) return fail(c, BTF_EINVAL, "btf_collect_monotone: not that many collected samples");
+  HIPCHK(c, hipSetDevice(c->dev));
+  Scratch s(c, c->stream);
+  const size_t nV = (size_t)nsamples * c->M * c->T * c->K;
+  if (Ws) {
+    const double* dW = s.upload(Ws, (size_t)nsamples * c->N * c->K);
+    double* dV = s.upload(Vs, nV);
+    return mono_run(s, dW, dV, dV, nsamples, c->N, c->M, c->T, c->K, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
+  }
+  double* dVout = in_place ? c->smp_V : s.alloc<double>(nV);
+  return mono_run(s, c->smp_W, c->smp_V, dVout, nsamples, c->N, c->M, c->T, c->K, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
 }
 
 // ---------------------------------------------------------------- folding new rows in (btf_fold_in.h)

@@ -214,6 +214,29 @@ def posterior_feature_association(Ws, Vs, Us, which="auc", stats=("r",), q=(5, 9
                                 of_means=of_means, Ws=Ws, Vs=Vs, device=device, _scratch_bytes=_scratch_bytes)
 
 
+def posterior_monotone(Ws, Vs, q=(5, 95), transform=None, increasing=False, return_V=True, device=0):
+    """Project posterior samples to monotone curves on the GPU, without a model: the stateless form of
+    BayesianTensorFiltering.posterior_monotone.  What doseresponse/fit.py:365-374 does on the host, sample by sample.
+
+    Ws (S,N,K), Vs (S,M,T,K).  For sample s and column j, V'_s[j] = factor_pav(Ws[s], Vs[s, j]), bit for bit: the
+    left-to-right pool-adjacent-violators sweep after which no row's curve w_i . v'_jt increases with depth
+    (increasing=True: -factor_pav(Ws[s], -Vs[s, j]), no curve decreases).  All S x M blocks are projected in one launch;
+    Ws is not changed.  functionalmf_amd.monotone.project_host is the definition in numpy.
+
+    Returns a dict: mean (N,M,T) and quantiles (len(q),N,M,T) of f(W_s V'_s) over the samples - posterior_summary's
+    numbers on the projected states, which never leave the device for it (q=None: neither); pools (S,M) int32 = T minus
+    the merges made for that sample and column (T: it was monotone already); changed (M,) = the share of samples in
+    which the column needed a merge; V (S,M,T,K), the projected samples, with return_V - dict(W=Ws, V=out["V"]) goes
+    into every other posterior_* call; nsamples.
+    At most 16384 samples with a summary; 8 T K + 4 T <= 65536 (a column block in LDS, as factor_pav).  There is no CPU
+    fallback."""
+    from . import _analysis, monotone
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    return monotone.evaluate((N,) + Vs.shape[1:3], K, S, q=q, transform=transform, increasing=increasing, return_V=return_V,
+                             Ws=Ws, Vs=Vs, device=device)
+
+
 def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summary=True, q=(5, 95), transform=None,
                  inner_sweeps=None, trials=None, first_sample=0, device=0):
     """Embeddings of rows the chain never saw, one draw per kept sample, on the GPU, without a model: the stateless form of

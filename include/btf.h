@@ -674,6 +674,26 @@ int btf_collect_association(btf_ctx* ctx, int nsamples, int nfeatures, const dou
                             double* nmean_out, double* values_out, double* of_means_out, double* sdx_out, double* sdy_out,
                             long long scratch_bytes);
 
+/* ---- monotone projection of the posterior (csrc/btf_monotone.h) ---------------------------------------------------------
+ * What doseresponse/fit.py:365-374 does on the host before it reports anything: for kept sample s and column j,
+ * V'_s[j] = factor_pav(W_s, V_s[j]) (btf_nmf_pav; functionalmf/utils.py:218-252) - the left-to-right pool-adjacent-
+ * violators sweep under which no row's curve w_i . v'_jt increases with t - for all S x M blocks in one launch, equal to
+ * btf_nmf_pav per sample bit for bit.  increasing != 0: -factor_pav(W_s, -V_s[j]) (no curve decreases).  W is not changed.
+ * Outputs, each NULL (skipped) or: V_out (S,M,T,K) the projected samples; pools_out (S,M) = T minus the merges this call
+ * made in that block (T: it was monotone already); mean_out (N,M,T) and q_out (nq,N,M,T): btf_posterior_summary of the
+ * projected states, run where they lie (mean_out NULL: no summary, and nq must be 0; nsamples <= 16384 with one).
+ * Limits: 8 T K + 4 T <= 65536 (the column in LDS: the bound of btf_nmf_pav), nembeds 1..10; BTF_EINVAL beyond.
+ * btf_collect_monotone: Ws = Vs = NULL reads the first nsamples collected states where they lie (BTF_EINVAL beyond the
+ * collected count) and projects into scratch - or, with in_place != 0, overwrites the collected V samples, so that every
+ * later btf_collect_* / btf_crit_* call on them sees the projected posterior; that cannot be undone short of collecting
+ * again.  Ws, Vs given: those states are uploaded instead (in_place is then BTF_EINVAL).  The sampler's state is not
+ * touched.  fp64, no atomics: two calls return identical bits.  Launches are counted under BTF_K_CRITERIA.  Synchronous. */
+int btf_posterior_monotone(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws,
+                           const double* Vs, int increasing, int transform, const double* q, int nq, double* V_out,
+                           int* pools_out, double* mean_out, double* q_out);
+int btf_collect_monotone(btf_ctx* ctx, int nsamples, const double* Ws, const double* Vs, int increasing, int in_place,
+                         int transform, const double* q, int nq, double* V_out, int* pools_out, double* mean_out, double* q_out);
+
 /* ---- folding new rows into a fitted posterior (csrc/btf_fold_in.h) ---------------------------------------------------
  * Given V the rows of W are conditionally independent (factor.py:333) with prior N(0, sigma2 I), so a row that was not in
  * the fitted tensor has, under kept sample s, the conditional _resample_W draws from (factor.py:333-362):
