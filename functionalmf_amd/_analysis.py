@@ -74,6 +74,23 @@ def check_scalars(name, v, S, positive=True):
     return a
 
 
+def check_r_eff(r_eff, shape):
+    """The r_eff of loo(): None, or a scalar / (N,M) array, finite and > 0, as a contiguous (N,M) float64 array."""
+    if r_eff is None:
+        return None
+    r_eff = np.asarray(r_eff, dtype=float)
+    if r_eff.shape not in ((), tuple(shape)):
+        raise ValueError("r_eff must be a scalar or a (%d,%d) array" % tuple(shape))
+    if not (np.all(np.isfinite(r_eff)) and np.all(r_eff > 0)):
+        raise ValueError("r_eff must be finite and > 0")
+    return _native.as_f64(np.broadcast_to(r_eff, tuple(shape)))
+
+
+def check_loo_samples(S, what="loo"):
+    if S > _criteria.LOO_MAX_SAMPLES:
+        raise ValueError("%s: %d samples, at most %d" % (what, S, _criteria.LOO_MAX_SAMPLES))
+
+
 def summary(call, shape, q, transform):
     """(mean (N,M,T), quantiles (len(q),N,M,T)) of f(W V') from a summary entry point: call(code, q, nq, mean, quantiles)
     runs it with whatever precedes those five arguments (btf_collect_summary, btf_posterior_summary)."""
@@ -148,10 +165,15 @@ class PosteriorAnalysis:
         bound = getattr(self, "_data_ref", None)
         bound = bound if isinstance(bound, (tuple, list)) else (bound,)
         slot = 0 if len(bound) == len(arrays) and all(a is b for a, b in zip(arrays, bound)) else 1
-        S1, cnt, c0, c1, obs = _criteria.statistics(family, data, (self.nrows, self.ncols, self.ndepth), param)
-        self._ctx.call("btf_crit_set_data", slot, _native.dptr(S1), _native.dptr(cnt), _native.dptr(c0), _native.dptr(c1))
+        obs = self._crit_upload(slot, family, data, param)
         self._crit_keys[slot], self._crit_obs[slot], self._crit_refs[slot] = key, obs, data     # (refs: ids stay unique)
         return slot, obs
+
+    def _crit_upload(self, slot, family, data, param):
+        """The statistics of `data` into the slot; returns the observed-curve mask."""
+        S1, cnt, c0, c1, obs = _criteria.statistics(family, data, (self.nrows, self.ncols, self.ndepth), param)
+        self._ctx.call("btf_crit_set_data", slot, _native.dptr(S1), _native.dptr(cnt), _native.dptr(c0), _native.dptr(c1))
+        return obs
 
     def _crit_check(self):
         """Refusals before any work: sharded contexts, likelihoods without a device form."""
@@ -205,6 +227,7 @@ class PosteriorAnalysis:
         n_curves, nsamples, loglik_per_sample (S,) and curves = {lppd, p_waic, mean_ll, ll_at_mean} of (N,M) arrays;
         pointwise=True adds loglik (S,N,M), the full matrix (S*N*M doubles of host memory; PSIS-LOO from it stays on the
         device: loo()).
+        A gamma_grid model is refused here (NotImplementedError): gamma_grid_criteria / gamma_grid_loo score it.
         Device memory: the criteria statistics, 16 B per cell (functionalmf_amd/criteria.py), and 8 B per cell of scratch."""
         self._crit_check()
         S, Ws, Vs = self._samples(results)
@@ -235,17 +258,10 @@ class PosteriorAnalysis:
         self._crit_check()
         code = transform_code(transform)
         shape = (self.nrows, self.ncols, self.ndepth)
-        if r_eff is not None:
-            r_eff = np.asarray(r_eff, dtype=float)
-            if r_eff.shape not in ((), shape[:2]):
-                raise ValueError("r_eff must be a scalar or a (%d,%d) array" % shape[:2])
-            if not (np.all(np.isfinite(r_eff)) and np.all(r_eff > 0)):
-                raise ValueError("r_eff must be finite and > 0")
-            r_eff = _native.as_f64(np.broadcast_to(r_eff, shape[:2]))
+        r_eff = check_r_eff(r_eff, shape[:2])
         S, Ws, Vs = self._samples(results)
         noise = self._crit_noise(results, S)
-        if S > _criteria.LOO_MAX_SAMPLES:
-            raise ValueError("loo: %d samples, at most %d" % (S, _criteria.LOO_MAX_SAMPLES))
+        check_loo_samples(S)
         head, obs = self._crit_head(data, S, Ws, Vs, noise)
         return _criteria.loo_evaluate(self._ctx, head, shape, obs, r_eff=r_eff, transform=code, mean=mean, log_weights=log_weights)
 

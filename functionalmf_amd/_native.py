@@ -20,7 +20,8 @@ SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.h
            os.path.join(CSRC, "btf_predict.hip"), os.path.join(CSRC, "btf_functionals.hip"), os.path.join(CSRC, "btf_fold_in.hip"),
            os.path.join(CSRC, "btf_loo.hip"), os.path.join(CSRC, "btf_ranking.hip")]
 # compilation units added since: SOURCES keeps its eleven entries (build() addresses them by index); (source, object suffix)
-MORE_SOURCES = [(os.path.join(CSRC, "btf_assoc.hip"), "_assoc.o"), (os.path.join(CSRC, "btf_monotone.hip"), "_monotone.o")]
+MORE_SOURCES = [(os.path.join(CSRC, "btf_assoc.hip"), "_assoc.o"), (os.path.join(CSRC, "btf_monotone.hip"), "_monotone.o"),
+                (os.path.join(CSRC, "btf_gg_criteria.hip"), "_gg_criteria.o")]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -33,6 +34,7 @@ PEER_DESC_BYTES = 256             # BTF_PEER_DESC_BYTES
 OPT_SAMPLER, OPT_NB_HISTOGRAMS, OPT_FUSE_GRAM, OPT_PG_EXACT, OPT_CURVE_COUNTS, OPT_SPLIT_ACCUM, OPT_FUSED_SWEEP, OPT_FUSED_STEP, OPT_FUSED_DATAFLOW = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ESS_HOST_LIKELIHOOD = -1          # BTF_ESS_HOST_LIKELIHOOD of include/btf.h
 CRIT_NOISE_PER_SAMPLE, CRIT_CURRENT = 1, 2   # BTF_CRIT_* flags of btf_crit_eval
+CRIT_FAMILY_GAMMA_GRID = 5        # family 5 of btf_crit_eval / btf_crit_loo (= link 5 of btf_ess_*)
 PRED_AUX_PER_SAMPLE, PRED_AUX_ROWS, PRED_AUX_COLS, PRED_AUX_DEPTH = 1, 2, 4, 8   # BTF_PRED_AUX_* flags of btf_predict_eval
 SAMPLERS = {"banded": 0, "spectral": 1, "chain": 2, "generic": 3, "banded_nopanel": 4}
 
@@ -116,6 +118,7 @@ SIGNATURES = {
     "btf_collect_end": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
     "btf_collect_summary": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),
     "btf_crit_set_data": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "btf_crit_set_logsum": (C.c_int, [_ctx, C.c_int, _c_dp]),
     "btf_crit_eval": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
     "btf_crit_loo": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp,
                                _c_dp]),

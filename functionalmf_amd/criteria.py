@@ -17,11 +17,16 @@ csrc/btf_criteria.h (btf_crit_eval).  This module holds the two host halves arou
                 (S,N,M) log-likelihood matrix; loo_combine() builds the dictionary of BayesianTensorFiltering.loo()
                 and compare() the paired elpd difference of two models scored on the same data.
 
+  gamma_grid_statistics() / gamma_grid_loglik()  the same two halves for the gamma-grid likelihood (family 5,
+                csrc/btf_gg_criteria.h): its three per-cell statistics, and the written definition of what the kernel
+                computes - the host class, one sample at a time.
+
 It deliberately does not read the sampler's accumulation layouts: those differ by model and data form.
 """
 import numpy as np
 
 FAMILY_POISSON_LOG, FAMILY_POISSON_IDENTITY, FAMILY_LOGIT, FAMILY_GAUSSIAN, FAMILY_NEGBIN = 0, 1, 2, 3, 4
+FAMILY_GAMMA_GRID = 5     # CRIT_FAM_GAMMA_GRID of csrc/btf_gg_criteria.h: statistics from gamma_grid_statistics, not statistics
 CURVE_OUTPUTS = 5         # CRIT_OUT of csrc/btf_criteria.h: sumexp, max, mean, M2, ll at the plug-in
 GRID_KEYS = ("lam2", "min_lam2", "max_lam2", "num_lam2")
 
@@ -141,6 +146,77 @@ def from_loglik(L, observed, L_at_mean):
             "waic_se": 2.0 * np.sqrt(obs.sum() * np.var(elpd_i)), "dic": 2 * mean_dev - dev_mean, "p_dic": mean_dev - dev_mean,
             "mean_deviance": mean_dev, "deviance_at_mean": dev_mean, "n_curves": int(obs.sum()), "nsamples": S,
             "loglik_per_sample": tot, "curves": {"lppd": lppd, "p_waic": p_waic}}
+
+
+# ---- the gamma-grid likelihood (loglikelihood="gamma_grid"; csrc/btf_gg_criteria.h).  Conventions:
+#   cell values     exactly gg_term's (csrc/btf_gamma_grid.h) = likelihoods.GammaGridLikelihood.logpdf: an unobserved cell
+#                   inside an observed curve contributes lsp = log sum_g p_g, an observed cell with w.v <= 0 gives -inf, so
+#                   L[s] equals model.logprob(Y, reduce="curve", W=Ws[s], V=Vs[s]);
+#   unobserved curves  count 0 and are left out of n_curves, as for every other family;
+#   the reference's DIC (doseresponse/select_btf.py:9-23: a nansum of logpdf over EVERY cell) therefore equals ours minus
+#                   2 lsp T (number of unobserved curves): each such curve adds T lsp to every log-likelihood there, so
+#                   -2 T lsp to 2 mean_D - D_mean.  lsp is 0 for the normalised weights estimate_likelihood always produces:
+#                   the two agree on real tables (tests/golden/g18_gamma_grid_dic.npz checks both kinds). ----
+def gamma_grid_statistics(Y, shape):
+    """The three per-cell statistics of the gamma-grid criteria kernel.  Y: (N,M,T) or (N,M,T,R) with NaN = missing.
+    Returns (S1, cnt, L) - sum_r y, the observed replicates, sum_r log y - as contiguous [M][T][N] float64 arrays, and the
+    bool (N,M) mask of curves with at least one observation.  ValueError if an observed y <= 0."""
+    S1, cnt, y4, obs4 = _cells(Y, shape)
+    if isinstance(y4, tuple):
+        raise ValueError("the gamma_grid likelihood takes one tensor, not a (Y, N) pair")
+    if np.any(obs4 & (y4 <= 0)):
+        raise ValueError("the gamma_grid likelihood needs every observed y > 0")
+    L = np.where(obs4, np.log(np.where(obs4, y4, 1.0)), 0.0).sum(axis=3)
+    layout = lambda a: np.ascontiguousarray(a.transpose(1, 2, 0), dtype=np.float64)      # (N,M,T) -> [M][T][N]
+    return layout(S1), layout(cnt), layout(L), obs4.any(axis=(2, 3))
+
+
+def gamma_grid_loglik(Y, Ws, Vs, likelihood):
+    """The written definition of the gamma-grid criteria kernel, by the host class one sample at a time.
+
+    Y: (N,M,T) / (N,M,T,R), NaN = missing; Ws (S,N,K), Vs (S,M,T,K); likelihood: anything likelihoods.gamma_grid_table
+    accepts.  Returns (L (S,N,M), L_at_mean (N,M), observed (N,M)): L[s,i,j] = sum_t logpdf(Y[i,j,t,:], w_i^s . v_jt^s),
+    L_at_mean the same at Mu-bar = mean_s W_s V_s' (what select_btf.py plugs in); both 0 on curves without observations.
+    from_loglik(L, observed, L_at_mean) gives the criteria dictionary."""
+    from . import likelihoods
+    lik = likelihoods.GammaGridLikelihood.from_table(*likelihoods.gamma_grid_table(likelihood))
+    Y = np.asarray(Y, dtype=float)
+    if Y.ndim not in (3, 4):
+        raise AssertionError('Observations must be 3- or 4-tensor.')
+    Y4 = Y[..., None] if Y.ndim == 3 else Y
+    Ws, Vs = np.asarray(Ws, dtype=float), np.asarray(Vs, dtype=float)
+    if Ws.ndim != 3 or Vs.ndim != 4 or Ws.shape[::2] != Vs.shape[::3] or Y4.shape[:3] != (Ws.shape[1],) + Vs.shape[1:3]:
+        raise ValueError("Ws must be (S,N,K), Vs (S,M,T,K) and Y (N,M,T[,R]), got %r / %r / %r" % (Ws.shape, Vs.shape, Y.shape))
+    observed = np.any(~np.isnan(Y4), axis=(2, 3))
+    S = Ws.shape[0]
+    L = np.zeros((S,) + observed.shape)
+    mu = np.zeros(Y4.shape[:3])
+    for s in range(S):
+        eta = np.einsum("nk,mtk->nmt", Ws[s], Vs[s])
+        mu += eta
+        L[s] = np.where(observed, lik.logpdf(Y4, eta[..., None]).sum(axis=-1), 0.0)
+    L_at_mean = np.where(observed, lik.logpdf(Y4, (mu / S)[..., None]).sum(axis=-1), 0.0)
+    return L, L_at_mean, observed
+
+
+def gamma_grid_upload(ctx, slot, Y, shape):
+    """The gamma-grid statistics of Y into criteria slot `slot` of `ctx` (a _native.Context whose table is set:
+    btf_set_likelihood_table); returns the observed-curve mask."""
+    from . import _native
+    S1, cnt, L, obs = gamma_grid_statistics(Y, shape)
+    zero = np.zeros(tuple(shape)[:2])
+    ctx.call("btf_crit_set_data", int(slot), _native.dptr(S1), _native.dptr(cnt), _native.dptr(zero), _native.dptr(zero))
+    ctx.call("btf_crit_set_logsum", int(slot), _native.dptr(L))
+    return obs
+
+
+def gamma_grid_head(slot, nsamples, Ws=None, Vs=None):
+    """The arguments btf_crit_eval and btf_crit_loo share (evaluate / loo_evaluate's `head`) for the gamma-grid family.
+    Ws = Vs = None: the device-collected samples."""
+    from . import _native
+    Ws = None if Ws is None else _native.as_f64(Ws)
+    Vs = None if Vs is None else _native.as_f64(Vs)
+    return (int(slot), FAMILY_GAMMA_GRID, 0.0, int(nsamples), _native.dptr(Ws), _native.dptr(Vs), None, 0)
 
 
 # ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-curve-out (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson,

@@ -14,6 +14,7 @@
 #include "btf_fused.h"
 #include "btf_diag.h"         // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
+#include "btf_gg_criteria.h"    // the same for the gamma-grid likelihood (kernels in btf_gg_criteria.hip)
 #include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
@@ -152,6 +153,7 @@ struct btf_ctx {
   // model-selection criteria (btf_crit_*): the compact statistics of slot 0 (bound data) / 1 (held-out data)
   double* crit_S1[2] = {nullptr, nullptr}; double* crit_cnt[2] = {nullptr, nullptr};
   double* crit_c0[2] = {nullptr, nullptr}; double* crit_c1[2] = {nullptr, nullptr};
+  double* crit_L[2] = {nullptr, nullptr};        // family 5: sum_r log y per cell (btf_crit_set_logsum)
   int col_every = 0, col_slot = 0, col_count = 0;       // btf_collect_schedule: btf_gibbs_sweeps keeps every col_every-th state
   double* hyp = nullptr;        // device-resident scalars [HYP_COUNT] (nu2, sigma2, lam2, lam2_a, ...)
   bool dev_scalars = false;     // kernels read nu2 / sigma2 / lam2 from hyp instead of the host copies
@@ -1102,7 +1104,7 @@ void btf_destroy(btf_ctx* c) {
   for (void* p : {(void*)c->nb_data, (void*)c->nb_S, (void*)c->nb_cnt, (void*)c->nb_R, (void*)c->nb_C, (void*)c->nb_tmp, (void*)c->nb_out, (void*)c->nb_H, (void*)c->nb_Hd, (void*)c->nb_Hs, (void*)c->nb_G, (void*)c->nb_L, (void*)c->nb_optr, (void*)c->nb_oval, (void*)c->fill_tab, (void*)c->C8_wT, (void*)c->C8_v, (void*)c->smp_W, (void*)c->smp_V, (void*)c->smp_T, (void*)c->smp_s})
     if (p) (void)hipFree(p);
   for (int sl = 0; sl < 2; ++sl)
-    for (void* p : {(void*)c->crit_S1[sl], (void*)c->crit_cnt[sl], (void*)c->crit_c0[sl], (void*)c->crit_c1[sl]})
+    for (void* p : {(void*)c->crit_S1[sl], (void*)c->crit_cnt[sl], (void*)c->crit_c0[sl], (void*)c->crit_c1[sl], (void*)c->crit_L[sl]})
       if (p) (void)hipFree(p);
   if (c->hyp) (void)hipFree(c->hyp);
   if (c->fz_words) (void)hipFree(c->fz_words);
@@ -3605,6 +3607,7 @@ int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt,
   HIPCHK(c, hipSetDevice(c->dev));
   HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistics)
   double** bufs[4] = {&c->crit_S1[slot], &c->crit_cnt[slot], &c->crit_c0[slot], &c->crit_c1[slot]};
+  if (c->crit_L[slot]) { (void)hipFree(c->crit_L[slot]); c->crit_L[slot] = nullptr; }      // (the old data's log sums)
   if (!S1 && !cnt && !curve_c0 && !curve_c1) {       // free the slot
     for (double** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
     return BTF_OK;
@@ -3622,7 +3625,28 @@ int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt,
   return BTF_OK;
 }
 
+int btf_crit_set_logsum(btf_ctx* c, int slot, const double* L) {
+  if (!c || slot < 0 || slot > 1) return fail(c, BTF_EINVAL, "criteria slot must be 0 or 1");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistic)
+  if (!L) {
+    if (c->crit_L[slot]) (void)hipFree(c->crit_L[slot]);
+    c->crit_L[slot] = nullptr;
+    return BTF_OK;
+  }
+  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, "btf_crit_set_logsum: no statistics in this slot (btf_crit_set_data first)");
+  const size_t cells = (size_t)c->M * c->T * c->N;
+  int rc;
+  if ((rc = dev_alloc(c, &c->crit_L[slot], cells))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->crit_L[slot], L, cells * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BTF_OK;
+}
+
 namespace {
+// families 0..4 of FAM_SWITCH, or the gamma-grid family of btf_gg_criteria.h
+bool crit_family_ok(int family) { return (family >= 0 && family < CRIT_FAM_COUNT) || family == CRIT_FAM_GAMMA_GRID; }
+
 // the device side of a criteria call: its scratch (the uploaded states, crit_kernel's outputs) and the kernels' arguments
 struct CritRun {
   Scratch s;
@@ -3645,6 +3669,9 @@ int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double pa
   if (per_sample && !noise && (Ws || current)) return fail(c, BTF_EINVAL, "per-sample noise of uploaded / current states: pass `noise`");
   if (!per_sample && (family == CRIT_FAM_GAUSSIAN || family == CRIT_FAM_NEGBIN) && !(param > 0.0))
     return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
+  const bool gamma_grid = family == CRIT_FAM_GAMMA_GRID;
+  if (gamma_grid && (!c->gg_tab || !c->crit_L[slot]))
+    return fail(c, BTF_ESTATE, who + ": the gamma-grid family needs its table (btf_set_likelihood_table) and the slot's L (btf_crit_set_logsum)");
   HIPCHK(c, hipSetDevice(c->dev));
   const int S = nsamples, N = c->N, M = c->M, T = c->T, K = c->K;
   const dim3 grid((N + WAVE - 1) / WAVE, M);
@@ -3659,9 +3686,12 @@ int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double pa
   a.mu = s.alloc<double>((size_t)M * T * N); a.curve = s.alloc<double>(CRIT_OUT * NM);
   a.tot_part = s.alloc<double>((size_t)S * nwg); r.tot = s.alloc<double>((size_t)S);
   if (pointwise) a.pw = s.alloc<double>((size_t)S * NM);
-  K_SWITCH(K, FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_kernel<KT, FT>, grid, dim3(CRIT_WAVES * WAVE), 0, a)));
+  const GgTab gt{c->crit_L[slot], c->gg_tab, c->gg_G, c->gg_lsp};
+  if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_fn(K), grid, dim3(GGC_WAVES * WAVE), 0, a, gt);
+  else K_SWITCH(K, FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_kernel<KT, FT>, grid, dim3(CRIT_WAVES * WAVE), 0, a)));
   if (reduce) {
-    FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_plugin_kernel<FT>, grid, dim3(WAVE), 0, a));
+    if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_plugin_fn(), grid, dim3(WAVE), 0, a, gt);
+    else FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_plugin_kernel<FT>, grid, dim3(WAVE), 0, a));
     launch_counted(s, BTF_K_CRITERIA, crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.tot_part, S, nwg, r.tot);
   }
   return s.rc();
@@ -3670,7 +3700,7 @@ int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double pa
 
 int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
                   const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out) {
-  if (!c || slot < 0 || slot > 1 || family < 0 || family >= CRIT_FAM_COUNT || nsamples < 1 || !curve_out || !total_out ||
+  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !curve_out || !total_out ||
       (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
     return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
   CritRun r(c);
@@ -3687,7 +3717,7 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
 int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
                  const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
                  double* logw_out) {
-  if (!c || slot < 0 || slot > 1 || family < 0 || family >= CRIT_FAM_COUNT || nsamples < 1 || !loo_out ||
+  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !loo_out ||
       (flags & ~BTF_CRIT_NOISE_PER_SAMPLE) || (!Ws) != (!Vs) || transform < 0 || transform > 2)
     return fail(c, BTF_EINVAL, "bad btf_crit_loo arguments");
   if (nsamples > LOO_MAX_S)

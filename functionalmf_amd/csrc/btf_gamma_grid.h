@@ -49,7 +49,8 @@ GgLLKernel gg_ll_cols_fn(int K);
 GgEvalKernel gg_eval_fn(bool rows, bool ep);
 GgLogsumKernel gg_logsum_fn();
 
-#ifdef BTF_GAMMA_GRID_UNIT
+// the cell term, shared by this unit's kernels and the criteria kernels of btf_gg_criteria.h (BTF_GG_CRIT_UNIT)
+#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT)
 // table and exp / log tables into LDS (then a barrier, by the caller)
 __device__ __forceinline__ void gg_stage(const GgTab& t, GgComp* tab, double2* ltab, double2* etab) {
   for (int g = threadIdx.x; g < t.G; g += blockDim.x) tab[g] = t.tab[g];
@@ -76,7 +77,9 @@ __device__ __forceinline__ double gg_term(double s1, double L, double cnt, doubl
   if (!(m > -INFINITY)) return -INFINITY;
   return m + log_tab(s, ltab) - L;
 }
+#endif  // BTF_GAMMA_GRID_UNIT || BTF_GG_CRIT_UNIT
 
+#ifdef BTF_GAMMA_GRID_UNIT
 template <int K>
 __global__ __launch_bounds__(ESS_THREADS) void gg_ll_rows_kernel(GgLLArgs a, GgTab t) {
   __shared__ double red[ESS_THREADS / WAVE];

@@ -1379,6 +1379,82 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
             raise NotImplementedError("posterior predictive is not available for the gamma_grid likelihood")
         return self._crit_family()
 
+    # ---- WAIC, DIC and PSIS-LOO under the gamma_grid likelihood (csrc/btf_gg_criteria.h).  Under names of their own:
+    # information_criteria / loo / posterior_predictive keep refusing a gamma_grid model. ----
+    def _gg_check(self, what, instead):
+        self._unsharded(what)
+        if self._callback or self._link != 5:
+            raise ValueError("%s scores the gamma_grid likelihood, and this model's is %s: use %s" % (
+                what, "a Python function" if self._callback else repr(self.loglikelihood), instead))
+
+    def _crit_upload(self, slot, family, data, param):
+        if family != _criteria.FAMILY_GAMMA_GRID:
+            return super()._crit_upload(slot, family, data, param)
+        return _criteria.gamma_grid_upload(self._ctx, slot, data, (self.nrows, self.ncols, self.ndepth))
+
+    def _gg_head(self, data, nsamples, Ws, Vs):
+        slot, obs = self._crit_slot(data, _criteria.FAMILY_GAMMA_GRID, None)
+        return _criteria.gamma_grid_head(slot, nsamples, Ws, Vs), obs
+
+    def gamma_grid_criteria(self, results=None, data=None, pointwise=False):
+        """WAIC and DIC of the posterior samples under the gamma_grid likelihood, on the GPU: the dictionary of
+        information_criteria (see there for results, data, pointwise and every key), from the per-curve log-likelihood
+        of csrc/btf_gg_criteria.h.  What doseresponse/select_btf.py:9-23 computes on the host, one sample at a time.
+
+        A cell's value is the host class's (likelihoods.GammaGridLikelihood.logpdf): a cell without observations inside
+        an observed curve contributes log sum_g p_g, an observed cell with w.v <= 0 gives -inf (that curve's p_waic is
+        nan).  Curves without observations count 0 and are left out of n_curves; the reference's DIC counts T log sum_g p_g
+        for each of them in every log-likelihood, so it equals this `dic` minus 2 T log(sum_g p_g) (number of unobserved
+        curves) - the same number for the normalised weights its estimate_likelihood produces.
+        criteria.gamma_grid_loglik is the written definition.  ValueError on a model with another likelihood.
+        Device memory: 24 B per cell of statistics, and 8 B per cell of scratch for the call."""
+        self._gg_check("gamma_grid_criteria", "information_criteria")
+        S, Ws, Vs = self._samples(results)
+        head, obs = self._gg_head(data, S, Ws, Vs)
+        curve, totals, pw = _criteria.evaluate(self._ctx, head, (self.nrows, self.ncols), pointwise)
+        return _criteria.combine(curve, totals, obs, pw)
+
+    def gamma_grid_loo(self, results=None, data=None, r_eff=None, mean=False, transform=None, log_weights=False):
+        """PSIS-LOO under the gamma_grid likelihood, on the GPU: the dictionary of loo() (see there for every argument and
+        key), the pointwise matrix of gamma_grid_criteria handed to the PSIS kernels of csrc/btf_loo.h where it lies.
+        `lppd` is gamma_grid_criteria's, bit for bit.  ValueError on a model with another likelihood."""
+        from ._analysis import check_loo_samples, check_r_eff, transform_code
+        self._gg_check("gamma_grid_loo", "loo")
+        code = transform_code(transform)
+        shape = (self.nrows, self.ncols, self.ndepth)
+        r_eff = check_r_eff(r_eff, shape[:2])
+        S, Ws, Vs = self._samples(results)
+        check_loo_samples(S, "gamma_grid_loo")
+        head, obs = self._gg_head(data, S, Ws, Vs)
+        return _criteria.loo_evaluate(self._ctx, head, shape, obs, r_eff=r_eff, transform=code, mean=mean, log_weights=log_weights)
+
+    def run_gibbs(self, data, nburn=1000, nthin=1, nsamples=1000, verbose=True, print_freq=100, callback=None, **kwargs):
+        """genlasso.py:37-66, the result dict gathered as before.  A gamma_grid model with rng="device" also keeps every
+        kept state on the device (btf_collect: a device-to-device copy behind the sweep, nothing of the chain is touched),
+        so that gamma_grid_criteria() / gamma_grid_loo() read the samples where they lie."""
+        if self._callback or self._link != 5 or not self._dev_scalars or nsamples < 1:
+            return super().run_gibbs(data, nburn=nburn, nthin=nthin, nsamples=nsamples, verbose=verbose, print_freq=print_freq,
+                                     callback=callback, **kwargs)
+        self._ctx.call("btf_collect_begin", int(nsamples))
+        self._collected = 0
+
+        def keep(model, d, step, **kw):
+            if callback is not None:
+                callback(model, d, step, **kw)
+            kept, rem = divmod(step - nburn, nthin)
+            if step >= nburn and rem == 0:
+                self._push_state()                     # (anything the caller's callback touched)
+                self._ctx.call("btf_collect", kept)
+        out = super().run_gibbs(data, nburn=nburn, nthin=nthin, nsamples=nsamples, verbose=verbose, print_freq=print_freq,
+                                callback=keep, **kwargs)
+        self._collected = nsamples
+        return out
+
+    def _dic_score(self, results):
+        if not self._callback and self._link == 5:
+            return self.gamma_grid_criteria(results)["dic"]
+        return super()._dic_score(results)
+
     def _bind_data(self, data):
         if self._callback:           # the function's `data` is its own business (any object): nothing goes to the device
             return

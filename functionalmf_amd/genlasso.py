@@ -49,10 +49,16 @@ class _BayesianModel(object):
         else:
             hyperparams['lam2'] = np.atleast_1d(np.asarray(lam2, dtype=float))
 
+    def _dic_score(self, results):
+        """The score select_hyperparams_DIC gives a grid point's samples; a gamma_grid model scores through
+        gamma_grid_criteria (factor.py)."""
+        return self.information_criteria(results)["dic"]
+
     def select_hyperparams_DIC(self, data, verbose=True, **kwargs):
         """Grid search of the hyper-parameters by the deviance information criterion (genlasso.py:69-136, made to run):
         for every grid point the hyper-parameters are set, run_gibbs(data, verbose=False, **kwargs) continues the chain
-        from where the previous point left it, and the point is scored by information_criteria(results)["dic"]
+        from where the previous point left it, and the point is scored by _dic_score(results): information_criteria(results)["dic"],
+        for a gamma_grid model gamma_grid_criteria(results)["dic"]
         (DIC = 2 mean_s D(theta_s) - D(plug-in), D = -2 log-likelihood; see information_criteria).  The grid keywords
         (lam2, min_lam2, max_lam2, num_lam2) are taken off before run_gibbs.  The best point's values are left set.
         Returns {'scores', 'options', 'best', 'fit'}: the DIC per grid point, the grid, the best values and the best
@@ -75,7 +81,7 @@ class _BayesianModel(object):
                 print(' '.join('{}={}'.format(k, v) for k, v in cur.items()))
             self._set_hyperparameters(cur)
             results = self.run_gibbs(data, verbose=False, **rest)
-            dic_scores[score_idx] = self.information_criteria(results)["dic"]
+            dic_scores[score_idx] = self._dic_score(results)
             if best_idx is None or dic_scores[score_idx] < dic_scores[best_idx]:
                 best_results, best_idx = results, score_idx
         best_options = {param_names[p]: param_options[p][v] for p, v in enumerate(all_indices[best_idx])}

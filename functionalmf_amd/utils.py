@@ -129,6 +129,57 @@ def posterior_predictive(Ws, Vs, family, data=None, q=(2.5, 97.5), draws_per_sam
         ctx.close()
 
 
+def _gamma_grid_context(Ws, Vs, Y, likelihood, device):
+    """A context for one model-free gamma-grid criteria call: the table set, the statistics of Y in slot 0.  Returns
+    (ctx, head of btf_crit_eval / btf_crit_loo, (N,M,T), observed-curve mask); the caller closes ctx."""
+    from . import _analysis, _native, criteria, likelihoods
+    table = likelihoods.gamma_grid_table(likelihood)               # (a bad table raises before any device call)
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    ctx = _native.Context(N, shape[1], shape[2], K, 0, device=device)
+    try:
+        ctx.call("btf_set_likelihood_table", criteria.FAMILY_GAMMA_GRID, *(_native.dptr(v) for v in table), int(table[0].size))
+        obs = criteria.gamma_grid_upload(ctx, 0, Y, shape)
+    except Exception:
+        ctx.close()
+        raise
+    return ctx, criteria.gamma_grid_head(0, S, Ws, Vs), shape, obs
+
+
+def gamma_grid_criteria(Ws, Vs, Y, likelihood, pointwise=False, device=0):
+    """WAIC and DIC of saved samples under the gamma-grid likelihood on the GPU, without a model: the stateless form of
+    NonconjugateBayesianTensorFiltering.gamma_grid_criteria (see there), the shape doseresponse/select_btf.py has.
+
+    Ws (S,N,K), Vs (S,M,T,K); Y (N,M,T) or (N,M,T,R), NaN = missing, every observed y > 0; likelihood: the reference's
+    (mean_grid, mean_probs, variance) or an object with shape_grid / scale_grid / probs_grid (likelihoods.gamma_grid_table).
+    Needs ndepth >= 2 (a context is opened for the call).  No CPU fallback."""
+    from . import criteria
+    ctx, head, shape, obs = _gamma_grid_context(Ws, Vs, Y, likelihood, device)
+    try:
+        curve, totals, pw = criteria.evaluate(ctx, head, shape[:2], pointwise)
+    finally:
+        ctx.close()
+    return criteria.combine(curve, totals, obs, pw)
+
+
+def gamma_grid_loo(Ws, Vs, Y, likelihood, r_eff=None, mean=False, transform=None, log_weights=False, device=0):
+    """PSIS-LOO of saved samples under the gamma-grid likelihood on the GPU, without a model: the stateless form of
+    NonconjugateBayesianTensorFiltering.gamma_grid_loo (see there and BayesianTensorFiltering.loo); arguments as
+    gamma_grid_criteria.  S <= 4096."""
+    from . import _analysis, criteria
+    code = _analysis.transform_code(transform)
+    S, N = np.shape(Ws)[:2] if np.ndim(Ws) == 3 else (0, 0)
+    M = np.shape(Vs)[1] if np.ndim(Vs) == 4 else 0
+    r_eff = _analysis.check_r_eff(r_eff, (N, M))
+    _analysis.check_loo_samples(S, "gamma_grid_loo")
+    ctx, head, shape, obs = _gamma_grid_context(Ws, Vs, Y, likelihood, device)
+    try:
+        return criteria.loo_evaluate(ctx, head, shape, obs, r_eff=r_eff, transform=code, mean=mean, log_weights=log_weights)
+    finally:
+        ctx.close()
+
+
 def posterior_functionals(Ws, Vs, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None, curves=None,
                           pointwise=False, device=0):
     """Per-curve functionals of f(w_s[i] . v_s[j,:]) over depth, summarised over the kept samples, on the GPU, without a

@@ -768,9 +768,17 @@ int btf_collect_summary(btf_ctx* ctx, int nsamples, int transform, const double*
  *   and noise = NULL the collected nu2; otherwise every sample has variance `param`.
  *   curve_out [5][N][M]: per curve, over the samples in ascending order, the max-shifted sum of exp(ll_s), the max, the
  *   mean, Welford's M2, and ll at the plug-in (mean_s w.v per cell, mean variance); total_out (S,): sum_ij ll_s;
- *   pointwise_out (S,N,M) or NULL.  No floating-point atomics: two calls return identical bits.  Synchronises.       */
+ *   pointwise_out (S,N,M) or NULL.  No floating-point atomics: two calls return identical bits.  Synchronises.
+ * Family 5, the gamma grid (link 5 of btf_ess_*; csrc/btf_gg_criteria.h), in btf_crit_eval and btf_crit_loo alike: the
+ *   table is the context's (btf_set_likelihood_table) and the slot carries a third per-cell statistic,
+ *   btf_crit_set_logsum: L [M][T][N] = sum_r log y over the observed replicates, after btf_crit_set_data on that slot
+ *   (with zero curve_c0 / curve_c1), else BTF_ESTATE; NULL frees it; btf_crit_set_data on the slot, or freeing the slot,
+ *   drops it.  8 B per cell more on the device.  Without the table or L the calls return BTF_ESTATE and launch nothing;
+ *   `param` is ignored, BTF_CRIT_NOISE_PER_SAMPLE is BTF_EINVAL.  A cell without observations inside an observed curve
+ *   contributes log sum_g p_g, an observed cell with w.v <= 0 gives -inf, a curve without any observation counts 0.  */
 enum { BTF_CRIT_NOISE_PER_SAMPLE = 1, BTF_CRIT_CURRENT = 2 };
 int btf_crit_set_data(btf_ctx* ctx, int slot, const double* S1, const double* cnt, const double* curve_c0, const double* curve_c1);
+int btf_crit_set_logsum(btf_ctx* ctx, int slot, const double* L);
 int btf_crit_eval(btf_ctx* ctx, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
                   const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out);
 
