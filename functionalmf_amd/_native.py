@@ -15,13 +15,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("BTF_LIB_PATH") or os.path.join(HERE, "libbtf_hip.so")   # override: A/B builds
-SOURCES = [os.path.join(CSRC, "btf_abi.hip"), os.path.join(CSRC, "btf_criteria.hip"), os.path.join(CSRC, "btf_nmf.hip"),
-           os.path.join(CSRC, "btf_gass_ep.hip"), os.path.join(CSRC, "btf_gamma_grid.hip"), os.path.join(CSRC, "btf_diag.hip"),
-           os.path.join(CSRC, "btf_predict.hip"), os.path.join(CSRC, "btf_functionals.hip"), os.path.join(CSRC, "btf_fold_in.hip"),
-           os.path.join(CSRC, "btf_loo.hip"), os.path.join(CSRC, "btf_ranking.hip")]
-# compilation units added since: SOURCES keeps its eleven entries (build() addresses them by index); (source, object suffix)
-MORE_SOURCES = [(os.path.join(CSRC, "btf_assoc.hip"), "_assoc.o"), (os.path.join(CSRC, "btf_monotone.hip"), "_monotone.o"),
-                (os.path.join(CSRC, "btf_gg_criteria.hip"), "_gg_criteria.o")]
+# the compilation units beside the parts of btf_instances.hip: (source, object suffix)
+UNITS = [(os.path.join(CSRC, "btf_%s.hip" % name), suffix) for name, suffix in [
+    ("abi", "_abi.o"), ("analysis", "_analysis.o"), ("criteria", "_crit.o"), ("nmf", "_nmf.o"), ("gass_ep", "_gass_ep.o"),
+    ("gamma_grid", "_gamma_grid.o"), ("diag", "_diag.o"), ("predict", "_predict.o"), ("functionals", "_functionals.o"),
+    ("fold_in", "_fold_in.o"), ("loo", "_loo.o"), ("ranking", "_ranking.o"), ("assoc", "_assoc.o"), ("monotone", "_monotone.o"),
+    ("gg_criteria", "_gg_criteria.o")]]
+SOURCES = [src for src, _ in UNITS]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
 
@@ -213,9 +213,9 @@ OBJ_DIR = os.path.join(ROOT, "build", "obj")          # git- and gpurun-ignored
 
 
 def build(force=False, verbose=False, jobs=None):
-    """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU): the C-ABI unit and the
+    """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU): the units of UNITS and the
     parts of btf_instances.hip (the large kernel families, one compilation each) in parallel, then one link."""
-    deps = SOURCES + [src for src, _ in MORE_SOURCES] + [INST_SOURCE] + HEADERS
+    deps = SOURCES + [INST_SOURCE] + HEADERS
     if not force and os.path.exists(LIB_PATH) and \
             os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(p) for p in deps):
         return LIB_PATH
@@ -228,13 +228,7 @@ def build(force=False, verbose=False, jobs=None):
     base = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function",
             "-mllvm", "-amdgpu-kernarg-preload-count=16",
             "-I", os.path.join(ROOT, "include")] + os.environ.get("BTF_BUILD_DEFS", "").split()   # A/B builds: -DBTF_... tuning macros
-    units = [(SOURCES[0], os.path.join(OBJ_DIR, tag + "_abi.o"), []), (SOURCES[1], os.path.join(OBJ_DIR, tag + "_crit.o"), [])]
-    units += [(SOURCES[2], os.path.join(OBJ_DIR, tag + "_nmf.o"), []), (SOURCES[3], os.path.join(OBJ_DIR, tag + "_gass_ep.o"), [])]
-    units += [(SOURCES[4], os.path.join(OBJ_DIR, tag + "_gamma_grid.o"), []), (SOURCES[5], os.path.join(OBJ_DIR, tag + "_diag.o"), [])]
-    units += [(SOURCES[6], os.path.join(OBJ_DIR, tag + "_predict.o"), []), (SOURCES[7], os.path.join(OBJ_DIR, tag + "_functionals.o"), [])]
-    units += [(SOURCES[8], os.path.join(OBJ_DIR, tag + "_fold_in.o"), []), (SOURCES[9], os.path.join(OBJ_DIR, tag + "_loo.o"), [])]
-    units += [(SOURCES[10], os.path.join(OBJ_DIR, tag + "_ranking.o"), [])]
-    units += [(src, os.path.join(OBJ_DIR, tag + suffix), []) for src, suffix in MORE_SOURCES]
+    units = [(src, os.path.join(OBJ_DIR, tag + suffix), []) for src, suffix in UNITS]
     units += [(INST_SOURCE, os.path.join(OBJ_DIR, "%s_inst%d.o" % (tag, p)), ["-DBTF_INST_PART=%d" % p])
               for p in range(INST_PARTS)]
 
@@ -246,7 +240,7 @@ def build(force=False, verbose=False, jobs=None):
         subprocess.run(cmd, check=True, cwd=CSRC)
         return obj
 
-    jobs = jobs or max(1, min(len(units), os.cpu_count() or 1))
+    jobs = jobs or max(1, min(len(units), int(os.environ.get("MAX_JOBS") or os.cpu_count() or 1)))
     with ThreadPoolExecutor(max_workers=jobs) as pool:
         objs = list(pool.map(compile_unit, units))
     cmd = ["hipcc", "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB_PATH] + objs + os.environ.get("BTF_LINK_FLAGS", "").split()

@@ -12,19 +12,10 @@
 #include "btf_gass_features.h"
 #include "btf_gamma_grid.h"    // the gamma-grid likelihood (instances in btf_gamma_grid.hip)
 #include "btf_fused.h"
-#include "btf_diag.h"         // convergence diagnostics (instances in btf_diag.hip)
-#include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
-#include "btf_gg_criteria.h"    // the same for the gamma-grid likelihood (kernels in btf_gg_criteria.hip)
-#include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
-#include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
-#include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
-#include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
-#include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
-#include "btf_monotone.h"       // monotone projection of the posterior (kernel in btf_monotone.hip)
-#include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
+#include "btf_functionals.h"    // FUNC_SORT_LDS / FUNC_SORT_CELLS (btf_host_selftest walks every sort geometry)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
-#include "btf_scratch.h"        // Scratch: the device buffers of one analysis / stateless call
+#include "btf_ctx.h"            // struct btf_ctx, Scratch and the host plumbing shared with btf_analysis.hip
 #include <hip/hip_ext.h>
 #include <unistd.h>
 
@@ -41,280 +32,37 @@
 using namespace btf;
 
 namespace {
-
-constexpr int MAX_K = 10;
 constexpr int MAX_EVENTS = 8192;
-
-struct EvPair { hipEvent_t a, b; int kid; };
-
+thread_local std::string g_err;      // the error text of this thread's last context-free call
 }  // namespace
 
-struct btf_ctx {
-  int N = 0, M = 0, T = 0, K = 0, TF = 0, nD = 0, KK = 0;
-  int dev = 0;
-  int ncu = 256;                     // compute units of the device (hipDeviceAttributeMultiprocessorCount)
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  int row0 = 0, nl = 0, col0 = 0, ml = 0;
-  int hrow = -1, hcol = -1;  // btf_set_shard_halo: global index of the ONE stale-weight source row / column outside the blocks (-1: none);
-                             // its statistics sit at local index nl / ml of the slabs (never updated, never summed - only its weights are read)
-  int ldw = 0, ldv = 0;      // padded leading dimensions of A_wT / A_v
-  int R = 1;
-  bool have_data = false, binomial = false, weighted = false;
-  double* A_wT = nullptr; double* C_wT = nullptr; double* A_v = nullptr; double* C_v = nullptr;
-  double* B_wT = nullptr; double* B_v = nullptr;   // binomial: trials (0 where missing)
-  unsigned char* C8_wT = nullptr; unsigned char* C8_v = nullptr;   // Gaussian data with missing replicates: counts as bytes (C_* freed)
-  signed char* A8_wT = nullptr; signed char* A8_v = nullptr;       // Binomial data with integer counts: 2 (Y - N/2) as bytes
-  double* W = nullptr; double* V = nullptr;
-  double* Tau2 = nullptr;
-  double lam2 = 1.0, sigma2 = 1.0, nu2 = 1.0;
-  bool have_W = false, have_V = false, have_hyper = false;
-  double* part = nullptr; size_t part_elems = 0;
-  double* gpart = nullptr; int ngp_gram = 16;      // partial Grams of the last gram_kernel launch
-  double* zbuf = nullptr; size_t z_elems = 0;
-  double* bsum = nullptr; size_t bsum_elems = 0;
-  double* gband = nullptr; size_t gband_stride = 0;
-  int* status = nullptr;   // [0] flag [1] index
-  int* tries = nullptr;
-  int* st_ptr = nullptr; int* st_row = nullptr; double* st_coef = nullptr;
-  int* st_drow = nullptr; double* st_dcoef = nullptr; bool st_dense_ok = false;   // VS_MAXE slots per (t,d) (spectral sampler)
-  int* srcmap_w = nullptr; int* srcmap_v = nullptr;   // per-output source index of the cached weights
-  bool stale_w = false, stale_v = false;
-  int v_part_mode = 0;               // accumulation mode of the V half-sweep's partials in c->part (2: Gram blocks at the source columns)
-  double ssw = 0.0, nobs = 0.0, sa2 = 0.0;      // within-cell SS, observation count, sum S1^2/cnt (Gaussian data)
-  double nobs_global = -1.0;                    // sharded runs: observation count over all ranks (btf_set_global_nobs)
-  bool w_part_valid = false; int w_part_mode = 0, w_part_nch = 0, w_part_rpb = 0; bool w_part_gv = false;   // W-step partials current?
-  int rpb_w = 0, rpb_v = 0;
-  int sampler = BTF_SAMPLER_BANDED;   // BTF_OPT_SAMPLER
-  double* eig = nullptr;              // gram_eig_kernel output (spectral sampler): K eigenvalues, K*K vectors, sweeps
-  // elliptical slice sampling (btf_ess_*): current state, prior draw, per-chain {hh, lo, hi, theta, ll}, partial sums
-  double* essX0 = nullptr; double* essNu = nullptr; double* ess_st = nullptr; double* ess_theta = nullptr; int* ess_done = nullptr;
-  double* ess_part = nullptr; size_t ess_part_elems = 0; int ess_last_chains = 0;
-  // generalized analytic slice sampling (btf_gass_*): constraints, per-chain grids / candidates / likelihoods
-  double* gs_cons = nullptr; double* gs_cc = nullptr; double* gs_rc = nullptr; int gs_J = 0, gs_nrc = 0;
-  int* gs_cptr = nullptr; int* gs_cidx = nullptr; double* gs_cval = nullptr; int gs_cnnz = 0;     // the constraint matrix by its non-zeros
-  double* gs_av = nullptr; unsigned char* gs_mask = nullptr; int* gs_info = nullptr;
-  double* gs_thetas = nullptr; int* gs_ntheta = nullptr; double* gs_ll = nullptr; double* gs_llp = nullptr; size_t gs_llp_elems = 0; double* gs_hh = nullptr; double* gs_cur = nullptr;
-  int* gs_nacc = nullptr; double* gs_u = nullptr;
-  int gs_chains = 0, gs_what = -1, gs_link = 0;
-  // binary row features (btf_gass_set_row_features, btf_gass_features.h): the codes in both orientations, U, the user's
-  // row constraints on the host (gs_rc holds them followed by the 2F derived rows), the rows' side term of the current
-  // state, and the feature chains' own grids / candidates / likelihoods (what = 2)
-  int ft_F = 0; unsigned char* ft_rows = nullptr; unsigned char* ft_cols = nullptr; double* ft_U = nullptr;
-  std::vector<double> gs_rc_host; double* ft_side = nullptr;
-  double* ft_X0 = nullptr; double* ft_Nu = nullptr; double* ft_z = nullptr; unsigned char* ft_mask = nullptr; int* ft_info = nullptr;
-  double* ft_thetas = nullptr; int* ft_ntheta = nullptr; double* ft_ll = nullptr; double* ft_hh = nullptr; double* ft_cur = nullptr;
-  double* ft_part = nullptr; int* ft_nacc = nullptr; double* ft_u = nullptr; double* ft_theta = nullptr; int* ft_keep = nullptr;
-  // EP-centred GASS (btf_gass_set_ep): per-cell (Mu, p) in the row and the column layout, per-chain constants, the centre
-  // and the current state's correction of the last begin, the twisted envelope of the column systems
-  double2* ep_rows = nullptr; double2* ep_cols = nullptr; double* ep_crow = nullptr; double* ep_ccol = nullptr;
-  double* ep_mu = nullptr; double* ep_corr = nullptr; double* ep_pband = nullptr; double* ep_envg = nullptr;
-  int* ep_f = nullptr; int* ep_off = nullptr; int ep_env = 0, ep_bwe = 0; bool ep_on = false, gs_ep = false;
-  double lik_par[ESS_FAM_COUNT] = {0, 0, 0, 1.0, 1.0, 0};     // parameter per likelihood family (btf_set_likelihood_param)
-  // the gamma-grid family (btf_gamma_grid.h): component table, log sum p, and L = sum_r log y in both layouts of S1
-  GgComp* gg_tab = nullptr; int gg_G = 0; double gg_lsp = 0.0;
-  double* gg_Lw = nullptr; double* gg_Lv = nullptr; bool gg_have_L = false;
-  long long* dbg = nullptr;
-  double* vc_scratch = nullptr; size_t vc_scratch_elems = 0;     // factor records of the chunked chain sampler
-#ifdef BTF_ACC_STAMPS
-  long long* acc_stamps = nullptr;
-#endif
-  double* pband = nullptr;
-  double* pimg = nullptr; unsigned long long pimg_version = 0;       // the band as LDS images [P | Pm] (dataflow tails of the fused V launch)
-  // what the precomputed prior band (fused V launch, btf_fused.h) was formed from: every change of Tau2 / lam2 / the shard
-  // moves prior_version on; the band is rebuilt (prior_band_kernel) when pband_version lags behind
-  unsigned long long prior_version = 1, pband_version = 0, last_v_prior_version = 0;
-  double* Ta = nullptr; double* Tb = nullptr; double* Tc = nullptr; double* lsum = nullptr;   // horseshoe+ chain (device mode)
-  int* dr_ptr = nullptr; int* dr_col = nullptr; double* dr_val = nullptr;                   // Delta, CSR by row
-  bool have_chain = false;
-  double* pin = nullptr; size_t pin_elems = 0;   // pinned host staging (async SSE partials + W)
-  size_t sse_nb = 0; bool sse_pending = false;
-  double* pin_lsum = nullptr;
-  // Negative-Binomial counts: raw replicates, per-cell sums / counts, rate buffers
-  double* nb_data = nullptr; double* nb_S = nullptr; double* nb_cnt = nullptr;
-  double* nb_R = nullptr; double* nb_C = nullptr; size_t nb_relems = 0;
-  double* nb_tmp = nullptr; size_t nb_tmp_elems = 0;
-  double* nb_out = nullptr; size_t nb_out_elems = 0;
-  int nb_Rr = 0; bool counts = false; bool nb_bwt_written = false;
-  unsigned int* nb_H = nullptr; double* nb_Hd = nullptr; double* nb_Hs = nullptr;   // per-row count histograms (u32, f64) and their sum over rows
-  double* nb_L = nullptr;            // [N + 1]: per-row sum cnt*log(1-p), then the total
-  int* fill_tab = nullptr; int fill_n = 0; int fill_key = -1;   // band assembly program of the twisted kernel
-  int* nb_optr = nullptr; double* nb_oval = nullptr; int nb_nout = 0;   // per-row outlier lists (CSR)
-  int nb_ymax = 0;                   // largest tabulated count present (histogram bins above it are empty)
-  double* nb_G = nullptr;            // suffix sums of the histogram of all counts: nb_G[k] = #{observations > k}, k < NB_TAB
-  bool nb_tabulable = false;        // every observed count is an integer in [0, NB_TAB)
-  bool nb_L_valid = false;          // nb_L matches the current W, V
-  bool nb_hist = true;              // BTF_OPT_NB_HISTOGRAMS
-  int pg_mode = PG_MODE_DEFAULT;    // BTF_OPT_PG_EXACT: PG_MODE_DEFAULT / PG_MODE_EXACT_ALL / PG_MODE_SERIES_ALL
-  // trial counts below the normal range: any integer up to PG_AUTO_EXACT_MAX / any larger integer / any non-integer
-  bool pg_has_small = true, pg_has_big = true, pg_has_frac = true;
-  // on-device sample collection (run_gibbs, rng="device"): [nsamp] slots of W, V, Tau2 and the scalars
-  double* smp_W = nullptr; double* smp_V = nullptr; double* smp_T = nullptr; double* smp_s = nullptr; int smp_n = 0;
-  // model-selection criteria (btf_crit_*): the compact statistics of slot 0 (bound data) / 1 (held-out data)
-  double* crit_S1[2] = {nullptr, nullptr}; double* crit_cnt[2] = {nullptr, nullptr};
-  double* crit_c0[2] = {nullptr, nullptr}; double* crit_c1[2] = {nullptr, nullptr};
-  double* crit_L[2] = {nullptr, nullptr};        // family 5: sum_r log y per cell (btf_crit_set_logsum)
-  int col_every = 0, col_slot = 0, col_count = 0;       // btf_collect_schedule: btf_gibbs_sweeps keeps every col_every-th state
-  double* hyp = nullptr;        // device-resident scalars [HYP_COUNT] (nu2, sigma2, lam2, lam2_a, ...)
-  bool dev_scalars = false;     // kernels read nu2 / sigma2 / lam2 from hyp instead of the host copies
-  double* pin_hyp = nullptr;
-  double* gsum_v = nullptr; bool w_part_gsum = false;   // V'V summed by a side workgroup of the W accumulation launch (GramSide.sum_*): w_solve reads KK doubles
-  double* gpart_w = nullptr; int ngp_w = 0;   // W'W partials written by w_solve (valid until W changes otherwise)
-  double* gpart_v = nullptr; int ngp_v = 0;   // V'V partials written by the fast banded sampler
-  bool fuse_gram = true;
-  // curve-structured replicate counts (btf_kernels.h, CurveLists): counts constant along the depth axis
-  bool curve = false, curve_opt = true;
-  std::vector<unsigned char> cv_cij;                                  // host copy of c_ij [N][M] (stale-source test)
-  int* cv_cptr = nullptr; int* cv_crow = nullptr; double* cv_cdef = nullptr;   // by column: deficient rows
-  int* cv_rptr = nullptr; int* cv_rcol = nullptr; double* cv_rdef = nullptr;   // by row: deficient columns
-  double* eig_cols = nullptr;                                         // [M][K + K*K + 8] per-column eigen-systems
-  int* cv_dcols = nullptr; int cv_ndef = 0;                           // the columns that have deficient rows
-  bool w_part_curve = false;                                          // the W-step partials were made in curve mode
-  // sharded runs, BTF_OPT_SPLIT_ACCUM: the chunks of the rank's own block of the fixed factor are accumulated right
-  // behind the kernel that drew it (no exchange needed), the rest behind the all-gather
-  bool split_accum = false;
-  bool w_local_done = false, v_local_done = false;                    // own-block chunks of the next W / V accumulation are in c->part
-  int w_local_rpb = 0, w_local_mode = 0, v_local_rpb = 0, v_local_mode = 0;
-  hipEvent_t ev_draw = nullptr, ev_join = nullptr;                    // behind the last draw kernel / the comm stream's tail
-  // the ctx-owned communicator (btf_comm_init; btf_comm.h).  comm_rank / comm_world are the communicator's; gather_rank /
-  // gather_world the block decomposition the all-gathers reassemble - the same, except in a rehearsal (btf_comm_rehearse:
-  // a one-rank communicator moving the messages of rank gather_rank of gather_world through scratch buffers)
-  ncclComm_t comm = nullptr; int comm_rank = 0, comm_world = 1, gather_rank = 0, gather_world = 1;
-  bool comm_rehearse = false;
-  hipStream_t comm_stream = nullptr;                                  // the overlapped exchange runs its gathers here
-  double* comm_scr = nullptr; size_t comm_scr_elems = 0;              // rehearsal: [send | recv] of the larger message
-  double* comm_words = nullptr;                                       // 16 device doubles: btf_allreduce_sum's staging
-  // the peer-window transport (btf_comm.h): this rank's mailbox, the table of where every rank's buffers are mapped
-  // here, the mappings to close, the collective counter
-  PeerMailbox* peer_box = nullptr;
-  PeerTable* peer_tab = nullptr;
-  unsigned* peer_counters = nullptr;
-  std::vector<void*> peer_opened;
-  bool peer_on = false;
-  unsigned long long peer_epoch = 0;
-  long long peer_timeout_ticks = 0;
-  bool tau_pending = false; unsigned long long tau_seed = 0; double tau_stability = 1e-6;   // btf_queue_Tau2
-  // the four-launch sweep (BTF_OPT_FUSED_SWEEP): per-column residual parts left by the spectral V sampler, and a queued
-  // nu2 / sigma2 draw that the next W accumulation launch carries as a side workgroup (btf_queue_scalars)
-  bool fused_sweep = true;
-  double* sse_cols = nullptr; bool sse_cols_valid = false;
-  double* vs_rec = nullptr; size_t vs_rec_elems = 0;       // HBM scratch of the spectral sampler's pivot records (long depth axes)
-  bool nu2_drawn_since_v = false;      // a device nu2 draw happened since the last V half-sweep: the caller runs full sweeps
-  bool sc_pending = false; unsigned long long sc_seed = 0; int sc_which = 0; double sc_prior[4] = {0, 0, 0, 0};
-  bool lam_pending = false; unsigned long long lam_seed = 0; int lam_exact = 0;            // btf_queue_lam2
-  bool band_in_wsolve = true;                                         // (A/B aid: BTF_BAND_IN_WSOLVE=0: the band's own launch)
-  bool v_wants_band = false, band_img = false; int band_PB = 0;       // the last fused V launch loaded the precomputed prior band (and its LDS image)
-  bool lam_in_wsolve = true;                                          // (A/B aid: BTF_LAM_IN_WSOLVE=0 leaves the draw to the V launch)
-  unsigned long long sweep_w = 0, sweep_v = 0;
-  // the two-launch W+V step (BTF_OPT_FUSED_STEP, btf_fused.h): tickets / flags (zeroed once; 32 words = one 128-byte line
-  // per flag), the write-through copies the tails read, the epoch of the hand-offs (one per fused launch, never reused)
-  int fused_dataflow = 1;            // BTF_OPT_FUSED_DATAFLOW: 1 (default) the fused V launch runs the barrier-free tail where it applies
-  int fused_step = 1;                // BTF_OPT_FUSED_STEP: 0 four launches, 1 (default) the V launch carries its sampler, 2 the W launch its solve too
-  unsigned* fz_words = nullptr; int fz_tiles_w = 0, fz_tiles_v = 0;
-  double* fz_pub = nullptr;
-  unsigned fz_epoch = 0, fz_gram_total = 0, fz_w_total = 0;
-  bool profiling = false;
-  std::vector<EvPair> ev_pool;
-  size_t ev_used = 0;
-  double ms_total[BTF_K_COUNT] = {0};
-  int64_t launches[BTF_K_COUNT] = {0};
-  std::string err;
-  int fail_index = -1;
-};
-
-namespace {
-
-thread_local std::string g_err;
-
-int fail(btf_ctx* c, int code, const std::string& msg) {
+namespace btf {
+// posterior_summary_kernel on device states W (S,rows,K), V (S,MT,K), on the scratch's stream: the one place that launches it
+void launch_summary(Scratch& s, const double* W, const double* V, int S, int rows, int MT, int K, int transform, const double* dq,
+                    int nq, double* mean, double* quant) {
+  const SortGeom g = sort_geom(S, SUMMARY_SORT_LDS, SUMMARY_SORT_CELLS);
+  const dim3 grid((MT + g.cells - 1) / g.cells, rows);
+  K_SWITCH(K, {
+    const auto kern = posterior_summary_kernel<KT>;
+    allow_lds(s, kern, g.lds);
+    s.launch(kern, grid, dim3(256), g.lds, W, V, S, rows, MT, g.P, g.cells, transform, dq, nq, mean, quant);
+  });
+}
+// the text btf_last_error returns: the context's, or this thread's last context-free call's (fail, Scratch, btf_nmf.hip)
+int report_error(btf_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   g_err = msg;
   return code;
 }
-
-}  // namespace
-
-namespace btf {
-// the error text of the context-free entry points of other compilation units (btf_nmf.hip), and of Scratch (btf_scratch.h)
-int set_global_error(int code, const std::string& msg) { return fail(nullptr, code, msg); }
-int report_error(btf_ctx* c, int code, const std::string& msg) { return fail(c, code, msg); }
 }  // namespace btf
 
 namespace {
-
-#define HIPCHK(ctx, call)                                                                  \
-  do {                                                                                     \
-    hipError_t e__ = (call);                                                               \
-    if (e__ != hipSuccess)                                                                 \
-      return fail(ctx, BTF_EHIP, std::string(#call) + ": " + hipGetErrorString(e__));      \
-  } while (0)
-
-template <typename T>
-int dev_alloc(btf_ctx* c, T** p, size_t n) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (n == 0) n = 1;
-  HIPCHK(c, hipMalloc((void**)p, n * sizeof(T)));
-  return BTF_OK;
-}
 
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // "this function's attribute was set on device d": hipFuncSetAttribute is per device, and `device=` is a public
 // constructor keyword - a process-wide flag would skip the call for a second context on another GPU
 inline bool dev_flag_is_set(const std::atomic<unsigned long long>& f, int dev) { return dev >= 0 && dev < 64 && ((f.load() >> dev) & 1ULL); }
 inline void dev_flag_set(std::atomic<unsigned long long>& f, int dev) { if (dev >= 0 && dev < 64) f.fetch_or(1ULL << dev); }
-
-// One kernel launch, counted per BTF_K_* id.  With profiling on the launch goes through
-// hipExtLaunchKernelGGL so that the two events bracket exactly this dispatch (its start
-// and completion timestamps), not the gaps around it.
-struct Prof {
-  btf_ctx* c; int kid; EvPair* ev = nullptr;
-  Prof(btf_ctx* c_, int kid_) : c(c_), kid(kid_) {
-    c->launches[kid]++;
-    if (c->profiling && c->ev_used < c->ev_pool.size()) {
-      ev = &c->ev_pool[c->ev_used++];
-      ev->kid = kid;
-    }
-  }
-  template <typename F, typename... Args>
-  void launch(F kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
-    launch_on(c->stream, kernel, grid, block, lds, args...);
-  }
-  template <typename F, typename... Args>
-  void launch_on(hipStream_t st, F kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
-    if (ev) hipExtLaunchKernelGGL(kernel, grid, block, (unsigned)lds, st, ev->a, ev->b, 0, args...);
-    else hipLaunchKernelGGL(kernel, grid, block, (unsigned)lds, st, args...);
-  }
-};
-
-// One launch of an analysis entry point on its scratch's stream: counted under kid when the call has a context, and not
-// made at all once an allocation or copy of the scratch has failed.
-template <typename F, typename... Args>
-void launch_counted(Scratch& s, int kid, F kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
-  if (!s.ctx()) return s.launch(kernel, grid, block, lds, args...);
-  if (s.rc()) return;
-  { Prof p(s.ctx(), kid); p.launch_on(s.stream(), kernel, grid, block, lds, args...); }
-  s.check(hipGetLastError(), "hipGetLastError (kernel launch)");
-}
-// dynamic LDS beyond the default 64 KiB has to be allowed per kernel
-template <typename F>
-void allow_lds(Scratch& s, F kernel, size_t lds) {
-  s.check(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute");
-}
-
-// LDS geometry of the kernels that sort the n values of a cell in a row of P doubles: P the power of two >= n (and >= 2),
-// as many cells per workgroup as `budget` bytes hold, at least one (a row over the budget still gets its workgroup) and at
-// most `cap`.
-struct SortGeom { int P, cells; size_t lds; };
-SortGeom sort_geom(int n, size_t budget, int cap) {
-  SortGeom g;
-  g.P = 2;
-  while (g.P < n) g.P <<= 1;
-  g.cells = std::max(1, std::min(cap, (int)(budget / ((size_t)g.P * sizeof(double)))));
-  g.lds = (size_t)g.cells * g.P * sizeof(double);
-  return g;
-}
-constexpr size_t SUMMARY_SORT_LDS = 128 * 1024, PRED_SORT_LDS = 64 * 1024;
-constexpr int SUMMARY_SORT_CELLS = 16, PRED_SORT_CELLS = 16;
 
 // Delta' diag(lambda) Delta stencil: for every (t,d), d = 0..tf+1, the Delta rows r that
 // touch both t and t+d with the coefficient product Delta[r,t]*Delta[r,t+d].
@@ -855,32 +603,6 @@ void launch_ess_ll(btf_ctx* c, int what, int mode, int link, int nbx) {
   }
 }
 
-#define K_SWITCH(K, CALL)                                          \
-  switch (K) {                                                     \
-    case 1: { constexpr int KT = 1; CALL; } break;                 \
-    case 2: { constexpr int KT = 2; CALL; } break;                 \
-    case 3: { constexpr int KT = 3; CALL; } break;                 \
-    case 4: { constexpr int KT = 4; CALL; } break;                 \
-    case 5: { constexpr int KT = 5; CALL; } break;                 \
-    case 6: { constexpr int KT = 6; CALL; } break;                 \
-    case 7: { constexpr int KT = 7; CALL; } break;                 \
-    case 8: { constexpr int KT = 8; CALL; } break;                 \
-    case 9: { constexpr int KT = 9; CALL; } break;                 \
-    case 10: { constexpr int KT = 10; CALL; } break;               \
-    default: break;                                                \
-  }
-// the same over the five likelihood families of the criteria and predictive kernels (CRIT_FAM_* / PRED_FAM_*), as FT
-#define FAM_SWITCH(F, CALL)                                        \
-  switch (F) {                                                     \
-    case 0: { constexpr int FT = 0; CALL; } break;                 \
-    case 1: { constexpr int FT = 1; CALL; } break;                 \
-    case 2: { constexpr int FT = 2; CALL; } break;                 \
-    case 3: { constexpr int FT = 3; CALL; } break;                 \
-    case 4: { constexpr int FT = 4; CALL; } break;                 \
-    default: break;                                                \
-  }
-static_assert(CRIT_FAM_COUNT == 5 && PRED_FAM_COUNT == 5, "FAM_SWITCH covers families 0..4");
-
 int check_status(btf_ctx* c) {
   int st[2] = {0, -1};
   HIPCHK(c, hipMemcpyAsync(st, c->status, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1055,8 +777,7 @@ int btf_create(btf_ctx** out, int nrows, int ncols, int ndepth, int nembeds, int
   c->N = nrows; c->M = ncols; c->T = ndepth; c->K = nembeds; c->TF = tf_order; c->KK = tri(nembeds);
   c->dev = device;
   c->row0 = 0; c->nl = nrows; c->col0 = 0; c->ml = ncols;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) { g_err = std::string("hipSetDevice: ") + hipGetErrorString(e); delete c; return BTF_EHIP; }
+  if (int rc = use_device(device)) { delete c; return rc; }
   { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) c->ncu = n; }
   { const char* e = std::getenv("BTF_FUSED_STEP"); if (e) c->fused_step = std::max(0, std::min(2, std::atoi(e))); }      // (A/B aid; BTF_OPT_FUSED_STEP is the interface)
   { const char* e = std::getenv("BTF_LAM_IN_WSOLVE"); if (e) c->lam_in_wsolve = std::atoi(e) != 0; }
@@ -1064,7 +785,7 @@ int btf_create(btf_ctx** out, int nrows, int ncols, int ndepth, int nembeds, int
   { const char* e = std::getenv("BTF_VF_DATAFLOW"); if (e) c->fused_dataflow = std::atoi(e) != 0 ? 1 : 0; }             // (A/B aid; BTF_OPT_FUSED_DATAFLOW is the interface)
   if (stream) { c->stream = (hipStream_t)stream; }
   else {
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    const hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { g_err = std::string("hipStreamCreate: ") + hipGetErrorString(e); delete c; return BTF_EHIP; }
     c->own_stream = true;
   }
@@ -1119,8 +840,7 @@ void btf_destroy(btf_ctx* c) {
 }
 
 const char* btf_last_error(const btf_ctx* c) { return c ? c->err.c_str() : g_err.c_str(); }
-int fold_fail_index();   // (defined with the fold-in entry points)
-int btf_fail_index(const btf_ctx* c) { return c ? c->fail_index : fold_fail_index(); }
+int btf_fail_index(const btf_ctx* c) { return c ? c->fail_index : fold_fail_index(); }      // (btf_analysis.hip)
 
 int btf_set_shard(btf_ctx* c, int row0, int nrows_local, int col0, int ncols_local) {
   if (!c) return BTF_EINVAL;
@@ -3546,312 +3266,6 @@ int btf_collect_end(btf_ctx* c, int nsamples, double* W, double* V, double* Tau2
   return check_status(c);
 }
 
-namespace {
-// posterior_summary_kernel on device states W (S,rows,K), V (S,MT,K), on the scratch's stream: the one place that launches it
-void launch_summary(Scratch& s, const double* W, const double* V, int S, int rows, int MT, int K, int transform, const double* dq,
-                    int nq, double* mean, double* quant) {
-  const SortGeom g = sort_geom(S, SUMMARY_SORT_LDS, SUMMARY_SORT_CELLS);
-  const dim3 grid((MT + g.cells - 1) / g.cells, rows);
-  K_SWITCH(K, {
-    const auto kern = posterior_summary_kernel<KT>;
-    allow_lds(s, kern, g.lds);
-    s.launch(kern, grid, dim3(256), g.lds, W, V, S, rows, MT, g.P, g.cells, transform, dq, nq, mean, quant);
-  });
-}
-
-// the summary of btf_posterior_summary, btf_collect_summary and fold-in's last stage: its buffers, the launch, the downloads
-void summary_stage(Scratch& s, const double* W, const double* V, int S, int rows, int MT, int K, int transform, const double* q,
-                   int nq, double* mean_out, double* q_out) {
-  const size_t n = (size_t)rows * MT;
-  double* dm = s.alloc<double>(n);
-  const double* dq = nq ? s.upload(q, (size_t)nq) : s.alloc<double>(1);
-  double* dqo = s.alloc<double>((size_t)nq * n);
-  launch_summary(s, W, V, S, rows, MT, K, transform, dq, nq, dm, dqo);
-  s.download(mean_out, dm, n);
-  if (nq) s.download(q_out, dqo, (size_t)nq * n);
-}
-
-// Which states an analysis call reads and where its per-sample noise lies: the uploaded Ws / Vs, else the context's
-// current W / V (`current`), else the collected ones; the uploaded `noise` (`per` values a sample), else the collected
-// nu2 of every kept state.  The callers have refused what they do not take.
-struct States { const double *W, *V, *noise; long long noise_stride; };
-States resolve_states(btf_ctx* c, Scratch& s, int S, const double* Ws, const double* Vs, bool current, bool per_sample,
-                      const double* noise, size_t per) {
-  States r = {c->smp_W, c->smp_V, nullptr, 1};
-  if (Ws) {
-    r.W = s.upload(Ws, (size_t)S * c->N * c->K);
-    r.V = s.upload(Vs, (size_t)S * c->M * c->T * c->K);
-  } else if (current) {
-    r.W = c->W; r.V = c->V;
-  }
-  if (per_sample && noise) { r.noise = s.upload(noise, (size_t)S * per); r.noise_stride = (long long)per; }
-  else if (per_sample) { r.noise = c->smp_s + HYP_NU2; r.noise_stride = HYP_COUNT; }
-  return r;
-}
-}  // namespace
-
-// posterior summaries straight from the collected samples (no upload); see btf_posterior_summary
-int btf_collect_summary(btf_ctx* c, int nsamples, int transform, const double* q, int nq, double* mean_out, double* q_out) {
-  if (!c || nsamples < 1 || nsamples > c->smp_n || nsamples > 16384 || !mean_out || nq < 0 || (nq > 0 && (!q || !q_out)) ||
-      transform < 0 || transform > 2)
-    return fail(c, BTF_EINVAL, "bad collect_summary arguments");
-  HIPCHK(c, hipSetDevice(c->dev));
-  Scratch s(c, c->stream);
-  summary_stage(s, c->smp_W, c->smp_V, nsamples, c->N, c->M * c->T, c->K, transform, q, nq, mean_out, q_out);
-  return s.finish();
-}
-
-// ---------------------------------------------------------- model-selection criteria (btf_criteria.h)
-int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt, const double* curve_c0, const double* curve_c1) {
-  if (!c || slot < 0 || slot > 1) return fail(c, BTF_EINVAL, "criteria slot must be 0 or 1");
-  HIPCHK(c, hipSetDevice(c->dev));
-  HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistics)
-  double** bufs[4] = {&c->crit_S1[slot], &c->crit_cnt[slot], &c->crit_c0[slot], &c->crit_c1[slot]};
-  if (c->crit_L[slot]) { (void)hipFree(c->crit_L[slot]); c->crit_L[slot] = nullptr; }      // (the old data's log sums)
-  if (!S1 && !cnt && !curve_c0 && !curve_c1) {       // free the slot
-    for (double** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-    return BTF_OK;
-  }
-  if (!S1 || !cnt || !curve_c0 || !curve_c1) return fail(c, BTF_EINVAL, "btf_crit_set_data: all four arrays, or none");
-  const size_t cells = (size_t)c->M * c->T * c->N, curves = (size_t)c->N * c->M;
-  const double* src[4] = {S1, cnt, curve_c0, curve_c1};
-  const size_t n[4] = {cells, cells, curves, curves};
-  for (int q = 0; q < 4; ++q) {
-    int rc;
-    if ((rc = dev_alloc(c, bufs[q], n[q]))) return rc;
-    HIPCHK(c, hipMemcpyAsync(*bufs[q], src[q], n[q] * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return BTF_OK;
-}
-
-int btf_crit_set_logsum(btf_ctx* c, int slot, const double* L) {
-  if (!c || slot < 0 || slot > 1) return fail(c, BTF_EINVAL, "criteria slot must be 0 or 1");
-  HIPCHK(c, hipSetDevice(c->dev));
-  HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistic)
-  if (!L) {
-    if (c->crit_L[slot]) (void)hipFree(c->crit_L[slot]);
-    c->crit_L[slot] = nullptr;
-    return BTF_OK;
-  }
-  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, "btf_crit_set_logsum: no statistics in this slot (btf_crit_set_data first)");
-  const size_t cells = (size_t)c->M * c->T * c->N;
-  int rc;
-  if ((rc = dev_alloc(c, &c->crit_L[slot], cells))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->crit_L[slot], L, cells * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return BTF_OK;
-}
-
-namespace {
-// families 0..4 of FAM_SWITCH, or the gamma-grid family of btf_gg_criteria.h
-bool crit_family_ok(int family) { return (family >= 0 && family < CRIT_FAM_COUNT) || family == CRIT_FAM_GAMMA_GRID; }
-
-// the device side of a criteria call: its scratch (the uploaded states, crit_kernel's outputs) and the kernels' arguments
-struct CritRun {
-  Scratch s;
-  CritArgs a{};
-  double* tot = nullptr;      // [S] per-sample totals (crit_total_kernel)
-  explicit CritRun(btf_ctx* c) : s(c, c->stream) {}
-};
-
-// Checks the arguments that btf_crit_eval and btf_crit_loo share, uploads the states and queues crit_kernel (with
-// `reduce` also the plug-in and per-sample-total kernels) on the context's stream.  `who` names the caller in messages.
-int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
-             const double* noise, int flags, bool pointwise, bool reduce, CritRun& r) {
-  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, who + ": no statistics in this slot (btf_crit_set_data)");
-  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, who + " needs an unsharded context");
-  const bool current = (flags & BTF_CRIT_CURRENT) != 0, per_sample = (flags & BTF_CRIT_NOISE_PER_SAMPLE) != 0;
-  if (current && (Ws || nsamples != 1 || !c->have_W || !c->have_V))
-    return fail(c, BTF_EINVAL, "BTF_CRIT_CURRENT scores the context's own W, V: one sample, Ws = Vs = NULL");
-  if (!Ws && !current && (!c->smp_W || nsamples > c->smp_n)) return fail(c, BTF_ESTATE, who + ": not that many collected samples");
-  if (per_sample && family != CRIT_FAM_GAUSSIAN) return fail(c, BTF_EINVAL, "per-sample noise is the Gaussian family's");
-  if (per_sample && !noise && (Ws || current)) return fail(c, BTF_EINVAL, "per-sample noise of uploaded / current states: pass `noise`");
-  if (!per_sample && (family == CRIT_FAM_GAUSSIAN || family == CRIT_FAM_NEGBIN) && !(param > 0.0))
-    return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
-  const bool gamma_grid = family == CRIT_FAM_GAMMA_GRID;
-  if (gamma_grid && (!c->gg_tab || !c->crit_L[slot]))
-    return fail(c, BTF_ESTATE, who + ": the gamma-grid family needs its table (btf_set_likelihood_table) and the slot's L (btf_crit_set_logsum)");
-  HIPCHK(c, hipSetDevice(c->dev));
-  const int S = nsamples, N = c->N, M = c->M, T = c->T, K = c->K;
-  const dim3 grid((N + WAVE - 1) / WAVE, M);
-  const int nwg = (int)(grid.x * grid.y);
-  const size_t NM = (size_t)N * M;
-  Scratch& s = r.s;
-  CritArgs& a = r.a;
-  a.S1 = c->crit_S1[slot]; a.cnt = c->crit_cnt[slot]; a.c0 = c->crit_c0[slot]; a.c1 = c->crit_c1[slot];
-  const States st = resolve_states(c, s, S, Ws, Vs, current, per_sample, noise, 1);
-  a.W = st.W; a.V = st.V; a.noise = st.noise; a.noise_stride = st.noise_stride;
-  a.par = param; a.S = S; a.N = N; a.M = M; a.T = T;
-  a.mu = s.alloc<double>((size_t)M * T * N); a.curve = s.alloc<double>(CRIT_OUT * NM);
-  a.tot_part = s.alloc<double>((size_t)S * nwg); r.tot = s.alloc<double>((size_t)S);
-  if (pointwise) a.pw = s.alloc<double>((size_t)S * NM);
-  const GgTab gt{c->crit_L[slot], c->gg_tab, c->gg_G, c->gg_lsp};
-  if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_fn(K), grid, dim3(GGC_WAVES * WAVE), 0, a, gt);
-  else K_SWITCH(K, FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_kernel<KT, FT>, grid, dim3(CRIT_WAVES * WAVE), 0, a)));
-  if (reduce) {
-    if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_plugin_fn(), grid, dim3(WAVE), 0, a, gt);
-    else FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_plugin_kernel<FT>, grid, dim3(WAVE), 0, a));
-    launch_counted(s, BTF_K_CRITERIA, crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.tot_part, S, nwg, r.tot);
-  }
-  return s.rc();
-}
-}  // namespace
-
-int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
-                  const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out) {
-  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !curve_out || !total_out ||
-      (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
-    return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
-  CritRun r(c);
-  int rc = crit_run(c, "btf_crit_eval", slot, family, param, nsamples, Ws, Vs, noise, flags, pointwise_out != nullptr, true, r);
-  if (rc) return rc;
-  const size_t S = (size_t)nsamples, NM = (size_t)c->N * c->M;
-  r.s.download(curve_out, r.a.curve, CRIT_OUT * NM);
-  r.s.download(total_out, r.tot, S);
-  r.s.download(pointwise_out, r.a.pw, S * NM);
-  return r.s.finish();        // (not check_status: the sampler's status word is not this call's)
-}
-
-// ---------------------------------------------------------- PSIS-LOO (btf_loo.h)
-int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
-                 const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
-                 double* logw_out) {
-  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !loo_out ||
-      (flags & ~BTF_CRIT_NOISE_PER_SAMPLE) || (!Ws) != (!Vs) || transform < 0 || transform > 2)
-    return fail(c, BTF_EINVAL, "bad btf_crit_loo arguments");
-  if (nsamples > LOO_MAX_S)
-    return fail(c, BTF_EINVAL, "btf_crit_loo: " + std::to_string(nsamples) + " samples, at most " + std::to_string(LOO_MAX_S));
-  const int S = nsamples, N = c->N, M = c->M, T = c->T;
-  const size_t NM = (size_t)N * M;
-  // the tail length Mt = min(floor(0.2 S), ceil(3 sqrt(S / r_eff))) of every curve, on the host: IEEE sqrt and division
-  auto tail = [S](double re) { return (int)std::min((double)(S / 5), std::ceil(3.0 * std::sqrt((double)S / re))); };
-  std::vector<int> mt;
-  if (r_eff) {
-    mt.resize(NM);
-    for (size_t o = 0; o < NM; ++o) {
-      if (!(r_eff[o] > 0.0) || !std::isfinite(r_eff[o]))
-        return fail(c, BTF_EINVAL, "btf_crit_loo: r_eff must be finite and > 0 (curve " + std::to_string(o) + ")");
-      mt[o] = tail(r_eff[o]);
-    }
-  }
-  CritRun r(c);
-  int rc = crit_run(c, "btf_crit_loo", slot, family, param, nsamples, Ws, Vs, noise, flags, true, false, r);
-  if (rc) return rc;
-  Scratch& s = r.s;
-  double* dloo = s.alloc<double>(2 * NM);
-  LooArgs a{};
-  a.pw = r.a.pw; a.mt = r_eff ? s.upload(mt.data(), NM) : nullptr; a.mt_all = tail(1.0); a.S = S; a.NM = (int)NM; a.out = dloo;
-  a.P = 64; while (a.P < S) a.P <<= 1;
-  a.per_xcd = (int)((NM + 7) / 8);
-  const size_t lds = (size_t)a.P * (2 * sizeof(double) + sizeof(unsigned short));
-  void (*const psis)(LooArgs) = (mean_out || logw_out) ? loo_psis_kernel<1> : loo_psis_kernel<0>;      // <1> keeps the log weights
-  allow_lds(s, psis, lds);
-  launch_counted(s, BTF_K_CRITERIA, psis, dim3(8 * a.per_xcd), dim3(WAVE), lds, a);
-  if (mean_out) {
-    LooMeanArgs ma{};
-    ma.lw = r.a.pw; ma.W = r.a.W; ma.V = r.a.V; ma.S = S; ma.N = N; ma.M = M; ma.T = T; ma.transform = transform;
-    ma.mean = s.alloc<double>(NM * T);
-    K_SWITCH(c->K, launch_counted(s, BTF_K_CRITERIA, loo_mean_kernel<KT>, dim3((N + WAVE - 1) / WAVE, M), dim3(LOO_WAVES * WAVE), 0, ma));
-    s.download(mean_out, ma.mean, NM * T);
-  }
-  // loo_out: elpd_loo, pareto_k, then crit_kernel's two accumulators of lppd (curve_out[0], [1] of btf_crit_eval)
-  s.download(loo_out, dloo, 2 * NM);
-  s.download(loo_out + 2 * NM, r.a.curve, 2 * NM);
-  s.download(logw_out, r.a.pw, (size_t)S * NM);
-  return s.finish();
-}
-
-// ---------------------------------------------------------- posterior predictive (btf_predict.h)
-int btf_predict_batch(int device, int family, int64_t n, const double* eta, const double* aux, uint64_t seed, double* out) {
-  if (family < 0 || family >= PRED_FAM_COUNT || n < 1 || !eta || !aux || !out) return fail(nullptr, BTF_EINVAL, "bad predict_batch arguments");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  Scratch s(nullptr, nullptr);
-  const double *de = s.upload(eta, (size_t)n), *da = s.upload(aux, (size_t)n);
-  double* dout = s.alloc<double>((size_t)n);
-  const dim3 grid((unsigned)((n + PRED_THREADS - 1) / PRED_THREADS)), block(PRED_THREADS);
-  FAM_SWITCH(family, s.launch(pred_batch_kernel<FT>, grid, block, 0, de, da, (long long)n, (unsigned long long)seed, dout));
-  s.download(out, dout, (size_t)n);
-  return s.finish();
-}
-
-int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const double* Ws, const double* Vs,
-                     const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps,
-                     int draws_per_sample, uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
-                     double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out, double* pit_hi_out,
-                     double* inside_out, double* nobs_out, double* rmse_out, double* mae_out, double* draws_out) {
-  if (!c || family < 0 || family >= PRED_FAM_COUNT || nsamples < 1 || draws_per_sample < 1 || (!Ws) != (!Vs) || nq < 0 ||
-      (nq > 0 && !q) || (q_out && nq < 1) || ncells < 0 || (ncells > 0 && (!cells || !draws_out)) || (Y && nreps < 1) ||
-      (aux_flags & ~(BTF_PRED_AUX_PER_SAMPLE | BTF_PRED_AUX_ROWS | BTF_PRED_AUX_COLS | BTF_PRED_AUX_DEPTH)))
-    return fail(c, BTF_EINVAL, "bad btf_predict_eval arguments");
-  if (!Y && (pit_lo_out || pit_hi_out || inside_out || nobs_out || rmse_out || mae_out))
-    return fail(c, BTF_EINVAL, "btf_predict_eval: pit / inside / nobs / rmse / mae compare with observations: pass Y");
-  if ((long long)nsamples * draws_per_sample > PRED_MAX_DRAWS)
-    return fail(c, BTF_EINVAL, "btf_predict_eval: nsamples * draws_per_sample = " + std::to_string((long long)nsamples * draws_per_sample) +
-                " exceeds 16384 (the draws of a cell are sorted in LDS)");
-  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_predict_eval needs an unsharded context");
-  if (!Ws && (!c->smp_W || nsamples > c->smp_n)) return fail(c, BTF_ESTATE, "btf_predict_eval: not that many collected samples");
-  const bool per_sample = (aux_flags & BTF_PRED_AUX_PER_SAMPLE) != 0;
-  const bool needs_par = family == PRED_FAM_GAUSSIAN || family == PRED_FAM_NEGBIN;
-  if (per_sample && !needs_par) return fail(c, BTF_EINVAL, "per-sample parameters are the Gaussian (variance) and Negative-Binomial (rate) families'");
-  if (per_sample && !aux_sample && (Ws || family != PRED_FAM_GAUSSIAN))
-    return fail(c, BTF_EINVAL, "per-sample parameters of uploaded states (and every Negative-Binomial rate): pass aux_sample");
-  if (!per_sample && needs_par && !(param > 0.0))
-    return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
-  for (int k = 0; k < nq; ++k)
-    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
-  const int S = nsamples, R = draws_per_sample, N = c->N, M = c->M, T = c->T, K = c->K, MT = M * T, n = S * R;
-  const size_t ncell = (size_t)N * MT;
-  if (ncell > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: more than 2^31 - 1 cells");
-  for (int k = 0; k < ncells; ++k)
-    if (cells[k] < 0 || (size_t)cells[k] >= ncell) return fail(c, BTF_EINVAL, "btf_predict_eval: cell index out of range");
-  HIPCHK(c, hipSetDevice(c->dev));
-  PredArgs a{};
-  a.aux_n0 = a.aux_n1 = a.aux_n2 = 1;
-  if (per_sample && family == PRED_FAM_NEGBIN) {
-    a.aux_n0 = (aux_flags & BTF_PRED_AUX_ROWS) ? N : 1; a.aux_n1 = (aux_flags & BTF_PRED_AUX_COLS) ? M : 1; a.aux_n2 = (aux_flags & BTF_PRED_AUX_DEPTH) ? T : 1;
-  }
-  const size_t naux = (size_t)a.aux_n0 * a.aux_n1 * a.aux_n2;
-  const SortGeom g = sort_geom(n, PRED_SORT_LDS, PRED_SORT_CELLS);
-  const size_t nblk = (size_t)N * ((MT + g.cells - 1) / g.cells);
-  if (nblk > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: too many workgroups for one launch");
-  const int chunks = (int)((ncell + PRED_SCORE_CELLS - 1) / PRED_SCORE_CELLS);
-  const bool score = rmse_out || mae_out;
-  Scratch s(c, c->stream);
-  const States st = resolve_states(c, s, S, Ws, Vs, false, per_sample, aux_sample, naux);
-  a.W = st.W; a.V = st.V; a.aux = st.noise; a.aux_stride = st.noise_stride;
-  if (trials) a.trials = s.upload(trials, ncell);
-  if (Y) { a.Y = s.upload(Y, ncell * (size_t)nreps); a.nreps = nreps; }
-  if (nq) a.q = s.upload(q, (size_t)nq);
-  a.nq = nq;
-  if (ncells) { a.list = s.upload(cells, (size_t)ncells); a.nlist = ncells; a.draws = s.alloc<double>((size_t)ncells * n); }
-  if (mean_out) a.mean = s.alloc<double>(ncell);
-  if (ymean_out) a.y_mean = s.alloc<double>(ncell);
-  if (yvar_out) a.y_var = s.alloc<double>(ncell);
-  if (q_out) a.quant = s.alloc<double>((size_t)nq * ncell);
-  if (pit_lo_out) a.pit_lo = s.alloc<double>(ncell);
-  if (pit_hi_out) a.pit_hi = s.alloc<double>(ncell);
-  if (inside_out) a.inside = s.alloc<double>(ncell);
-  if (nobs_out) a.nobs = s.alloc<double>(ncell);
-  double* dsc = nullptr;      // [rmse | mae] per sample
-  if (score) { a.score_part = s.alloc<double>((size_t)3 * S * chunks); dsc = s.alloc<double>((size_t)2 * S); }
-  a.par = param; a.S = S; a.R = R; a.N = N; a.M = M; a.T = T; a.K = K; a.P = g.P; a.cells = g.cells; a.seed = seed; a.chunks = chunks;
-  FAM_SWITCH(family, {
-    allow_lds(s, pred_kernel<FT>, g.lds);
-    s.launch(pred_kernel<FT>, dim3((unsigned)nblk), dim3(PRED_THREADS), g.lds, a);
-    if (score) s.launch(pred_score_kernel<FT>, dim3(chunks, S), dim3(PRED_THREADS), 0, a);
-  });
-  if (score) s.launch(pred_score_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.score_part, S, chunks, dsc);
-  s.download(mean_out, a.mean, ncell); s.download(ymean_out, a.y_mean, ncell); s.download(yvar_out, a.y_var, ncell);
-  s.download(q_out, a.quant, (size_t)nq * ncell);
-  s.download(pit_lo_out, a.pit_lo, ncell); s.download(pit_hi_out, a.pit_hi, ncell); s.download(inside_out, a.inside, ncell);
-  s.download(nobs_out, a.nobs, ncell);
-  if (score && !s.rc()) { s.download(rmse_out, dsc, (size_t)S); s.download(mae_out, dsc + S, (size_t)S); }
-  if (ncells) s.download(draws_out, a.draws, (size_t)ncells * n);
-  return s.finish();        // (not check_status: the sampler's status word is not this call's)
-}
-
 // ---------------------------------------------------------- device-resident scalars
 int btf_device_scalars(btf_ctx* c, int enable) {
   if (!c) return BTF_EINVAL;
@@ -4093,680 +3507,13 @@ int btf_pg_draw(btf_ctx* c, uint64_t seed) {
   return BTF_OK;
 }
 
-// ---------------------------------------------------------------- posterior summaries
-int btf_posterior_summary(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws,
-                          const double* Vs, int transform, const double* q, int nq, double* mean_out, double* q_out) {
-  if (nsamples < 1 || nsamples > 16384 || nrows < 1 || ncols < 1 || ndepth < 1 || nembeds < 1 || nembeds > MAX_K || !Ws || !Vs ||
-      !mean_out || nq < 0 || (nq > 0 && (!q || !q_out)) || transform < 0 || transform > 2)
-    return fail(nullptr, BTF_EINVAL, "bad posterior_summary arguments");
-  for (int k = 0; k < nq; ++k)
-    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(nullptr, BTF_EINVAL, "percentiles must lie in [0, 100]");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  const int MT = ncols * ndepth;
-  Scratch s(nullptr, nullptr);
-  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
-  const double* dV = s.upload(Vs, (size_t)nsamples * MT * nembeds);
-  summary_stage(s, dW, dV, nsamples, nrows, MT, nembeds, transform, q, nq, mean_out, q_out);
-  return s.finish();
-}
-
-// ---------------------------------------------------------------- posterior curve functionals (btf_functionals.h)
-namespace {
-
-struct FuncOut { double *mean, *var, *quant, *defined, *prob, *curves, *pw; };
-
-// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): scratch, the launches chunk by chunk, the downloads.
-// The scratch's context may be null (the stateless form: default stream, launches not counted).
-int functionals_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform,
-                    const int* which, int nwhich, const double* x, double level, double exceed, const double* q, int nq,
-                    const int* curves, int ncurves, const FuncOut& o) {
-  FuncArgs a = {};
-  a.W = dW; a.V = dV; a.level = level; a.exceed = exceed;
-  a.S = S; a.N = N; a.M = M; a.T = T; a.nslots = nwhich; a.nq = nq;
-  for (int f = 0; f < FUNC_COUNT; ++f) a.slot[f] = -1;
-  for (int k = 0; k < nwhich; ++k) { a.slot[which[k]] = k; a.code[k] = which[k]; }
-  const SortGeom g = sort_geom(S, FUNC_SORT_LDS, FUNC_SORT_CELLS);
-  a.P = g.P; a.cells = g.cells;
-  const size_t NM = (size_t)N * M, per_col = (size_t)nwhich * S * N;      // doubles of scratch a column takes
-  const int jc_max = (int)std::max<size_t>(1, std::min<size_t>(std::min(M, 65535), FUNC_SCRATCH_BYTES / (per_col * sizeof(double))));   // (a grid's y extent)
-  FuncKernel sweep = func_sweep_fn(K, transform), sort = func_sort_fn();
-  if (!sweep) return fail(s.ctx(), BTF_EINVAL, "posterior functionals: nembeds must be 1..10 and transform 0..2");
-  a.x = s.upload(x, (size_t)T);
-  a.vals = s.alloc<double>(per_col * jc_max);
-  if (o.mean) a.mean = s.alloc<double>(nwhich * NM);
-  if (o.var) a.var = s.alloc<double>(nwhich * NM);
-  if (o.prob) a.prob = s.alloc<double>(nwhich * NM);
-  if (o.defined) a.defined = s.alloc<double>(NM);
-  if (nq) { a.q = s.upload(q, (size_t)nq); a.quant = s.alloc<double>((size_t)nq * nwhich * NM); }
-  const int* dcv = nullptr;
-  double* dcur = nullptr;
-  if (ncurves) { dcv = s.upload(curves, (size_t)2 * ncurves); dcur = s.alloc<double>((size_t)nwhich * ncurves * S); }
-  if (o.pw) a.pw = s.alloc<double>((size_t)nwhich * S * NM);
-  allow_lds(s, sort, g.lds);
-  const int rowblocks = (N + WAVE - 1) / WAVE;
-  const bool reduce = o.mean || o.var || o.prob || o.defined || nq;
-  for (int j0 = 0; j0 < M; j0 += jc_max) {
-    a.j0 = j0; a.jc = std::min(jc_max, M - j0);
-    // sample slices: enough workgroups to fill the chip when rows x columns alone do not (geometry only)
-    const int zs = std::max(1, std::min((S + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * a.jc - 1) / (rowblocks * a.jc)));
-    launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, a.jc, zs), dim3(FUNC_WAVES * WAVE), 0, a);
-    if (ncurves) launch_counted(s, BTF_K_CRITERIA, func_gather_fn(), dim3(ncurves, nwhich), dim3(256), 0, a, dcv, ncurves, dcur);
-    if (reduce) launch_counted(s, BTF_K_CRITERIA, sort, dim3((N + a.cells - 1) / a.cells, a.jc, nwhich), dim3(256), g.lds, a);
-  }
-  s.download(o.mean, a.mean, nwhich * NM);
-  s.download(o.var, a.var, nwhich * NM);
-  s.download(o.prob, a.prob, nwhich * NM);
-  if (o.defined) {
-    if (a.slot[FUNC_CROSSING] < 0 && !s.rc()) s.check(hipMemsetAsync(a.defined, 0, NM * sizeof(double), s.stream()), "hipMemsetAsync");
-    s.download(o.defined, a.defined, NM);
-  }
-  if (nq) s.download(o.quant, a.quant, (size_t)nq * nwhich * NM);
-  if (ncurves) s.download(o.curves, dcur, (size_t)nwhich * ncurves * S);
-  s.download(o.pw, a.pw, (size_t)nwhich * S * NM);
-  return s.finish();
-}
-
-// argument checks shared by the two entry points; everything here runs before any device call
-int functionals_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, const int* which, int nwhich, const double* x,
-                      double level, const double* q, int nq, const int* curves, int ncurves, const FuncOut& o) {
-  if (S < 1 || N < 1 || M < 1 || K < 1 || K > MAX_K || transform < 0 || transform > 2 || !which || nwhich < 1 || nwhich > FUNC_COUNT ||
-      !x || nq < 0 || (nq > 0 && (!q || !o.quant)) || ncurves < 0 || (ncurves > 0 && (!curves || !o.curves)))
-    return fail(c, BTF_EINVAL, "bad posterior functionals arguments");
-  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior functionals: at most " + std::to_string(FUNC_MAX_S) + " samples (one curve's values are sorted in LDS)");
-  if (T < 2) return fail(c, BTF_EINVAL, "posterior functionals: a curve needs ndepth >= 2");
-  bool seen[FUNC_COUNT] = {false};
-  for (int k = 0; k < nwhich; ++k) {
-    if (which[k] < 0 || which[k] >= FUNC_COUNT || seen[which[k]]) return fail(c, BTF_EINVAL, "posterior functionals: functional codes must be distinct and in 0..6");
-    seen[which[k]] = true;
-  }
-  if (seen[FUNC_CROSSING] && !(level == level)) return fail(c, BTF_EINVAL, "posterior functionals: crossing needs a level");
-  for (int t = 1; t < T; ++t)
-    if (!(x[t] > x[t - 1])) return fail(c, BTF_EINVAL, "posterior functionals: x must be strictly increasing");
-  for (int k = 0; k < nq; ++k)
-    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
-  for (int k = 0; k < ncurves; ++k)
-    if (curves[2 * k] < 0 || curves[2 * k] >= N || curves[2 * k + 1] < 0 || curves[2 * k + 1] >= M)
-      return fail(c, BTF_EINVAL, "posterior functionals: curve index out of range");
-  return BTF_OK;
-}
-
-}  // namespace
-
-int btf_posterior_functionals(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
-                              int transform, const int* which, int nwhich, const double* x, double level, double exceed,
-                              const double* q, int nq, const int* curves, int ncurves, double* mean_out, double* var_out,
-                              double* q_out, double* defined_out, double* prob_out, double* curves_out, double* pointwise_out) {
-  const FuncOut o = {mean_out, var_out, q_out, defined_out, prob_out, curves_out, pointwise_out};
-  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior functionals arguments");
-  int rc = functionals_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, q, nq, curves, ncurves, o);
-  if (rc) return rc;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  Scratch s(nullptr, nullptr);
-  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
-  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
-  return functionals_run(s, dW, dV, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, exceed, q, nq,
-                         curves, ncurves, o);
-}
-
-// the same on the first nsamples collected states, read where they lie (no upload)
-int btf_collect_functionals(btf_ctx* c, int nsamples, int transform, const int* which, int nwhich, const double* x, double level,
-                            double exceed, const double* q, int nq, const int* curves, int ncurves, double* mean_out, double* var_out,
-                            double* q_out, double* defined_out, double* prob_out, double* curves_out, double* pointwise_out) {
-  if (!c) return fail(c, BTF_EINVAL, "bad posterior functionals arguments");
-  const FuncOut o = {mean_out, var_out, q_out, defined_out, prob_out, curves_out, pointwise_out};
-  int rc = functionals_check(c, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, q, nq, curves, ncurves, o);
-  if (rc) return rc;
-  if (!c->smp_W || !c->smp_V || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_functionals: not that many collected samples");
-  HIPCHK(c, hipSetDevice(c->dev));
-  Scratch s(c, c->stream);
-  return functionals_run(s, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
-                         q, nq, curves, ncurves, o);
-}
-
-// ---------------------------------------------------------------- posterior ranking (btf_ranking.h)
-namespace {
-
-struct RankOut { double *expected, *var, *ptop; int* ranks; double *prob_less, *prob_defined; };
-
-// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): per chunk of samples the functionals' sweep into the
-// scratch, the gather and count of the pairs, the rank kernel; then the finish kernel and the downloads.  scratch_bytes
-// caps the chunk's scratch (0: FUNC_SCRATCH_BYTES; one sample is the least a chunk holds).
-int ranking_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform, int which,
-                const double* x, double level, int along, int descending, const int* top, int ntop, const int* pairs, int npairs,
-                const RankOut& o, long long scratch_bytes) {
-  FuncKernel sweep = func_sweep_fn(K, transform);
-  if (!sweep) return fail(s.ctx(), BTF_EINVAL, "posterior ranking: nembeds must be 1..10 and transform 0..2");
-  const size_t NM = (size_t)N * M, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
-  const int sc_max = (int)std::max<size_t>(1, std::min<size_t>(S, cap / (NM * sizeof(double))));
-  FuncArgs f = {};
-  f.level = level; f.exceed = std::nan(""); f.N = N; f.M = M; f.T = T; f.nslots = 1;
-  for (int k = 0; k < FUNC_COUNT; ++k) f.slot[k] = -1;
-  f.slot[which] = 0; f.code[0] = which;
-  f.x = s.upload(x, (size_t)T);
-  double* vals = s.alloc<double>(NM * sc_max);
-  RankArgs r = {};
-  r.vals = vals; r.S = S; r.N = N; r.M = M; r.along = along; r.ntop = ntop; r.P = npairs;
-  for (int k = 0; k < ntop; ++k) r.top[k] = std::min(top[k], RANK_MAX_L + 1);      // (a rank never exceeds RANK_MAX_L)
-  r.L = along ? N : M;
-  while ((1 << r.lshift) < r.L) ++r.lshift;
-  r.Lp = 1 << r.lshift;
-  const int ngroups = along ? M : N;
-  r.G = std::max(1, std::min(ngroups, std::min(RANK_MAX_L / r.Lp, RANK_MAX_GROUPS)));
-  const size_t lds = rank_lds_bytes(r.G, r.Lp);
-  const int tiles = (ngroups + r.G - 1) / r.G;
-  r.A = s.alloc<unsigned long long>(NM);
-  r.B = s.alloc<unsigned long long>(NM);
-  r.C = s.alloc<unsigned int>((size_t)ntop * NM);
-  if (o.ranks) r.ranks = s.alloc<int>((size_t)S * NM);
-  r.expected = s.alloc<double>(NM); r.var = s.alloc<double>(NM); r.ptop = s.alloc<double>((size_t)ntop * NM);
-  const int* dpairs = nullptr;
-  double* dpv = nullptr;
-  if (npairs) {
-    dpairs = s.upload(pairs, (size_t)4 * npairs);             // (i,j,i2,j2) rows = 2 npairs (i,j) curves for the gather
-    dpv = s.alloc<double>((size_t)2 * npairs * sc_max);
-    r.pvals = dpv;
-    r.pless = s.alloc<unsigned int>(npairs); r.pdef = s.alloc<unsigned int>(npairs);
-    r.prob_less = s.alloc<double>(npairs); r.prob_defined = s.alloc<double>(npairs);
-  }
-  auto zero = [&](void* p, size_t bytes) { if (!s.rc()) s.check(hipMemsetAsync(p, 0, bytes, s.stream()), "hipMemsetAsync"); };
-  zero(r.A, NM * sizeof(unsigned long long)); zero(r.B, NM * sizeof(unsigned long long)); zero(r.C, (size_t)ntop * NM * sizeof(unsigned int));
-  if (npairs) { zero(r.pless, npairs * sizeof(unsigned int)); zero(r.pdef, npairs * sizeof(unsigned int)); }
-  RankKernel rank = rank_fn(descending != 0);
-  const int rowblocks = (N + WAVE - 1) / WAVE, JMAX = 65535;   // (a grid's y extent)
-  for (int s0 = 0; s0 < S; s0 += sc_max) {
-    const int sc = std::min(sc_max, S - s0);
-    f.W = dW + (size_t)s0 * N * K; f.V = dV + (size_t)s0 * M * T * K; f.S = sc;
-    for (int j0 = 0; j0 < M; j0 += JMAX) {                     // vals[column][sample of the chunk][row]
-      f.j0 = j0; f.jc = std::min(JMAX, M - j0); f.vals = vals + (size_t)j0 * sc * N;
-      const int zs = std::max(1, std::min((sc + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * f.jc - 1) / (rowblocks * f.jc)));
-      launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, f.jc, zs), dim3(FUNC_WAVES * WAVE), 0, f);
-    }
-    r.s0 = s0; r.sc = sc;
-    if (npairs) {
-      f.j0 = 0; f.jc = M; f.vals = vals;
-      launch_counted(s, BTF_K_CRITERIA, func_gather_fn(), dim3(2 * npairs, 1), dim3(256), 0, f, dpairs, 2 * npairs, dpv);
-      launch_counted(s, BTF_K_CRITERIA, rank_pairs_fn(), dim3(npairs), dim3(256), 0, r);
-    }
-    // sample slices: enough workgroups for two per CU when the tiles alone are fewer (geometry only)
-    const int ys = std::max(1, std::min(sc, (1024 + tiles - 1) / tiles));
-    launch_counted(s, BTF_K_CRITERIA, rank, dim3(tiles, ys), dim3(RANK_THREADS), lds, r);
-  }
-  launch_counted(s, BTF_K_CRITERIA, rank_finish_fn(), dim3((unsigned)((NM + npairs + 255) / 256)), dim3(256), 0, r);
-  s.download(o.expected, r.expected, NM);
-  s.download(o.var, r.var, NM);
-  s.download(o.ptop, r.ptop, (size_t)ntop * NM);
-  s.download(o.ranks, r.ranks, (size_t)S * NM);
-  if (npairs) { s.download(o.prob_less, r.prob_less, (size_t)npairs); s.download(o.prob_defined, r.prob_defined, (size_t)npairs); }
-  return s.finish();
-}
-
-// argument checks shared by the two entry points; everything here runs before any device call
-int ranking_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, int which, const double* x, double level, int along,
-                  int descending, const int* top, int ntop, const int* pairs, int npairs, const RankOut& o, long long scratch_bytes) {
-  if (S < 1 || N < 1 || M < 1 || K < 1 || K > MAX_K || transform < 0 || transform > 2 || which < 0 || which >= FUNC_COUNT || !x ||
-      along < 0 || along > 1 || descending < 0 || descending > 1 || !top || ntop < 1 || ntop > RANK_MAX_TOP || npairs < 0 ||
-      (npairs > 0 && (!pairs || !o.prob_less || !o.prob_defined)) || scratch_bytes < 0)
-    return fail(c, BTF_EINVAL, "bad posterior ranking arguments");
-  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior ranking: at most " + std::to_string(FUNC_MAX_S) + " samples");
-  if ((along ? N : M) > RANK_MAX_L)
-    return fail(c, BTF_EINVAL, "posterior ranking: at most " + std::to_string(RANK_MAX_L) + " members in a group (it is sorted in LDS)");
-  if (T < 2) return fail(c, BTF_EINVAL, "posterior ranking: a curve needs ndepth >= 2");
-  if (which == FUNC_CROSSING && !(level == level)) return fail(c, BTF_EINVAL, "posterior ranking: crossing needs a level");
-  for (int t = 1; t < T; ++t)
-    if (!(x[t] > x[t - 1])) return fail(c, BTF_EINVAL, "posterior ranking: x must be strictly increasing");
-  for (int k = 0; k < ntop; ++k) {
-    if (top[k] < 1) return fail(c, BTF_EINVAL, "posterior ranking: top must hold integers >= 1");
-    for (int l = 0; l < k; ++l)
-      if (top[l] == top[k]) return fail(c, BTF_EINVAL, "posterior ranking: top must hold distinct integers");
-  }
-  for (int k = 0; k < 2 * npairs; ++k)
-    if (pairs[2 * k] < 0 || pairs[2 * k] >= N || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= M)
-      return fail(c, BTF_EINVAL, "posterior ranking: pair index out of range");
-  return BTF_OK;
-}
-
-}  // namespace
-
-int btf_posterior_ranking(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
-                          int transform, int which, const double* x, double level, int along, int descending, const int* top, int ntop,
-                          const int* pairs, int npairs, double* expected_out, double* var_out, double* ptop_out, int* ranks_out,
-                          double* prob_less_out, double* prob_defined_out, long long scratch_bytes) {
-  const RankOut o = {expected_out, var_out, ptop_out, ranks_out, prob_less_out, prob_defined_out};
-  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior ranking arguments");
-  int rc = ranking_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, which, x, level, along, descending, top, ntop,
-                         pairs, npairs, o, scratch_bytes);
-  if (rc) return rc;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  Scratch s(nullptr, nullptr);
-  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
-  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
-  return ranking_run(s, dW, dV, nsamples, nrows, ncols, ndepth, nembeds, transform, which, x, level, along, descending, top, ntop,
-                     pairs, npairs, o, scratch_bytes);
-}
-
-// the same on the first nsamples collected states, read where they lie (no upload)
-int btf_collect_ranking(btf_ctx* c, int nsamples, int transform, int which, const double* x, double level, int along, int descending,
-                        const int* top, int ntop, const int* pairs, int npairs, double* expected_out, double* var_out,
-                        double* ptop_out, int* ranks_out, double* prob_less_out, double* prob_defined_out, long long scratch_bytes) {
-  if (!c) return fail(c, BTF_EINVAL, "bad posterior ranking arguments");
-  const RankOut o = {expected_out, var_out, ptop_out, ranks_out, prob_less_out, prob_defined_out};
-  int rc = ranking_check(c, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop, pairs, npairs,
-                         o, scratch_bytes);
-  if (rc) return rc;
-  if (!c->smp_W || !c->smp_V || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_ranking: not that many collected samples");
-  HIPCHK(c, hipSetDevice(c->dev));
-  Scratch s(c, c->stream);
-  return ranking_run(s, c->smp_W, c->smp_V, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop,
-                     pairs, npairs, o, scratch_bytes);
-}
-
-// ---------------------------------------------------------------- posterior feature association (btf_assoc.h)
-namespace {
-
-struct AssocOut { double *mean, *var, *quant, *prob, *defined, *nmean, *values, *of_means, *sdx, *sdy; };
-
-// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K), dU (S,F,K): per chunk of samples the functionals' sweep
-// into the scratch, the moments of every (sample, column) and the running curve means; then the reduction over the samples
-// per (feature, column), the raw values of the requested pairs, the plug-in table, and the downloads.  scratch_bytes caps
-// the chunk's scratch (0: FUNC_SCRATCH_BYTES; one sample is the least a chunk holds).
-int assoc_run(Scratch& s, const double* dW, const double* dV, const double* dU, int S, int N, int M, int T, int K, int F, int transform,
-              int which, const double* x, double level, const int* stats, int nstats, const double* q, int nq, const int* pairs,
-              int npairs, const AssocOut& o, long long scratch_bytes) {
-  FuncKernel sweep = func_sweep_fn(K, transform);
-  AssocKernel moments = assoc_moments_fn(K), reduce = assoc_reduce_fn(K);
-  if (!sweep || !moments || !reduce) return fail(s.ctx(), BTF_EINVAL, "posterior association: nembeds must be 1..10 and transform 0..2");
-  const size_t NM = (size_t)N * M, FM = (size_t)F * M, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
-  const int sc_max = (int)std::max<size_t>(1, std::min<size_t>(S, cap / (NM * sizeof(double))));
-  FuncArgs f = {};
-  f.level = level; f.exceed = std::nan(""); f.N = N; f.M = M; f.T = T; f.nslots = 1;
-  for (int k = 0; k < FUNC_COUNT; ++k) f.slot[k] = -1;
-  f.slot[which] = 0; f.code[0] = which;
-  f.x = s.upload(x, (size_t)T);
-  double* vals = s.alloc<double>(NM * sc_max);
-  AssocArgs a = {};
-  a.vals = vals; a.W = dW; a.U = dU; a.S = S; a.N = N; a.M = M; a.F = F;
-  a.mom = s.alloc<double>((size_t)S * M * assoc_nmom(K));
-  a.nst = nstats;
-  for (int k = 0; k < nstats; ++k) a.st[k] = stats[k];
-  const SortGeom g = sort_geom(S, ASSOC_SORT_LDS, ASSOC_ROWS);      // rows of P doubles; a pair takes one per statistic
-  a.P = g.P;
-  while ((1 << a.pshift) < a.P) ++a.pshift;
-  a.cells = std::max(1, std::min(g.cells / nstats, F));
-  const size_t lds = (size_t)a.cells * nstats * a.P * sizeof(double);
-  a.nq = nq;
-  if (nq) { a.q = s.upload(q, (size_t)nq); a.quant = s.alloc<double>((size_t)nstats * nq * FM); }
-  a.mean = s.alloc<double>(nstats * FM); a.var = s.alloc<double>(nstats * FM); a.prob = s.alloc<double>(nstats * FM);
-  a.defined = s.alloc<double>(FM); a.nmean = s.alloc<double>(M);
-  if (npairs) { a.npairs = npairs; a.pairs = s.upload(pairs, (size_t)2 * npairs); a.values = s.alloc<double>((size_t)nstats * npairs * S); }
-  const bool plug = o.of_means != nullptr;
-  auto zero = [&](void* p, size_t bytes) { if (!s.rc()) s.check(hipMemsetAsync(p, 0, bytes, s.stream()), "hipMemsetAsync"); };
-  if (plug) {
-    a.pbar = s.alloc<double>((size_t)F * N); a.gbar = s.alloc<double>(NM); a.gcnt = s.alloc<int>(NM);
-    a.om = s.alloc<double>(ASSOC_OM * FM); a.sdx = s.alloc<double>(F); a.sdy = s.alloc<double>(M);
-    zero(a.gbar, NM * sizeof(double)); zero(a.gcnt, NM * sizeof(int));
-  }
-  allow_lds(s, reduce, lds);
-  const int rowblocks = (N + WAVE - 1) / WAVE, JMAX = 65535;   // (a grid's y extent)
-  const unsigned rb = (unsigned)((N + ASSOC_THREADS - 1) / ASSOC_THREADS);
-  for (int s0 = 0; s0 < S; s0 += sc_max) {
-    const int sc = std::min(sc_max, S - s0);
-    f.W = dW + (size_t)s0 * N * K; f.V = dV + (size_t)s0 * M * T * K; f.S = sc;
-    for (int j0 = 0; j0 < M; j0 += JMAX) {                     // vals[column][sample of the chunk][row]
-      f.j0 = j0; f.jc = std::min(JMAX, M - j0); f.vals = vals + (size_t)j0 * sc * N;
-      const int zs = std::max(1, std::min((sc + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * f.jc - 1) / (rowblocks * f.jc)));
-      launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, f.jc, zs), dim3(FUNC_WAVES * WAVE), 0, f);
-    }
-    a.s0 = s0; a.sc = sc;
-    launch_counted(s, BTF_K_CRITERIA, moments, dim3(M, sc), dim3(WAVE), 0, a);
-    if (plug) launch_counted(s, BTF_K_CRITERIA, assoc_gbar_fn(), dim3(rb * M), dim3(ASSOC_THREADS), 0, a);
-  }
-  const unsigned ftiles = (unsigned)((F + a.cells - 1) / a.cells);
-  launch_counted(s, BTF_K_CRITERIA, reduce, dim3(ftiles * M), dim3(ASSOC_THREADS), lds, a);
-  if (npairs) launch_counted(s, BTF_K_CRITERIA, assoc_values_fn(K), dim3(npairs), dim3(ASSOC_THREADS), 0, a);
-  if (plug) {
-    launch_counted(s, BTF_K_CRITERIA, assoc_pbar_fn(K), dim3(rb * ((F + ASSOC_FT - 1) / ASSOC_FT)), dim3(ASSOC_THREADS), 0, a);
-    launch_counted(s, BTF_K_CRITERIA, assoc_gbar_finish_fn(), dim3((unsigned)((NM + ASSOC_THREADS - 1) / ASSOC_THREADS)), dim3(ASSOC_THREADS), 0, a);
-    launch_counted(s, BTF_K_CRITERIA, assoc_cross_fn(), dim3((unsigned)F * ((M + 3) / 4)), dim3(ASSOC_THREADS), 0, a);
-  }
-  s.download(o.mean, a.mean, nstats * FM);
-  s.download(o.var, a.var, nstats * FM);
-  s.download(o.prob, a.prob, nstats * FM);
-  if (nq) s.download(o.quant, a.quant, (size_t)nstats * nq * FM);
-  s.download(o.defined, a.defined, FM);
-  s.download(o.nmean, a.nmean, (size_t)M);
-  if (npairs) s.download(o.values, a.values, (size_t)nstats * npairs * S);
-  if (plug) { s.download(o.of_means, a.om, ASSOC_OM * FM); s.download(o.sdx, a.sdx, (size_t)F); s.download(o.sdy, a.sdy, (size_t)M); }
-  return s.finish();
-}
-
-// argument checks shared by the two entry points; everything here runs before any device call
-int assoc_check(btf_ctx* c, int S, int N, int M, int T, int K, int F, const double* Us, int transform, int which, const double* x,
-                double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs, const AssocOut& o,
-                long long scratch_bytes) {
-  if (S < 1 || N < 1 || M < 1 || F < 1 || K < 1 || K > MAX_K || !Us || transform < 0 || transform > 2 || which < 0 || which >= FUNC_COUNT ||
-      !x || !stats || nstats < 1 || nstats > ASSOC_NSTATS || nq < 0 || (nq > 0 && (!q || !o.quant)) || npairs < 0 ||
-      (npairs > 0 && (!pairs || !o.values)) || (o.of_means && (!o.sdx || !o.sdy)) || scratch_bytes < 0)
-    return fail(c, BTF_EINVAL, "bad posterior association arguments");
-  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior association: at most " + std::to_string(FUNC_MAX_S) + " samples (the values of a pair are sorted in LDS)");
-  if ((long long)F * M > 0x7fffffffLL || (long long)N * M > 0x7fffffffLL * (long long)ASSOC_THREADS)
-    return fail(c, BTF_EINVAL, "posterior association: too many (feature, column) pairs or curves for one launch");
-  if (T < 2) return fail(c, BTF_EINVAL, "posterior association: a curve needs ndepth >= 2");
-  if (which == FUNC_CROSSING && !(level == level)) return fail(c, BTF_EINVAL, "posterior association: crossing needs a level");
-  for (int t = 1; t < T; ++t)
-    if (!(x[t] > x[t - 1])) return fail(c, BTF_EINVAL, "posterior association: x must be strictly increasing");
-  for (int k = 0; k < nstats; ++k)
-    if (stats[k] < 0 || stats[k] >= ASSOC_NSTATS || (k > 0 && stats[k] == stats[0]))
-      return fail(c, BTF_EINVAL, "posterior association: statistic codes must be distinct and in 0..1");
-  for (int k = 0; k < nq; ++k)
-    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
-  for (int k = 0; k < npairs; ++k)
-    if (pairs[2 * k] < 0 || pairs[2 * k] >= F || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= M)
-      return fail(c, BTF_EINVAL, "posterior association: pair index out of range");
-  return BTF_OK;
-}
-
-}  // namespace
-
-int btf_posterior_association(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, int nfeatures, const double* Ws,
-                              const double* Vs, const double* Us, int transform, int which, const double* x, double level,
-                              const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs, double* mean_out,
-                              double* var_out, double* q_out, double* prob_out, double* defined_out, double* nmean_out,
-                              double* values_out, double* of_means_out, double* sdx_out, double* sdy_out, long long scratch_bytes) {
-  const AssocOut o = {mean_out, var_out, q_out, prob_out, defined_out, nmean_out, values_out, of_means_out, sdx_out, sdy_out};
-  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior association arguments");
-  int rc = assoc_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, nfeatures, Us, transform, which, x, level, stats, nstats, q, nq,
-                       pairs, npairs, o, scratch_bytes);
-  if (rc) return rc;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  Scratch s(nullptr, nullptr);
-  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
-  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
-  const double* dU = s.upload(Us, (size_t)nsamples * nfeatures * nembeds);
-  return assoc_run(s, dW, dV, dU, nsamples, nrows, ncols, ndepth, nembeds, nfeatures, transform, which, x, level, stats, nstats, q, nq,
-                   pairs, npairs, o, scratch_bytes);
-}
-
-// the same on the first nsamples collected states, read where they lie; only Us (the host keeps U) is uploaded
-int btf_collect_association(btf_ctx* c, int nsamples, int nfeatures, const double* Us, int transform, int which, const double* x,
-                            double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs,
-                            double* mean_out, double* var_out, double* q_out, double* prob_out, double* defined_out, double* nmean_out,
-                            double* values_out, double* of_means_out, double* sdx_out, double* sdy_out, long long scratch_bytes) {
-  if (!c) return fail(c, BTF_EINVAL, "bad posterior association arguments");
-  const AssocOut o = {mean_out, var_out, q_out, prob_out, defined_out, nmean_out, values_out, of_means_out, sdx_out, sdy_out};
-  int rc = assoc_check(c, nsamples, c->N, c->M, c->T, c->K, nfeatures, Us, transform, which, x, level, stats, nstats, q, nq, pairs, npairs,
-                       o, scratch_bytes);
-  if (rc) return rc;
-  if (!c->smp_W || !c->smp_V || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_association: not that many collected samples");
-  HIPCHK(c, hipSetDevice(c->dev));
-  Scratch s(c, c->stream);
-  const double* dU = s.upload(Us, (size_t)nsamples * nfeatures * c->K);
-  return assoc_run(s, c->smp_W, c->smp_V, dU, nsamples, c->N, c->M, c->T, c->K, nfeatures, transform, which, x, level, stats, nstats, q, nq,
-                   pairs, npairs, o, scratch_bytes);
-}
-
-// ---------------------------------------------------------------- monotone projection of the posterior (btf_monotone.h)
-namespace {
-
-// The projection of the device states dW (S,N,K), dVin (S,M,T,K) into dVout (dVin itself: in place), the summary of the
-// projected states where they lie, and the downloads.  Null outputs are skipped; mean_out null: no summary.
-int mono_run(Scratch& s, const double* dW, const double* dVin, double* dVout, int S, int N, int M, int T, int K, int increasing,
-             int transform, const double* q, int nq, double* V_out, int* pools_out, double* mean_out, double* q_out) {
-  MonoKernel project = mono_project_fn(K);
-  if (!project) return fail(s.ctx(), BTF_EINVAL, "posterior monotone: nembeds must be 1..10");
-  const size_t nW = (size_t)N * K, nV = (size_t)M * T * K, YMAX = 65535;   // (a grid's y extent)
-  int* dpools = s.alloc<int>((size_t)S * M);
-  MonoArgs a = {};
-  a.N = N; a.M = M; a.T = T; a.increasing = increasing ? 1 : 0;
-  for (size_t s0 = 0; s0 < (size_t)S; s0 += YMAX) {
-    const unsigned sc = (unsigned)std::min<size_t>(YMAX, (size_t)S - s0);
-    a.W = dW + s0 * nW; a.Vin = dVin + s0 * nV; a.Vout = dVout + s0 * nV; a.pools = dpools + s0 * M;
-    launch_counted(s, BTF_K_CRITERIA, project, dim3((unsigned)M, sc), dim3(MONO_THREADS), mono_lds(T, K), a);
-  }
-  if (mean_out) summary_stage(s, dW, dVout, S, N, M * T, K, transform, q, nq, mean_out, q_out);
-  s.download(V_out, (const double*)dVout, (size_t)S * nV);
-  s.download(pools_out, (const int*)dpools, (size_t)S * M);
-  return s.finish();
-}
-
-// argument checks shared by the two entry points; everything here runs before any device call
-int mono_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, const double* q, int nq, const double* mean_out,
-               const double* q_out) {
-  if (S < 1 || N < 1 || M < 1 || T < 1 || K < 1 || K > MAX_K || nq < 0 || (nq > 0 && (!q || !q_out || !mean_out)) ||
-      (mean_out && (transform < 0 || transform > 2)))
-    return fail(c, BTF_EINVAL, "bad posterior monotone arguments");
-  if (mean_out && S > 16384) return fail(c, BTF_EINVAL, "posterior monotone: at most 16384 samples with a summary (its values are sorted in LDS)");
-  if (!mono_fits(T, K))
-    return fail(c, BTF_EINVAL, "posterior monotone: ndepth * nembeds too large for the PAV kernels (pav_fits: 8 T K + 4 T <= 65536 bytes of LDS)");
-  if ((long long)M * T > 0x7fffffffLL) return fail(c, BTF_EINVAL, "posterior monotone: too many cells for one launch");
-  for (int k = 0; k < nq; ++k)
-    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
-  return BTF_OK;
-}
-
-}  // namespace
-
-int btf_posterior_monotone(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
-                           int increasing, int transform, const double* q, int nq, double* V_out, int* pools_out, double* mean_out,
-                           double* q_out) {
-  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior monotone arguments");
-  int rc = mono_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, q, nq, mean_out, q_out);
-  if (rc) return rc;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  Scratch s(nullptr, nullptr);
-  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
-  double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);       // the scratch's own copy: projected where it lies
-  return mono_run(s, dW, dV, dV, nsamples, nrows, ncols, ndepth, nembeds, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
-}
-
-// the same on the first nsamples collected states, read where they lie (Ws = Vs = NULL), or on uploaded states on the
-// context's device and stream; in_place overwrites the collected V samples and needs no second copy of them
-int btf_collect_monotone(btf_ctx* c, int nsamples, const double* Ws, const double* Vs, int increasing, int in_place, int transform,
-                         const double* q, int nq, double* V_out, int* pools_out, double* mean_out, double* q_out) {
-  if (!c || (Ws == nullptr) != (Vs == nullptr)) return fail(c, BTF_EINVAL, "bad posterior monotone arguments");
-  int rc = mono_check(c, nsamples, c->N, c->M, c->T, c->K, transform, q, nq, mean_out, q_out);
-  if (rc) return rc;
-  if (in_place && Ws) return fail(c, BTF_EINVAL, "btf_collect_monotone: in_place projects the collected samples, not uploaded states");
-  if (!Ws && (!c->smp_W || !c->smp_V || nsamples > c->smp_n)) return fail(c, BTF_EINVAL, "btf_collect_monotone: not that many collected samples");
-  HIPCHK(c, hipSetDevice(c->dev));
-  Scratch s(c, c->stream);
-  const size_t nV = (size_t)nsamples * c->M * c->T * c->K;
-  if (Ws) {
-    const double* dW = s.upload(Ws, (size_t)nsamples * c->N * c->K);
-    double* dV = s.upload(Vs, nV);
-    return mono_run(s, dW, dV, dV, nsamples, c->N, c->M, c->T, c->K, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
-  }
-  double* dVout = in_place ? c->smp_V : s.alloc<double>(nV);
-  return mono_run(s, c->smp_W, c->smp_V, dVout, nsamples, c->N, c->M, c->T, c->K, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
-}
-
-// ---------------------------------------------------------------- folding new rows in (btf_fold_in.h)
-namespace {
-
-thread_local int g_fold_fail_index = -1;      // btf_fail_index(NULL): the failing (sample, row) of the last stateless call
-
-struct FoldIn {
-  int family, S, R, M, T, K;
-  const double *count, *ysum, *trials, *z;
-  unsigned long long seed;
-  int inner_sweeps;
-  long long sample0;
-  double *W_out, *Wmean_out;
-  int transform;
-  const double* q; int nq;
-  double *mean_out, *q_out;
-};
-
-// everything that can be refused without a device
-int fold_in_check(btf_ctx* c, const FoldIn& f) {
-  if (f.family < FOLD_GAUSSIAN || f.family > FOLD_BINOMIAL || f.S < 1 || f.R < 1 || f.M < 1 || f.T < 1 || f.K < 1 || f.K > MAX_K ||
-      !f.ysum || !f.W_out || f.sample0 < 0 || f.nq < 0 || (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2)
-    return fail(c, BTF_EINVAL, "bad fold_in arguments");
-  if (f.family == FOLD_GAUSSIAN && !f.count) return fail(c, BTF_EINVAL, "fold_in: the Gaussian family needs count");
-  if (f.family == FOLD_BINOMIAL && (!f.trials || f.z || f.inner_sweeps < 1))
-    return fail(c, BTF_EINVAL, "fold_in: the Binomial family needs trials and inner_sweeps >= 1, and takes no z");
-  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "fold_in: the summary stage takes at most 16384 samples");
-  if ((double)(f.sample0 + f.S) * f.R >= 2147483647.0 || (double)f.R * f.M * f.T >= 2147483647.0)
-    return fail(c, BTF_EINVAL, "fold_in: (sample0 + nsamples) * nrows_new and nrows_new * ncols * ndepth must stay below 2^31");
-  for (int k = 0; k < f.nq; ++k)
-    if (!(f.q[k] >= 0.0 && f.q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
-  const size_t n = (size_t)f.R * f.M * f.T;
-  const double* cw = f.family == FOLD_GAUSSIAN ? f.count : f.trials;
-  for (size_t e = 0; e < n; ++e) {
-    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(f.ysum[e]) < INFINITY))
-      return fail(c, BTF_EINVAL, "fold_in: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
-    if (f.family == FOLD_BINOMIAL && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLD_MAX_TRIALS))
-      return fail(c, BTF_EINVAL, "fold_in: Binomial trial counts must be integers up to " + std::to_string(FOLD_MAX_TRIALS));
-  }
-  return BTF_OK;
-}
-
-// The launches on device states dV (S,M,T,K) and per-sample scalars on the device (noise may be null: 1).  The scratch's
-// context may be null (the stateless form: default stream, launches not counted).  W stays on the device between the draw
-// and the summary.
-int fold_in_run(Scratch& s, const double* dV, const double* dnoise, int nstride, const double* dsig, int sstride, const FoldIn& f) {
-  btf_ctx* c = s.ctx();
-  const int S = f.S, R = f.R, MT = f.M * f.T, K = f.K;
-  FoldKernel kern = fold_in_fn(K, f.family);
-  if (!kern) return fail(c, BTF_EINVAL, "fold_in: nembeds must be 1..10 and family 0..1");
-  // row statistics in the kernel's [cell][row] layout; Binomial: kappa = successes - trials / 2
-  std::vector<double> hc((size_t)MT * R), hy((size_t)MT * R);
-  const double* cw = f.family == FOLD_GAUSSIAN ? f.count : f.trials;
-  for (int r = 0; r < R; ++r)
-    for (int jt = 0; jt < MT; ++jt) {
-      const double cv = cw[(size_t)r * MT + jt], yv = f.ysum[(size_t)r * MT + jt];
-      hc[(size_t)jt * R + r] = cv;
-      hy[(size_t)jt * R + r] = f.family == FOLD_BINOMIAL ? (cv > 0.0 ? yv - 0.5 * cv : 0.0) : (cv > 0.0 ? yv : 0.0);
-    }
-  const size_t nW = (size_t)S * R * K, cellsN = (size_t)R * MT;
-  const int stat0[2] = {0, INT_MAX};
-  FoldArgs a = {};
-  a.V = dV; a.noise = dnoise; a.sigma2 = dsig; a.nstride = nstride; a.sstride = sstride;
-  a.cnt = s.upload(hc.data(), cellsN); a.ysum = s.upload(hy.data(), cellsN);
-  a.W = s.alloc<double>(nW); a.status = s.upload(stat0, 2);
-  if (f.Wmean_out) a.Wmean = s.alloc<double>(nW);
-  if (f.z) a.z = s.upload(f.z, nW);
-  a.seed = f.seed; a.sample0 = f.sample0; a.S = S; a.R = R; a.MT = MT; a.sweeps = f.inner_sweeps;
-  launch_counted(s, BTF_K_CRITERIA, kern, dim3(S, (R + WAVE - 1) / WAVE), dim3(FOLD_PARTS * WAVE), 0, a);
-  // the summary stage reads the device-resident W (S,R,K) and V
-  if (f.mean_out) summary_stage(s, a.W, dV, S, R, MT, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
-  int stat[2] = {0, INT_MAX};
-  s.download(stat, a.status, 2);
-  s.download(f.W_out, a.W, nW);
-  s.download(f.Wmean_out, a.Wmean, nW);
-  const int rc = s.finish();
-  if (rc) return rc;
-  if (stat[0]) {
-    if (c) c->fail_index = stat[1];
-    g_fold_fail_index = stat[1];
-    return fail(c, BTF_ENOTPD, "fold_in: the precision of (sample, row) index " + std::to_string(stat[1]) +
-                                   " = sample * nrows_new + row is not positive definite (or nu2 / sigma2 / V not finite)");
-  }
-  return BTF_OK;
-}
-
-}  // namespace
-
-int fold_fail_index() { return g_fold_fail_index; }
-
-int btf_fold_in_rows(int device, int family, int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs,
-                     const double* noise, const double* sigma2, const double* count, const double* ysum, const double* trials,
-                     const double* z, unsigned long long seed, int inner_sweeps, long long sample0, double* W_out, double* Wmean_out,
-                     int transform, const double* q, int nq, double* mean_out, double* q_out) {
-  const FoldIn f = {family, nsamples, nrows_new, ncols, ndepth, nembeds, count, ysum, trials, z, seed, inner_sweeps, sample0,
-                    W_out, Wmean_out, transform, q, nq, mean_out, q_out};
-  g_fold_fail_index = -1;
-  if (!Vs || !sigma2 || (family == FOLD_GAUSSIAN && !noise)) return fail(nullptr, BTF_EINVAL, "bad fold_in arguments");
-  int rc = fold_in_check(nullptr, f);
-  if (rc) return rc;
-  for (int s = 0; s < nsamples; ++s)
-    if (!(sigma2[s] > 0.0 && sigma2[s] < INFINITY) || (family == FOLD_GAUSSIAN && !(noise[s] > 0.0 && noise[s] < INFINITY)))
-      return fail(nullptr, BTF_EINVAL, "fold_in: nu2 and sigma2 must be finite and positive");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  Scratch s(nullptr, nullptr);
-  const double* dV = s.upload(Vs, (size_t)nsamples * ncols * ndepth * nembeds);
-  const double* ds = s.upload(sigma2, (size_t)nsamples);
-  const double* dn = family == FOLD_GAUSSIAN ? s.upload(noise, (size_t)nsamples) : nullptr;
-  return fold_in_run(s, dV, dn, 1, ds, 1, f);
-}
-
-// the same on the first nsamples collected states, read where they lie (no upload): V from the sample slots, nu2_s and
-// sigma2_s from the collected scalars
-int btf_collect_fold_in(btf_ctx* c, int family, int nsamples, int nrows_new, const double* count, const double* ysum,
-                        const double* trials, const double* z, unsigned long long seed, int inner_sweeps, long long sample0,
-                        double* W_out, double* Wmean_out, int transform, const double* q, int nq, double* mean_out, double* q_out) {
-  if (!c) return fail(c, BTF_EINVAL, "bad fold_in arguments");
-  const FoldIn f = {family, nsamples, nrows_new, c->M, c->T, c->K, count, ysum, trials, z, seed, inner_sweeps, sample0,
-                    W_out, Wmean_out, transform, q, nq, mean_out, q_out};
-  int rc = fold_in_check(c, f);
-  if (rc) return rc;
-  if (!c->smp_V || !c->smp_s || nsamples > c->smp_n) return fail(c, BTF_ESTATE, "btf_collect_fold_in: not that many collected samples");
-  HIPCHK(c, hipSetDevice(c->dev));
-  Scratch s(c, c->stream);
-  return fold_in_run(s, c->smp_V, family == FOLD_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT,
-                     c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, f);
-}
-
-// ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)
-int btf_diag_eval(int device, int nchains, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* const* Ws,
-                  const double* const* Vs, btf_ctx* const* ctxs, int transform, double* out) {
-  if (nchains < 1 || nchains > DIAG_MAX_CHAINS || nsamples < 4 || (long long)nchains * nsamples > DIAG_MAX_DRAWS || nrows < 1 ||
-      ncols < 1 || ndepth < 1 || nembeds < 1 || nembeds > MAX_K || transform < 0 || transform > 2 || !out ||
-      (long long)nrows * ncols * ndepth > 0x7fffffffLL)
-    return fail(nullptr, BTF_EINVAL, "bad btf_diag_eval arguments");
-  for (int c = 0; c < nchains; ++c) {
-    const btf_ctx* x = ctxs ? ctxs[c] : nullptr;
-    if (x) {
-      if (x->dev != device || x->N != nrows || x->M != ncols || x->T != ndepth || x->K != nembeds)
-        return fail(nullptr, BTF_EINVAL, "btf_diag_eval: a context of another device or shape");
-      if (x->nl != x->N || x->ml != x->M) return fail(nullptr, BTF_ESTATE, "btf_diag_eval needs unsharded contexts");
-      if (!x->smp_W || !x->smp_V || nsamples > x->smp_n) return fail(nullptr, BTF_ESTATE, "btf_diag_eval: not that many collected samples");
-    } else if (!Ws || !Vs || !Ws[c] || !Vs[c]) {
-      return fail(nullptr, BTF_EINVAL, "btf_diag_eval: chain without host arrays or a context");
-    }
-  }
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  const int MT = ncols * ndepth;
-  const size_t cells = (size_t)nrows * MT;
-  const size_t nW = (size_t)nsamples * nrows * nembeds, nV = (size_t)nsamples * MT * nembeds;
-  Scratch s(nullptr, nullptr);
-  std::vector<const double*> pw(nchains), pv(nchains);
-  for (int c = 0; c < nchains; ++c) {
-    const btf_ctx* x = ctxs ? ctxs[c] : nullptr;
-    if (x) {                                               // the collection copies may still be in flight on its stream
-      s.check(hipStreamSynchronize(x->stream), "hipStreamSynchronize");
-      pw[c] = x->smp_W; pv[c] = x->smp_V;
-    } else {
-      pw[c] = s.upload(Ws[c], nW); pv[c] = s.upload(Vs[c], nV);
-    }
-  }
-  double* dout = s.alloc<double>(DIAG_OUT * cells);
-  int P = 2;
-  while (P < nchains * nsamples) P <<= 1;
-  DiagArgs a{s.upload(pw.data(), (size_t)nchains), s.upload(pv.data(), (size_t)nchains), nchains, nsamples, nrows, MT, P, transform, dout};
-  const size_t lds = (size_t)(nchains * nsamples + P) * sizeof(double);
-  K_SWITCH(nembeds, {
-    allow_lds(s, diag_kernel<KT>, lds);
-    s.launch(diag_kernel<KT>, dim3((unsigned)cells), dim3(DIAG_THREADS), lds, a);
-  });
-  s.download(out, dout, DIAG_OUT * cells);
-  return s.finish();
-}
-
 int btf_pg_batch(int device, int64_t n, const double* b, const double* psi, uint64_t seed, double* out) {
   return btf_pg_batch_mode(device, n, b, psi, seed, 0, out);
 }
 
 int btf_pg_batch_mode(int device, int64_t n, const double* b, const double* psi, uint64_t seed, int mode, double* out) {
   if (n < 1 || !b || !psi || !out || mode < 0 || mode > PG_MODE_REF_F64 + 1) return fail(nullptr, BTF_EINVAL, "bad pg_batch arguments");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (int rc = use_device(device)) return rc;
   Scratch s(nullptr, nullptr);
   double *db = s.upload(b, (size_t)n), *dp = s.upload(psi, (size_t)n), *dout = s.alloc<double>((size_t)n);
   const bool allf64 = mode == PG_MODE_REF_F64 + 1;      // 4: PG_MODE_EXACT_ALL with every trip of the flat sampler repeated in f64
@@ -4785,8 +3532,7 @@ int btf_pg_batch_mode(int device, int64_t n, const double* b, const double* psi,
 
 int btf_sym_eig(int device, int K, int nparts, const double* parts, double* out, const double* warm_from) {
   if (K < 1 || K > EIG_MAXK || nparts < 1 || !parts || !out) return fail(nullptr, BTF_EINVAL, "bad sym_eig arguments");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (int rc = use_device(device)) return rc;
   const size_t np = (size_t)nparts * tri(K), no = (size_t)K + K * K + 2;
   // the solution slot: zeros, or a previous solution to refine: eigenvalues, vectors, (sweeps), then the "valid" word
   std::vector<double> w(no, 0.0);
@@ -4814,8 +3560,7 @@ __global__ __launch_bounds__(1024) void read_probe_kernel(const double2* __restr
 }  // namespace
 int btf_read_probe(int device, size_t bytes, int reps, double* gb_per_s) {
   if (bytes < 1024 || reps < 1 || !gb_per_s) return fail(nullptr, BTF_EINVAL, "bad read_probe arguments");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (int rc = use_device(device)) return rc;
   const size_t n2 = bytes / sizeof(double2);
   Scratch s(nullptr, nullptr);
   double2* x = s.alloc<double2>(n2);
@@ -4824,7 +3569,7 @@ int btf_read_probe(int device, size_t bytes, int reps, double* gb_per_s) {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     ~Events() { if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
   } ev;
-  if (!s.rc()) s.check(hipMemsetAsync(x, 0, n2 * sizeof(double2), nullptr), "hipMemsetAsync");
+  s.zero(x, n2 * sizeof(double2));
   s.check(hipEventCreate(&ev.t0), "hipEventCreate");
   s.check(hipEventCreate(&ev.t1), "hipEventCreate");
   s.launch(read_probe_kernel, dim3(512), dim3(1024), 0, (const double2*)x, n2, out);      // warm-up
@@ -4851,8 +3596,7 @@ int btf_sync(btf_ctx* c) {
 int btf_mvn_banded(int device, int batch, int n, int bw, const double* band, const double* mu_part, const double* z,
                    uint64_t seed, double eps0, int attempts, double* x_out, int32_t* tries_out) {
   if (batch < 1 || n < 1 || bw < 0 || bw > 63 || !band || !x_out) return fail(nullptr, BTF_EINVAL, "bad mvn arguments");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (int rc = use_device(device)) return rc;
   const int R1 = bw + 1;
   const size_t nb = (size_t)batch * n * R1, nv = (size_t)batch * n;
   const int st0[2] = {0, 0};
@@ -4879,8 +3623,7 @@ int btf_mvn_dense(int device, int batch, int n, const double* A, int form, const
                   const double* z, uint64_t seed, double eps0, int attempts, double* x_out, int32_t* tries_out) {
   if (batch < 1 || n < 1 || n > 1024 || !A || !x_out || (form & ~3) || (mu && mu_part))
     return fail(nullptr, BTF_EINVAL, "bad dense mvn arguments (1 <= n <= 1024; mu and mu_part are mutually exclusive)");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(nullptr, BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (int rc = use_device(device)) return rc;
   const size_t nm = (size_t)batch * n * n, nv = (size_t)batch * n;
   const int st0[2] = {0, 0};
   Scratch s(nullptr, nullptr);

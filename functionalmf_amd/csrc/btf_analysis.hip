@@ -1,0 +1,955 @@
+// The posterior analyses behind the C ABI (include/btf.h): summaries, criteria, PSIS-LOO, predictive, functionals, ranking,
+// association, monotone projection, fold-in, diagnostics.  Host code over kernels in units of their own.  gfx950 only.
+#include "btf_ctx.h"            // struct btf_ctx, fail, Scratch, launch_counted, K_SWITCH / FAM_SWITCH
+#include "btf_diag.h"           // convergence diagnostics (instances in btf_diag.hip)
+#include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
+#include "btf_gg_criteria.h"    // the same for the gamma-grid likelihood (kernels in btf_gg_criteria.hip)
+#include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
+#include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
+#include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
+#include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
+#include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
+#include "btf_monotone.h"       // monotone projection of the posterior (kernel in btf_monotone.hip)
+#include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace btf;
+static_assert(CRIT_FAM_COUNT == 5 && PRED_FAM_COUNT == 5, "FAM_SWITCH covers families 0..4");
+
+extern "C" {
+namespace {
+// the summary of btf_*_summary, the monotone projection and fold-in: its buffers, the launch (btf_abi.hip), the downloads
+void summary_stage(Scratch& s, const double* W, const double* V, int S, int rows, int MT, int K, int transform, const double* q,
+                   int nq, double* mean_out, double* q_out) {
+  const size_t n = (size_t)rows * MT;
+  double* dm = s.alloc<double>(n);
+  const double* dq = nq ? s.upload(q, (size_t)nq) : s.alloc<double>(1);
+  double* dqo = s.alloc<double>((size_t)nq * n);
+  launch_summary(s, W, V, S, rows, MT, K, transform, dq, nq, dm, dqo);
+  s.download(mean_out, dm, n);
+  if (nq) s.download(q_out, dqo, (size_t)nq * n);
+}
+
+struct States { double *W, *V; const double* noise; long long noise_stride; };
+// W, V on the device: the uploaded host arrays (Ws null: the call reads no W), else the context's current state
+// (`current`), else its collected ones, where they lie
+States states_of(btf_ctx* c, Scratch& s, int S, int N, int MT, int K, const double* Ws, const double* Vs, bool current) {
+  if (Vs) return {Ws ? s.upload(Ws, (size_t)S * N * K) : nullptr, s.upload(Vs, (size_t)S * MT * K), nullptr, 1};
+  return current ? States{c->W, c->V, nullptr, 1} : States{c->smp_W, c->smp_V, nullptr, 1};
+}
+// The same for criteria and predictive, with their per-sample noise: the uploaded `noise` (`per` values a sample), else
+// the collected nu2 of every kept state.  The callers have refused what they do not take.
+States resolve_states(btf_ctx* c, Scratch& s, int S, const double* Ws, const double* Vs, bool current, bool per_sample,
+                      const double* noise, size_t per) {
+  States r = states_of(c, s, S, c->N, c->M * c->T, c->K, Ws, Vs, current);
+  if (per_sample && noise) { r.noise = s.upload(noise, (size_t)S * per); r.noise_stride = (long long)per; }
+  else if (per_sample) { r.noise = c->smp_s + HYP_NU2; r.noise_stride = HYP_COUNT; }
+  return r;
+}
+
+// the first S collected states of c are there (btf_collect_begin allocates the slot arrays together), and the refusal
+bool has_collected(const btf_ctx* c, int S) { return c->smp_W && c->smp_V && c->smp_s && S <= c->smp_n; }
+int no_collected(btf_ctx* c, int code, const std::string& who) { return fail(c, code, who + ": not that many collected samples"); }
+
+// The states of one call of a pair btf_posterior_X / btf_collect_X, after its checks: selects the device (the scratch's
+// context's, else `device`), resolves W, V; collected states that are not there are refused with `code` under `who`.
+int resolve_pair(Scratch& s, int device, const char* who, int code, int S, int N, int MT, int K, const double* Ws, const double* Vs,
+                 States& st) {
+  btf_ctx* c = s.ctx();
+  if (c && !Vs && !has_collected(c, S)) return no_collected(c, code, who);
+  if (c) HIPCHK(c, hipSetDevice(c->dev));
+  else if (int rc = use_device(device)) return rc;
+  st = states_of(c, s, S, N, MT, K, Ws, Vs, false);
+  return BTF_OK;
+}
+
+int check_percentiles(btf_ctx* c, const double* q, int nq) {
+  for (int k = 0; k < nq; ++k)
+    if (!(q[k] >= 0.0 && q[k] <= 100.0)) return fail(c, BTF_EINVAL, "percentiles must lie in [0, 100]");
+  return BTF_OK;
+}
+
+// The curve axis x (T depths) and the functional codes of a request, refused under the feature's name `who` in the order
+// every feature refuses them.  (Ranking and association hand in their one code, already range-checked.)
+int check_curve_axis(btf_ctx* c, const std::string& who, int T, const double* x, const int* which, int nwhich, double level) {
+  if (T < 2) return fail(c, BTF_EINVAL, who + ": a curve needs ndepth >= 2");
+  bool seen[FUNC_COUNT] = {false};
+  for (int k = 0; k < nwhich; ++k) {
+    if (which[k] < 0 || which[k] >= FUNC_COUNT || seen[which[k]]) return fail(c, BTF_EINVAL, who + ": functional codes must be distinct and in 0..6");
+    seen[which[k]] = true;
+  }
+  if (seen[FUNC_CROSSING] && !(level == level)) return fail(c, BTF_EINVAL, who + ": crossing needs a level");
+  for (int t = 1; t < T; ++t)
+    if (!(x[t] > x[t - 1])) return fail(c, BTF_EINVAL, who + ": x must be strictly increasing");
+  return BTF_OK;
+}
+
+// sample slices of a func_sweep launch: enough workgroups to fill the chip when rows x columns alone do not (geometry only)
+int func_sweep_slices(int S, int rowblocks, int jc) {
+  return std::max(1, std::min((S + FUNC_WAVES - 1) / FUNC_WAVES, (2048 + rowblocks * jc - 1) / (rowblocks * jc)));
+}
+
+// One curve functional of the device states dW (S,N,K), dV (S,M,T,K), swept a chunk of samples at a time into the scratch
+// vals[column][sample of the chunk][row]; scratch_bytes caps it (0: FUNC_SCRATCH_BYTES; one sample is the least).
+struct FuncSweep { Scratch* s; FuncKernel kern; FuncArgs f; const double *dW, *dV; double* vals; int K, sc_max; };
+// false, before anything is allocated: no kernel for this nembeds / transform
+bool func_sweep_init(FuncSweep& w, Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform,
+                     int which, const double* x, double level, long long scratch_bytes) {
+  w = FuncSweep{&s, func_sweep_fn(K, transform), {}, dW, dV, nullptr, K, 1};
+  if (!w.kern) return false;
+  const size_t NM = (size_t)N * M, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
+  w.sc_max = (int)std::max<size_t>(1, std::min<size_t>(S, cap / (NM * sizeof(double))));
+  FuncArgs& f = w.f;
+  f.level = level; f.exceed = std::nan(""); f.N = N; f.M = M; f.T = T; f.nslots = 1;
+  for (int k = 0; k < FUNC_COUNT; ++k) f.slot[k] = -1;
+  f.slot[which] = 0; f.code[0] = which;
+  f.x = s.upload(x, (size_t)T);
+  w.vals = s.alloc<double>(NM * w.sc_max);
+  return true;
+}
+// the sc samples from s0 on
+void sweep_chunk(FuncSweep& w, int s0, int sc) {
+  FuncArgs& f = w.f;
+  const int rowblocks = (f.N + WAVE - 1) / WAVE, JMAX = 65535;   // (a grid's y extent)
+  f.W = w.dW + (size_t)s0 * f.N * w.K; f.V = w.dV + (size_t)s0 * f.M * f.T * w.K; f.S = sc;
+  for (int j0 = 0; j0 < f.M; j0 += JMAX) {
+    f.j0 = j0; f.jc = std::min(JMAX, f.M - j0); f.vals = w.vals + (size_t)j0 * sc * f.N;
+    launch_counted(*w.s, BTF_K_CRITERIA, w.kern, dim3(rowblocks, f.jc, func_sweep_slices(sc, rowblocks, f.jc)), dim3(FUNC_WAVES * WAVE), 0, f);
+  }
+}
+}  // namespace
+
+// posterior summaries straight from the collected samples (no upload); see btf_posterior_summary
+int btf_collect_summary(btf_ctx* c, int nsamples, int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  if (!c || nsamples < 1 || nsamples > c->smp_n || nsamples > 16384 || !mean_out || nq < 0 || (nq > 0 && (!q || !q_out)) ||
+      transform < 0 || transform > 2)
+    return fail(c, BTF_EINVAL, "bad collect_summary arguments");
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_summary", BTF_EINVAL, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  summary_stage(s, st.W, st.V, nsamples, c->N, c->M * c->T, c->K, transform, q, nq, mean_out, q_out);
+  return s.finish();
+}
+
+// ---------------------------------------------------------- model-selection criteria (btf_criteria.h)
+int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt, const double* curve_c0, const double* curve_c1) {
+  if (!c || slot < 0 || slot > 1) return fail(c, BTF_EINVAL, "criteria slot must be 0 or 1");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistics)
+  double** bufs[4] = {&c->crit_S1[slot], &c->crit_cnt[slot], &c->crit_c0[slot], &c->crit_c1[slot]};
+  if (c->crit_L[slot]) { (void)hipFree(c->crit_L[slot]); c->crit_L[slot] = nullptr; }      // (the old data's log sums)
+  if (!S1 && !cnt && !curve_c0 && !curve_c1) {       // free the slot
+    for (double** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    return BTF_OK;
+  }
+  if (!S1 || !cnt || !curve_c0 || !curve_c1) return fail(c, BTF_EINVAL, "btf_crit_set_data: all four arrays, or none");
+  const size_t cells = (size_t)c->M * c->T * c->N, curves = (size_t)c->N * c->M;
+  const double* src[4] = {S1, cnt, curve_c0, curve_c1};
+  const size_t n[4] = {cells, cells, curves, curves};
+  for (int q = 0; q < 4; ++q) {
+    int rc;
+    if ((rc = dev_alloc(c, bufs[q], n[q]))) return rc;
+    HIPCHK(c, hipMemcpyAsync(*bufs[q], src[q], n[q] * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BTF_OK;
+}
+
+int btf_crit_set_logsum(btf_ctx* c, int slot, const double* L) {
+  if (!c || slot < 0 || slot > 1) return fail(c, BTF_EINVAL, "criteria slot must be 0 or 1");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistic)
+  if (!L) {
+    if (c->crit_L[slot]) (void)hipFree(c->crit_L[slot]);
+    c->crit_L[slot] = nullptr;
+    return BTF_OK;
+  }
+  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, "btf_crit_set_logsum: no statistics in this slot (btf_crit_set_data first)");
+  const size_t cells = (size_t)c->M * c->T * c->N;
+  int rc;
+  if ((rc = dev_alloc(c, &c->crit_L[slot], cells))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->crit_L[slot], L, cells * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BTF_OK;
+}
+
+namespace {
+// families 0..4 of FAM_SWITCH, or the gamma-grid family of btf_gg_criteria.h
+bool crit_family_ok(int family) { return (family >= 0 && family < CRIT_FAM_COUNT) || family == CRIT_FAM_GAMMA_GRID; }
+
+// the device side of a criteria call: its scratch (the uploaded states, crit_kernel's outputs) and the kernels' arguments
+struct CritRun {
+  Scratch s;
+  CritArgs a{};
+  double* tot = nullptr;      // [S] per-sample totals (crit_total_kernel)
+  explicit CritRun(btf_ctx* c) : s(c, c->stream) {}
+};
+
+// Checks the arguments that btf_crit_eval and btf_crit_loo share, uploads the states and queues crit_kernel (with
+// `reduce` also the plug-in and per-sample-total kernels) on the context's stream.  `who` names the caller in messages.
+int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+             const double* noise, int flags, bool pointwise, bool reduce, CritRun& r) {
+  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, who + ": no statistics in this slot (btf_crit_set_data)");
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, who + " needs an unsharded context");
+  const bool current = (flags & BTF_CRIT_CURRENT) != 0, per_sample = (flags & BTF_CRIT_NOISE_PER_SAMPLE) != 0;
+  if (current && (Ws || nsamples != 1 || !c->have_W || !c->have_V))
+    return fail(c, BTF_EINVAL, "BTF_CRIT_CURRENT scores the context's own W, V: one sample, Ws = Vs = NULL");
+  if (!Ws && !current && !has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, who);
+  if (per_sample && family != CRIT_FAM_GAUSSIAN) return fail(c, BTF_EINVAL, "per-sample noise is the Gaussian family's");
+  if (per_sample && !noise && (Ws || current)) return fail(c, BTF_EINVAL, "per-sample noise of uploaded / current states: pass `noise`");
+  if (!per_sample && (family == CRIT_FAM_GAUSSIAN || family == CRIT_FAM_NEGBIN) && !(param > 0.0))
+    return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
+  const bool gamma_grid = family == CRIT_FAM_GAMMA_GRID;
+  if (gamma_grid && (!c->gg_tab || !c->crit_L[slot]))
+    return fail(c, BTF_ESTATE, who + ": the gamma-grid family needs its table (btf_set_likelihood_table) and the slot's L (btf_crit_set_logsum)");
+  HIPCHK(c, hipSetDevice(c->dev));
+  const int S = nsamples, N = c->N, M = c->M, T = c->T, K = c->K;
+  const dim3 grid((N + WAVE - 1) / WAVE, M);
+  const int nwg = (int)(grid.x * grid.y);
+  const size_t NM = (size_t)N * M;
+  Scratch& s = r.s;
+  CritArgs& a = r.a;
+  a.S1 = c->crit_S1[slot]; a.cnt = c->crit_cnt[slot]; a.c0 = c->crit_c0[slot]; a.c1 = c->crit_c1[slot];
+  const States st = resolve_states(c, s, S, Ws, Vs, current, per_sample, noise, 1);
+  a.W = st.W; a.V = st.V; a.noise = st.noise; a.noise_stride = st.noise_stride;
+  a.par = param; a.S = S; a.N = N; a.M = M; a.T = T;
+  a.mu = s.alloc<double>((size_t)M * T * N); a.curve = s.alloc<double>(CRIT_OUT * NM);
+  a.tot_part = s.alloc<double>((size_t)S * nwg); r.tot = s.alloc<double>((size_t)S);
+  if (pointwise) a.pw = s.alloc<double>((size_t)S * NM);
+  const GgTab gt{c->crit_L[slot], c->gg_tab, c->gg_G, c->gg_lsp};
+  if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_fn(K), grid, dim3(GGC_WAVES * WAVE), 0, a, gt);
+  else K_SWITCH(K, FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_kernel<KT, FT>, grid, dim3(CRIT_WAVES * WAVE), 0, a)));
+  if (reduce) {
+    if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_plugin_fn(), grid, dim3(WAVE), 0, a, gt);
+    else FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_plugin_kernel<FT>, grid, dim3(WAVE), 0, a));
+    launch_counted(s, BTF_K_CRITERIA, crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.tot_part, S, nwg, r.tot);
+  }
+  return s.rc();
+}
+}  // namespace
+
+int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                  const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out) {
+  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !curve_out || !total_out ||
+      (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
+    return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
+  CritRun r(c);
+  int rc = crit_run(c, "btf_crit_eval", slot, family, param, nsamples, Ws, Vs, noise, flags, pointwise_out != nullptr, true, r);
+  if (rc) return rc;
+  const size_t S = (size_t)nsamples, NM = (size_t)c->N * c->M;
+  r.s.download(curve_out, r.a.curve, CRIT_OUT * NM);
+  r.s.download(total_out, r.tot, S);
+  r.s.download(pointwise_out, r.a.pw, S * NM);
+  return r.s.finish();        // (not check_status: the sampler's status word is not this call's)
+}
+
+// ---------------------------------------------------------- PSIS-LOO (btf_loo.h)
+int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                 const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
+                 double* logw_out) {
+  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !loo_out ||
+      (flags & ~BTF_CRIT_NOISE_PER_SAMPLE) || (!Ws) != (!Vs) || transform < 0 || transform > 2)
+    return fail(c, BTF_EINVAL, "bad btf_crit_loo arguments");
+  if (nsamples > LOO_MAX_S)
+    return fail(c, BTF_EINVAL, "btf_crit_loo: " + std::to_string(nsamples) + " samples, at most " + std::to_string(LOO_MAX_S));
+  const int S = nsamples, N = c->N, M = c->M, T = c->T;
+  const size_t NM = (size_t)N * M;
+  // the tail length Mt = min(floor(0.2 S), ceil(3 sqrt(S / r_eff))) of every curve, on the host: IEEE sqrt and division
+  auto tail = [S](double re) { return (int)std::min((double)(S / 5), std::ceil(3.0 * std::sqrt((double)S / re))); };
+  std::vector<int> mt;
+  if (r_eff) {
+    mt.resize(NM);
+    for (size_t o = 0; o < NM; ++o) {
+      if (!(r_eff[o] > 0.0) || !std::isfinite(r_eff[o]))
+        return fail(c, BTF_EINVAL, "btf_crit_loo: r_eff must be finite and > 0 (curve " + std::to_string(o) + ")");
+      mt[o] = tail(r_eff[o]);
+    }
+  }
+  CritRun r(c);
+  int rc = crit_run(c, "btf_crit_loo", slot, family, param, nsamples, Ws, Vs, noise, flags, true, false, r);
+  if (rc) return rc;
+  Scratch& s = r.s;
+  double* dloo = s.alloc<double>(2 * NM);
+  LooArgs a{};
+  a.pw = r.a.pw; a.mt = r_eff ? s.upload(mt.data(), NM) : nullptr; a.mt_all = tail(1.0); a.S = S; a.NM = (int)NM; a.out = dloo;
+  a.P = 64; while (a.P < S) a.P <<= 1;
+  a.per_xcd = (int)((NM + 7) / 8);
+  const size_t lds = (size_t)a.P * (2 * sizeof(double) + sizeof(unsigned short));
+  void (*const psis)(LooArgs) = (mean_out || logw_out) ? loo_psis_kernel<1> : loo_psis_kernel<0>;      // <1> keeps the log weights
+  allow_lds(s, psis, lds);
+  launch_counted(s, BTF_K_CRITERIA, psis, dim3(8 * a.per_xcd), dim3(WAVE), lds, a);
+  if (mean_out) {
+    LooMeanArgs ma{};
+    ma.lw = r.a.pw; ma.W = r.a.W; ma.V = r.a.V; ma.S = S; ma.N = N; ma.M = M; ma.T = T; ma.transform = transform;
+    ma.mean = s.alloc<double>(NM * T);
+    K_SWITCH(c->K, launch_counted(s, BTF_K_CRITERIA, loo_mean_kernel<KT>, dim3((N + WAVE - 1) / WAVE, M), dim3(LOO_WAVES * WAVE), 0, ma));
+    s.download(mean_out, ma.mean, NM * T);
+  }
+  // loo_out: elpd_loo, pareto_k, then crit_kernel's two accumulators of lppd (curve_out[0], [1] of btf_crit_eval)
+  s.download(loo_out, dloo, 2 * NM);
+  s.download(loo_out + 2 * NM, r.a.curve, 2 * NM);
+  s.download(logw_out, r.a.pw, (size_t)S * NM);
+  return s.finish();
+}
+
+// ---------------------------------------------------------- posterior predictive (btf_predict.h)
+int btf_predict_batch(int device, int family, int64_t n, const double* eta, const double* aux, uint64_t seed, double* out) {
+  if (family < 0 || family >= PRED_FAM_COUNT || n < 1 || !eta || !aux || !out) return fail(nullptr, BTF_EINVAL, "bad predict_batch arguments");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double *de = s.upload(eta, (size_t)n), *da = s.upload(aux, (size_t)n);
+  double* dout = s.alloc<double>((size_t)n);
+  const dim3 grid((unsigned)((n + PRED_THREADS - 1) / PRED_THREADS)), block(PRED_THREADS);
+  FAM_SWITCH(family, s.launch(pred_batch_kernel<FT>, grid, block, 0, de, da, (long long)n, (unsigned long long)seed, dout));
+  s.download(out, dout, (size_t)n);
+  return s.finish();
+}
+
+int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                     const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps,
+                     int draws_per_sample, uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
+                     double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out, double* pit_hi_out,
+                     double* inside_out, double* nobs_out, double* rmse_out, double* mae_out, double* draws_out) {
+  if (!c || family < 0 || family >= PRED_FAM_COUNT || nsamples < 1 || draws_per_sample < 1 || (!Ws) != (!Vs) || nq < 0 ||
+      (nq > 0 && !q) || (q_out && nq < 1) || ncells < 0 || (ncells > 0 && (!cells || !draws_out)) || (Y && nreps < 1) ||
+      (aux_flags & ~(BTF_PRED_AUX_PER_SAMPLE | BTF_PRED_AUX_ROWS | BTF_PRED_AUX_COLS | BTF_PRED_AUX_DEPTH)))
+    return fail(c, BTF_EINVAL, "bad btf_predict_eval arguments");
+  if (!Y && (pit_lo_out || pit_hi_out || inside_out || nobs_out || rmse_out || mae_out))
+    return fail(c, BTF_EINVAL, "btf_predict_eval: pit / inside / nobs / rmse / mae compare with observations: pass Y");
+  if ((long long)nsamples * draws_per_sample > PRED_MAX_DRAWS)
+    return fail(c, BTF_EINVAL, "btf_predict_eval: nsamples * draws_per_sample = " + std::to_string((long long)nsamples * draws_per_sample) +
+                " exceeds 16384 (the draws of a cell are sorted in LDS)");
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_predict_eval needs an unsharded context");
+  if (!Ws && !has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, "btf_predict_eval");
+  const bool per_sample = (aux_flags & BTF_PRED_AUX_PER_SAMPLE) != 0;
+  const bool needs_par = family == PRED_FAM_GAUSSIAN || family == PRED_FAM_NEGBIN;
+  if (per_sample && !needs_par) return fail(c, BTF_EINVAL, "per-sample parameters are the Gaussian (variance) and Negative-Binomial (rate) families'");
+  if (per_sample && !aux_sample && (Ws || family != PRED_FAM_GAUSSIAN))
+    return fail(c, BTF_EINVAL, "per-sample parameters of uploaded states (and every Negative-Binomial rate): pass aux_sample");
+  if (!per_sample && needs_par && !(param > 0.0))
+    return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
+  if (int rc = check_percentiles(c, q, nq)) return rc;
+  const int S = nsamples, R = draws_per_sample, N = c->N, M = c->M, T = c->T, K = c->K, MT = M * T, n = S * R;
+  const size_t ncell = (size_t)N * MT;
+  if (ncell > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: more than 2^31 - 1 cells");
+  for (int k = 0; k < ncells; ++k)
+    if (cells[k] < 0 || (size_t)cells[k] >= ncell) return fail(c, BTF_EINVAL, "btf_predict_eval: cell index out of range");
+  HIPCHK(c, hipSetDevice(c->dev));
+  PredArgs a{};
+  a.aux_n0 = a.aux_n1 = a.aux_n2 = 1;
+  if (per_sample && family == PRED_FAM_NEGBIN) {
+    a.aux_n0 = (aux_flags & BTF_PRED_AUX_ROWS) ? N : 1; a.aux_n1 = (aux_flags & BTF_PRED_AUX_COLS) ? M : 1; a.aux_n2 = (aux_flags & BTF_PRED_AUX_DEPTH) ? T : 1;
+  }
+  const size_t naux = (size_t)a.aux_n0 * a.aux_n1 * a.aux_n2;
+  const SortGeom g = sort_geom(n, PRED_SORT_LDS, PRED_SORT_CELLS);
+  const size_t nblk = (size_t)N * ((MT + g.cells - 1) / g.cells);
+  if (nblk > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: too many workgroups for one launch");
+  const int chunks = (int)((ncell + PRED_SCORE_CELLS - 1) / PRED_SCORE_CELLS);
+  const bool score = rmse_out || mae_out;
+  Scratch s(c, c->stream);
+  const States st = resolve_states(c, s, S, Ws, Vs, false, per_sample, aux_sample, naux);
+  a.W = st.W; a.V = st.V; a.aux = st.noise; a.aux_stride = st.noise_stride;
+  if (trials) a.trials = s.upload(trials, ncell);
+  if (Y) { a.Y = s.upload(Y, ncell * (size_t)nreps); a.nreps = nreps; }
+  if (nq) a.q = s.upload(q, (size_t)nq);
+  a.nq = nq;
+  if (ncells) { a.list = s.upload(cells, (size_t)ncells); a.nlist = ncells; a.draws = s.alloc<double>((size_t)ncells * n); }
+  if (mean_out) a.mean = s.alloc<double>(ncell);
+  if (ymean_out) a.y_mean = s.alloc<double>(ncell);
+  if (yvar_out) a.y_var = s.alloc<double>(ncell);
+  if (q_out) a.quant = s.alloc<double>((size_t)nq * ncell);
+  if (pit_lo_out) a.pit_lo = s.alloc<double>(ncell);
+  if (pit_hi_out) a.pit_hi = s.alloc<double>(ncell);
+  if (inside_out) a.inside = s.alloc<double>(ncell);
+  if (nobs_out) a.nobs = s.alloc<double>(ncell);
+  double* dsc = nullptr;      // [rmse | mae] per sample
+  if (score) { a.score_part = s.alloc<double>((size_t)3 * S * chunks); dsc = s.alloc<double>((size_t)2 * S); }
+  a.par = param; a.S = S; a.R = R; a.N = N; a.M = M; a.T = T; a.K = K; a.P = g.P; a.cells = g.cells; a.seed = seed; a.chunks = chunks;
+  FAM_SWITCH(family, {
+    allow_lds(s, pred_kernel<FT>, g.lds);
+    s.launch(pred_kernel<FT>, dim3((unsigned)nblk), dim3(PRED_THREADS), g.lds, a);
+    if (score) s.launch(pred_score_kernel<FT>, dim3(chunks, S), dim3(PRED_THREADS), 0, a);
+  });
+  if (score) s.launch(pred_score_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.score_part, S, chunks, dsc);
+  s.download(mean_out, a.mean, ncell); s.download(ymean_out, a.y_mean, ncell); s.download(yvar_out, a.y_var, ncell);
+  s.download(q_out, a.quant, (size_t)nq * ncell);
+  s.download(pit_lo_out, a.pit_lo, ncell); s.download(pit_hi_out, a.pit_hi, ncell); s.download(inside_out, a.inside, ncell);
+  s.download(nobs_out, a.nobs, ncell);
+  if (score && !s.rc()) { s.download(rmse_out, dsc, (size_t)S); s.download(mae_out, dsc + S, (size_t)S); }
+  if (ncells) s.download(draws_out, a.draws, (size_t)ncells * n);
+  return s.finish();        // (not check_status: the sampler's status word is not this call's)
+}
+
+// ---------------------------------------------------------------- posterior summaries
+int btf_posterior_summary(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws,
+                          const double* Vs, int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  if (nsamples < 1 || nsamples > 16384 || nrows < 1 || ncols < 1 || ndepth < 1 || nembeds < 1 || nembeds > MAX_K || !Ws || !Vs ||
+      !mean_out || nq < 0 || (nq > 0 && (!q || !q_out)) || transform < 0 || transform > 2)
+    return fail(nullptr, BTF_EINVAL, "bad posterior_summary arguments");
+  if (int rc = check_percentiles(nullptr, q, nq)) return rc;
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, nrows, ncols * ndepth, nembeds, Ws, Vs, st)) return rc;
+  summary_stage(s, st.W, st.V, nsamples, nrows, ncols * ndepth, nembeds, transform, q, nq, mean_out, q_out);
+  return s.finish();
+}
+
+// ---------------------------------------------------------------- posterior curve functionals (btf_functionals.h)
+namespace {
+struct FuncOut { double *mean, *var, *quant, *defined, *prob, *curves, *pw; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): scratch, the launches chunk by chunk, the downloads.
+// The scratch's context may be null (the stateless form: default stream, launches not counted).
+int functionals_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform,
+                    const int* which, int nwhich, const double* x, double level, double exceed, const double* q, int nq,
+                    const int* curves, int ncurves, const FuncOut& o) {
+  FuncArgs a = {};
+  a.W = dW; a.V = dV; a.level = level; a.exceed = exceed;
+  a.S = S; a.N = N; a.M = M; a.T = T; a.nslots = nwhich; a.nq = nq;
+  for (int f = 0; f < FUNC_COUNT; ++f) a.slot[f] = -1;
+  for (int k = 0; k < nwhich; ++k) { a.slot[which[k]] = k; a.code[k] = which[k]; }
+  const SortGeom g = sort_geom(S, FUNC_SORT_LDS, FUNC_SORT_CELLS);
+  a.P = g.P; a.cells = g.cells;
+  const size_t NM = (size_t)N * M, per_col = (size_t)nwhich * S * N;      // doubles of scratch a column takes
+  const int jc_max = (int)std::max<size_t>(1, std::min<size_t>(std::min(M, 65535), FUNC_SCRATCH_BYTES / (per_col * sizeof(double))));   // (a grid's y extent)
+  FuncKernel sweep = func_sweep_fn(K, transform), sort = func_sort_fn();
+  if (!sweep) return fail(s.ctx(), BTF_EINVAL, "posterior functionals: nembeds must be 1..10 and transform 0..2");
+  a.x = s.upload(x, (size_t)T);
+  a.vals = s.alloc<double>(per_col * jc_max);
+  if (o.mean) a.mean = s.alloc<double>(nwhich * NM);
+  if (o.var) a.var = s.alloc<double>(nwhich * NM);
+  if (o.prob) a.prob = s.alloc<double>(nwhich * NM);
+  if (o.defined) a.defined = s.alloc<double>(NM);
+  if (nq) { a.q = s.upload(q, (size_t)nq); a.quant = s.alloc<double>((size_t)nq * nwhich * NM); }
+  const int* dcv = nullptr;
+  double* dcur = nullptr;
+  if (ncurves) { dcv = s.upload(curves, (size_t)2 * ncurves); dcur = s.alloc<double>((size_t)nwhich * ncurves * S); }
+  if (o.pw) a.pw = s.alloc<double>((size_t)nwhich * S * NM);
+  allow_lds(s, sort, g.lds);
+  const int rowblocks = (N + WAVE - 1) / WAVE;
+  const bool reduce = o.mean || o.var || o.prob || o.defined || nq;
+  for (int j0 = 0; j0 < M; j0 += jc_max) {
+    a.j0 = j0; a.jc = std::min(jc_max, M - j0);
+    launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, a.jc, func_sweep_slices(S, rowblocks, a.jc)), dim3(FUNC_WAVES * WAVE), 0, a);
+    if (ncurves) launch_counted(s, BTF_K_CRITERIA, func_gather_fn(), dim3(ncurves, nwhich), dim3(256), 0, a, dcv, ncurves, dcur);
+    if (reduce) launch_counted(s, BTF_K_CRITERIA, sort, dim3((N + a.cells - 1) / a.cells, a.jc, nwhich), dim3(256), g.lds, a);
+  }
+  s.download(o.mean, a.mean, nwhich * NM);
+  s.download(o.var, a.var, nwhich * NM);
+  s.download(o.prob, a.prob, nwhich * NM);
+  if (o.defined) {
+    if (a.slot[FUNC_CROSSING] < 0) s.zero(a.defined, NM * sizeof(double));
+    s.download(o.defined, a.defined, NM);
+  }
+  if (nq) s.download(o.quant, a.quant, (size_t)nq * nwhich * NM);
+  if (ncurves) s.download(o.curves, dcur, (size_t)nwhich * ncurves * S);
+  s.download(o.pw, a.pw, (size_t)nwhich * S * NM);
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int functionals_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, const int* which, int nwhich, const double* x,
+                      double level, const double* q, int nq, const int* curves, int ncurves, const FuncOut& o) {
+  if (S < 1 || N < 1 || M < 1 || K < 1 || K > MAX_K || transform < 0 || transform > 2 || !which || nwhich < 1 || nwhich > FUNC_COUNT ||
+      !x || nq < 0 || (nq > 0 && (!q || !o.quant)) || ncurves < 0 || (ncurves > 0 && (!curves || !o.curves)))
+    return fail(c, BTF_EINVAL, "bad posterior functionals arguments");
+  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior functionals: at most " + std::to_string(FUNC_MAX_S) + " samples (one curve's values are sorted in LDS)");
+  if (int rc = check_curve_axis(c, "posterior functionals", T, x, which, nwhich, level)) return rc;
+  if (int rc = check_percentiles(c, q, nq)) return rc;
+  for (int k = 0; k < ncurves; ++k)
+    if (curves[2 * k] < 0 || curves[2 * k] >= N || curves[2 * k + 1] < 0 || curves[2 * k + 1] >= M)
+      return fail(c, BTF_EINVAL, "posterior functionals: curve index out of range");
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_posterior_functionals(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                              int transform, const int* which, int nwhich, const double* x, double level, double exceed,
+                              const double* q, int nq, const int* curves, int ncurves, double* mean_out, double* var_out,
+                              double* q_out, double* defined_out, double* prob_out, double* curves_out, double* pointwise_out) {
+  const FuncOut o = {mean_out, var_out, q_out, defined_out, prob_out, curves_out, pointwise_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior functionals arguments");
+  if (int rc = functionals_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, q, nq, curves, ncurves, o)) return rc;
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, nrows, ncols * ndepth, nembeds, Ws, Vs, st)) return rc;
+  return functionals_run(s, st.W, st.V, nsamples, nrows, ncols, ndepth, nembeds, transform, which, nwhich, x, level, exceed, q, nq,
+                         curves, ncurves, o);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload)
+int btf_collect_functionals(btf_ctx* c, int nsamples, int transform, const int* which, int nwhich, const double* x, double level,
+                            double exceed, const double* q, int nq, const int* curves, int ncurves, double* mean_out, double* var_out,
+                            double* q_out, double* defined_out, double* prob_out, double* curves_out, double* pointwise_out) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior functionals arguments");
+  const FuncOut o = {mean_out, var_out, q_out, defined_out, prob_out, curves_out, pointwise_out};
+  if (int rc = functionals_check(c, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, q, nq, curves, ncurves, o)) return rc;
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_functionals", BTF_ESTATE, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  return functionals_run(s, st.W, st.V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
+                         q, nq, curves, ncurves, o);
+}
+
+// ---------------------------------------------------------------- posterior ranking (btf_ranking.h)
+namespace {
+struct RankOut { double *expected, *var, *ptop; int* ranks; double *prob_less, *prob_defined; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): per chunk of samples the functionals' sweep into the
+// scratch, the gather and count of the pairs, the rank kernel; then the finish kernel and the downloads.  scratch_bytes
+// caps the chunk's scratch (0: FUNC_SCRATCH_BYTES; one sample is the least a chunk holds).
+int ranking_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform, int which,
+                const double* x, double level, int along, int descending, const int* top, int ntop, const int* pairs, int npairs,
+                const RankOut& o, long long scratch_bytes) {
+  FuncSweep w;
+  if (!func_sweep_init(w, s, dW, dV, S, N, M, T, K, transform, which, x, level, scratch_bytes))
+    return fail(s.ctx(), BTF_EINVAL, "posterior ranking: nembeds must be 1..10 and transform 0..2");
+  const size_t NM = (size_t)N * M;
+  RankArgs r = {};
+  r.vals = w.vals; r.S = S; r.N = N; r.M = M; r.along = along; r.ntop = ntop; r.P = npairs;
+  for (int k = 0; k < ntop; ++k) r.top[k] = std::min(top[k], RANK_MAX_L + 1);      // (a rank never exceeds RANK_MAX_L)
+  r.L = along ? N : M;
+  while ((1 << r.lshift) < r.L) ++r.lshift;
+  r.Lp = 1 << r.lshift;
+  const int ngroups = along ? M : N;
+  r.G = std::max(1, std::min(ngroups, std::min(RANK_MAX_L / r.Lp, RANK_MAX_GROUPS)));
+  const size_t lds = rank_lds_bytes(r.G, r.Lp);
+  const int tiles = (ngroups + r.G - 1) / r.G;
+  r.A = s.alloc<unsigned long long>(NM);
+  r.B = s.alloc<unsigned long long>(NM);
+  r.C = s.alloc<unsigned int>((size_t)ntop * NM);
+  if (o.ranks) r.ranks = s.alloc<int>((size_t)S * NM);
+  r.expected = s.alloc<double>(NM); r.var = s.alloc<double>(NM); r.ptop = s.alloc<double>((size_t)ntop * NM);
+  const int* dpairs = nullptr; double* dpv = nullptr;
+  if (npairs) {
+    dpairs = s.upload(pairs, (size_t)4 * npairs);             // (i,j,i2,j2) rows = 2 npairs (i,j) curves for the gather
+    dpv = s.alloc<double>((size_t)2 * npairs * w.sc_max);
+    r.pvals = dpv;
+    r.pless = s.alloc<unsigned int>(npairs); r.pdef = s.alloc<unsigned int>(npairs);
+    r.prob_less = s.alloc<double>(npairs); r.prob_defined = s.alloc<double>(npairs);
+  }
+  s.zero(r.A, NM * sizeof(unsigned long long)); s.zero(r.B, NM * sizeof(unsigned long long)); s.zero(r.C, (size_t)ntop * NM * sizeof(unsigned int));
+  if (npairs) { s.zero(r.pless, npairs * sizeof(unsigned int)); s.zero(r.pdef, npairs * sizeof(unsigned int)); }
+  RankKernel rank = rank_fn(descending != 0);
+  for (int s0 = 0; s0 < S; s0 += w.sc_max) {
+    const int sc = std::min(w.sc_max, S - s0);
+    sweep_chunk(w, s0, sc);
+    r.s0 = s0; r.sc = sc;
+    if (npairs) {
+      w.f.j0 = 0; w.f.jc = M; w.f.vals = w.vals;                // (the gather reads the chunk's scratch over every column)
+      launch_counted(s, BTF_K_CRITERIA, func_gather_fn(), dim3(2 * npairs, 1), dim3(256), 0, w.f, dpairs, 2 * npairs, dpv);
+      launch_counted(s, BTF_K_CRITERIA, rank_pairs_fn(), dim3(npairs), dim3(256), 0, r);
+    }
+    // sample slices: enough workgroups for two per CU when the tiles alone are fewer (geometry only)
+    const int ys = std::max(1, std::min(sc, (1024 + tiles - 1) / tiles));
+    launch_counted(s, BTF_K_CRITERIA, rank, dim3(tiles, ys), dim3(RANK_THREADS), lds, r);
+  }
+  launch_counted(s, BTF_K_CRITERIA, rank_finish_fn(), dim3((unsigned)((NM + npairs + 255) / 256)), dim3(256), 0, r);
+  s.download(o.expected, r.expected, NM);
+  s.download(o.var, r.var, NM);
+  s.download(o.ptop, r.ptop, (size_t)ntop * NM);
+  s.download(o.ranks, r.ranks, (size_t)S * NM);
+  if (npairs) { s.download(o.prob_less, r.prob_less, (size_t)npairs); s.download(o.prob_defined, r.prob_defined, (size_t)npairs); }
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int ranking_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, int which, const double* x, double level, int along,
+                  int descending, const int* top, int ntop, const int* pairs, int npairs, const RankOut& o, long long scratch_bytes) {
+  if (S < 1 || N < 1 || M < 1 || K < 1 || K > MAX_K || transform < 0 || transform > 2 || which < 0 || which >= FUNC_COUNT || !x ||
+      along < 0 || along > 1 || descending < 0 || descending > 1 || !top || ntop < 1 || ntop > RANK_MAX_TOP || npairs < 0 ||
+      (npairs > 0 && (!pairs || !o.prob_less || !o.prob_defined)) || scratch_bytes < 0)
+    return fail(c, BTF_EINVAL, "bad posterior ranking arguments");
+  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior ranking: at most " + std::to_string(FUNC_MAX_S) + " samples");
+  if ((along ? N : M) > RANK_MAX_L)
+    return fail(c, BTF_EINVAL, "posterior ranking: at most " + std::to_string(RANK_MAX_L) + " members in a group (it is sorted in LDS)");
+  if (int rc = check_curve_axis(c, "posterior ranking", T, x, &which, 1, level)) return rc;
+  for (int k = 0; k < ntop; ++k) {
+    if (top[k] < 1) return fail(c, BTF_EINVAL, "posterior ranking: top must hold integers >= 1");
+    for (int l = 0; l < k; ++l)
+      if (top[l] == top[k]) return fail(c, BTF_EINVAL, "posterior ranking: top must hold distinct integers");
+  }
+  for (int k = 0; k < 2 * npairs; ++k)
+    if (pairs[2 * k] < 0 || pairs[2 * k] >= N || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= M)
+      return fail(c, BTF_EINVAL, "posterior ranking: pair index out of range");
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_posterior_ranking(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                          int transform, int which, const double* x, double level, int along, int descending, const int* top, int ntop,
+                          const int* pairs, int npairs, double* expected_out, double* var_out, double* ptop_out, int* ranks_out,
+                          double* prob_less_out, double* prob_defined_out, long long scratch_bytes) {
+  const RankOut o = {expected_out, var_out, ptop_out, ranks_out, prob_less_out, prob_defined_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior ranking arguments");
+  if (int rc = ranking_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, which, x, level, along, descending, top, ntop,
+                             pairs, npairs, o, scratch_bytes)) return rc;
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, nrows, ncols * ndepth, nembeds, Ws, Vs, st)) return rc;
+  return ranking_run(s, st.W, st.V, nsamples, nrows, ncols, ndepth, nembeds, transform, which, x, level, along, descending, top, ntop,
+                     pairs, npairs, o, scratch_bytes);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload)
+int btf_collect_ranking(btf_ctx* c, int nsamples, int transform, int which, const double* x, double level, int along, int descending,
+                        const int* top, int ntop, const int* pairs, int npairs, double* expected_out, double* var_out,
+                        double* ptop_out, int* ranks_out, double* prob_less_out, double* prob_defined_out, long long scratch_bytes) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior ranking arguments");
+  const RankOut o = {expected_out, var_out, ptop_out, ranks_out, prob_less_out, prob_defined_out};
+  if (int rc = ranking_check(c, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop, pairs, npairs,
+                             o, scratch_bytes)) return rc;
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_ranking", BTF_ESTATE, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  return ranking_run(s, st.W, st.V, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop,
+                     pairs, npairs, o, scratch_bytes);
+}
+
+// ---------------------------------------------------------------- posterior feature association (btf_assoc.h)
+namespace {
+struct AssocOut { double *mean, *var, *quant, *prob, *defined, *nmean, *values, *of_means, *sdx, *sdy; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K), dU (S,F,K): per chunk of samples the functionals' sweep
+// into the scratch, the moments of every (sample, column) and the running curve means; then the reduction over the samples
+// per (feature, column), the raw values of the requested pairs, the plug-in table, and the downloads.  scratch_bytes caps
+// the chunk's scratch (0: FUNC_SCRATCH_BYTES; one sample is the least a chunk holds).
+int assoc_run(Scratch& s, const double* dW, const double* dV, const double* dU, int S, int N, int M, int T, int K, int F, int transform,
+              int which, const double* x, double level, const int* stats, int nstats, const double* q, int nq, const int* pairs,
+              int npairs, const AssocOut& o, long long scratch_bytes) {
+  AssocKernel moments = assoc_moments_fn(K), reduce = assoc_reduce_fn(K);
+  FuncSweep w;
+  if (!moments || !reduce || !func_sweep_init(w, s, dW, dV, S, N, M, T, K, transform, which, x, level, scratch_bytes))
+    return fail(s.ctx(), BTF_EINVAL, "posterior association: nembeds must be 1..10 and transform 0..2");
+  const size_t NM = (size_t)N * M, FM = (size_t)F * M;
+  AssocArgs a = {};
+  a.vals = w.vals; a.W = dW; a.U = dU; a.S = S; a.N = N; a.M = M; a.F = F;
+  a.mom = s.alloc<double>((size_t)S * M * assoc_nmom(K));
+  a.nst = nstats;
+  for (int k = 0; k < nstats; ++k) a.st[k] = stats[k];
+  const SortGeom g = sort_geom(S, ASSOC_SORT_LDS, ASSOC_ROWS);      // rows of P doubles; a pair takes one per statistic
+  a.P = g.P;
+  while ((1 << a.pshift) < a.P) ++a.pshift;
+  a.cells = std::max(1, std::min(g.cells / nstats, F));
+  const size_t lds = (size_t)a.cells * nstats * a.P * sizeof(double);
+  a.nq = nq;
+  if (nq) { a.q = s.upload(q, (size_t)nq); a.quant = s.alloc<double>((size_t)nstats * nq * FM); }
+  a.mean = s.alloc<double>(nstats * FM); a.var = s.alloc<double>(nstats * FM); a.prob = s.alloc<double>(nstats * FM);
+  a.defined = s.alloc<double>(FM); a.nmean = s.alloc<double>(M);
+  if (npairs) { a.npairs = npairs; a.pairs = s.upload(pairs, (size_t)2 * npairs); a.values = s.alloc<double>((size_t)nstats * npairs * S); }
+  const bool plug = o.of_means != nullptr;
+  if (plug) {
+    a.pbar = s.alloc<double>((size_t)F * N); a.gbar = s.alloc<double>(NM); a.gcnt = s.alloc<int>(NM);
+    a.om = s.alloc<double>(ASSOC_OM * FM); a.sdx = s.alloc<double>(F); a.sdy = s.alloc<double>(M);
+    s.zero(a.gbar, NM * sizeof(double)); s.zero(a.gcnt, NM * sizeof(int));
+  }
+  allow_lds(s, reduce, lds);
+  const unsigned rb = (unsigned)((N + ASSOC_THREADS - 1) / ASSOC_THREADS);
+  for (int s0 = 0; s0 < S; s0 += w.sc_max) {
+    const int sc = std::min(w.sc_max, S - s0);
+    sweep_chunk(w, s0, sc);
+    a.s0 = s0; a.sc = sc;
+    launch_counted(s, BTF_K_CRITERIA, moments, dim3(M, sc), dim3(WAVE), 0, a);
+    if (plug) launch_counted(s, BTF_K_CRITERIA, assoc_gbar_fn(), dim3(rb * M), dim3(ASSOC_THREADS), 0, a);
+  }
+  const unsigned ftiles = (unsigned)((F + a.cells - 1) / a.cells);
+  launch_counted(s, BTF_K_CRITERIA, reduce, dim3(ftiles * M), dim3(ASSOC_THREADS), lds, a);
+  if (npairs) launch_counted(s, BTF_K_CRITERIA, assoc_values_fn(K), dim3(npairs), dim3(ASSOC_THREADS), 0, a);
+  if (plug) {
+    launch_counted(s, BTF_K_CRITERIA, assoc_pbar_fn(K), dim3(rb * ((F + ASSOC_FT - 1) / ASSOC_FT)), dim3(ASSOC_THREADS), 0, a);
+    launch_counted(s, BTF_K_CRITERIA, assoc_gbar_finish_fn(), dim3((unsigned)((NM + ASSOC_THREADS - 1) / ASSOC_THREADS)), dim3(ASSOC_THREADS), 0, a);
+    launch_counted(s, BTF_K_CRITERIA, assoc_cross_fn(), dim3((unsigned)F * ((M + 3) / 4)), dim3(ASSOC_THREADS), 0, a);
+  }
+  s.download(o.mean, a.mean, nstats * FM);
+  s.download(o.var, a.var, nstats * FM);
+  s.download(o.prob, a.prob, nstats * FM);
+  if (nq) s.download(o.quant, a.quant, (size_t)nstats * nq * FM);
+  s.download(o.defined, a.defined, FM);
+  s.download(o.nmean, a.nmean, (size_t)M);
+  if (npairs) s.download(o.values, a.values, (size_t)nstats * npairs * S);
+  if (plug) { s.download(o.of_means, a.om, ASSOC_OM * FM); s.download(o.sdx, a.sdx, (size_t)F); s.download(o.sdy, a.sdy, (size_t)M); }
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int assoc_check(btf_ctx* c, int S, int N, int M, int T, int K, int F, const double* Us, int transform, int which, const double* x,
+                double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs, const AssocOut& o,
+                long long scratch_bytes) {
+  if (S < 1 || N < 1 || M < 1 || F < 1 || K < 1 || K > MAX_K || !Us || transform < 0 || transform > 2 || which < 0 || which >= FUNC_COUNT ||
+      !x || !stats || nstats < 1 || nstats > ASSOC_NSTATS || nq < 0 || (nq > 0 && (!q || !o.quant)) || npairs < 0 ||
+      (npairs > 0 && (!pairs || !o.values)) || (o.of_means && (!o.sdx || !o.sdy)) || scratch_bytes < 0)
+    return fail(c, BTF_EINVAL, "bad posterior association arguments");
+  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior association: at most " + std::to_string(FUNC_MAX_S) + " samples (the values of a pair are sorted in LDS)");
+  if ((long long)F * M > 0x7fffffffLL || (long long)N * M > 0x7fffffffLL * (long long)ASSOC_THREADS)
+    return fail(c, BTF_EINVAL, "posterior association: too many (feature, column) pairs or curves for one launch");
+  if (int rc = check_curve_axis(c, "posterior association", T, x, &which, 1, level)) return rc;
+  for (int k = 0; k < nstats; ++k)
+    if (stats[k] < 0 || stats[k] >= ASSOC_NSTATS || (k > 0 && stats[k] == stats[0]))
+      return fail(c, BTF_EINVAL, "posterior association: statistic codes must be distinct and in 0..1");
+  if (int rc = check_percentiles(c, q, nq)) return rc;
+  for (int k = 0; k < npairs; ++k)
+    if (pairs[2 * k] < 0 || pairs[2 * k] >= F || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= M)
+      return fail(c, BTF_EINVAL, "posterior association: pair index out of range");
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_posterior_association(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, int nfeatures, const double* Ws,
+                              const double* Vs, const double* Us, int transform, int which, const double* x, double level,
+                              const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs, double* mean_out,
+                              double* var_out, double* q_out, double* prob_out, double* defined_out, double* nmean_out,
+                              double* values_out, double* of_means_out, double* sdx_out, double* sdy_out, long long scratch_bytes) {
+  const AssocOut o = {mean_out, var_out, q_out, prob_out, defined_out, nmean_out, values_out, of_means_out, sdx_out, sdy_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior association arguments");
+  if (int rc = assoc_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, nfeatures, Us, transform, which, x, level, stats, nstats, q, nq,
+                           pairs, npairs, o, scratch_bytes)) return rc;
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, nrows, ncols * ndepth, nembeds, Ws, Vs, st)) return rc;
+  const double* dU = s.upload(Us, (size_t)nsamples * nfeatures * nembeds);
+  return assoc_run(s, st.W, st.V, dU, nsamples, nrows, ncols, ndepth, nembeds, nfeatures, transform, which, x, level, stats, nstats, q, nq,
+                   pairs, npairs, o, scratch_bytes);
+}
+
+// the same on the first nsamples collected states, read where they lie; only Us (the host keeps U) is uploaded
+int btf_collect_association(btf_ctx* c, int nsamples, int nfeatures, const double* Us, int transform, int which, const double* x,
+                            double level, const int* stats, int nstats, const double* q, int nq, const int* pairs, int npairs,
+                            double* mean_out, double* var_out, double* q_out, double* prob_out, double* defined_out, double* nmean_out,
+                            double* values_out, double* of_means_out, double* sdx_out, double* sdy_out, long long scratch_bytes) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior association arguments");
+  const AssocOut o = {mean_out, var_out, q_out, prob_out, defined_out, nmean_out, values_out, of_means_out, sdx_out, sdy_out};
+  if (int rc = assoc_check(c, nsamples, c->N, c->M, c->T, c->K, nfeatures, Us, transform, which, x, level, stats, nstats, q, nq, pairs, npairs,
+                           o, scratch_bytes)) return rc;
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_association", BTF_ESTATE, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  const double* dU = s.upload(Us, (size_t)nsamples * nfeatures * c->K);
+  return assoc_run(s, st.W, st.V, dU, nsamples, c->N, c->M, c->T, c->K, nfeatures, transform, which, x, level, stats, nstats, q, nq,
+                   pairs, npairs, o, scratch_bytes);
+}
+
+// ---------------------------------------------------------------- monotone projection of the posterior (btf_monotone.h)
+namespace {
+// The projection of the device states dW (S,N,K), dVin (S,M,T,K) into dVout (dVin itself: in place), the summary of the
+// projected states where they lie, and the downloads.  Null outputs are skipped; mean_out null: no summary.
+int mono_run(Scratch& s, const double* dW, const double* dVin, double* dVout, int S, int N, int M, int T, int K, int increasing,
+             int transform, const double* q, int nq, double* V_out, int* pools_out, double* mean_out, double* q_out) {
+  MonoKernel project = mono_project_fn(K);
+  if (!project) return fail(s.ctx(), BTF_EINVAL, "posterior monotone: nembeds must be 1..10");
+  const size_t nW = (size_t)N * K, nV = (size_t)M * T * K, YMAX = 65535;   // (a grid's y extent)
+  int* dpools = s.alloc<int>((size_t)S * M);
+  MonoArgs a = {};
+  a.N = N; a.M = M; a.T = T; a.increasing = increasing ? 1 : 0;
+  for (size_t s0 = 0; s0 < (size_t)S; s0 += YMAX) {
+    const unsigned sc = (unsigned)std::min<size_t>(YMAX, (size_t)S - s0);
+    a.W = dW + s0 * nW; a.Vin = dVin + s0 * nV; a.Vout = dVout + s0 * nV; a.pools = dpools + s0 * M;
+    launch_counted(s, BTF_K_CRITERIA, project, dim3((unsigned)M, sc), dim3(MONO_THREADS), mono_lds(T, K), a);
+  }
+  if (mean_out) summary_stage(s, dW, dVout, S, N, M * T, K, transform, q, nq, mean_out, q_out);
+  s.download(V_out, (const double*)dVout, (size_t)S * nV);
+  s.download(pools_out, (const int*)dpools, (size_t)S * M);
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int mono_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, const double* q, int nq, const double* mean_out,
+               const double* q_out) {
+  if (S < 1 || N < 1 || M < 1 || T < 1 || K < 1 || K > MAX_K || nq < 0 || (nq > 0 && (!q || !q_out || !mean_out)) ||
+      (mean_out && (transform < 0 || transform > 2)))
+    return fail(c, BTF_EINVAL, "bad posterior monotone arguments");
+  if (mean_out && S > 16384) return fail(c, BTF_EINVAL, "posterior monotone: at most 16384 samples with a summary (its values are sorted in LDS)");
+  if (!mono_fits(T, K))
+    return fail(c, BTF_EINVAL, "posterior monotone: ndepth * nembeds too large for the PAV kernels (pav_fits: 8 T K + 4 T <= 65536 bytes of LDS)");
+  if ((long long)M * T > 0x7fffffffLL) return fail(c, BTF_EINVAL, "posterior monotone: too many cells for one launch");
+  if (int rc = check_percentiles(c, q, nq)) return rc;
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_posterior_monotone(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                           int increasing, int transform, const double* q, int nq, double* V_out, int* pools_out, double* mean_out,
+                           double* q_out) {
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior monotone arguments");
+  if (int rc = mono_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, q, nq, mean_out, q_out)) return rc;
+  Scratch s(nullptr, nullptr); States st;      // (V: the scratch's own copy, projected where it lies)
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, nrows, ncols * ndepth, nembeds, Ws, Vs, st)) return rc;
+  return mono_run(s, st.W, st.V, st.V, nsamples, nrows, ncols, ndepth, nembeds, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
+}
+
+// the same on the first nsamples collected states, read where they lie (Ws = Vs = NULL), or on uploaded states on the
+// context's device and stream; in_place overwrites the collected V samples and needs no second copy of them
+int btf_collect_monotone(btf_ctx* c, int nsamples, const double* Ws, const double* Vs, int increasing, int in_place, int transform,
+                         const double* q, int nq, double* V_out, int* pools_out, double* mean_out, double* q_out) {
+  if (!c || (Ws == nullptr) != (Vs == nullptr)) return fail(c, BTF_EINVAL, "bad posterior monotone arguments");
+  if (int rc = mono_check(c, nsamples, c->N, c->M, c->T, c->K, transform, q, nq, mean_out, q_out)) return rc;
+  if (in_place && Ws) return fail(c, BTF_EINVAL, "btf_collect_monotone: in_place projects the collected samples, not uploaded states");
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_monotone", BTF_EINVAL, nsamples, c->N, c->M * c->T, c->K, Ws, Vs, st)) return rc;
+  if (Ws) return mono_run(s, st.W, st.V, st.V, nsamples, c->N, c->M, c->T, c->K, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
+  double* dVout = in_place ? st.V : s.alloc<double>((size_t)nsamples * c->M * c->T * c->K);
+  return mono_run(s, st.W, st.V, dVout, nsamples, c->N, c->M, c->T, c->K, increasing, transform, q, nq, V_out, pools_out, mean_out, q_out);
+}
+
+// ---------------------------------------------------------------- folding new rows in (btf_fold_in.h)
+namespace {
+thread_local int g_fold_fail_index = -1;      // btf_fail_index(NULL): the failing (sample, row) of the last stateless call
+
+struct FoldIn {
+  int family, S, R, M, T, K;
+  const double *count, *ysum, *trials, *z;
+  unsigned long long seed;
+  int inner_sweeps;
+  long long sample0;
+  double *W_out, *Wmean_out;
+  int transform;
+  const double* q; int nq;
+  double *mean_out, *q_out;
+};
+
+// everything that can be refused without a device
+int fold_in_check(btf_ctx* c, const FoldIn& f) {
+  if (f.family < FOLD_GAUSSIAN || f.family > FOLD_BINOMIAL || f.S < 1 || f.R < 1 || f.M < 1 || f.T < 1 || f.K < 1 || f.K > MAX_K ||
+      !f.ysum || !f.W_out || f.sample0 < 0 || f.nq < 0 || (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2)
+    return fail(c, BTF_EINVAL, "bad fold_in arguments");
+  if (f.family == FOLD_GAUSSIAN && !f.count) return fail(c, BTF_EINVAL, "fold_in: the Gaussian family needs count");
+  if (f.family == FOLD_BINOMIAL && (!f.trials || f.z || f.inner_sweeps < 1))
+    return fail(c, BTF_EINVAL, "fold_in: the Binomial family needs trials and inner_sweeps >= 1, and takes no z");
+  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "fold_in: the summary stage takes at most 16384 samples");
+  if ((double)(f.sample0 + f.S) * f.R >= 2147483647.0 || (double)f.R * f.M * f.T >= 2147483647.0)
+    return fail(c, BTF_EINVAL, "fold_in: (sample0 + nsamples) * nrows_new and nrows_new * ncols * ndepth must stay below 2^31");
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  const size_t n = (size_t)f.R * f.M * f.T;
+  const double* cw = f.family == FOLD_GAUSSIAN ? f.count : f.trials;
+  for (size_t e = 0; e < n; ++e) {
+    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(f.ysum[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, "fold_in: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
+    if (f.family == FOLD_BINOMIAL && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLD_MAX_TRIALS))
+      return fail(c, BTF_EINVAL, "fold_in: Binomial trial counts must be integers up to " + std::to_string(FOLD_MAX_TRIALS));
+  }
+  return BTF_OK;
+}
+
+// The launches on device states dV (S,M,T,K) and per-sample scalars on the device (noise may be null: 1).  The scratch's
+// context may be null (the stateless form: default stream, launches not counted).  W stays on the device between the draw
+// and the summary.
+int fold_in_run(Scratch& s, const double* dV, const double* dnoise, int nstride, const double* dsig, int sstride, const FoldIn& f) {
+  btf_ctx* c = s.ctx();
+  const int S = f.S, R = f.R, MT = f.M * f.T, K = f.K;
+  FoldKernel kern = fold_in_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, "fold_in: nembeds must be 1..10 and family 0..1");
+  // row statistics in the kernel's [cell][row] layout; Binomial: kappa = successes - trials / 2
+  std::vector<double> hc((size_t)MT * R), hy((size_t)MT * R);
+  const double* cw = f.family == FOLD_GAUSSIAN ? f.count : f.trials;
+  for (int r = 0; r < R; ++r)
+    for (int jt = 0; jt < MT; ++jt) {
+      const double cv = cw[(size_t)r * MT + jt], yv = f.ysum[(size_t)r * MT + jt];
+      hc[(size_t)jt * R + r] = cv;
+      hy[(size_t)jt * R + r] = f.family == FOLD_BINOMIAL ? (cv > 0.0 ? yv - 0.5 * cv : 0.0) : (cv > 0.0 ? yv : 0.0);
+    }
+  const size_t nW = (size_t)S * R * K, cellsN = (size_t)R * MT;
+  const int stat0[2] = {0, INT_MAX};
+  FoldArgs a = {};
+  a.V = dV; a.noise = dnoise; a.sigma2 = dsig; a.nstride = nstride; a.sstride = sstride;
+  a.cnt = s.upload(hc.data(), cellsN); a.ysum = s.upload(hy.data(), cellsN);
+  a.W = s.alloc<double>(nW); a.status = s.upload(stat0, 2);
+  if (f.Wmean_out) a.Wmean = s.alloc<double>(nW);
+  if (f.z) a.z = s.upload(f.z, nW);
+  a.seed = f.seed; a.sample0 = f.sample0; a.S = S; a.R = R; a.MT = MT; a.sweeps = f.inner_sweeps;
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3(S, (R + WAVE - 1) / WAVE), dim3(FOLD_PARTS * WAVE), 0, a);
+  // the summary stage reads the device-resident W (S,R,K) and V
+  if (f.mean_out) summary_stage(s, a.W, dV, S, R, MT, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
+  int stat[2] = {0, INT_MAX};
+  s.download(stat, a.status, 2);
+  s.download(f.W_out, a.W, nW);
+  s.download(f.Wmean_out, a.Wmean, nW);
+  const int rc = s.finish();
+  if (rc) return rc;
+  if (stat[0]) {
+    if (c) c->fail_index = stat[1];
+    g_fold_fail_index = stat[1];
+    return fail(c, BTF_ENOTPD, "fold_in: the precision of (sample, row) index " + std::to_string(stat[1]) +
+                                   " = sample * nrows_new + row is not positive definite (or nu2 / sigma2 / V not finite)");
+  }
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_fold_in_rows(int device, int family, int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs,
+                     const double* noise, const double* sigma2, const double* count, const double* ysum, const double* trials,
+                     const double* z, unsigned long long seed, int inner_sweeps, long long sample0, double* W_out, double* Wmean_out,
+                     int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  const FoldIn f = {family, nsamples, nrows_new, ncols, ndepth, nembeds, count, ysum, trials, z, seed, inner_sweeps, sample0,
+                    W_out, Wmean_out, transform, q, nq, mean_out, q_out};
+  g_fold_fail_index = -1;
+  if (!Vs || !sigma2 || (family == FOLD_GAUSSIAN && !noise)) return fail(nullptr, BTF_EINVAL, "bad fold_in arguments");
+  if (int rc = fold_in_check(nullptr, f)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(sigma2[s] > 0.0 && sigma2[s] < INFINITY) || (family == FOLD_GAUSSIAN && !(noise[s] > 0.0 && noise[s] < INFINITY)))
+      return fail(nullptr, BTF_EINVAL, "fold_in: nu2 and sigma2 must be finite and positive");
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, 0, ncols * ndepth, nembeds, nullptr, Vs, st)) return rc;
+  const double* ds = s.upload(sigma2, (size_t)nsamples);
+  const double* dn = family == FOLD_GAUSSIAN ? s.upload(noise, (size_t)nsamples) : nullptr;
+  return fold_in_run(s, st.V, dn, 1, ds, 1, f);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload): V from the sample slots, nu2_s and
+// sigma2_s from the collected scalars
+int btf_collect_fold_in(btf_ctx* c, int family, int nsamples, int nrows_new, const double* count, const double* ysum,
+                        const double* trials, const double* z, unsigned long long seed, int inner_sweeps, long long sample0,
+                        double* W_out, double* Wmean_out, int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  if (!c) return fail(c, BTF_EINVAL, "bad fold_in arguments");
+  const FoldIn f = {family, nsamples, nrows_new, c->M, c->T, c->K, count, ysum, trials, z, seed, inner_sweeps, sample0,
+                    W_out, Wmean_out, transform, q, nq, mean_out, q_out};
+  if (int rc = fold_in_check(c, f)) return rc;
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_fold_in", BTF_ESTATE, nsamples, 0, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  return fold_in_run(s, st.V, family == FOLD_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT,
+                     c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, f);
+}
+
+// ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)
+int btf_diag_eval(int device, int nchains, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* const* Ws,
+                  const double* const* Vs, btf_ctx* const* ctxs, int transform, double* out) {
+  if (nchains < 1 || nchains > DIAG_MAX_CHAINS || nsamples < 4 || (long long)nchains * nsamples > DIAG_MAX_DRAWS || nrows < 1 ||
+      ncols < 1 || ndepth < 1 || nembeds < 1 || nembeds > MAX_K || transform < 0 || transform > 2 || !out ||
+      (long long)nrows * ncols * ndepth > 0x7fffffffLL)
+    return fail(nullptr, BTF_EINVAL, "bad btf_diag_eval arguments");
+  for (int c = 0; c < nchains; ++c) {
+    const btf_ctx* x = ctxs ? ctxs[c] : nullptr;
+    if (x) {
+      if (x->dev != device || x->N != nrows || x->M != ncols || x->T != ndepth || x->K != nembeds)
+        return fail(nullptr, BTF_EINVAL, "btf_diag_eval: a context of another device or shape");
+      if (x->nl != x->N || x->ml != x->M) return fail(nullptr, BTF_ESTATE, "btf_diag_eval needs unsharded contexts");
+      if (!has_collected(x, nsamples)) return no_collected(nullptr, BTF_ESTATE, "btf_diag_eval");
+    } else if (!Ws || !Vs || !Ws[c] || !Vs[c]) {
+      return fail(nullptr, BTF_EINVAL, "btf_diag_eval: chain without host arrays or a context");
+    }
+  }
+  if (int rc = use_device(device)) return rc;
+  const int MT = ncols * ndepth;
+  const size_t cells = (size_t)nrows * MT;
+  const size_t nW = (size_t)nsamples * nrows * nembeds, nV = (size_t)nsamples * MT * nembeds;
+  Scratch s(nullptr, nullptr);
+  std::vector<const double*> pw(nchains), pv(nchains);
+  for (int c = 0; c < nchains; ++c) {
+    const btf_ctx* x = ctxs ? ctxs[c] : nullptr;
+    if (x) {                                               // the collection copies may still be in flight on its stream
+      s.check(hipStreamSynchronize(x->stream), "hipStreamSynchronize");
+      pw[c] = x->smp_W; pv[c] = x->smp_V;
+    } else {
+      pw[c] = s.upload(Ws[c], nW); pv[c] = s.upload(Vs[c], nV);
+    }
+  }
+  double* dout = s.alloc<double>(DIAG_OUT * cells);
+  int P = 2;
+  while (P < nchains * nsamples) P <<= 1;
+  DiagArgs a{s.upload(pw.data(), (size_t)nchains), s.upload(pv.data(), (size_t)nchains), nchains, nsamples, nrows, MT, P, transform, dout};
+  const size_t lds = (size_t)(nchains * nsamples + P) * sizeof(double);
+  K_SWITCH(nembeds, {
+    allow_lds(s, diag_kernel<KT>, lds);
+    s.launch(diag_kernel<KT>, dim3((unsigned)cells), dim3(DIAG_THREADS), lds, a);
+  });
+  s.download(out, dout, DIAG_OUT * cells);
+  return s.finish();
+}
+
+}  // extern "C"
+int btf::fold_fail_index() { return g_fold_fail_index; }

@@ -1,4 +1,4 @@
-// The posterior feature association (btf_assoc.h): the kernels, one compilation unit of their own.  btf_abi.hip launches
+// The posterior feature association (btf_assoc.h): the kernels, one compilation unit of their own.  btf_analysis.hip launches
 // them through the function pointers below (counted under BTF_K_CRITERIA).  gfx950 only.
 #define BTF_ASSOC_UNIT
 #include "btf_assoc.h"

@@ -7,6 +7,13 @@ namespace btf {
 
 constexpr int WAVE = 64;
 
+// device-resident scalar hyper-parameters (rng="device": drawn by scalars_kernel / lam2_kernel,
+// read by the half-sweep kernels, so that a full sweep needs no host round trip)
+enum { HYP_NU2 = 0, HYP_SIGMA2 = 1, HYP_LAM2 = 2, HYP_LAM2A = 3, HYP_SSE = 4, HYP_WSQ = 5, HYP_COUNT = 8 };
+// the likelihood families of the slice samplers (btf_ess.h has the table)
+enum { ESS_FAM_POISSON_LOG = 0, ESS_FAM_POISSON_IDENTITY = 1, ESS_FAM_BERNOULLI_LOGIT = 2, ESS_FAM_GAUSSIAN = 3, ESS_FAM_NEGBIN_LOGIT = 4,
+       ESS_FAM_GAMMA_GRID = 5, ESS_FAM_COUNT = 6 };
+
 __host__ __device__ constexpr int tri(int k) { return k * (k + 1) / 2; }
 // packed lower-triangular index of (a,b), a >= b
 __host__ __device__ constexpr int lidx(int a, int b) { return a * (a + 1) / 2 + b; }

@@ -36,8 +36,7 @@ namespace btf {
 // which takes the family and its parameter at run time (libm exp / log1p: one evaluation is still one pass).  Family 5
 // is not a function of (S1, cnt) alone: its kernels are in a unit of their own (btf_gamma_grid.h, ESS_LINK_GAMMA_GRID).
 enum { ESS_LINK_LOG = 0, ESS_LINK_IDENTITY = 1, ESS_LINK_GENERIC = 2, ESS_LINK_GAMMA_GRID = 3 };
-enum { ESS_FAM_POISSON_LOG = 0, ESS_FAM_POISSON_IDENTITY = 1, ESS_FAM_BERNOULLI_LOGIT = 2, ESS_FAM_GAUSSIAN = 3, ESS_FAM_NEGBIN_LOGIT = 4,
-       ESS_FAM_GAMMA_GRID = 5, ESS_FAM_COUNT = 6 };
+// (ESS_FAM_*: btf_device.h)
 struct LikFam { int fam; double par; };
 __host__ __device__ constexpr int ess_link_of(int fam) {
   return fam <= ESS_FAM_POISSON_IDENTITY ? fam : (fam == ESS_FAM_GAMMA_GRID ? ESS_LINK_GAMMA_GRID : ESS_LINK_GENERIC);

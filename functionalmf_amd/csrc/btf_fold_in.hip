@@ -1,4 +1,4 @@
-// Folding new rows into a fitted posterior (btf_fold_in.h): the kernel, one compilation unit of its own.  btf_abi.hip
+// Folding new rows into a fitted posterior (btf_fold_in.h): the kernel, one compilation unit of its own.  btf_analysis.hip
 // launches it through the function pointer below (counted under BTF_K_CRITERIA).  gfx950 only.
 #define BTF_FOLD_UNIT
 #include "btf_fold_in.h"

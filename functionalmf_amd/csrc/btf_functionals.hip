@@ -1,4 +1,4 @@
-// The posterior curve functionals (btf_functionals.h): the kernels, one compilation unit of their own.  btf_abi.hip
+// The posterior curve functionals (btf_functionals.h): the kernels, one compilation unit of their own.  btf_analysis.hip
 // launches them through the function pointers below (counted under BTF_K_CRITERIA).  gfx950 only.
 #define BTF_FUNC_UNIT
 #include "btf_functionals.h"

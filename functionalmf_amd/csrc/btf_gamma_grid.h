@@ -16,7 +16,12 @@
 //   gg_logsum_kernel                              L = sum_r log y of every cell, and a flag for an observed y <= 0
 // Every sum has a fixed order (no float atomics): two calls give identical bits.
 #pragma once
+#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT)
 #include "btf_gass.h"
+#else      // host code that needs the table's types alone (btf_ctx.h, btf_gg_criteria.h): no sampler kernels
+#include "btf_device.h"
+namespace btf { struct GassEvalArgs; }
+#endif
 
 namespace btf {
 

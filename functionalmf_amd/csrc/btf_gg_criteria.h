@@ -35,7 +35,7 @@ constexpr int GGC_SB = 16;              // samples per block: part[4][16][64] do
 
 // CritArgs (c0 / c1 / noise / par unused) and the table; GgTab::L is the slot's [M][T][N] log-sum statistic
 using GgCritKernel = void (*)(CritArgs, GgTab);
-// btf_gg_criteria.hip: the kernel by nembeds (nullptr outside 1..10), for launch_counted in btf_abi.hip
+// btf_gg_criteria.hip: the kernel by nembeds (nullptr outside 1..10), for launch_counted in btf_analysis.hip
 GgCritKernel gg_crit_fn(int K);
 GgCritKernel gg_crit_plugin_fn();
 

@@ -1,4 +1,4 @@
-// The gamma-grid criteria kernels (btf_gg_criteria.h): one compilation unit of their own.  btf_abi.hip launches them
+// The gamma-grid criteria kernels (btf_gg_criteria.h): one compilation unit of their own.  btf_analysis.hip launches them
 // through the function pointers below (counted under BTF_K_CRITERIA).  gfx950 only.
 #define BTF_GG_CRIT_UNIT
 #include "btf_gg_criteria.h"

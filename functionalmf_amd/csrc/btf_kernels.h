@@ -1158,9 +1158,7 @@ struct WSolveArgs {
 #define WS_STAMP(n) do {} while (0)
 #endif
 
-// device-resident scalar hyper-parameters (rng="device": drawn by scalars_kernel / lam2_kernel,
-// read by the half-sweep kernels, so that a full sweep needs no host round trip)
-enum { HYP_NU2 = 0, HYP_SIGMA2 = 1, HYP_LAM2 = 2, HYP_LAM2A = 3, HYP_SSE = 4, HYP_WSQ = 5, HYP_COUNT = 8 };
+// (HYP_*, the device-resident scalar hyper-parameters: btf_device.h)
 __device__ inline void band_side(const BandSide& bs, int j, double* itau, int nthreads) {
   const double* tau = bs.Tau2 + (size_t)(bs.col0 + j) * bs.nD;
   // independent of lam2: this thread's Tau2 values (two: nD <= 2 nthreads) and the CSR bounds of its entries (two)

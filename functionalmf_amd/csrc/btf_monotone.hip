@@ -1,4 +1,4 @@
-// The monotone projection of the posterior (btf_monotone.h): the kernel, one compilation unit of its own.  btf_abi.hip
+// The monotone projection of the posterior (btf_monotone.h): the kernel, one compilation unit of its own.  btf_analysis.hip
 // launches it through the function pointer below (counted under BTF_K_CRITERIA).  gfx950 only.
 #define BTF_MONOTONE_UNIT
 #include "btf_monotone.h"

@@ -2,17 +2,13 @@
 // include/btf.h, one compilation unit of their own.  gfx950 only.
 #include "../../include/btf.h"
 #include "btf_nmf.h"
-#include "btf_scratch.h"      // Scratch: the device buffers of btf_nmf_pav
+#include "btf_ctx.h"          // use_device; Scratch: the device buffers of btf_nmf_pav
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <string>
 #include <vector>
-
-namespace btf {
-int set_global_error(int code, const std::string& msg);   // btf_abi.hip: the text btf_last_error(NULL) returns
-}
 
 using namespace btf;
 
@@ -40,7 +36,7 @@ struct btf_nmf {
 
 namespace {
 
-int fail(int code, const std::string& msg) { return set_global_error(code, msg); }
+int fail(int code, const std::string& msg) { return report_error(nullptr, code, msg); }   // the text btf_last_error(NULL) returns
 
 #define NMFCHK(call)                                                                                        \
   do {                                                                                                      \
@@ -236,8 +232,7 @@ int btf_nmf_create(btf_nmf** out, int device, int nrows, int ncols, int ndepth, 
   if (nrows < 1 || ncols < 1 || ndepth < 1 || nreps < 1 || nreps > 255 || nembeds < 1 || nembeds > NMF_MAX_K || !S ||
       !(ssw >= 0.0) || (long long)ncols * ndepth > INT32_MAX / 2 || (long long)nrows * ncols * ndepth > (1LL << 40))
     return fail(BTF_EINVAL, "bad btf_nmf_create arguments");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(BTF_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (int rc = use_device(device)) return rc;
   btf_nmf* h = new btf_nmf;
   h->dev = device;
   h->N = nrows; h->M = ncols; h->T = ndepth; h->R = nreps; h->K = nembeds; h->MT = ncols * ndepth;

@@ -1,4 +1,4 @@
-// The posterior ranking (btf_ranking.h): the kernels, one compilation unit of their own.  btf_abi.hip launches them
+// The posterior ranking (btf_ranking.h): the kernels, one compilation unit of their own.  btf_analysis.hip launches them
 // through the function pointers below (counted under BTF_K_CRITERIA).  gfx950 only.
 #define BTF_RANK_UNIT
 #include "btf_ranking.h"

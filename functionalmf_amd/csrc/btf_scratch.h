@@ -48,7 +48,11 @@ class Scratch {
   void download(T* h, const T* d, size_t n) {
     if (h && !rc_) check(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st_), "hipMemcpyAsync (download)");
   }
-  // a launch the profile does not count (launch_counted of btf_abi.hip: the counted one)
+  // zeroes `bytes` of one of its buffers on the stream
+  void zero(void* p, size_t bytes) {
+    if (!rc_) check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync");
+  }
+  // a launch the profile does not count (launch_counted of btf_ctx.h: the counted one)
   template <typename F, typename... Args>
   void launch(F kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
     if (rc_) return;

@@ -1,6 +1,8 @@
 """The front end the posterior analysis features share (functionalmf_amd/_analysis.py, _native.check): the argument checks
 tested directly, and the refusals of every analysis method of a model - no samples, a sharded model, a malformed results
 dict - made before any device call.  No GPU."""
+import os
+import re
 import types
 
 import numpy as np
@@ -180,3 +182,18 @@ def test_malformed_results_are_a_value_error(name):
     for bad in (wrong_K, short_V, {}):
         with pytest.raises(ValueError):
             FROM_RESULTS[name](_model_without_a_device(collected=S), bad)
+
+
+# ---- the C++ side: the analysis entry points have a compilation unit of their own
+def test_analysis_entry_points_live_in_their_own_unit():
+    pattern = re.compile(r"btf_posterior_\w+|btf_collect_(summary|functionals|ranking|association|monotone|fold_in)|btf_crit_\w+|"
+                         r"btf_predict_\w+|btf_fold_in_rows|btf_diag_eval")
+    names = sorted(n for n in _native.SIGNATURES if pattern.fullmatch(n))
+    assert len(names) >= 19 and "btf_collect_begin" not in names and "btf_collect_end" not in names
+    unit = os.path.join(_native.CSRC, "btf_analysis.hip")
+    assert unit in _native.SOURCES
+    analysis, abi = open(unit).read(), open(os.path.join(_native.CSRC, "btf_abi.hip")).read()
+    for name in names:
+        definition = re.compile(r"^int %s\(" % name, re.M)
+        assert len(definition.findall(analysis)) == 1, name
+        assert not definition.search(abi), name

@@ -240,11 +240,11 @@ def test_new_abi_is_declared_exported_and_bound():
     assert hasattr(lib, "btf_posterior_association") and hasattr(lib, "btf_collect_association")
     assert len(_native.SIGNATURES["btf_posterior_association"][1]) == 31
     assert len(_native.SIGNATURES["btf_collect_association"][1]) == 25
-    assert any(src == os.path.join(_native.CSRC, "btf_assoc.hip") for src, _ in _native.MORE_SOURCES)
+    assert any(src == os.path.join(_native.CSRC, "btf_assoc.hip") for src, _ in _native.UNITS)
     assert os.path.join(_native.CSRC, "btf_assoc.h") in _native.HEADERS
     # the launches are counted under BTF_K_CRITERIA: the counter table keeps its length
     assert len(_native.KERNEL_NAMES) == 15 and re.search(r"BTF_K_COUNT = 15\b", text)
-    abi = open(os.path.join(_native.CSRC, "btf_abi.hip")).read()
+    abi = open(os.path.join(_native.CSRC, "btf_analysis.hip")).read()
     assert abi.count("assoc_run(s, ") == 2 and abi.count("assoc_check(") == 3      # one of each, behind both entry points
 
 

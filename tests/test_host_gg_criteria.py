@@ -107,10 +107,10 @@ def test_new_abi_is_declared_exported_and_bound():
     _native.build()
     lib = _native.load()
     assert hasattr(lib, "btf_crit_set_logsum")
-    assert any(src == os.path.join(_native.CSRC, "btf_gg_criteria.hip") for src, _ in _native.MORE_SOURCES)
+    assert any(src == os.path.join(_native.CSRC, "btf_gg_criteria.hip") for src, _ in _native.UNITS)
     assert os.path.join(_native.CSRC, "btf_gg_criteria.h") in _native.HEADERS
-    # unchanged: the eleven SOURCES, the counter table, the signatures family 5 enters through
-    assert len(_native.SOURCES) == 11 and len(_native.KERNEL_NAMES) == 15 and re.search(r"BTF_K_COUNT = 15\b", text)
+    # unchanged: the counter table, the signatures family 5 enters through
+    assert len(_native.KERNEL_NAMES) == 15 and re.search(r"BTF_K_COUNT = 15\b", text)
     assert len(_native.SIGNATURES["btf_crit_eval"][1]) == 12 and len(_native.SIGNATURES["btf_crit_loo"][1]) == 14
     assert criteria.FAMILY_GAMMA_GRID == _native.CRIT_FAMILY_GAMMA_GRID == 5
     # one copy of the cell formula: the criteria kernels call gg_term of btf_gamma_grid.h

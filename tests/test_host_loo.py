@@ -213,7 +213,7 @@ def test_new_abi_is_declared_exported_and_bound():
     assert os.path.join(_native.CSRC, "btf_loo.h") in _native.HEADERS
     _native.build()
     assert hasattr(_native.load(), "btf_crit_loo")
-    abi = open(os.path.join(_native.CSRC, "btf_abi.hip")).read()
+    abi = open(os.path.join(_native.CSRC, "btf_analysis.hip")).read()
     assert "LOO_MAX_S" in abi and re.search(r"LOO_MAX_S = %d;" % criteria.LOO_MAX_SAMPLES, open(os.path.join(_native.CSRC, "btf_loo.h")).read())
 
 

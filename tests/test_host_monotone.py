@@ -182,11 +182,11 @@ def test_new_abi_is_declared_exported_and_bound():
     assert hasattr(lib, "btf_posterior_monotone") and hasattr(lib, "btf_collect_monotone")
     assert len(_native.SIGNATURES["btf_posterior_monotone"][1]) == 16
     assert len(_native.SIGNATURES["btf_collect_monotone"][1]) == 13
-    assert any(src == os.path.join(_native.CSRC, "btf_monotone.hip") for src, _ in _native.MORE_SOURCES)
+    assert any(src == os.path.join(_native.CSRC, "btf_monotone.hip") for src, _ in _native.UNITS)
     assert os.path.join(_native.CSRC, "btf_monotone.h") in _native.HEADERS
     # the launches are counted under BTF_K_CRITERIA: the counter table keeps its length
     assert len(_native.KERNEL_NAMES) == 15 and re.search(r"BTF_K_COUNT = 15\b", text)
-    abi = open(os.path.join(_native.CSRC, "btf_abi.hip")).read()
+    abi = open(os.path.join(_native.CSRC, "btf_analysis.hip")).read()
     assert abi.count("return mono_run(s, ") == 3 and abi.count("mono_check(") == 3       # one run function behind both entry points
     nmf = open(os.path.join(_native.CSRC, "btf_nmf.h")).read()
     assert "void nmf_pav_kernel(" in nmf                                                # the chain-start kernel stays
