@@ -24,7 +24,16 @@ def _as_Y4(Y):
         raise ValueError("Y must be (N, M, T) or (N, M, T, R) with every dimension at least 1, got %s" % (Y.shape,))
     if Y.shape[3] > 255:
         raise ValueError("at most 255 replicates per cell")
+    if np.isinf(Y).any():
+        raise ValueError("Y must be finite or nan (missing)")
     return Y
+
+
+def _check_finite(name, a):
+    """A given factor holding nan or inf would make every dual of the device's NNLS compare false: each system would come
+    back as the 1e-3 floor and the run would spend max_steps.  Refused here, as scipy's nnls refuses it in the reference."""
+    if a is not None and not np.isfinite(np.asarray(a, dtype=np.float64)).all():
+        raise ValueError("%s must be finite" % name)
 
 
 def nmf_statistics(Y):
@@ -83,6 +92,8 @@ class NMFData:
         W = np.array(W, dtype=np.float64, order="C", copy=True)
         V = np.array(V, dtype=np.float64, order="C", copy=True)
         N, M, T = self.shape[:3]
+        for name, a in (("W", W), ("V", V), ("R", R)):
+            _check_finite(name, a)
         if max_entry is not None and not (np.isfinite(max_entry) and max_entry > 0):
             raise ValueError("max_entry must be positive and finite, got %r" % (max_entry,))
         if (row_features is None) != (R is None):
@@ -163,7 +174,12 @@ def tensor_nmf(Y, nembeds, max_steps=30, monotone=False, tol=1e-4, verbose=False
     functionalmf.utils.tensor_nmf (utils.py:276-419): the same starting point under np.random.seed, the same steps and
     stopping rule.  Returns (W, V) float64 of shapes (N, K) and (M, T, K), or (W, V, info) with return_info=True: info
     holds `steps` (ALS steps run) and `rmse` (per step: sqrt of the residual sum of squares).  Given W / V are not
-    modified.  `max_entry` and `row_features` raise NotImplementedError here: bounded_tensor_nmf takes them."""
+    modified.  `max_entry` and `row_features` raise NotImplementedError here: bounded_tensor_nmf takes them.
+
+    A given W or V (or R of bounded_tensor_nmf) holding nan or inf, and +-inf in Y, raise ValueError before any device
+    call; nan in Y is a missing entry.  The reference refuses such input too: its scipy.optimize.nnls calls
+    (utils.py:335, 366, 395) check the design matrix, built from the fixed factor, and the data with asarray_chkfinite.
+    It does so in the first solve that meets the value; here every argument is checked up front."""
     if max_entry is not None:
         raise NotImplementedError("tensor_nmf: max_entry (the reference's SLSQP projection) is bounded_tensor_nmf's")
     if row_features is not None:
@@ -189,6 +205,10 @@ def _als(Y, nembeds, max_entry, row_features, R, max_steps, monotone, tol, verbo
         raise ValueError("V must be (%d, %d, %d), got %s" % (M, T, K, np.shape(V)))
     if max_entry is not None and not (np.isfinite(max_entry) and max_entry > 0):
         raise ValueError("max_entry must be positive and finite, got %r" % (max_entry,))
+    for name, a in (("W", W), ("V", V), ("R", R)):
+        _check_finite(name, a)
+    if np.isinf(np.asarray(Yarr, dtype=np.float64)).any():
+        raise ValueError("Y must be finite or nan (missing)")
     X = None
     if row_features is not None:
         X = _check_features(row_features, N)

@@ -92,6 +92,43 @@ def test_unsupported_and_bad_arguments_raise_before_any_device_call(no_device):
         utils.factor_pav(np.ones((4, 11)), np.ones((5, 11)))
     with pytest.raises(ValueError):
         utils.factor_pav(np.ones(4), np.ones((5, 1)))
+    # non-finite input: a given factor with nan or inf, +-inf in the data (nan there is a missing entry)
+    for bad in (np.nan, np.inf, -np.inf):
+        Wb, Vb = np.ones((4, 2)), np.ones((3, 5, 2))
+        Wb[3, 1] = bad
+        Vb[2, 4, 0] = bad
+        with pytest.raises(ValueError, match="W must be finite"):
+            utils.tensor_nmf(Y, 2, W=Wb)
+        with pytest.raises(ValueError, match="V must be finite"):
+            utils.tensor_nmf(Y, 2, V=Vb, fit_V=False)
+        if np.isinf(bad):
+            Yb = Y.copy()
+            Yb[1, 2, 3, 0] = bad
+            with pytest.raises(ValueError, match="Y must be finite"):
+                utils.tensor_nmf(Yb, 2)
+            with pytest.raises(ValueError, match="Y must be finite"):
+                utils.tensor_nmf(Yb[..., 0], 2, W=np.ones((4, 2)), V=np.ones((3, 5, 2)))
+            with pytest.raises(ValueError, match="Y must be finite"):
+                nmf.NMFData(Yb, 2)
+            with pytest.raises(ValueError, match="Y must be finite"):
+                nmf.nmf_statistics(Yb)
+
+
+def test_a_handle_refuses_non_finite_factors_before_any_device_call(monkeypatch):
+    """NMFData.run checks its own arguments: the handle's library is never called."""
+    data = nmf.NMFData.__new__(nmf.NMFData)
+    data.shape, data.nembeds, data.lib, data.h, data._bounded = (4, 3, 5, 2), 2, _NoDevice(), None, False
+    W, V = np.ones((4, 2)), np.ones((3, 5, 2))
+    for bad in (np.nan, np.inf, -np.inf):
+        for name, idx in (("W", (0, 0)), ("V", (1, 2, 1))):
+            a = {"W": W.copy(), "V": V.copy()}
+            a[name][idx] = bad
+            with pytest.raises(ValueError, match=name + " must be finite"):
+                data.run(a["W"], a["V"], max_steps=1)
+        Rb = np.ones((2, 2))
+        Rb[1, 0] = bad
+        with pytest.raises(ValueError, match="R must be finite"):
+            data.run(W, V, max_steps=1, row_features=np.ones((4, 2)), R=Rb)
 
 
 def test_nmf_entry_points_are_declared():

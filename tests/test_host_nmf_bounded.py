@@ -20,6 +20,19 @@ def test_bad_arguments_raise_before_any_device_call(no_device):  # noqa: F811
                dict(W=np.ones((4, 3))), dict(V=np.ones((3, 4, 2))), dict(max_steps=-1)):
         with pytest.raises(ValueError):
             utils.bounded_tensor_nmf(Y, 2, **kw)
+    for bad in (np.nan, np.inf, -np.inf):                    # non-finite input (nan in Y or row_features is "missing")
+        Wb, Vb, Rb = np.ones((4, 2)), np.ones((3, 5, 2)), np.ones((2, 2))
+        Wb[0, 1] = bad
+        Vb[0, 0, 1] = bad
+        Rb[1, 1] = bad
+        for kw, name in ((dict(W=Wb), "W"), (dict(V=Vb), "V"), (dict(row_features=X, R=Rb), "R")):
+            with pytest.raises(ValueError, match=name + " must be finite"):
+                utils.bounded_tensor_nmf(Y, 2, max_entry=0.999, **kw)
+        if np.isinf(bad):
+            Yb = Y.copy()
+            Yb[3, 0, 0, 0] = bad
+            with pytest.raises(ValueError, match="Y must be finite"):
+                utils.bounded_tensor_nmf(Yb, 2, max_entry=0.999, row_features=X)
     for k in (0, 11, 2.5, True):
         with pytest.raises(ValueError):
             utils.bounded_tensor_nmf(Y, k, max_entry=0.999)
