@@ -36,6 +36,16 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// ---------------------------------------------------------------- PAV merge
+// The value of two merged pools of w0 and w1 depths, (w0 v0 + w1 v1) / (w0 + w1), every operation rounded on its own:
+// the arithmetic of the reference's numpy and of monotone.project_host.  The rounding intrinsics (__dmul_rn, __dadd_rn)
+// do not give that here: the toolchain's headers define them as the plain operators, and -ffp-contract=fast turned the
+// sum of the two products into one product and an FMA - an ulp away from the definition now and then.
+__device__ __forceinline__ double pav_merge(int w0, double v0, int w1, double v1) {
+#pragma clang fp contract(off)
+  const double a0 = (double)w0 * v0, a1 = (double)w1 * v1;
+  return (a0 + a1) / (double)(w0 + w1);
+}
 
 // ---------------------------------------------------------------- sc1 (write-through / L1-bypassing) accesses
 // 8-byte relaxed agent-scope atomics: global_store_dwordx2 ... sc1 / global_load_dwordx2 ... sc1.  The payload of every

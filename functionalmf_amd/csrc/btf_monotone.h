@@ -26,8 +26,8 @@
 //         pairs (lo-1, lo) and (hi, hi+1) become unknown.  The next sweep starts at the first unknown pair, and a sweep
 //         that could only find clean pairs is not run: the final empty sweep costs nothing.  A column that is already
 //         monotone costs the opening pass (T projections of its rows) and two barriers.
-//       The merge arithmetic (__dmul_rn, __dmul_rn, __dadd_rn, one division) is nmf_pav_kernel's, so the result equals
-//       utils.factor_pav bit for bit.  Thread 0 writes pools[s][j] = T - merges.  Vout may be Vin (in place): a workgroup
+//       The merge arithmetic (pav_merge of btf_device.h: two products, their sum and one division, none of them fused) is
+//       nmf_pav_kernel's and numpy's, so the result equals utils.factor_pav and monotone.project_host bit for bit.  Thread 0 writes pools[s][j] = T - merges.  Vout may be Vin (in place): a workgroup
 //       reads its block before it writes it, and no other workgroup touches it.
 // Build (hipcc -O3, gfx950; -Rpass-analysis=kernel-resource-usage): no instantiation spills or uses scratch.
 //   VGPRs  K = 1..5: 48, 62, 76, 90, 104 (4 rows in registers);  K = 6..10: 86, 96, 108, 116, 126 (2 rows)
@@ -170,10 +170,7 @@ __global__ __launch_bounds__(MONO_THREADS) void mono_project_kernel(MonoArgs a) 
       while (hi + 1 < T && (int)(pool[hi + 1] & MONO_START) == t + 1) ++hi;
       const int w0 = t + 1 - p0, w1 = hi - t;
       double nv = 0.0;
-      if (tid < K) {
-        const double a0 = __dmul_rn((double)w0, sv[(size_t)t * K + tid]), a1 = __dmul_rn((double)w1, sv[(size_t)(t + 1) * K + tid]);
-        nv = __dadd_rn(a0, a1) / (double)(w0 + w1);
-      }
+      if (tid < K) nv = pav_merge(w0, sv[(size_t)t * K + tid], w1, sv[(size_t)(t + 1) * K + tid]);
       __syncthreads();                                     // every thread has read the words and the two depths
       if (tid < K)
         for (int u = p0; u <= hi; ++u) sv[(size_t)u * K + tid] = nv;

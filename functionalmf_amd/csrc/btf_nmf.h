@@ -458,10 +458,7 @@ __global__ __launch_bounds__(256) void nmf_pav_kernel(const double* __restrict__
         if (in0 || in1) { lo = min(lo, u); hi = max(hi, u); }
       }
       double nv = 0.0;
-      if (tid < K) {
-        const double a0 = __dmul_rn((double)w0, sv[t * K + tid]), a1 = __dmul_rn((double)w1, sv[(t + 1) * K + tid]);
-        nv = __dadd_rn(a0, a1) / (double)(w0 + w1);
-      }
+      if (tid < K) nv = pav_merge(w0, sv[t * K + tid], w1, sv[(t + 1) * K + tid]);      // (no product fused into the sum)
       __syncthreads();                                   // every thread has read the pools and the two depths
       if (tid < K)
         for (int u = lo; u <= hi; ++u) sv[u * K + tid] = nv;

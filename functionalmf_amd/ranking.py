@@ -128,8 +128,11 @@ def check_args(which, along, order, top, transform, x, level, pairs, S, N, M, T)
         if len(pr) and (pr.min() < 0 or pr[:, ::2].max() >= N or pr[:, 1::2].max() >= M):
             raise ValueError("pairs must hold (i, j, i2, j2) with curves inside (%d, %d)" % (N, M))
         pr = np.ascontiguousarray(pr, dtype=np.int32)
-    return (which, functionals.CODES[which], ALONG[along], ORDER[order], np.ascontiguousarray(np.minimum(tp, MAX_GROUP + 1), dtype=np.int32),
-            tcode, xs, lev, pr)
+    # every entry above MAX_GROUP is certain whatever its value: the device gets distinct stand-ins above MAX_GROUP for them
+    # (the library refuses repeated entries, and an entry need not fit 32 bits)
+    big = np.array([int(k) > MAX_GROUP for k in tp.tolist()])
+    tdev = np.where(big, MAX_GROUP + np.cumsum(big), np.where(big, 0, tp)).astype(np.int32)
+    return (which, functionals.CODES[which], ALONG[along], ORDER[order], np.ascontiguousarray(tdev), tcode, xs, lev, pr)
 
 
 def evaluate(shape, K, S, which="auc", along="cols", order="ascending", top=(1, 5), transform=None, x=None, level=None,

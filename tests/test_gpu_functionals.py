@@ -125,6 +125,28 @@ def test_functionals_match_numpy(S, N, M, T, K, transform, own_x):
             _close(out[name]["pointwise"], ref[name], tols[name], name + " pointwise")
 
 
+@pytest.mark.parametrize("transform", [None, "ilogit", "square"])
+@pytest.mark.parametrize("nembeds", range(1, 11))
+def test_every_nembeds_and_transform(nembeds, transform):
+    """All thirty instantiations of func_sweep_kernel<K, transform> behind func_sweep_fn, each on inputs of its own: a kernel
+    of another nembeds reads W and V at another stride, and every functional of every curve is then wrong."""
+    S, N, M, T = 5, 70, 2, 6                     # a full 64-row block and a partial one
+    rs = np.random.RandomState(100 * nembeds + len(transform or ""))
+    Ws, Vs = rs.normal(size=(S, N, nembeds)), rs.normal(size=(S, M, T, nembeds))
+    x = np.cumsum(rs.uniform(0.2, 3.0, size=T))
+    level = {None: 0.3, "ilogit": 0.55, "square": 0.3}[transform]
+    Mu = _tensor(Ws, Vs, transform)
+    _assert_no_branch_can_flip(Mu, level)
+    ref = functionals.curve_functionals(Mu, x, level=level)
+    assert np.isnan(ref["crossing"]).any() and not np.isnan(ref["crossing"]).all()
+    tols = _tols(Mu, x)
+    out = posterior_functionals(Ws, Vs, which=ALL, q=Q, transform=transform, x=x, level=level, exceed=0.4, pointwise=True)
+    assert set(out) == set(ALL)
+    for name in ALL:
+        _close(out[name]["pointwise"], ref[name], tols[name], "K=%d %s %s pointwise" % (nembeds, transform, name))
+    _check_summaries(out, ref, tols, Q, exceed=0.4)
+
+
 def test_exact_ties_and_zeros_with_integer_factors():
     """Integer W, V, x and level: every dot product, difference and comparison is exact, so the first-occurrence and
     the d == 0 rules are tested as such."""

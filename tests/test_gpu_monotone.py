@@ -37,14 +37,18 @@ CASES = {
 FIXTURE_CASES = ["c0", "c1", "c2", "c3", "c4"]
 
 
-def _inputs(name):
-    (S, N, M, T, K), noise, seed = CASES[name]
+def _recipe(dims, noise, seed):
+    S, N, M, T, K = dims
     rs = np.random.RandomState(seed)
     Ws = rs.gamma(1, 1, (S, N, K))
     Vs = np.ascontiguousarray(0.2 * rs.gamma(1, 1, (S, M, T, K)).cumsum(axis=2)[:, :, ::-1] + rs.gamma(1.0, noise, (S, M, T, K)))
     Ws.setflags(write=False)
     Vs.setflags(write=False)
     return Ws, Vs
+
+
+def _inputs(name):
+    return _recipe(*CASES[name])
 
 
 @pytest.fixture(scope="module")
@@ -111,6 +115,105 @@ def test_gpu_only_cases_against_the_numpy_definition(runs, name):
         assert np.array_equal(out["V"], Vs) and (out["pools"] == 1).all() and (out["changed"] == 0).all()
     else:
         assert (runs[name, False][2]["pools"] < CASES[name][0][3]).any()
+
+
+# ---------------------------------------------------------------- every nembeds, register-row bound and depth loop
+# mono_project_kernel<K> keeps nr = min(mono_rows(K), ceil(N / 256)) rows of W per thread in registers (mono_rows = 4 at
+# K <= 5, 2 at K >= 6) and reads the rows from 256 * mono_rows(K) on from global memory at every vote; its loops over the
+# depths step by 256 threads.  name -> (S, N, M, T, K), noise, seed: the module's recipe.
+SHAPES = {}
+for _k in range(1, 11):
+    SHAPES["K%d" % _k] = ((2, 70, 2, 12, _k), 0.15, 20 + _k)
+for _k, _ns in ((1, (255, 256, 257, 512, 513, 768, 769, 1024, 1025)), (5, (255, 256, 257, 512, 513, 768, 769, 1024, 1025)),
+                (6, (256, 257, 512, 513)), (10, (256, 257, 512, 513))):
+    for _n in _ns:                               # nr = 1 | 2 | 3 | 4 | 4 + fallback (K <= 5);  1 | 2 | 2 + fallback (K >= 6)
+        SHAPES["N%d_K%d" % (_n, _k)] = ((2, _n, 2, 8, _k), 0.15, 1000 * _k + _n)
+for _t in (2, 257, 300):                         # one trip of the depth loops, a second trip of one thread, of 44
+    SHAPES["T%d" % _t] = ((2, 20, 2, _t, 3), 0.15, 40 + _t)
+
+
+def _nr(N, K):
+    """(register rows in use, rows read from global memory at every vote)."""
+    rows = 4 if K <= 5 else 2
+    return min(rows, -(-N // 256)), max(0, N - 256 * rows)
+
+
+def _host_with_margin(Ws, Vs, inc):
+    """monotone.project_host's walk once more, recording the smallest non-zero |w_i . v_t - w_i . v_{t+1}| any vote saw, over
+    the largest |w_i . v_t|: a vote can differ between numpy's dot product and the device's FMA chain (about 1e-16 of the
+    scale apart) only below it.  Exact zeros are the pairs inside a pool: bit-identical depths on both sides.
+    Returns (V', pools, margin)."""
+    out, pools, margin = np.empty_like(Vs), np.empty(Vs.shape[:2], dtype=np.int32), np.inf
+    for s in range(Vs.shape[0]):
+        W = Ws[s]
+        for j in range(Vs.shape[1]):
+            V = np.array(Vs[s, j])
+            T = V.shape[0]
+            scale = np.abs(W @ V.T).max()
+            first, merges, merged = np.arange(T), 0, True
+            while merged:
+                merged, t = False, 0
+                while t < T - 1:
+                    step = (W @ V[t + 1] - W @ V[t]) if inc else (W @ V[t] - W @ V[t + 1])
+                    nz = np.abs(step[step != 0])
+                    if nz.size:
+                        margin = min(margin, nz.min() / scale)
+                    if np.any(step < 0):
+                        mine, next_ = first == first[t], first == first[t + 1]
+                        w0, w1 = int(mine.sum()), int(next_.sum())
+                        V[mine | next_] = (w0 * V[t] + w1 * V[t + 1]) / (w0 + w1)
+                        first[next_] = first[t]
+                        merges, merged, t = merges + 1, True, t + w1
+                    else:
+                        t += 1
+            out[s, j], pools[s, j] = V, T - merges
+    return out, pools, margin
+
+
+def test_the_shapes_reach_every_register_row_count():
+    assert {_nr(SHAPES[n][0][1], SHAPES[n][0][4]) for n in SHAPES if n.startswith("N") and n.endswith(("_K1", "_K5"))} == \
+        {(1, 0), (2, 0), (3, 0), (4, 0), (4, 1)}
+    assert {_nr(SHAPES[n][0][1], SHAPES[n][0][4]) for n in SHAPES if n.endswith(("_K6", "_K10"))} == {(1, 0), (2, 0), (2, 1)}
+
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_shapes_bit_for_bit_against_the_numpy_definition(name):
+    dims, noise, seed = SHAPES[name]
+    S, N, M, T, K = dims
+    Ws, Vs = _recipe(dims, noise, seed)
+    for inc in (False, True):
+        ref, pools = monotone.project_host(Ws, Vs, increasing=inc)
+        again, pools2, margin = _host_with_margin(Ws, Vs, inc)
+        assert np.array_equal(again, ref) and np.array_equal(pools2, pools)          # the walk above is the definition's
+        print("%s increasing=%s: smallest non-zero step of a vote %.3g of the scale, pools %d..%d of %d"
+              % (name, inc, margin, pools.min(), pools.max(), T))
+        assert margin > 1e-9, (name, inc, margin)                                    # no vote can flip
+        out = utils.posterior_monotone(Ws, Vs, q=None, increasing=inc)
+        print("%s increasing=%s: largest difference %.3g" % (name, inc, np.abs(out["V"] - ref).max()))
+        assert np.array_equal(out["pools"], pools), (name, inc)
+        assert np.array_equal(out["V"], ref), (name, inc)
+        assert pools.min() >= 1 and (pools < T).any()
+        if T > 256:                                   # merges among the depths a thread reaches on its second trip
+            assert (ref[:, :, 256:] != Vs[:, :, 256:]).any(), (name, inc)
+
+
+def test_monotone_columns_stay_as_they_are_and_the_other_direction_is_one_pool():
+    """Positive W and a V that falls in every component: decreasing already (pools == T, the bits of the input; the stateless
+    entry point projects its device copy where it lies, so this is the kernel's in-place path that writes nothing), and
+    increasing=True merges every column into a single pool, the mean of its depths built up pair by pair."""
+    S, N, M, T, K = 2, 300, 3, 9, 4
+    rs = np.random.RandomState(12)
+    Ws = rs.gamma(1, 1, (S, N, K))
+    Vs = np.ascontiguousarray(rs.gamma(1, 1, (S, M, T, K)).cumsum(axis=2)[:, :, ::-1])
+    same = utils.posterior_monotone(Ws, Vs, q=None, increasing=False)
+    assert (same["pools"] == T).all() and np.array_equal(same["V"], Vs) and (same["changed"] == 0).all()
+    ref, pools, margin = _host_with_margin(Ws, Vs, True)
+    assert (pools == 1).all() and margin > 1e-9
+    assert np.array_equal(ref, monotone.project_host(Ws, Vs, increasing=True)[0])
+    one = utils.posterior_monotone(Ws, Vs, q=None, increasing=True)
+    assert (one["pools"] == 1).all() and np.array_equal(one["V"], ref) and (one["changed"] == 1).all()
+    assert (one["V"] == one["V"][:, :, :1]).all()
+    assert np.abs(one["V"][:, :, 0] - Vs.mean(axis=2)).max() <= 1e-12 * np.abs(Vs).max()
 
 
 @pytest.mark.parametrize("name,inc", [("c0", False), ("c4", True), ("N1100_K2", False), ("T1", False), ("M1_S1", True)])

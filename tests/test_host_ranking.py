@@ -74,6 +74,16 @@ def test_summaries_by_hand():
     assert ranking.ranks(g, "cols", "descending")[:, 0].tolist() == [[1, 2], [1, 2], [1, 2]]
 
 
+def test_top_entries_above_the_largest_group_reach_the_library_distinct():
+    """4097, 100000 and 2**40 all mean "certain"; the library refuses repeated entries, so each gets a stand-in of its own
+    above MAX_GROUP (they used to be clamped to one value, and the call was refused)."""
+    top = (ranking.MAX_GROUP + 1, 1, 100000, 4, ranking.MAX_GROUP, 5, 2 ** 40, 2)
+    dev = ranking.check_args("auc", "cols", "ascending", top, None, None, None, None, 3, 4, 5, 3)[4]
+    assert dev.dtype == np.int32 and len(set(dev.tolist())) == len(top)
+    small = np.array(top) <= ranking.MAX_GROUP
+    assert np.array_equal(dev[small], np.array(top)[small]) and (dev[~small] > ranking.MAX_GROUP).all()
+
+
 def test_integer_sums_stay_exact_at_the_limits():
     S, L = ranking.MAX_SAMPLES, ranking.MAX_GROUP
     assert S * S * L * L < 2 ** 53
