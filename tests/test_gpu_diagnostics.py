@@ -81,7 +81,7 @@ def test_cells_match_the_numpy_definition(K, C, S, transform):
                 cands = _nudged(x[i, j, t]) if transform == "ilogit" else [x[i, j, t]]
                 wants = [spec(y) for y in cands]
                 assert any(_close(got, w) for w in wants), (i, j, t, got, wants[0])
-                assert abs(res["mean"][i, j, t] - x[i, j, t].mean()) <= 1e-12 * max(1.0, abs(x[i, j, t]).max()), tag
+                assert abs(res["mean"][i, j, t] - x[i, j, t].mean()) <= 1e-12 * max(1.0, abs(x[i, j, t]).max()), (i, j, t)
     assert res["nchains"] == C and res["ndraws"] == S
     assert res["max_rhat"] == np.nanmax(res["rhat"])
     assert res["n_rhat_above"] == int(np.sum(res["rhat"] > 1.01))

@@ -29,7 +29,8 @@ def _rhat(x):
     return np.sqrt((B / W + n - 1) / n)
 
 
-def _ess(x):
+def _ess(x, pairs=None):
+    """pairs: a list that receives every (even, odd) the rule reads, the first (1, rho[1]) included."""
     C, n = x.shape
     xc = x - x.mean(1, keepdims=True)
     acov = np.array([[np.dot(xc[c, :n - t], xc[c, t:]) / n for t in range(n)] for c in range(C)])
@@ -38,10 +39,14 @@ def _ess(x):
     rho = np.zeros(n)
     rho[0] = even = 1.0
     rho[1] = odd = 1.0 - (mean_var - acov[:, 1].mean()) / var_plus
+    if pairs is not None:
+        pairs.append((even, odd))
     t = 1
     while t < n - 3 and even + odd > 0:
         even = 1.0 - (mean_var - acov[:, t + 1].mean()) / var_plus
         odd = 1.0 - (mean_var - acov[:, t + 2].mean()) / var_plus
+        if pairs is not None:
+            pairs.append((even, odd))
         if even + odd >= 0:
             rho[t + 1], rho[t + 2] = even, odd
         t += 2
@@ -58,15 +63,36 @@ def _ess(x):
     return C * n / tau
 
 
-def spec(x):
+def spec(x, pairs=None):
+    """pairs: a list that receives four lists, the (even, odd) pairs of the bulk, q05, q95 and raw series (see _ess)."""
+    p = [None] * 4 if pairs is None else [[] for _ in range(4)]
     s = _split(x)
     folded = np.abs(x - np.median(x))
     r = max(_rhat(_zscale(s)), _rhat(_zscale(_split(folded))))
-    eb = _ess(_zscale(s))
+    eb = _ess(_zscale(s), p[0])
     q05, q95 = np.quantile(x, [0.05, 0.95])
-    et = min(_ess(_split((x <= q05).astype(float))), _ess(_split((x <= q95).astype(float))))
-    mcse = np.std(x, ddof=1) / np.sqrt(_ess(s))
+    et = min(_ess(_split((x <= q05).astype(float)), p[1]), _ess(_split((x <= q95).astype(float)), p[2]))
+    mcse = np.std(x, ddof=1) / np.sqrt(_ess(s, p[3]))
+    if pairs is not None:
+        pairs.extend(p)
     return np.array([r, eb, et, mcse])
+
+
+def pairs_margin(pairs):
+    """The smallest |even + odd| and |even| over the pairs of the four series, as spec(x, pairs) lists them.  Geyer's rule
+    branches on the sign of exactly these values, so a series with a small margin may legitimately come out differently
+    from two correct float64 evaluations.  A pair of a constant series is nan (0 / 0, exactly, in any order of summation)
+    and compares false either way: it is left out."""
+    with np.errstate(invalid="ignore"):
+        v = np.array([[abs(e + o), abs(e)] for series in pairs for e, o in series])
+    return float(np.nanmin(v))
+
+
+def geyer_margin(x):
+    pairs = []
+    with np.errstate(divide="ignore", invalid="ignore"):
+        spec(x, pairs)
+    return pairs_margin(pairs)
 
 
 def got(x):
@@ -134,6 +160,29 @@ def test_one_dimensional_input_is_one_chain():
     assert np.array_equal(got(x), got(x[None]))
     with pytest.raises(ValueError):
         diagnostics.chain_diagnostics(np.ones((2, 3)))
+
+
+def test_geyer_margin_counts_every_pair_and_skips_a_constant_series():
+    x = ar1(np.random.RandomState(7), 2, 40, 0.9)
+    pairs = []
+    spec(x, pairs)
+    assert len(pairs) == 4 and all(p[0][0] == 1.0 and len(p) >= 2 for p in pairs)
+    assert geyer_margin(x) == min(min(abs(e + o), abs(e)) for p in pairs for e, o in p) > 0
+    y = CASES["heavy_ties_q95"](np.random.RandomState(7))           # the q95 indicator is constant: its one pair is nan
+    assert np.isfinite(geyer_margin(y))
+
+
+def test_every_series_of_the_gpu_shape_suite_meets_its_conditions():
+    """tests/test_gpu_diagnostics_shapes.py compares the kernel with spec only on series where Geyer's rule is away from
+    its branch points and no R-hat is 0 / 0; the same builders, the same assertion, no GPU."""
+    import test_gpu_diagnostics_shapes as shapes
+    count = 0
+    for cid, xs in shapes.host_cases():
+        for i, x in enumerate(xs):
+            want, _, margin, posed = shapes.conditions(x)
+            assert margin > shapes.MARGIN and posed and np.all(np.isfinite(want)), (cid, i, margin, posed, want)
+            count += 1
+    assert count > 800
 
 
 # ---- refusals before any device call
