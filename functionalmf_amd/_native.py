@@ -20,7 +20,7 @@ UNITS = [(os.path.join(CSRC, "btf_%s.hip" % name), suffix) for name, suffix in [
     ("abi", "_abi.o"), ("analysis", "_analysis.o"), ("criteria", "_crit.o"), ("nmf", "_nmf.o"), ("gass_ep", "_gass_ep.o"),
     ("gamma_grid", "_gamma_grid.o"), ("diag", "_diag.o"), ("predict", "_predict.o"), ("functionals", "_functionals.o"),
     ("fold_in", "_fold_in.o"), ("loo", "_loo.o"), ("ranking", "_ranking.o"), ("assoc", "_assoc.o"), ("monotone", "_monotone.o"),
-    ("gg_criteria", "_gg_criteria.o")]]
+    ("gg_criteria", "_gg_criteria.o"), ("gg_predict", "_gg_predict.o")]]
 SOURCES = [src for src, _ in UNITS]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
@@ -125,6 +125,9 @@ SIGNATURES = {
     "btf_predict_batch": (C.c_int, [C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_uint64, _c_dp]),
     "btf_predict_eval": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, C.c_int,
                                    C.c_uint64, _c_dp, C.c_int, _c_ip, C.c_int] + [_c_dp] * 11),
+    "btf_predict_gg_eval": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_uint64, _c_dp, C.c_int, _c_ip, C.c_int] +
+                            [_c_dp] * 11),
+    "btf_predict_gg_batch": (C.c_int, [C.c_int, C.c_int64, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, C.c_uint64, _c_dp, _c_ip]),
     "btf_nmf_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp,
                                  C.POINTER(C.c_uint8), C.c_double]),
     "btf_nmf_run": (C.c_int, [C.c_void_p, _c_dp, _c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _c_ip, _c_dp,

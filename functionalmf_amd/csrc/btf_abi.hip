@@ -2759,6 +2759,7 @@ int btf_set_likelihood_table(btf_ctx* c, int family, const double* shape, const 
   HIPCHK(c, hipMemcpy(c->gg_tab, h.data(), h.size() * sizeof(GgComp), hipMemcpyHostToDevice));
   c->gg_G = (int)h.size();
   c->gg_lsp = std::log(psum);
+  gg_pred_table(shape, scale, prob, G, c->gg_pred, c->gg_mbar);      // (the checks above are its own)
   return BTF_OK;
 }
 

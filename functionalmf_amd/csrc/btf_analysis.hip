@@ -6,6 +6,7 @@
 #include "btf_gg_criteria.h"    // the same for the gamma-grid likelihood (kernels in btf_gg_criteria.hip)
 #include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
+#include "btf_gg_predict.h"     // the same for the gamma-grid likelihood (kernels in btf_gg_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
 #include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
 #include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
@@ -20,6 +21,12 @@
 
 using namespace btf;
 static_assert(CRIT_FAM_COUNT == 5 && PRED_FAM_COUNT == 5, "FAM_SWITCH covers families 0..4");
+// Cells per workgroup of the predictive launch: the rows of a workgroup get what half the 160 KiB of a CU leaves beside
+// the family's static table (the gamma grid's 3 KiB; none for the other five), at most PRED_SORT_LDS - so two workgroups
+// fit a CU with or without a table, and while the table stays under 16 KiB all six families have one geometry.
+constexpr size_t PRED_CU_LDS = 160 * 1024;
+constexpr size_t pred_row_budget(size_t table_bytes) { return std::min(PRED_SORT_LDS, PRED_CU_LDS / 2 - table_bytes); }
+static_assert(pred_row_budget(GGP_TAB_DOUBLES * sizeof(double)) == PRED_SORT_LDS, "the gamma-grid table costs the rows nothing");
 
 extern "C" {
 namespace {
@@ -309,22 +316,39 @@ int btf_predict_batch(int device, int family, int64_t n, const double* eta, cons
   return s.finish();
 }
 
-int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const double* Ws, const double* Vs,
-                     const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps,
-                     int draws_per_sample, uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
-                     double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out, double* pit_hi_out,
-                     double* inside_out, double* nobs_out, double* rmse_out, double* mae_out, double* draws_out) {
-  if (!c || family < 0 || family >= PRED_FAM_COUNT || nsamples < 1 || draws_per_sample < 1 || (!Ws) != (!Vs) || nq < 0 ||
+namespace {
+// where the outputs of btf_predict_eval / btf_predict_gg_eval go on the host, in the order of their arguments
+struct PredOut { double *mean, *ymean, *yvar, *q, *pit_lo, *pit_hi, *inside, *nobs, *rmse, *mae, *draws; };
+struct PredKernels { void (*draw)(PredArgs); void (*score)(PredArgs); };
+PredKernels pred_kernels(int family) {
+  PredKernels k{nullptr, nullptr};
+  if (family == PRED_FAM_GAMMA_GRID) { k.draw = gg_pred_fn(); k.score = gg_pred_score_fn(); }
+  else FAM_SWITCH(family, { k.draw = pred_kernel<FT>; k.score = pred_score_kernel<FT>; });
+  return k;
+}
+
+// btf_predict_eval (families 0..4) and btf_predict_gg_eval (family 5: the context's table, param = its mbar) under the
+// name `who`: one set of limits and refusals, one launch geometry
+int predict_run(btf_ctx* c, const std::string& who, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps, int draws_per_sample,
+                uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells, const PredOut& o) {
+  double *const mean_out = o.mean, *const ymean_out = o.ymean, *const yvar_out = o.yvar, *const q_out = o.q, *const pit_lo_out = o.pit_lo,
+         *const pit_hi_out = o.pit_hi, *const inside_out = o.inside, *const nobs_out = o.nobs, *const rmse_out = o.rmse,
+         *const mae_out = o.mae, *const draws_out = o.draws;
+  const bool gamma_grid = family == PRED_FAM_GAMMA_GRID;
+  if (!c || (!gamma_grid && (family < 0 || family >= PRED_FAM_COUNT)) || nsamples < 1 || draws_per_sample < 1 || (!Ws) != (!Vs) || nq < 0 ||
       (nq > 0 && !q) || (q_out && nq < 1) || ncells < 0 || (ncells > 0 && (!cells || !draws_out)) || (Y && nreps < 1) ||
       (aux_flags & ~(BTF_PRED_AUX_PER_SAMPLE | BTF_PRED_AUX_ROWS | BTF_PRED_AUX_COLS | BTF_PRED_AUX_DEPTH)))
-    return fail(c, BTF_EINVAL, "bad btf_predict_eval arguments");
+    return fail(c, BTF_EINVAL, "bad " + who + " arguments");
+  if (gamma_grid && c->gg_pred.empty())
+    return fail(c, BTF_ESTATE, who + ": the gamma-grid family needs its table (btf_set_likelihood_table)");
   if (!Y && (pit_lo_out || pit_hi_out || inside_out || nobs_out || rmse_out || mae_out))
-    return fail(c, BTF_EINVAL, "btf_predict_eval: pit / inside / nobs / rmse / mae compare with observations: pass Y");
+    return fail(c, BTF_EINVAL, who + ": pit / inside / nobs / rmse / mae compare with observations: pass Y");
   if ((long long)nsamples * draws_per_sample > PRED_MAX_DRAWS)
-    return fail(c, BTF_EINVAL, "btf_predict_eval: nsamples * draws_per_sample = " + std::to_string((long long)nsamples * draws_per_sample) +
+    return fail(c, BTF_EINVAL, who + ": nsamples * draws_per_sample = " + std::to_string((long long)nsamples * draws_per_sample) +
                 " exceeds 16384 (the draws of a cell are sorted in LDS)");
-  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_predict_eval needs an unsharded context");
-  if (!Ws && !has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, "btf_predict_eval");
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, who + " needs an unsharded context");
+  if (!Ws && !has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, who);
   const bool per_sample = (aux_flags & BTF_PRED_AUX_PER_SAMPLE) != 0;
   const bool needs_par = family == PRED_FAM_GAUSSIAN || family == PRED_FAM_NEGBIN;
   if (per_sample && !needs_par) return fail(c, BTF_EINVAL, "per-sample parameters are the Gaussian (variance) and Negative-Binomial (rate) families'");
@@ -335,9 +359,9 @@ int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const d
   if (int rc = check_percentiles(c, q, nq)) return rc;
   const int S = nsamples, R = draws_per_sample, N = c->N, M = c->M, T = c->T, K = c->K, MT = M * T, n = S * R;
   const size_t ncell = (size_t)N * MT;
-  if (ncell > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: more than 2^31 - 1 cells");
+  if (ncell > 0x7fffffffULL) return fail(c, BTF_EINVAL, who + ": more than 2^31 - 1 cells");
   for (int k = 0; k < ncells; ++k)
-    if (cells[k] < 0 || (size_t)cells[k] >= ncell) return fail(c, BTF_EINVAL, "btf_predict_eval: cell index out of range");
+    if (cells[k] < 0 || (size_t)cells[k] >= ncell) return fail(c, BTF_EINVAL, who + ": cell index out of range");
   HIPCHK(c, hipSetDevice(c->dev));
   PredArgs a{};
   a.aux_n0 = a.aux_n1 = a.aux_n2 = 1;
@@ -345,9 +369,9 @@ int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const d
     a.aux_n0 = (aux_flags & BTF_PRED_AUX_ROWS) ? N : 1; a.aux_n1 = (aux_flags & BTF_PRED_AUX_COLS) ? M : 1; a.aux_n2 = (aux_flags & BTF_PRED_AUX_DEPTH) ? T : 1;
   }
   const size_t naux = (size_t)a.aux_n0 * a.aux_n1 * a.aux_n2;
-  const SortGeom g = sort_geom(n, PRED_SORT_LDS, PRED_SORT_CELLS);
+  const SortGeom g = sort_geom(n, pred_row_budget(gamma_grid ? GGP_TAB_DOUBLES * sizeof(double) : 0), PRED_SORT_CELLS);
   const size_t nblk = (size_t)N * ((MT + g.cells - 1) / g.cells);
-  if (nblk > 0x7fffffffULL) return fail(c, BTF_EINVAL, "btf_predict_eval: too many workgroups for one launch");
+  if (nblk > 0x7fffffffULL) return fail(c, BTF_EINVAL, who + ": too many workgroups for one launch");
   const int chunks = (int)((ncell + PRED_SCORE_CELLS - 1) / PRED_SCORE_CELLS);
   const bool score = rmse_out || mae_out;
   Scratch s(c, c->stream);
@@ -369,11 +393,11 @@ int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const d
   double* dsc = nullptr;      // [rmse | mae] per sample
   if (score) { a.score_part = s.alloc<double>((size_t)3 * S * chunks); dsc = s.alloc<double>((size_t)2 * S); }
   a.par = param; a.S = S; a.R = R; a.N = N; a.M = M; a.T = T; a.K = K; a.P = g.P; a.cells = g.cells; a.seed = seed; a.chunks = chunks;
-  FAM_SWITCH(family, {
-    allow_lds(s, pred_kernel<FT>, g.lds);
-    s.launch(pred_kernel<FT>, dim3((unsigned)nblk), dim3(PRED_THREADS), g.lds, a);
-    if (score) s.launch(pred_score_kernel<FT>, dim3(chunks, S), dim3(PRED_THREADS), 0, a);
-  });
+  if (gamma_grid) { a.gg_G = (int)(c->gg_pred.size() / 3); a.gg = s.upload(c->gg_pred.data(), c->gg_pred.size()); }
+  const PredKernels k = pred_kernels(family);
+  allow_lds(s, k.draw, g.lds);
+  s.launch(k.draw, dim3((unsigned)nblk), dim3(PRED_THREADS), g.lds, a);
+  if (score) s.launch(k.score, dim3(chunks, S), dim3(PRED_THREADS), 0, a);
   if (score) s.launch(pred_score_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.score_part, S, chunks, dsc);
   s.download(mean_out, a.mean, ncell); s.download(ymean_out, a.y_mean, ncell); s.download(yvar_out, a.y_var, ncell);
   s.download(q_out, a.quant, (size_t)nq * ncell);
@@ -382,6 +406,48 @@ int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const d
   if (score && !s.rc()) { s.download(rmse_out, dsc, (size_t)S); s.download(mae_out, dsc + S, (size_t)S); }
   if (ncells) s.download(draws_out, a.draws, (size_t)ncells * n);
   return s.finish();        // (not check_status: the sampler's status word is not this call's)
+}
+}  // namespace
+
+int btf_predict_eval(btf_ctx* c, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                     const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps,
+                     int draws_per_sample, uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
+                     double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out, double* pit_hi_out,
+                     double* inside_out, double* nobs_out, double* rmse_out, double* mae_out, double* draws_out) {
+  if (family == PRED_FAM_GAMMA_GRID) family = -1;       // (its own entry point: btf_predict_gg_eval)
+  return predict_run(c, "btf_predict_eval", family, param, nsamples, Ws, Vs, aux_sample, aux_flags, trials, Y, nreps, draws_per_sample, seed,
+                     q, nq, cells, ncells, PredOut{mean_out, ymean_out, yvar_out, q_out, pit_lo_out, pit_hi_out, inside_out, nobs_out,
+                                                   rmse_out, mae_out, draws_out});
+}
+
+// ---------------------------------------------------------- the same for the gamma-grid likelihood (btf_gg_predict.h)
+int btf_predict_gg_eval(btf_ctx* c, int nsamples, const double* Ws, const double* Vs, const double* Y, int nreps, int draws_per_sample,
+                        uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
+                        double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out, double* pit_hi_out,
+                        double* inside_out, double* nobs_out, double* rmse_out, double* mae_out, double* draws_out) {
+  return predict_run(c, "btf_predict_gg_eval", PRED_FAM_GAMMA_GRID, c ? c->gg_mbar : 0.0, nsamples, Ws, Vs, nullptr, 0, nullptr, Y, nreps,
+                     draws_per_sample, seed, q, nq, cells, ncells, PredOut{mean_out, ymean_out, yvar_out, q_out, pit_lo_out, pit_hi_out,
+                                                                           inside_out, nobs_out, rmse_out, mae_out, draws_out});
+}
+
+int btf_predict_gg_batch(int device, int64_t n, const double* eta, int G, const double* shape, const double* scale, const double* prob,
+                         uint64_t seed, double* out, int32_t* comp_out) {
+  if (n < 1 || !eta || !out) return fail(nullptr, BTF_EINVAL, "bad predict_gg_batch arguments");
+  std::vector<double> tab;
+  double mbar;
+  if (!gg_pred_table(shape, scale, prob, G, tab, mbar))
+    return fail(nullptr, BTF_EINVAL, "btf_predict_gg_batch: the gamma grid has 1..128 components with finite shape > 0, scale > 0 and "
+                                     "weight >= 0, not all zero");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double *de = s.upload(eta, (size_t)n), *dt = s.upload(tab.data(), tab.size());
+  double* dout = s.alloc<double>((size_t)n);
+  int* dcomp = comp_out ? s.alloc<int>((size_t)n) : nullptr;
+  s.launch(gg_pred_batch_fn(), dim3((unsigned)((n + PRED_THREADS - 1) / PRED_THREADS)), dim3(PRED_THREADS), 0, de, dt, G, (long long)n,
+           (unsigned long long)seed, dout, dcomp);
+  s.download(out, dout, (size_t)n);
+  s.download((int*)comp_out, (const int*)dcomp, (size_t)n);
+  return s.finish();
 }
 
 // ---------------------------------------------------------------- posterior summaries

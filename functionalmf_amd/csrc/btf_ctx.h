@@ -83,6 +83,7 @@ struct btf_ctx {
   double lik_par[btf::ESS_FAM_COUNT] = {0, 0, 0, 1.0, 1.0, 0};     // parameter per likelihood family (btf_set_likelihood_param)
   // the gamma-grid family (btf_gamma_grid.h): component table, log sum p, and L = sum_r log y in both layouts of S1
   btf::GgComp* gg_tab = nullptr; int gg_G = 0; double gg_lsp = 0.0;
+  std::vector<double> gg_pred; double gg_mbar = 0.0;      // the same table for the predictive draw (gg_pred_table), on the host
   double* gg_Lw = nullptr; double* gg_Lv = nullptr; bool gg_have_L = false;
   long long* dbg = nullptr;
   double* vc_scratch = nullptr; size_t vc_scratch_elems = 0;     // factor records of the chunked chain sampler

@@ -22,6 +22,8 @@
 #include "btf_device.h"
 namespace btf { struct GassEvalArgs; }
 #endif
+#include <cmath>
+#include <vector>
 
 namespace btf {
 
@@ -44,6 +46,37 @@ struct GgLLArgs {
   const int* done; int per_row;
   double* part;
 };
+
+// The table of the predictive draw (btf_gg_predict.h), laid out [a | s | c] with G entries each, every component of the
+// table as given (a zero weight stays in its place and is never chosen): shape a_g, scale s_g and the cumulative weight
+// c_g = sum_{h<=g} w_h, w_g = p_g / sum_h p_h.  Both sums are accumulated once, in ascending g, in fp64, here on the
+// host, so that every call that holds the same table draws from the same bits.  From the last component with p_g > 0 on,
+// c_g = 2: a uniform that round-off left at or above the last cumulative weight takes that component.
+// mbar = sum_g w_g a_g s_g in ascending g: E[y | eta] = eta mbar.  false: a table btf_set_likelihood_table refuses.
+inline bool gg_pred_table(const double* shape, const double* scale, const double* prob, int G, std::vector<double>& tab, double& mbar) {
+  if (!shape || !scale || !prob || G < 1 || G > GG_MAXG) return false;
+  double psum = 0.0;
+  int last = -1;
+  for (int g = 0; g < G; ++g) {
+    const double a = shape[g], s = scale[g], p = prob[g];
+    if (!std::isfinite(a) || !std::isfinite(s) || !std::isfinite(p) || !(a > 0.0) || !(s > 0.0) || !(p >= 0.0)) return false;
+    psum += p;
+    if (p > 0.0) last = g;
+  }
+  if (last < 0) return false;
+  tab.assign((size_t)3 * G, 0.0);
+  double c = 0.0;
+  mbar = 0.0;
+  for (int g = 0; g < G; ++g) {
+    const double w = prob[g] / psum;
+    c += w;
+    mbar += w * shape[g] * scale[g];
+    tab[g] = shape[g];
+    tab[(size_t)G + g] = scale[g];
+    tab[(size_t)2 * G + g] = g < last ? c : 2.0;
+  }
+  return true;
+}
 
 using GgLLKernel = void (*)(GgLLArgs, GgTab);
 using GgEvalKernel = void (*)(GassEvalArgs, GgTab);

@@ -28,7 +28,8 @@
 namespace btf {
 
 enum { PRED_FAM_POISSON_LOG = 0, PRED_FAM_POISSON_IDENTITY = 1, PRED_FAM_LOGIT = 2, PRED_FAM_GAUSSIAN = 3, PRED_FAM_NEGBIN = 4,
-       PRED_FAM_COUNT = 5 };
+       PRED_FAM_COUNT = 5,                     // the families of btf_predict_eval
+       PRED_FAM_GAMMA_GRID = 5 };              // the table family of btf_gg_predict.h, behind entry points of its own
 constexpr int PRED_BLOCKS = 64;                 // Philox blocks reserved per draw
 constexpr double PRED_POIS_SWITCH = 10.0;       // Poisson: inversion below, PTRS from here
 constexpr double PRED_BINOM_SWITCH = 10.0;      // Binomial: inversion while n min(p,1-p) is below, BTRS from here
@@ -194,9 +195,10 @@ __host__ __device__ inline double pred_mean(double eta, double aux) {
 }
 
 #ifdef __HIPCC__
-// draw number g of y | eta, aux (aux: trials / variance / rate)
+// draw number g of y | eta, aux (aux: trials / variance / rate); tab, G: the table of a family that has one (pred_stage)
 template <int FAM>
-__device__ inline double pred_draw(double eta, double aux, unsigned long long seed, unsigned long long g) {
+__device__ inline double pred_draw(double eta, double aux, unsigned long long seed, unsigned long long g,
+                                   const double* tab = nullptr, int G = 0) {
   if constexpr (FAM == PRED_FAM_GAUSSIAN) {
     return aux >= 0.0 ? fma(sqrt(aux), philox_normal(seed, PRED_STREAM + FAM, g), eta) : NAN;
   } else {
@@ -234,7 +236,13 @@ struct PredArgs {
   double *mean, *y_mean, *y_var, *quant, *pit_lo, *pit_hi, *inside, *nobs, *draws;     // any may be null
   double *score_part;                    // [2][S][chunks] + counts [chunks]: pred_score_kernel
   int chunks;
+  const double* gg; int gg_G;            // gamma grid: the table [a | s | c] of gg_pred_table (par: mbar)
 };
+
+// The table of a family that draws from one, staged in LDS by every thread of the workgroup before the first draw
+// (btf_gg_predict.h specialises it); null: the family has none.
+template <int FAM>
+__device__ __forceinline__ const double* pred_stage(const PredArgs&) { return nullptr; }
 
 template <int FAM>
 __device__ __forceinline__ double pred_aux(const PredArgs& a, int s, int i, int j, int t) {
@@ -261,6 +269,7 @@ __global__ __launch_bounds__(PRED_THREADS) void pred_kernel(PredArgs a) {
   const int i = blockIdx.x % a.N, MT = a.M * a.T, jt0 = (blockIdx.x / a.N) * a.cells;
   const int nc = min(a.cells, MT - jt0), n = a.S * a.R, P = a.P, cells = a.cells;
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const double* tab = pred_stage<FAM>(a);
   // ---- draws: thread -> (cell c, draw d = s R + r), c fastest (V[s][jt0 + c][:] is contiguous over c)
   for (int e = threadIdx.x; e < cells * P; e += PRED_THREADS) {
     const int c = e % cells, d = e / cells;
@@ -269,7 +278,7 @@ __global__ __launch_bounds__(PRED_THREADS) void pred_kernel(PredArgs a) {
       const int s = d / a.R, jt = jt0 + c;
       const double eta = pred_eta(a, s, i, jt);
       const unsigned long long cell = (unsigned long long)i * MT + jt;
-      val = pred_draw<FAM>(eta, pred_aux<FAM>(a, s, i, jt / a.T, jt % a.T), a.seed, cell * (unsigned long long)n + d);
+      val = pred_draw<FAM>(eta, pred_aux<FAM>(a, s, i, jt / a.T, jt % a.T), a.seed, cell * (unsigned long long)n + d, tab, a.gg_G);
     }
     srt[(size_t)c * P + d] = val;
   }

@@ -1376,11 +1376,13 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
             raise NotImplementedError("posterior predictive needs a device sampler of the likelihood: a Python-callable "
                                       "loglikelihood says nothing about how y is drawn")
         if self._link == 5:
-            raise NotImplementedError("posterior predictive is not available for the gamma_grid likelihood")
+            raise NotImplementedError("posterior_predictive is not available for the gamma_grid likelihood: "
+                                      "gamma_grid_predictive draws from it")
         return self._crit_family()
 
-    # ---- WAIC, DIC and PSIS-LOO under the gamma_grid likelihood (csrc/btf_gg_criteria.h).  Under names of their own:
-    # information_criteria / loo / posterior_predictive keep refusing a gamma_grid model. ----
+    # ---- WAIC, DIC, PSIS-LOO (csrc/btf_gg_criteria.h) and the posterior predictive (csrc/btf_gg_predict.h) under the
+    # gamma_grid likelihood.  Under names of their own: information_criteria / loo / posterior_predictive keep refusing a
+    # gamma_grid model. ----
     def _gg_check(self, what, instead):
         self._unsharded(what)
         if self._callback or self._link != 5:
@@ -1427,6 +1429,34 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         check_loo_samples(S, "gamma_grid_loo")
         head, obs = self._gg_head(data, S, Ws, Vs)
         return _criteria.loo_evaluate(self._ctx, head, shape, obs, r_eff=r_eff, transform=code, mean=mean, log_weights=log_weights)
+
+    def gamma_grid_predictive(self, results=None, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=None, cells=None):
+        """Posterior predictive of the observations under the gamma_grid likelihood, on the GPU (csrc/btf_gg_predict.h): the
+        dictionary of posterior_predictive (see there for results, data, q, seed, cells and every key).  What
+        doseresponse/fit.py:475-478 does on the host - likelihood.sample(Mu_hat[None,i,j], size=[100, S, ndepth]) and
+        two percentiles per curve, in a Python loop over every (cell line, drug).
+
+        A draw is y = w.v * s_g * Gamma(a_g, 1) with the component g chosen by the weights of the fitted likelihood,
+        w_g = p_g / sum p.  The reference's sample picks g uniformly (np.random.choice(G)), whatever its mean_probs says;
+        utils.gamma_grid_predictive with a table of equal weights gives that.  One component per replicated observation:
+        the marginal predictive of one new observation.  mean = mean_s w.v * sum_g w_g a_g s_g (predictive.gamma_grid_mean);
+        a cell with w.v <= 0 in any sample has nan in mean and in every draw-based output, as under poisson_identity.
+        The data must have every observed y > 0 (ValueError).  After posterior_monotone(in_place=True) the projected states
+        are read, as by every later analysis call.  ValueError on a model with another likelihood.
+        S * draws_per_sample <= 16384; unsharded models."""
+        from . import predictive as _pred
+        self._gg_check("gamma_grid_predictive", "posterior_predictive")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        S, Ws, Vs = self._samples(results)
+        S, R = _pred.check_draws(S, draws_per_sample)
+        _pred.check_q(q)
+        _pred.check_cells(cells, shape)
+        if data is None:
+            data = getattr(self, "_data_ref", None)
+        Y4 = _pred.check_gamma_grid_data(data, shape)
+        if seed is None:
+            seed = self._next_seed()
+        return _pred.gamma_grid_evaluate(self._ctx, shape, self.nembeds, S, Ws, Vs, Y=Y4, q=q, draws_per_sample=R, seed=seed, cells=cells)
 
     def run_gibbs(self, data, nburn=1000, nthin=1, nsamples=1000, verbose=True, print_freq=100, callback=None, **kwargs):
         """genlasso.py:37-66, the result dict gathered as before.  A gamma_grid model with rng="device" also keeps every

@@ -52,6 +52,21 @@ class GammaGridLikelihood:
         out = np.where(cnt > 0, out, lsp)
         return np.where((cnt > 0) & ~(eta > 0), -np.inf, out)
 
+    def sample(self, effect, size=1, rng=None):
+        """Draws y = effect * scale_g * Gamma(shape_g, 1), the component g chosen with the weights probs_grid / sum - the
+        numpy statement of the device draw (csrc/btf_gg_predict.h), for tests and examples, never on a device path.  The
+        reference's sample (empirical_bayes.py:21-27) picks g by np.random.choice(G): uniformly, whatever mean_probs says;
+        equal weights give that.  `size` as numpy's; `effect` broadcasts against it; one component per drawn value.
+        effect <= 0 or nan gives nan.  rng: a np.random.RandomState / Generator (default: numpy's global state)."""
+        rng = np.random if rng is None else rng
+        a, s, p = gamma_grid_table(self)
+        size = tuple(np.atleast_1d(size))
+        effect = np.broadcast_to(np.asarray(effect, dtype=np.float64), size)
+        g = rng.choice(a.size, size=size, p=p / p.sum())
+        x = rng.gamma(a[g], 1.0, size=size)
+        with np.errstate(invalid="ignore"):
+            return np.where(effect > 0, effect * s[g] * x, np.nan)
+
 
 def gamma_grid_table(param):
     """(shape, scale, prob) float64 arrays of `param`: a (mean_grid, mean_probs, variance) triple - the arguments of

@@ -6,6 +6,10 @@ the (S,N,M,T) draws never leave the device.  This module holds the host halves a
 without a GPU): the family table, the mean function E[y | eta], the argument checks, and `evaluate`, the one caller of
 the C entry point that BayesianTensorFiltering.posterior_predictive and utils.posterior_predictive share.
 
+The gamma-grid likelihood (loglikelihood="gamma_grid") has entry points of its own, as its criteria have: gamma_grid_evaluate
+(btf_predict_gg_eval, behind NonconjugateBayesianTensorFiltering.gamma_grid_predictive and utils.gamma_grid_predictive),
+gamma_grid_batch (btf_predict_gg_batch) and gamma_grid_mean; family_code and FAMILIES keep to the five of btf_predict_eval.
+
 What the reference's benchmark applications do on the host (flutrends/benchmark.py:60-75, :129-134: Gaussian draws per
 kept sample, 2.5 / 97.5 percentiles per cell in a Python loop, coverage of the held-out years; politics/benchmark.py:
 147-172: per-sample RMSE / MAE of E[y | theta_s] with Mu = R p / (1 - p) for the Negative-Binomial model).
@@ -123,12 +127,12 @@ def rate_layout(R, nsamples, shape):
     return np.ascontiguousarray(R.reshape(nsamples, -1), dtype=np.float64), flags
 
 
-def evaluate(ctx, shape, nembeds, family, nsamples, Ws=None, Vs=None, param=None, aux=None, aux_flags=0, trials=None, Y=None,
-             q=(2.5, 97.5), draws_per_sample=1, seed=0, cells=None):
-    """btf_predict_eval on `ctx` (a _native.Context).  Ws / Vs None: the first `nsamples` device-collected samples.
-    aux / aux_flags: per-sample parameters (Gaussian variances (S,); rates from rate_layout).  Returns the result dict."""
+def _evaluate(ctx, entry, head, shape, nembeds, nsamples, Ws, Vs, tail, Y, q, draws_per_sample, seed, cells, check_Y=None):
+    """The checks, the output arrays and the result dict that btf_predict_eval and btf_predict_gg_eval share: `entry` is
+    called with head + (S, Ws, Vs) + tail(S) + (Y, nreps, R, seed, q, nq, cells, ncells) + the eleven outputs.
+    tail: the family's own arguments, checked against the sample count (arrays go over as pointers, None as NULL);
+    check_Y: the family's demands on the data."""
     from . import _native
-    code = family_code(family)
     N, M, T = shape
     S, R = check_draws(nsamples, draws_per_sample)
     qs = check_q(q)
@@ -139,12 +143,10 @@ def evaluate(ctx, shape, nembeds, family, nsamples, Ws=None, Vs=None, param=None
         if Ws.shape[0] != S:
             raise ValueError("nsamples does not match Ws")
     Y4 = check_observations(Y, shape)
-    trials = check_trials(trials, shape)
+    if check_Y is not None:
+        check_Y(Y4)
+    tail = tail(S)
     cl = check_cells(cells, shape)
-    if aux is not None:
-        aux = np.ascontiguousarray(aux, dtype=np.float64)
-        if aux.shape[0] != S:
-            raise ValueError("per-sample parameters: one per sample")
     n = S * R
     out = {"mean": np.zeros((N, M, T)), "y_mean": np.zeros((N, M, T)), "y_var": np.zeros((N, M, T)),
            "quantiles": np.zeros((len(qs), N, M, T))}
@@ -155,8 +157,8 @@ def evaluate(ctx, shape, nembeds, family, nsamples, Ws=None, Vs=None, param=None
         out[k] = np.zeros(S) if have_y else None
     out["draws"] = np.zeros((len(cl), n)) if cl is not None else None
     dp = _native.dptr
-    ctx.call("btf_predict_eval", code, float(param if param is not None else 0.0), S, dp(Ws), dp(Vs), dp(aux), int(aux_flags),
-             dp(trials), dp(Y4), Y4.shape[3] if have_y else 0, R, int(seed) & 0xFFFFFFFFFFFFFFFF, dp(qs), len(qs),
+    ctx.call(entry, *head, S, dp(Ws), dp(Vs), *(v if isinstance(v, int) else dp(v) for v in tail), dp(Y4),
+             Y4.shape[3] if have_y else 0, R, int(seed) & 0xFFFFFFFFFFFFFFFF, dp(qs), len(qs),
              cl.ctypes.data_as(_native._c_ip) if cl is not None else None, len(cl) if cl is not None else 0,
              dp(out["mean"]), dp(out["y_mean"]), dp(out["y_var"]), dp(out["quantiles"]) if len(qs) else None, dp(out["pit_lo"]),
              dp(out["pit_hi"]), dp(out["inside"]), dp(out["nobs"]), dp(out["rmse"]), dp(out["mae"]), dp(out["draws"]))
@@ -166,6 +168,23 @@ def evaluate(ctx, shape, nembeds, family, nsamples, Ws=None, Vs=None, param=None
     out.update(summarise(out.get("inside"), out.get("nobs"), qs))
     out["nsamples"], out["ndraws"] = S, n
     return out
+
+
+def evaluate(ctx, shape, nembeds, family, nsamples, Ws=None, Vs=None, param=None, aux=None, aux_flags=0, trials=None, Y=None,
+             q=(2.5, 97.5), draws_per_sample=1, seed=0, cells=None):
+    """btf_predict_eval on `ctx` (a _native.Context).  Ws / Vs None: the first `nsamples` device-collected samples.
+    aux / aux_flags: per-sample parameters (Gaussian variances (S,); rates from rate_layout).  Returns the result dict."""
+    code = family_code(family)
+
+    def tail(S):
+        tr, ax = check_trials(trials, shape), aux
+        if ax is not None:
+            ax = np.ascontiguousarray(ax, dtype=np.float64)
+            if ax.shape[0] != S:
+                raise ValueError("per-sample parameters: one per sample")
+        return ax, int(aux_flags), tr
+    return _evaluate(ctx, "btf_predict_eval", (code, float(param if param is not None else 0.0)), shape, nembeds, nsamples, Ws, Vs, tail,
+                     Y, q, draws_per_sample, seed, cells)
 
 
 def summarise(inside, nobs, qs):
@@ -192,3 +211,73 @@ def batch(family, eta, aux, seed=0, device=0):
     _native.check(lib.btf_predict_batch(int(device), code, eta.size, _native.dptr(eta), _native.dptr(aux),
                                         int(seed) & 0xFFFFFFFFFFFFFFFF, _native.dptr(out)), lib)
     return out
+
+
+# ---- the gamma-grid likelihood (loglikelihood="gamma_grid"; csrc/btf_gg_predict.h).  The draw, as the kernel makes it:
+# y | eta = eta s_g Gamma(a_g, 1), the component g chosen by the weights w_g = p_g / sum_h p_h of the table - NOT uniformly,
+# as the reference's GammaGridLikelihood.sample does (np.random.choice(G) ignores mean_probs); a table with equal weights
+# gives the reference's behaviour.  One component per replicated observation: the marginal predictive of one new
+# observation (the likelihood shares one component among the replicates of a cell). ----
+GAMMA_GRID_STREAM = 5       # PRED_FAM_GAMMA_GRID: the generator family of the draws
+
+
+def gamma_grid_weights(likelihood):
+    """(shape, scale, w, c, mbar) of anything likelihoods.gamma_grid_table accepts: the normalised weights w_g = p_g / sum p,
+    their cumulative sums c_g and mbar = sum_g w_g a_g s_g, every sum accumulated in ascending g in float64 - what
+    gg_pred_table of csrc/btf_gamma_grid.h computes (there c is 2 from the last positive weight on)."""
+    from . import likelihoods
+    a, s, p = likelihoods.gamma_grid_table(likelihood)
+    psum = 0.0
+    for v in p:
+        psum += float(v)
+    w = p / psum
+    c, acc, mbar = np.zeros(len(p)), 0.0, 0.0
+    for g in range(len(p)):
+        acc += float(w[g])
+        mbar += float(w[g]) * float(a[g]) * float(s[g])
+        c[g] = acc
+    return a, s, w, c, mbar
+
+
+def gamma_grid_mean(likelihood, eta):
+    """E[y | eta] = eta * sum_g w_g a_g s_g under the gamma-grid likelihood; nan where eta <= 0 (no such gamma)."""
+    mbar = gamma_grid_weights(likelihood)[4]
+    eta = np.asarray(eta, dtype=float)
+    with np.errstate(invalid="ignore"):
+        return np.where(eta > 0, eta * mbar, np.nan)
+
+
+def check_gamma_grid_data(Y, shape):
+    """Observations of a gamma-grid model as check_observations gives them; every observed y > 0, as gamma_grid_statistics
+    of criteria.py demands."""
+    if isinstance(Y, (tuple, list)):
+        raise ValueError("the gamma_grid likelihood takes one tensor, not a (Y, N) pair")
+    Y4 = check_observations(Y, shape)
+    if Y4 is not None and np.any(Y4 <= 0):                 # (nan = missing compares false)
+        raise ValueError("the gamma_grid likelihood needs every observed y > 0")
+    return Y4
+
+
+def gamma_grid_evaluate(ctx, shape, nembeds, nsamples, Ws=None, Vs=None, Y=None, q=(2.5, 97.5), draws_per_sample=1, seed=0, cells=None):
+    """btf_predict_gg_eval on `ctx` (a _native.Context whose table is set: btf_set_likelihood_table).  Ws / Vs None: the
+    first `nsamples` device-collected samples.  Returns the dictionary of `evaluate`."""
+    if isinstance(Y, (tuple, list)):
+        check_gamma_grid_data(Y, shape)
+    return _evaluate(ctx, "btf_predict_gg_eval", (), shape, nembeds, nsamples, Ws, Vs, lambda S: (), Y, q, draws_per_sample, seed, cells,
+                     check_Y=lambda Y4: check_gamma_grid_data(Y4, shape))
+
+
+def gamma_grid_batch(eta, likelihood, seed=0, device=0, components=False):
+    """out[i] = draw number i of y | eta[i] from the device sampler (btf_predict_gg_batch); likelihood: anything
+    likelihoods.gamma_grid_table accepts (a bad table raises before any device call).  components=True: (out, comp), comp
+    the int32 component of every draw (-1 where eta <= 0 or nan gave nan)."""
+    from . import _native, likelihoods
+    a, s, p = likelihoods.gamma_grid_table(likelihood)
+    eta = np.ascontiguousarray(np.atleast_1d(eta), dtype=np.float64).ravel()
+    out = np.zeros(eta.size)
+    comp = np.zeros(eta.size, dtype=np.int32) if components else None
+    lib = _native.load()
+    _native.check(lib.btf_predict_gg_batch(int(device), eta.size, _native.dptr(eta), int(a.size), _native.dptr(a), _native.dptr(s),
+                                           _native.dptr(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _native.dptr(out),
+                                           comp.ctypes.data_as(_native._c_ip) if components else None), lib)
+    return (out, comp) if components else out

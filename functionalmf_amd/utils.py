@@ -180,6 +180,32 @@ def gamma_grid_loo(Ws, Vs, Y, likelihood, r_eff=None, mean=False, transform=None
         ctx.close()
 
 
+def gamma_grid_predictive(Ws, Vs, likelihood, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=0, cells=None, device=0):
+    """Posterior predictive of the observations under the gamma-grid likelihood on the GPU, without a model: the stateless
+    form of NonconjugateBayesianTensorFiltering.gamma_grid_predictive (see there, and posterior_predictive for the outputs),
+    the shape doseresponse/fit.py:475-478, plot_example.py:86 and plot_results.py:90 have.
+
+    Ws (S,N,K), Vs (S,M,T,K); likelihood: as gamma_grid_criteria.  The component of a draw follows the table's weights; the
+    reference's sample picks it uniformly - pass a table with equal weights for that.  data: (N,M,T) or (N,M,T,R), NaN =
+    missing, every observed y > 0.  Needs ndepth >= 2 (a context is opened for the call).  No CPU fallback."""
+    from . import _analysis, _native, criteria, likelihoods, predictive
+    table = likelihoods.gamma_grid_table(likelihood)               # (a bad table raises before any device call)
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    predictive.check_draws(S, draws_per_sample)
+    predictive.check_q(q)
+    predictive.check_cells(cells, shape)
+    Y4 = predictive.check_gamma_grid_data(data, shape)
+    ctx = _native.Context(N, shape[1], shape[2], K, 0, device=device)
+    try:
+        ctx.call("btf_set_likelihood_table", criteria.FAMILY_GAMMA_GRID, *(_native.dptr(v) for v in table), int(table[0].size))
+        return predictive.gamma_grid_evaluate(ctx, shape, K, S, Ws, Vs, Y=Y4, q=q, draws_per_sample=draws_per_sample, seed=seed,
+                                              cells=cells)
+    finally:
+        ctx.close()
+
+
 def posterior_functionals(Ws, Vs, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None, curves=None,
                           pointwise=False, device=0):
     """Per-curve functionals of f(w_s[i] . v_s[j,:]) over depth, summarised over the kept samples, on the GPU, without a

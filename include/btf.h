@@ -834,6 +834,30 @@ int btf_predict_eval(btf_ctx* ctx, int family, double param, int nsamples, const
                      double* pit_hi_out, double* inside_out, double* nobs_out, double* rmse_out, double* mae_out,
                      double* draws_out);
 
+/* ---- the same for the gamma-grid likelihood (doseresponse/fit.py:475-478: likelihood.sample and the 5 / 95 percentiles
+ * per curve), csrc/btf_gg_predict.h ----
+ * The draw: y | eta = eta s_g Gamma(a_g, 1) with the component g chosen by the weights w_g = p_g / sum_h p_h of the table
+ *   (the reference's sample picks it uniformly, whatever mean_probs says; a table with equal weights gives that).  The
+ *   cumulative weights c_g = sum_{h<=g} w_h are summed once on the host in ascending g; draw number i uses the generator
+ *   of family 5 at global draw index i, whose first uniform u takes the smallest g with u < c_g (never a component of
+ *   weight 0; the last one with p_g > 0 where round-off leaves none), and the Gamma draw goes on with the same generator.
+ *   eta <= 0 or nan gives nan.  E[y | eta] = eta mbar, mbar = sum_g w_g a_g s_g.  One component per replicated
+ *   observation: the marginal predictive of one new observation.
+ * btf_predict_gg_eval: btf_predict_eval for the table the context holds (btf_set_likelihood_table; without one BTF_ESTATE,
+ *   nothing is launched): states, Y, draws_per_sample, seed, q, cells, every output, the global draw index, the limits
+ *   and the refusals as there.  A cell with eta <= 0 in a sample has nan in mean and in every draw-based output, and
+ *   every sample with such an observed cell a nan rmse / mae, as under family 1.  No floating-point atomics.  Synchronises.
+ * btf_predict_gg_batch (stateless, for validating the sampler): out[i] = draw number i at eta[i] from the table shape,
+ *   scale, prob (G entries each; 1 <= G <= 128, finite shape > 0, scale > 0, weight >= 0, not all zero, else BTF_EINVAL);
+ *   comp_out[i] (or NULL): its component, -1 where eta[i] gives no draw.                                             */
+int btf_predict_gg_eval(btf_ctx* ctx, int nsamples, const double* Ws, const double* Vs, const double* Y, int nreps,
+                        int draws_per_sample, uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells,
+                        double* mean_out, double* ymean_out, double* yvar_out, double* q_out, double* pit_lo_out,
+                        double* pit_hi_out, double* inside_out, double* nobs_out, double* rmse_out, double* mae_out,
+                        double* draws_out);
+int btf_predict_gg_batch(int device, int64_t n, const double* eta, int G, const double* shape, const double* scale,
+                         const double* prob, uint64_t seed, double* out, int32_t* comp_out);
+
 /* ---- non-negative tensor factorisation (replaces functionalmf.utils.tensor_nmf, utils.py:276-420, its max_entry
  * projection and row_features included) and the factor PAV projection (factor_pav, utils.py:218-252) ------------------
  * Context-free: a btf_nmf handle holds its own statistics, factors and a small device state on a stream of its own; no
