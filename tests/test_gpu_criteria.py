@@ -37,8 +37,11 @@ def _logdens(kind, Y4, Mu, par=None, nu2=None, Ntr=None):
     return np.where(np.isnan(Y4)[None], 0.0, ld).sum(axis=(3, 4))
 
 
-def _case(kind, N, M, T, R, K, S, seed, form="complete"):
-    """(model, data, results, per-curve reference matrix L, plug-in reference, observed mask)."""
+def _case(kind, N, M, T, R, K, S, seed, form="complete", bind=True, prepare=None):
+    """(model, data, results, per-curve reference matrix L, plug-in reference, observed mask).
+
+    bind=False builds the inputs and the references only (no model, no device: `model` is None).  prepare(Ws, Vs, Y4)
+    edits the states and the observations in place before the references are formed from them."""
     rs = np.random.RandomState(seed)
     positive = kind == "poisson_identity"
     Ws = rs.uniform(0.2, 1.0, size=(S, N, K)) if positive else rs.normal(0, 0.6, size=(S, N, K))
@@ -47,15 +50,17 @@ def _case(kind, N, M, T, R, K, S, seed, form="complete"):
     Mu0 = Mu[0]
     np.random.seed(seed)
     par, nu2, Ntr, extra = None, None, None, {}
+    tf_order = min(2, T - 2)                               # (2, the default, at every T >= 4)
+    make = None
     if kind == "gauss":
         Y4 = Mu0[..., None] + rs.normal(0, 0.5, size=(N, M, T, R))
         nu2 = rs.uniform(0.2, 0.4, size=S)
-        model = GaussianBayesianTensorFiltering(N, M, T, nembeds=K)
+        make = lambda: GaussianBayesianTensorFiltering(N, M, T, nembeds=K, tf_order=tf_order)
         extra["nu2"] = nu2[:, None]
     elif kind == "binom":
         Ntr = rs.randint(1, 9, size=(N, M, T)).astype(float)
         Y4 = rs.binomial(Ntr.astype(int), expit(Mu0)).astype(float)[..., None]
-        model = BinomialBayesianTensorFiltering(N, M, T, nembeds=K)
+        make = lambda: BinomialBayesianTensorFiltering(N, M, T, nembeds=K, tf_order=tf_order)
     else:
         lam = np.exp(Mu0) if kind == "poisson_log" else np.maximum(Mu0, 1e-3)
         if kind in ("poisson_log", "poisson_identity"):
@@ -68,11 +73,15 @@ def _case(kind, N, M, T, R, K, S, seed, form="complete"):
         else:
             par = 3.0
             Y4 = rs.negative_binomial(par, 1.0 - expit(Mu0)[..., None] * np.ones(R)).astype(float)
-        model = NonconjugateBayesianTensorFiltering(N, M, T, loglikelihood=kind, nembeds=K, likelihood_param=par)
+        make = lambda: NonconjugateBayesianTensorFiltering(N, M, T, loglikelihood=kind, nembeds=K, likelihood_param=par,
+                                                           tf_order=tf_order)
     if form == "missing":
         Y4[rs.uniform(size=Y4.shape) < 0.3] = np.nan
     elif form == "curve":
         Y4[:3, :3] = np.nan
+    if prepare is not None:
+        prepare(Ws, Vs, Y4)
+        Mu = np.einsum("snk,smtk->snmt", Ws, Vs)
     if kind == "binom":
         Y4[rs.uniform(size=Y4.shape) < 0.2] = np.nan
         Yb = Y4[..., 0].copy()
@@ -83,7 +92,11 @@ def _case(kind, N, M, T, R, K, S, seed, form="complete"):
     L = _logdens(kind, Y4, Mu, par=par, nu2=nu2, Ntr=Ntr)
     Lm = _logdens(kind, Y4, Mu.mean(axis=0)[None], par=par, nu2=None if nu2 is None else np.array([nu2.mean()]), Ntr=Ntr)[0]
     obs = ~np.all(np.isnan(Y4), axis=(2, 3))
-    model.set_data(data)
+    model = None
+    if bind:
+        np.random.seed(seed)
+        model = make()
+        model.set_data(data)
     results = dict(W=Ws, V=Vs, **extra)
     return model, data, results, L, Lm, obs
 

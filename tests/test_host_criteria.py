@@ -137,6 +137,28 @@ def test_combine_minus_infinity_follows_numpy():
     assert np.isnan(out["curves"]["p_waic"][1, 2]) and np.isnan(out["waic"])
 
 
+def _shape_groups():
+    import test_gpu_criteria_shapes as shapes
+    return shapes, list(shapes.GROUPS)
+
+
+@pytest.mark.parametrize("group", _shape_groups()[1])
+def test_shape_cases_of_the_gpu_suite_meet_their_conditions(group):
+    """Every builder of tests/test_gpu_criteria_shapes.py, without a device: `build` asserts that the scipy reference is
+    finite everywhere except where a poisson_identity design puts w . v = 0 under an observed cell, that those cells are
+    the only zeros of the linear predictor, and that the seeds differ."""
+    shapes = _shape_groups()[0]
+    specs = shapes.GROUPS[group]
+    assert len({shapes._seed(s) for s in specs}) == len(specs)
+    for spec in specs:
+        model, results, L, Lm, obs = shapes.build(spec, bind=False)
+        assert model is None and results["W"].shape == (spec[6], spec[1], spec[5])
+    if group == "infinities":
+        kinds = {s[8]: shapes.build(s, bind=False)[2] for s in specs}
+        assert (kinds["cells"] == -np.inf).sum() == 3 and np.isfinite(kinds["cells-unobserved"]).all()
+        assert (kinds["sample"] == -np.inf).sum() == 65
+
+
 class _Stub(_BayesianModel):
     """Scripted criteria: the DIC of each grid point is read off a table keyed by lam2."""
 
