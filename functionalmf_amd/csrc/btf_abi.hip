@@ -2744,21 +2744,16 @@ int btf_set_likelihood_table(btf_ctx* c, int family, const double* shape, const 
   if (family != ESS_FAM_GAMMA_GRID) return fail(c, BTF_EINVAL, "btf_set_likelihood_table: family 5 (gamma grid) only");
   if (!shape || !scale || !prob || G < 1 || G > GG_MAXG) return fail(c, BTF_EINVAL, "the gamma grid has 1..128 components");
   std::vector<GgComp> h;
-  double psum = 0.0;
-  for (int g = 0; g < G; ++g) {
-    const double a = shape[g], s = scale[g], p = prob[g];
-    if (!std::isfinite(a) || !std::isfinite(s) || !std::isfinite(p) || !(a > 0.0) || !(s > 0.0) || !(p >= 0.0))
-      return fail(c, BTF_EINVAL, "gamma grid: finite shape > 0, scale > 0 and weight >= 0 expected");
-    psum += p;
-    if (p > 0.0) h.push_back(GgComp{std::log(p), a, 1.0 / s, a * std::log(s) + std::lgamma(a)});    // (p = 0: no term)
-  }
-  if (h.empty()) return fail(c, BTF_EINVAL, "gamma grid: every weight is zero");
+  double lsp = 0.0;
+  const int bad = gg_comp_table(shape, scale, prob, G, h, lsp);
+  if (bad == 1) return fail(c, BTF_EINVAL, "gamma grid: finite shape > 0, scale > 0 and weight >= 0 expected");
+  if (bad) return fail(c, BTF_EINVAL, "gamma grid: every weight is zero");
   HIPCHK(c, hipSetDevice(c->dev));
   int rc;
   if ((rc = dev_alloc(c, &c->gg_tab, (size_t)GG_MAXG))) return rc;
   HIPCHK(c, hipMemcpy(c->gg_tab, h.data(), h.size() * sizeof(GgComp), hipMemcpyHostToDevice));
   c->gg_G = (int)h.size();
-  c->gg_lsp = std::log(psum);
+  c->gg_lsp = lsp;
   gg_pred_table(shape, scale, prob, G, c->gg_pred, c->gg_mbar);      // (the checks above are its own)
   return BTF_OK;
 }

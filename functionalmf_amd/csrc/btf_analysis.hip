@@ -1,5 +1,5 @@
 // The posterior analyses behind the C ABI (include/btf.h): summaries, criteria, PSIS-LOO, predictive, functionals, ranking,
-// association, monotone projection, fold-in, diagnostics.  Host code over kernels in units of their own.  gfx950 only.
+// association, monotone projection, fold-in (conjugate and slice-sampled), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
 #include "btf_ctx.h"            // struct btf_ctx, fail, Scratch, launch_counted, K_SWITCH / FAM_SWITCH
 #include "btf_diag.h"           // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
@@ -12,6 +12,7 @@
 #include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
 #include "btf_monotone.h"       // monotone projection of the posterior (kernel in btf_monotone.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
+#include "btf_slice_fold.h"     // the same for the slice-sampled models (kernels in btf_slice_fold.hip)
 
 #include <algorithm>
 #include <climits>
@@ -969,6 +970,180 @@ int btf_collect_fold_in(btf_ctx* c, int family, int nsamples, int nrows_new, con
   if (int rc = resolve_pair(s, 0, "btf_collect_fold_in", BTF_ESTATE, nsamples, 0, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
   return fold_in_run(s, st.V, family == FOLD_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT,
                      c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, f);
+}
+
+// ---------------------------------------------------------------- folding new rows into a slice-sampled fit (btf_slice_fold.h)
+namespace {
+struct SliceFold {
+  int family; double param;
+  int S, R, M, T, K;
+  const double *start, *S1, *cnt, *L;
+  const double* cons; int J;
+  const double* rcons; int nrc;
+  const double* Us; int F; const unsigned char* codes;
+  const double* draws;
+  unsigned long long seed;
+  int sweeps, max_rounds;
+  long long sample0;
+  double *W_out, *Wstart_out; int *rounds_out, *unf_out;
+  int transform;
+  const double* q; int nq;
+  double *mean_out, *q_out;
+};
+
+bool all_finite(const double* p, size_t n) {
+  for (size_t e = 0; e < n; ++e)
+    if (!(std::fabs(p[e]) < INFINITY)) return false;
+  return true;
+}
+
+// everything that can be refused without a device
+int slice_fold_check(btf_ctx* c, const SliceFold& f) {
+  if (f.family < 0 || f.family >= ESS_FAM_COUNT || f.S < 1 || f.R < 1 || f.M < 1 || f.T < 1 || f.K < 1 || f.K > MAX_K || !f.S1 || !f.cnt ||
+      !f.W_out || !f.rounds_out || !f.unf_out || f.sample0 < 0 || f.nq < 0 || (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) ||
+      f.transform < 0 || f.transform > 2 || f.J < 0 || (f.J > 0 && !f.cons) || f.nrc < 0 || (f.nrc > 0 && !f.rcons) || f.F < 0 ||
+      (f.F > 0 && (!f.Us || !f.codes)))
+    return fail(c, BTF_EINVAL, "bad slice_fold arguments");
+  if (f.sweeps < 1 || f.max_rounds < 1 || f.max_rounds > 65536) return fail(c, BTF_EINVAL, "slice_fold: sweeps >= 1 and max_rounds in 1..65536");
+  if (f.family == ESS_FAM_GAMMA_GRID && !f.L) return fail(c, BTF_EINVAL, "slice_fold: the gamma-grid family needs logsum");
+  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "slice_fold: the summary stage takes at most 16384 samples");
+  if ((double)(f.sample0 + f.S) * f.R >= 2147483647.0 || (double)f.R * f.M * f.T >= 2147483647.0 || (double)f.M * f.J >= 2147483647.0 ||
+      (double)f.sweeps * (f.K + 1 + f.max_rounds) >= 2147483647.0)
+    return fail(c, BTF_EINVAL, "slice_fold: (sample0 + nsamples) * nrows_new, nrows_new * ncols * ndepth, ncols * ncons and the draws of a chain must stay below 2^31");
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  const size_t n = (size_t)f.R * f.M * f.T;
+  for (size_t e = 0; e < n; ++e)
+    if (!(f.cnt[e] >= 0.0 && f.cnt[e] < 1e15) || !(std::fabs(f.S1[e]) < INFINITY) || (f.L && !(std::fabs(f.L[e]) < INFINITY)))
+      return fail(c, BTF_EINVAL, "slice_fold: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
+  if (!all_finite(f.cons, (size_t)f.J * (f.T + 1)) || !all_finite(f.rcons, (size_t)f.nrc * (f.K + 1)))
+    return fail(c, BTF_EINVAL, "slice_fold: constraints must be finite");
+  for (size_t e = 0; e < (size_t)f.R * f.F; ++e)
+    if (f.codes[e] > 2) return fail(c, BTF_EINVAL, "slice_fold: feature codes are 0, 1 or 2 (missing)");
+  return BTF_OK;
+}
+
+// The launches on device states dV (S,M,T,K), dW (S,N,K; read when the call has no start) and per-sample sigma2 on the
+// device; dgg: the gamma-grid table on the device (family 5).  The scratch's context may be null (the stateless form).
+// W stays on the device between the chains and the summary.
+int slice_fold_run(Scratch& s, const double* dV, const double* dW, int N, const double* dsig, int sstride, const GgComp* dgg, int G,
+                   double lsp, const SliceFold& f) {
+  btf_ctx* c = s.ctx();
+  const int S = f.S, R = f.R, MT = f.M * f.T, K = f.K, T = f.T;
+  SliceFoldKernel kern = slice_fold_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, "slice_fold: nembeds must be 1..10 and family 0..5");
+  // Constraints_A by its non-zeros (CSR over the constraints), the bounds beside it
+  std::vector<int> cptr(1, 0), cidx;
+  std::vector<double> cval, cc;
+  for (int q = 0; q < f.J; ++q) {
+    for (int t = 0; t < T; ++t)
+      if (f.cons[(size_t)q * (T + 1) + t] != 0.0) { cidx.push_back(t); cval.push_back(f.cons[(size_t)q * (T + 1) + t]); }
+    cptr.push_back((int)cidx.size());
+    cc.push_back(f.cons[(size_t)q * (T + 1) + T]);
+  }
+  const size_t nW = (size_t)S * R * K, cells = (size_t)R * MT, nch = (size_t)S * R;
+  const int stat0[2] = {0, INT_MAX};
+  SliceFoldArgs a = {};
+  a.V = dV; a.sigma2 = dsig; a.sstride = sstride;
+  a.S1 = s.upload(f.S1, cells); a.cnt = s.upload(f.cnt, cells);
+  if (f.L) a.L = s.upload(f.L, cells);
+  if (cidx.empty()) { cidx.push_back(0); cval.push_back(0.0); cc.push_back(0.0); }      // (never read: J = 0, or rows of zeros)
+  a.cs_ptr = s.upload(cptr.data(), cptr.size()); a.cs_idx = s.upload(cidx.data(), cidx.size());
+  a.cs_val = s.upload(cval.data(), cval.size()); a.Cc = s.upload(cc.data(), cc.size()); a.J = f.J;
+  if (f.nrc) a.Rc = s.upload(f.rcons, (size_t)f.nrc * (K + 1));
+  a.nrc = f.nrc;
+  if (f.F) { a.U = s.upload(f.Us, (size_t)S * f.F * K); a.codes = s.upload(f.codes, (size_t)R * f.F); }
+  a.F = f.F;
+  const int rec = K + 1 + f.max_rounds;
+  if (f.draws) a.draws = s.upload(f.draws, nch * f.sweeps * rec);
+  a.gg = dgg; a.G = G; a.lsp = lsp; a.fam = f.family; a.par = f.param;
+  double* dmean = nullptr;
+  if (f.start) { a.start = s.upload(f.start, nW); a.st_s = (long long)R * K; a.st_r = K; }
+  else {
+    dmean = s.alloc<double>((size_t)S * K);
+    const int nb = (int)(((size_t)S * K + 255) / 256);
+    launch_counted(s, BTF_K_CRITERIA, slice_fold_mean_fn(), dim3(nb), dim3(256), 0, dW, S, N, K, dmean);
+    a.start = dmean; a.st_s = K; a.st_r = 0;
+  }
+  double* dWout = s.alloc<double>(nW);
+  a.W = dWout; a.rounds = s.alloc<int>(nch); a.unfinished = s.alloc<int>(nch); a.status = s.upload(stat0, 2);
+  a.seed = f.seed; a.sample0 = f.sample0; a.S = S; a.R = R; a.M = f.M; a.T = T; a.sweeps = f.sweeps; a.max_rounds = f.max_rounds;
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3((unsigned)((nch + SF_CHAINS - 1) / SF_CHAINS)), dim3(SF_CHAINS * WAVE), 0, a);
+  // the summary stage reads the device-resident W (S,R,K) and V
+  if (f.mean_out) summary_stage(s, dWout, dV, S, R, MT, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
+  int stat[2] = {0, INT_MAX};
+  std::vector<double> hmean(dmean ? (size_t)S * K : 0);
+  s.download(stat, (const int*)a.status, 2);
+  s.download(f.W_out, (const double*)dWout, nW);
+  s.download(f.rounds_out, (const int*)a.rounds, nch);
+  s.download(f.unf_out, (const int*)a.unfinished, nch);
+  if (dmean && f.Wstart_out) s.download(hmean.data(), (const double*)dmean, hmean.size());
+  const int rc = s.finish();
+  if (rc) return rc;
+  if (f.Wstart_out) {
+    if (f.start) std::copy(f.start, f.start + nW, f.Wstart_out);
+    else
+      for (size_t e = 0; e < nW; ++e) f.Wstart_out[e] = hmean[(e / ((size_t)R * K)) * K + e % K];
+  }
+  if (stat[0]) {
+    if (c) c->fail_index = stat[1];
+    g_fold_fail_index = stat[1];
+    const long long sg = stat[1] / R;
+    return fail(c, BTF_ESTATE, "slice_fold: the start of (sample " + std::to_string(sg) + ", row " + std::to_string(stat[1] - sg * R) +
+                                   ") is infeasible or has a non-finite likelihood (index " + std::to_string(stat[1]) +
+                                   " = sample * nrows_new + row)");
+  }
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_slice_fold_rows(int device, int family, double param, const double* shape, const double* scale, const double* prob, int G,
+                        int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs, const double* Ws,
+                        int nrows_fit, const double* start, const double* sigma2, const double* S1, const double* cnt,
+                        const double* logsum, const double* constraints, int ncons, const double* row_constraints, int nrow_cons,
+                        const double* Us, int nfeatures, const unsigned char* codes, const double* draws, unsigned long long seed,
+                        int sweeps, int max_rounds, long long sample0, double* W_out, double* Wstart_out, int* rounds_out,
+                        int* unfinished_out, int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  const SliceFold f = {family, param, nsamples, nrows_new, ncols, ndepth, nembeds, start, S1, cnt, logsum, constraints, ncons,
+                       row_constraints, nrow_cons, Us, nfeatures, codes, draws, seed, sweeps, max_rounds, sample0, W_out, Wstart_out,
+                       rounds_out, unfinished_out, transform, q, nq, mean_out, q_out};
+  g_fold_fail_index = -1;
+  if (!Vs || !sigma2 || (!start && (!Ws || nrows_fit < 1))) return fail(nullptr, BTF_EINVAL, "bad slice_fold arguments");
+  if (int rc = slice_fold_check(nullptr, f)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(sigma2[s] > 0.0 && sigma2[s] < INFINITY)) return fail(nullptr, BTF_EINVAL, "slice_fold: sigma2 must be finite and positive");
+  if ((family == ESS_FAM_GAUSSIAN || family == ESS_FAM_NEGBIN_LOGIT) && !(param > 0.0 && param < INFINITY))
+    return fail(nullptr, BTF_EINVAL, "slice_fold: the parameter must be positive");
+  std::vector<GgComp> tab;
+  double lsp = 0.0;
+  if (family == ESS_FAM_GAMMA_GRID && gg_comp_table(shape, scale, prob, G, tab, lsp) != 0)
+    return fail(nullptr, BTF_EINVAL, "slice_fold: the gamma grid has 1..128 components with finite shape > 0, scale > 0, weight >= 0, not all zero");
+  Scratch s(nullptr, nullptr); States st;
+  const bool mean_start = start == nullptr;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, mean_start ? nrows_fit : 0, ncols * ndepth, nembeds, mean_start ? Ws : nullptr, Vs, st))
+    return rc;
+  const double* ds = s.upload(sigma2, (size_t)nsamples);
+  const GgComp* dgg = tab.empty() ? nullptr : s.upload(tab.data(), tab.size());
+  return slice_fold_run(s, st.V, st.W, nrows_fit, ds, 1, dgg, (int)tab.size(), lsp, f);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload): W and V from the sample slots,
+// sigma2_s from the collected scalars, the likelihood's parameter or table from the context
+int btf_collect_slice_fold(btf_ctx* c, int family, int nsamples, int nrows_new, const double* start, const double* S1,
+                           const double* cnt, const double* logsum, const double* constraints, int ncons,
+                           const double* row_constraints, int nrow_cons, const double* Us, int nfeatures,
+                           const unsigned char* codes, const double* draws, unsigned long long seed, int sweeps, int max_rounds,
+                           long long sample0, double* W_out, double* Wstart_out, int* rounds_out, int* unfinished_out,
+                           int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  if (!c || family < 0 || family >= ESS_FAM_COUNT) return fail(c, BTF_EINVAL, "bad slice_fold arguments");
+  const SliceFold f = {family, c->lik_par[family], nsamples, nrows_new, c->M, c->T, c->K, start, S1, cnt, logsum, constraints, ncons,
+                       row_constraints, nrow_cons, Us, nfeatures, codes, draws, seed, sweeps, max_rounds, sample0, W_out, Wstart_out,
+                       rounds_out, unfinished_out, transform, q, nq, mean_out, q_out};
+  if (int rc = slice_fold_check(c, f)) return rc;
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_collect_slice_fold needs an unsharded context");
+  if (family == ESS_FAM_GAMMA_GRID && !c->gg_tab) return fail(c, BTF_ESTATE, "btf_collect_slice_fold: the gamma-grid family needs its table (btf_set_likelihood_table)");
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_slice_fold", BTF_ESTATE, nsamples, 0, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  return slice_fold_run(s, st.V, st.W, c->N, c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, c->gg_tab, c->gg_G, c->gg_lsp, f);
 }
 
 // ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)

@@ -16,7 +16,7 @@
 //   gg_logsum_kernel                              L = sum_r log y of every cell, and a flag for an observed y <= 0
 // Every sum has a fixed order (no float atomics): two calls give identical bits.
 #pragma once
-#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT)
+#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT) || defined(BTF_SLICE_FOLD_UNIT)
 #include "btf_gass.h"
 #else      // host code that needs the table's types alone (btf_ctx.h, btf_gg_criteria.h): no sampler kernels
 #include "btf_device.h"
@@ -78,6 +78,23 @@ inline bool gg_pred_table(const double* shape, const double* scale, const double
   return true;
 }
 
+// The table of the likelihood kernels: {log p_g, a_g, 1 / s_g, a_g log s_g + lgamma a_g} for every component with p_g > 0,
+// in the order given, and lsp = log sum_g p_g.  0: built; 1: an entry that is not finite shape > 0, scale > 0, weight >= 0
+// (or G outside 1..128); 2: every weight is zero.
+inline int gg_comp_table(const double* shape, const double* scale, const double* prob, int G, std::vector<GgComp>& tab, double& lsp) {
+  if (!shape || !scale || !prob || G < 1 || G > GG_MAXG) return 1;
+  tab.clear();
+  double psum = 0.0;
+  for (int g = 0; g < G; ++g) {
+    const double a = shape[g], s = scale[g], p = prob[g];
+    if (!std::isfinite(a) || !std::isfinite(s) || !std::isfinite(p) || !(a > 0.0) || !(s > 0.0) || !(p >= 0.0)) return 1;
+    psum += p;
+    if (p > 0.0) tab.push_back(GgComp{std::log(p), a, 1.0 / s, a * std::log(s) + std::lgamma(a)});    // (p = 0: no term)
+  }
+  lsp = std::log(psum);
+  return tab.empty() ? 2 : 0;
+}
+
 using GgLLKernel = void (*)(GgLLArgs, GgTab);
 using GgEvalKernel = void (*)(GassEvalArgs, GgTab);
 using GgLogsumKernel = void (*)(const double*, int, int, int, int, int, double*, int*);
@@ -87,8 +104,9 @@ GgLLKernel gg_ll_cols_fn(int K);
 GgEvalKernel gg_eval_fn(bool rows, bool ep);
 GgLogsumKernel gg_logsum_fn();
 
-// the cell term, shared by this unit's kernels and the criteria kernels of btf_gg_criteria.h (BTF_GG_CRIT_UNIT)
-#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT)
+// the cell term, shared by this unit's kernels, the criteria kernels of btf_gg_criteria.h (BTF_GG_CRIT_UNIT) and the
+// slice fold-in kernel of btf_slice_fold.h (BTF_SLICE_FOLD_UNIT)
+#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT) || defined(BTF_SLICE_FOLD_UNIT)
 // table and exp / log tables into LDS (then a barrier, by the caller)
 __device__ __forceinline__ void gg_stage(const GgTab& t, GgComp* tab, double2* ltab, double2* etab) {
   for (int g = threadIdx.x; g < t.G; g += blockDim.x) tab[g] = t.tab[g];
@@ -115,7 +133,7 @@ __device__ __forceinline__ double gg_term(double s1, double L, double cnt, doubl
   if (!(m > -INFINITY)) return -INFINITY;
   return m + log_tab(s, ltab) - L;
 }
-#endif  // BTF_GAMMA_GRID_UNIT || BTF_GG_CRIT_UNIT
+#endif  // BTF_GAMMA_GRID_UNIT || BTF_GG_CRIT_UNIT || BTF_SLICE_FOLD_UNIT
 
 #ifdef BTF_GAMMA_GRID_UNIT
 template <int K>

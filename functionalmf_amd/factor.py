@@ -1458,6 +1458,74 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
             seed = self._next_seed()
         return _pred.gamma_grid_evaluate(self._ctx, shape, self.nembeds, S, Ws, Vs, Y=Y4, q=q, draws_per_sample=R, seed=seed, cells=cells)
 
+    # ---- folding new rows in (functionalmf_amd/slice_fold_in.py, csrc/btf_slice_fold.h) ----
+    def _fold_family(self):
+        raise NotImplementedError("%s: fold_in_rows needs a conjugate row conditional (Gaussian and Binomial models); "
+                                  "slice_fold_in_rows folds rows into this model" % type(self).__name__)
+
+    def _slice_fold_restrictions(self, row_features, R, results, S):
+        """(Constraints, Row_constraints, codes (R,F) or None, Us (S,F,K) or None) of a slice_fold_in_rows call."""
+        if row_features is not None:
+            raise ValueError("row_features: this model has no row features (ConstrainedNonconjugateBayesianTensorFiltering "
+                             "with row_features= has)")
+        return None, None, None, None
+
+    def slice_fold_in_rows(self, Y_new, results=None, row_features=None, start=None, seed=None, draws=None, sweeps=None,
+                           max_rounds=40, summary=True, q=(5, 95), transform=None):
+        """Embeddings and curves of rows the chain never saw (a new cell line with a handful of drugs tested), with
+        uncertainty, for the slice-sampled models, on the GPU (csrc/btf_slice_fold.h): fold_in_rows for the likelihoods
+        without a conjugate row conditional.  The row prior is N(0, sigma2 I) (factor.py:685-686) and, given V_s (and U_s),
+        every restriction on a row is linear in w - the feasible set is convex - so elliptical slice sampling with the
+        restrictions as a likelihood of minus infinity samples p(w_new | y_new, V_s, U_s): `sweeps` updates per kept sample
+        and row (default: functionalmf_amd.slice_fold_in.DEFAULT_SWEEPS), each with at most max_rounds proposals, all of
+        them in one launch.  functionalmf_amd.slice_fold_in.chain is the definition in numpy.
+
+        Y_new: (R,M,T) or (R,M,T,nreps), NaN = missing; a row with no observation at all is allowed.  None with
+            row_features: curves predicted from the features alone.
+        results: a run_gibbs result dict (W (S,N,K) - read for the default start only -, V (S,M,T,K), sigma2 one value per
+            sample; with row_features U (S,F,K)), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device - no upload of W and V, and sigma2_s is read from the collected scalars.
+        row_features: (R,F) of 0 / 1 / nan for a constrained model with row features: the row then also carries
+            sum_f x log(w . u_f) + (1 - x) log(1 - w . u_f) under 0 <= w . u_f <= 1, with U of every kept sample from
+            results["U"] (U is not collected on the device: results= is needed).  None on such a model: the features of
+            the new rows are unknown, and neither the term nor the restriction applies.
+        start: (K,), (R,K) or (S,R,K); default: the mean of the fitted rows of W_s, which lies in the convex feasible set.
+            A start that is infeasible or has a non-finite likelihood raises RuntimeError naming (sample, row).
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        draws: optional (S,R,sweeps,K+1+max_rounds) replacing the device generator: per sweep the K normals, u_h, u_a and
+            the shrink uniforms - slice_fold_in.chain with the same record replays the chain.
+        ep_approx of a constrained model is ignored: it only centres the proposals of the sampler, the target is the same.
+
+        Returns a dict: W (S,R,K) the last state of every chain, one draw per kept sample; W_start (S,R,K); rounds (S,R)
+        likelihood evaluations; unfinished (S,R) sweeps that used all max_rounds proposals (they keep their state); with
+        summary=True, mean (R,M,T) and quantiles (len(q),R,M,T) of f(w_new^s . v_jt^s) from the summary kernel on the
+        device-resident W and V (transform as posterior_summary; at most 16384 samples); nsamples.  out["W"] together with
+        results["V"] goes straight into utils.posterior_summary, posterior_functionals, posterior_ranking and
+        gamma_grid_predictive.  The sampler's state is not touched.  Unsharded models, device likelihoods, nembeds <= 10.
+        The Negative-Binomial model (its rate is sampled) and new columns are out of scope."""
+        from . import slice_fold_in as _sf
+        from ._analysis import check_scalars
+        self._unsharded("slice_fold_in_rows")
+        if self._callback:
+            raise NotImplementedError("slice_fold_in_rows needs a device likelihood: a Python-callable loglikelihood is "
+                                      "evaluated on the host only")
+        M, T, K = self.ncols, self.ndepth, self.nembeds
+        family = self.loglikelihood
+        param = self._gg_table if self._link == 5 else self.likelihood_param
+        codes = None if row_features is None else _sf.feature_codes(row_features)
+        R, S1, cnt, L = _sf.row_statistics(Y_new, family, M, T, R=None if codes is None else codes.shape[0])
+        S, Ws, Vs = self._samples(results, need=("W", "V") if start is None else ("V",))
+        cons, rcons, codes, Us = self._slice_fold_restrictions(row_features, R, results, S)
+        _sf.check_args(family, param, S, R, K, start, draws, sweeps, max_rounds, summary, q, transform, 0, Us, codes)
+        _sf.check_constraints(cons, rcons, T, K)
+        sigma2 = check_scalars("results: sigma2", results.get("sigma2"), S) if results is not None else None
+        if seed is None:
+            seed = self._next_seed() if draws is None else 0
+        return _sf.evaluate(family, param, S, R, M, T, K, S1, cnt, L, start=start, Constraints=cons, Row_constraints=rcons, Us=Us,
+                            codes=codes, draws=draws, seed=seed, sweeps=sweeps, max_rounds=max_rounds, summary=summary, q=q,
+                            transform=transform, ctx=self._ctx, Vs=Vs, Ws=Ws, sigma2=sigma2, device=self._ctx.device)
+
     def run_gibbs(self, data, nburn=1000, nthin=1, nsamples=1000, verbose=True, print_freq=100, callback=None, **kwargs):
         """genlasso.py:37-66, the result dict gathered as before.  A gamma_grid model with rng="device" also keeps every
         kept state on the device (btf_collect: a device-to-device copy behind the sweep, nothing of the chain is touched),
@@ -1752,6 +1820,26 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
             i, f = np.unravel_index(np.argmax(np.where(np.isnan(viol), np.inf, viol)), viol.shape)
             raise ValueError("invalid starting point: w_%d . u_%d = %r is outside [0, 1] (row %d, feature %d is the worst pair)"
                              % (i, f, float(P[i, f]), i, f))
+
+    def _slice_fold_restrictions(self, row_features, R, results, S):
+        """The model's Constraints and Row_constraints, and - with row_features of the new rows - their codes and the
+        feature embeddings of every kept sample, results["U"] (S,F,K)."""
+        from . import slice_fold_in as _sf
+        if row_features is None:
+            return self._cons, self.Row_constraints, None, None
+        if self._X_codes is None:
+            raise ValueError("row_features: the model was built without row features")
+        codes = _sf.feature_codes(row_features, R)
+        if codes.shape[1] != self.nfeatures:
+            raise ValueError("row_features must be (R, F) = (%d, %d), got %r" % (R, self.nfeatures, codes.shape))
+        Us = results.get("U") if isinstance(results, dict) else None
+        if Us is None:
+            raise ValueError("row_features needs the feature embeddings of every kept sample: results['U'] (S,F,K) - U is not "
+                             "collected on the device, pass the run_gibbs result dict as results=")
+        Us = _native.as_f64(Us)
+        if Us.shape != (S, self.nfeatures, self.nembeds):
+            raise ValueError("results: U must be (S,F,K) = (%d,%d,%d), got %r" % (S, self.nfeatures, self.nembeds, Us.shape))
+        return self._cons, self.Row_constraints, codes, Us
 
     @property
     def U(self):

@@ -337,6 +337,37 @@ def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summa
                             inner_sweeps=inner_sweeps, first_sample=first_sample, Vs=Vs, nu2=nu2, sigma2=sigma2, device=device)
 
 
+def slice_fold_in_rows(Y_new, Vs, family, sigma2=None, Ws=None, likelihood_param=None, Constraints=None, Row_constraints=None,
+                       row_features=None, Us=None, start=None, seed=0, draws=None, sweeps=None, max_rounds=40, summary=True,
+                       q=(5, 95), transform=None, first_sample=0, device=0):
+    """Embeddings of rows the chain never saw for a slice-sampled fit, one draw per kept sample, on the GPU, without a
+    model: the stateless form of NonconjugateBayesianTensorFiltering.slice_fold_in_rows (see there for the method, the
+    arguments and the outputs).
+
+    Vs (S,M,T,K); sigma2 one value per sample; family: a device likelihood name ("poisson", "poisson_identity",
+    "bernoulli_logit", "gaussian", "negbin_logit", "gamma_grid") with likelihood_param as the model class takes it.
+    Ws (S,N,K): the fitted rows, read for the default start (their mean per sample) only; start= replaces it.
+    Constraints (J,T+1) / Row_constraints (n,K+1) as ConstrainedNonconjugateBayesianTensorFiltering takes them;
+    row_features (R,F) of 0 / 1 / nan with Us (S,F,K).  Y_new=None with row_features: rows known by their features alone.
+    first_sample: the index of Vs[0] among the kept samples - with it a call over a slice of the samples returns the bits
+    of the whole call.  functionalmf_amd.slice_fold_in.chain is the definition in numpy.  There is no CPU fallback."""
+    from . import _analysis, slice_fold_in as _sf
+    _sf.family_code(family)
+    Ws, Vs = _analysis.check_states(Ws if start is None else None, Vs)
+    S, M, T, K = Vs.shape
+    param = _sf.check_param(family, likelihood_param)
+    codes = None if row_features is None else _sf.feature_codes(row_features)
+    R, S1, cnt, L = _sf.row_statistics(Y_new, family, M, T, R=None if codes is None else codes.shape[0])
+    _sf.check_args(family, param, S, R, K, start, draws, sweeps, max_rounds, summary, q, transform, first_sample, Us, codes,
+                   have_W=Ws is not None)
+    _sf.check_constraints(Constraints, Row_constraints, T, K)
+    sigma2 = _analysis.check_scalars("sigma2", sigma2, S)
+    return _sf.evaluate(family, param, S, R, M, T, K, S1, cnt, L, start=start, Constraints=Constraints,
+                        Row_constraints=Row_constraints, Us=Us, codes=codes, draws=draws, seed=seed, sweeps=sweeps,
+                        max_rounds=max_rounds, summary=summary, q=q, transform=transform, first_sample=first_sample, Vs=Vs, Ws=Ws,
+                        sigma2=sigma2, device=device)
+
+
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
 from .nmf import bounded_tensor_nmf, factor_pav, tensor_nmf  # noqa: E402,F401
 

@@ -721,6 +721,43 @@ int btf_collect_fold_in(btf_ctx* ctx, int family, int nsamples, int nrows_new, c
                         double* W_out, double* Wmean_out, int transform, const double* q, int nq, double* mean_out,
                         double* q_out);
 
+/* ---- folding new rows into a slice-sampled fit (csrc/btf_slice_fold.h) -----------------------------------------------
+ * The row prior of the slice-sampled models is N(0, sigma2 I) (factor.py:685-686) and, given V_s (and U_s), every
+ * restriction on a row is linear in w, so elliptical slice sampling (elliptical_slice.py:59-124, mu = 0) with the
+ * restrictions as a likelihood of minus infinity samples p(w_new | y_new, V_s, U_s): `sweeps` updates per (sample, row),
+ * each with at most max_rounds proposals (a sweep that uses them all keeps its state and is counted in unfinished_out),
+ * all of them in ONE launch.  family: the codes of btf_ess_* (0..5); param: the parameter of families 3 (1 / variance) and
+ * 4 (rate) as btf_set_likelihood_param takes it; shape / scale / prob (G): the gamma-grid table of family 5 as
+ * btf_set_likelihood_table takes it (NULL otherwise).  S1 / cnt (R,M,T): sum and number of the observed replicates of the
+ * cell (0, 0: missing), logsum (R,M,T): their sum of logs (family 5, NULL otherwise).  The chain of (s, r) starts at
+ * start[s][r] ((S,R,K), non-NULL) or at the mean of the nrows_fit rows of Ws[s] ((S,nrows_fit,K); start NULL).
+ * constraints (ncons, T+1): sum_t A[c,t] (w . v_jt) >= A[c,T] for every column j; row_constraints (nrow_cons, K+1):
+ * a . w >= a[K]; Us (S,F,K) with codes (R,F) of 0, 1, 2 = missing: 0 <= w . u_f <= 1 and the term
+ * sum_f x log(w . u_f) + (1 - x) log(1 - w . u_f) beside the likelihood (nfeatures 0: none).  draws
+ * (S,R,sweeps,K+1+max_rounds): per sweep the K normals, u_h, u_a and the shrink uniforms, or NULL: Philox keyed (seed,
+ * (sample0 + s) << 32 | r, sweep * (K+1+max_rounds) + position).  W_out (S,R,K): the last state of every chain;
+ * Wstart_out (S,R,K): its start; rounds_out (S,R): likelihood evaluations of proposals; unfinished_out (S,R).  mean_out
+ * non-NULL adds the summary stage as in btf_fold_in_rows.  A start that is infeasible or has a non-finite likelihood: that
+ * chain's W_out is nan, the call returns BTF_ESTATE, and btf_fail_index (ctx, or NULL after the stateless call) =
+ * (sample0 + s) * nrows_new + r of the first such pair.  fp64, no floating-point atomics, every sum in a fixed order: two
+ * calls return identical bits whatever the launch geometry and wherever the states come from.  btf_collect_slice_fold
+ * reads W, V and sigma2_s of the first nsamples collected slots without an upload, takes param / the table from the
+ * context (btf_set_likelihood_param / btf_set_likelihood_table) and touches none of the sampler's state.  Launches are
+ * counted under BTF_K_CRITERIA.  Synchronous.                                                                          */
+int btf_slice_fold_rows(int device, int family, double param, const double* shape, const double* scale, const double* prob, int G,
+                        int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs, const double* Ws,
+                        int nrows_fit, const double* start, const double* sigma2, const double* S1, const double* cnt,
+                        const double* logsum, const double* constraints, int ncons, const double* row_constraints, int nrow_cons,
+                        const double* Us, int nfeatures, const unsigned char* codes, const double* draws, unsigned long long seed,
+                        int sweeps, int max_rounds, long long sample0, double* W_out, double* Wstart_out, int* rounds_out,
+                        int* unfinished_out, int transform, const double* q, int nq, double* mean_out, double* q_out);
+int btf_collect_slice_fold(btf_ctx* ctx, int family, int nsamples, int nrows_new, const double* start, const double* S1,
+                           const double* cnt, const double* logsum, const double* constraints, int ncons,
+                           const double* row_constraints, int nrow_cons, const double* Us, int nfeatures,
+                           const unsigned char* codes, const double* draws, unsigned long long seed, int sweeps, int max_rounds,
+                           long long sample0, double* W_out, double* Wstart_out, int* rounds_out, int* unfinished_out,
+                           int transform, const double* q, int nq, double* mean_out, double* q_out);
+
 /* ---- convergence diagnostics (csrc/btf_diag.h) ----------------------------------------------------------------------
  * Split R-hat (rank-normalised, max of bulk and folded), bulk ESS, tail ESS (min over the 5 % / 95 % indicators), MCSE of
  * the mean and the mean, per cell of f(W V') over nchains chains of nsamples draws (Vehtari et al. 2021; one chain: its
