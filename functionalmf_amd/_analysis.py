@@ -227,7 +227,8 @@ class PosteriorAnalysis:
         n_curves, nsamples, loglik_per_sample (S,) and curves = {lppd, p_waic, mean_ll, ll_at_mean} of (N,M) arrays;
         pointwise=True adds loglik (S,N,M), the full matrix (S*N*M doubles of host memory; PSIS-LOO from it stays on the
         device: loo()).
-        A gamma_grid model is refused here (NotImplementedError): gamma_grid_criteria / gamma_grid_loo score it.
+        A gamma_grid model is refused here (NotImplementedError): gamma_grid_criteria / gamma_grid_loo score it; so is the
+        Negative-Binomial model with its sampled rate: negbin_criteria / negbin_loo.
         Device memory: the criteria statistics, 16 B per cell (functionalmf_amd/criteria.py), and 8 B per cell of scratch."""
         self._crit_check()
         S, Ws, Vs = self._samples(results)

@@ -20,7 +20,8 @@ UNITS = [(os.path.join(CSRC, "btf_%s.hip" % name), suffix) for name, suffix in [
     ("abi", "_abi.o"), ("analysis", "_analysis.o"), ("criteria", "_crit.o"), ("nmf", "_nmf.o"), ("gass_ep", "_gass_ep.o"),
     ("gamma_grid", "_gamma_grid.o"), ("diag", "_diag.o"), ("predict", "_predict.o"), ("functionals", "_functionals.o"),
     ("fold_in", "_fold_in.o"), ("loo", "_loo.o"), ("ranking", "_ranking.o"), ("assoc", "_assoc.o"), ("monotone", "_monotone.o"),
-    ("gg_criteria", "_gg_criteria.o"), ("gg_predict", "_gg_predict.o"), ("slice_fold", "_slice_fold.o")]]
+    ("gg_criteria", "_gg_criteria.o"), ("gg_predict", "_gg_predict.o"), ("slice_fold", "_slice_fold.o"),
+    ("nb_criteria", "_nb_criteria.o")]]
 SOURCES = [src for src, _ in UNITS]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
@@ -130,6 +131,9 @@ SIGNATURES = {
     "btf_crit_eval": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
     "btf_crit_loo": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp,
                                _c_dp]),
+    "btf_crit_set_counts": (C.c_int, [_ctx, C.c_int, _c_dp, C.c_int]),
+    "btf_nb_crit_eval": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "btf_nb_crit_loo": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
     "btf_predict_batch": (C.c_int, [C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_uint64, _c_dp]),
     "btf_predict_eval": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, C.c_int,
                                    C.c_uint64, _c_dp, C.c_int, _c_ip, C.c_int] + [_c_dp] * 11),

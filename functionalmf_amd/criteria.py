@@ -21,6 +21,10 @@ csrc/btf_criteria.h (btf_crit_eval).  This module holds the two host halves arou
                 csrc/btf_gg_criteria.h): its three per-cell statistics, and the written definition of what the kernel
                 computes - the host class, one sample at a time.
 
+  negbin_statistics() / negbin_rates() / negbin_loglik()  the same for the conjugate Negative-Binomial model, whose rate is
+                sampled (csrc/btf_nb_criteria.h): the statistics and raw counts of a slot, the (S + 1, extent) rate array
+                with R-bar appended, and the written definition by numpy / scipy.
+
 It deliberately does not read the sampler's accumulation layouts: those differ by model and data form.
 """
 import numpy as np
@@ -219,6 +223,124 @@ def gamma_grid_head(slot, nsamples, Ws=None, Vs=None):
     return (int(slot), FAMILY_GAMMA_GRID, 0.0, int(nsamples), _native.dptr(Ws), _native.dptr(Vs), None, 0)
 
 
+# ---- the conjugate Negative-Binomial model, whose rate R is sampled (csrc/btf_nb_criteria.h; btf_nb_crit_eval /
+# btf_nb_crit_loo).  Family 4 above has one known rate and folds lgamma(y+r) - lgamma(r) into the curve constant; here
+# that part depends on the sample and is the device's (nb_crit_const_kernel), c0 keeps - sum lgamma(y+1) only. ----
+FAMILY_NEGBIN_RATES = "negbin_rates"      # the slot-cache key of PosteriorAnalysis._crit_slot; not a family of btf_crit_eval
+
+
+def _rate_tensor(Rs, nsamples, shape):
+    """Rs as (S, n0, n1, n2) with every n full or 1, and the BTF_PRED_AUX_* flags (predictive.rate_layout's checks), every
+    rate finite and > 0."""
+    from . import predictive
+    flat, flags = predictive.rate_layout(Rs, nsamples, shape)
+    if not (np.isfinite(flat).all() and (flat > 0).all()):
+        raise ValueError("every Negative-Binomial rate must be finite and > 0")
+    from . import _native
+    tail = tuple(full if flags & bit else 1
+                 for full, bit in zip(shape, (_native.PRED_AUX_ROWS, _native.PRED_AUX_COLS, _native.PRED_AUX_DEPTH)))
+    return flat.reshape((nsamples,) + tail), flags
+
+
+def negbin_rates(Rs, nsamples, shape):
+    """The rate array of btf_nb_crit_eval / btf_nb_crit_loo: (S + 1, extent) float64 - the S rate tensors and, as tensor S,
+    R-bar = np.mean(Rs, axis=0), the plug-in's rate - and its BTF_PRED_AUX_* axis flags.  Rs: what predictive.rate_layout
+    accepts, every rate finite and > 0 (ValueError)."""
+    R4, flags = _rate_tensor(Rs, nsamples, shape)
+    out = np.concatenate([R4, np.mean(R4, axis=0)[None]], axis=0)
+    return np.ascontiguousarray(out.reshape(nsamples + 1, -1), dtype=np.float64), flags
+
+
+def negbin_statistics(Y, shape):
+    """The statistics of a count tensor for the Negative-Binomial criteria kernels.  Y: (N,M,T) or (N,M,T,R), NaN = missing.
+    Returns (S1, cnt) as contiguous [M][T][N] arrays, c0 [N][M] = - sum lgamma(y+1) over the curve's observed counts, the
+    raw counts as a contiguous (N,M,T,R) array and the bool (N,M) mask of curves with an observation.  ValueError for an
+    observed y < 0 (or infinite)."""
+    if isinstance(Y, (tuple, list)):
+        raise ValueError("negative-binomial data is the count tensor itself, not a (Y, N) pair")
+    S1, cnt, c0, _, observed = statistics(FAMILY_POISSON_LOG, Y, shape)
+    Y = np.asarray(Y, dtype=float)
+    Y4 = np.ascontiguousarray(Y[..., None] if Y.ndim == 3 else Y, dtype=np.float64)
+    if np.any(Y4 < 0) or np.any(np.isinf(Y4)):            # (NaN compares False: missing replicates pass)
+        raise ValueError("the Negative-Binomial likelihood needs every observed y finite and >= 0")
+    return S1, cnt, c0, Y4, observed
+
+
+def negbin_loglik(Y, Ws, Vs, Rs):
+    """The written definition of the Negative-Binomial criteria kernels (csrc/btf_nb_criteria.h), by numpy / scipy.
+
+    Y: (N,M,T) / (N,M,T,R) counts, NaN = missing; Ws (S,N,K), Vs (S,M,T,K); Rs: (S,) + a shape that broadcasts against
+    (N,M,T) with every axis full or 1, or (S,) / (S,1) - what predictive.rate_layout accepts.
+    Returns (L (S,N,M), L_at_mean (N,M), observed (N,M)):
+        L[s,i,j] = sum over observed (t,r) of scipy.stats.nbinom.logpmf(y_ijtr, R_s[i,j,t], 1 - ilogit(w_i^s . v_jt^s))
+                 = sum lgamma(y+R) - lgamma(R) - lgamma(y+1) + y eta - (y+R) softplus(eta),
+    the linear predictor eta not clipped (as family 4 and the predictive sampler); L_at_mean the same at
+    Mu-bar = mean_s W_s V_s' and R-bar = mean_s R_s elementwise (the analogue of the Gaussian plug-in's mean nu2); both 0
+    on curves without observations.  from_loglik(L, observed, L_at_mean) gives the criteria dictionary, psis_loo_host the
+    PSIS-LOO one.  ValueError for an observed y < 0, a rate <= 0 or not finite, a rate array whose leading dimension is
+    not S."""
+    from scipy.special import gammaln
+    Ws, Vs = np.asarray(Ws, dtype=float), np.asarray(Vs, dtype=float)
+    Y = np.asarray(Y, dtype=float)
+    if Y.ndim not in (3, 4):
+        raise AssertionError('Observations must be 3- or 4-tensor.')
+    Y4 = Y[..., None] if Y.ndim == 3 else Y
+    if Ws.ndim != 3 or Vs.ndim != 4 or Ws.shape[::2] != Vs.shape[::3] or Y4.shape[:3] != (Ws.shape[1],) + Vs.shape[1:3]:
+        raise ValueError("Ws must be (S,N,K), Vs (S,M,T,K) and Y (N,M,T[,R]), got %r / %r / %r" % (Ws.shape, Vs.shape, Y.shape))
+    S = Ws.shape[0]
+    R4, _ = _rate_tensor(Rs, S, Y4.shape[:3])
+    obs4 = ~np.isnan(Y4)
+    y = np.where(obs4, Y4, 0.0)
+    if np.any(y < 0) or np.any(np.isinf(y)):
+        raise ValueError("the Negative-Binomial likelihood needs every observed y finite and >= 0")
+    observed = obs4.any(axis=(2, 3))
+
+    def curves(eta, R):
+        r, e = R[..., None], eta[..., None]
+        ll = gammaln(y + r) - gammaln(r) - gammaln(y + 1.0) + y * e - (y + r) * np.logaddexp(0.0, e)
+        return np.where(obs4, ll, 0.0).sum(axis=(2, 3))
+
+    L = np.zeros((S,) + observed.shape)
+    mu = np.zeros(Y4.shape[:3])
+    for s in range(S):
+        eta = np.einsum("nk,mtk->nmt", Ws[s], Vs[s])
+        mu += eta
+        L[s] = curves(eta, R4[s])
+    L_at_mean = curves(mu / S, np.mean(R4, axis=0))
+    return L, L_at_mean, observed
+
+
+def negbin_upload(ctx, slot, Y, shape):
+    """The Negative-Binomial statistics and raw counts of Y into criteria slot `slot` of `ctx` (a _native.Context); returns
+    the observed-curve mask."""
+    from . import _native
+    S1, cnt, c0, Y4, obs = negbin_statistics(Y, shape)
+    zero = np.zeros(tuple(shape)[:2])
+    ctx.call("btf_crit_set_data", int(slot), _native.dptr(S1), _native.dptr(cnt), _native.dptr(c0), _native.dptr(zero))
+    ctx.call("btf_crit_set_counts", int(slot), _native.dptr(Y4), int(Y4.shape[3]))
+    return obs
+
+
+def negbin_head(slot, nsamples, Ws, Vs, rates, flags):
+    """The arguments btf_nb_crit_eval and btf_nb_crit_loo share: slot, nsamples, Ws, Vs (None: the context's current
+    state), the (S + 1, extent) rates of negbin_rates and their axis flags."""
+    from . import _native
+    Ws = None if Ws is None else _native.as_f64(Ws)
+    Vs = None if Vs is None else _native.as_f64(Vs)
+    return (int(slot), int(nsamples), _native.dptr(Ws), _native.dptr(Vs), _native.dptr(rates), int(flags))
+
+
+def negbin_evaluate(ctx, head, shape, pointwise=False, current=False):
+    """btf_nb_crit_eval on `ctx`; head: negbin_head's; shape (N,M).  Returns what evaluate() does."""
+    from . import _native
+    S = head[1]
+    curve = np.zeros((CURVE_OUTPUTS,) + tuple(shape))
+    totals = np.zeros(S)
+    pw = np.zeros((S,) + tuple(shape)) if pointwise else None
+    ctx.call("btf_nb_crit_eval", *head, _native.CRIT_CURRENT if current else 0, _native.dptr(curve), _native.dptr(totals), _native.dptr(pw))
+    return curve, totals, pw
+
+
 # ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-curve-out (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson,
 # Gelman, Yao, Gabry 2024).  psis_loo_host is the definition; the kernel of csrc/btf_loo.h implements the same steps. ----
 LOO_MAX_SAMPLES = 4096    # LOO_MAX_S of csrc/btf_loo.h (the bound of btf_diag_eval)
@@ -338,16 +460,18 @@ def loo_combine(elpd_loo, pareto_k, lppd, observed, nsamples, mean=None, log_wei
     return out
 
 
-def loo_evaluate(ctx, head, shape, observed, r_eff=None, transform=0, mean=False, log_weights=False):
+def loo_evaluate(ctx, head, shape, observed, r_eff=None, transform=0, mean=False, log_weights=False, negbin=False):
     """btf_crit_loo on `ctx` (a _native.Context) and the dictionary of BayesianTensorFiltering.loo().  head: as evaluate();
-    shape (N,M,T); r_eff: None or a contiguous (N,M) array; transform: the code of the leave-curve-out mean."""
+    shape (N,M,T); r_eff: None or a contiguous (N,M) array; transform: the code of the leave-curve-out mean.
+    negbin: btf_nb_crit_loo, with negbin_head's head."""
     from . import _native
     N, M, T = shape
-    S = head[3]
+    S = head[1] if negbin else head[3]
     out = np.zeros((4, N, M))
     mean_out = np.zeros((N, M, T)) if mean else None
     lw = np.zeros((S, N, M)) if log_weights else None
-    ctx.call("btf_crit_loo", *head, _native.dptr(r_eff), int(transform), _native.dptr(out), _native.dptr(mean_out), _native.dptr(lw))
+    ctx.call("btf_nb_crit_loo" if negbin else "btf_crit_loo", *head, _native.dptr(r_eff), int(transform), _native.dptr(out),
+             _native.dptr(mean_out), _native.dptr(lw))
     with np.errstate(divide="ignore", invalid="ignore"):
         lppd = out[3] + np.log(out[2]) - np.log(S)            # (as combine forms it: the same bits)
     return loo_combine(out[0], out[1], lppd, observed, S, mean=mean_out, log_weights=lw)

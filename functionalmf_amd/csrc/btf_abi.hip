@@ -825,7 +825,7 @@ void btf_destroy(btf_ctx* c) {
   for (void* p : {(void*)c->nb_data, (void*)c->nb_S, (void*)c->nb_cnt, (void*)c->nb_R, (void*)c->nb_C, (void*)c->nb_tmp, (void*)c->nb_out, (void*)c->nb_H, (void*)c->nb_Hd, (void*)c->nb_Hs, (void*)c->nb_G, (void*)c->nb_L, (void*)c->nb_optr, (void*)c->nb_oval, (void*)c->fill_tab, (void*)c->C8_wT, (void*)c->C8_v, (void*)c->smp_W, (void*)c->smp_V, (void*)c->smp_T, (void*)c->smp_s})
     if (p) (void)hipFree(p);
   for (int sl = 0; sl < 2; ++sl)
-    for (void* p : {(void*)c->crit_S1[sl], (void*)c->crit_cnt[sl], (void*)c->crit_c0[sl], (void*)c->crit_c1[sl], (void*)c->crit_L[sl]})
+    for (void* p : {(void*)c->crit_S1[sl], (void*)c->crit_cnt[sl], (void*)c->crit_c0[sl], (void*)c->crit_c1[sl], (void*)c->crit_L[sl], (void*)c->crit_Y[sl]})
       if (p) (void)hipFree(p);
   if (c->hyp) (void)hipFree(c->hyp);
   if (c->fz_words) (void)hipFree(c->fz_words);

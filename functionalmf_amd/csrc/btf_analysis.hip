@@ -4,6 +4,7 @@
 #include "btf_diag.h"           // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
 #include "btf_gg_criteria.h"    // the same for the gamma-grid likelihood (kernels in btf_gg_criteria.hip)
+#include "btf_nb_criteria.h"    // the same for the Negative-Binomial model's sampled rate (kernels in btf_nb_criteria.hip)
 #include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_gg_predict.h"     // the same for the gamma-grid likelihood (kernels in btf_gg_predict.hip)
@@ -17,6 +18,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -150,6 +152,7 @@ int btf_crit_set_data(btf_ctx* c, int slot, const double* S1, const double* cnt,
   HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old statistics)
   double** bufs[4] = {&c->crit_S1[slot], &c->crit_cnt[slot], &c->crit_c0[slot], &c->crit_c1[slot]};
   if (c->crit_L[slot]) { (void)hipFree(c->crit_L[slot]); c->crit_L[slot] = nullptr; }      // (the old data's log sums)
+  if (c->crit_Y[slot]) { (void)hipFree(c->crit_Y[slot]); c->crit_Y[slot] = nullptr; c->crit_nreps[slot] = 0; }   // (and raw counts)
   if (!S1 && !cnt && !curve_c0 && !curve_c1) {       // free the slot
     for (double** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
     return BTF_OK;
@@ -185,7 +188,38 @@ int btf_crit_set_logsum(btf_ctx* c, int slot, const double* L) {
   return BTF_OK;
 }
 
+int btf_crit_set_counts(btf_ctx* c, int slot, const double* Y, int nreps) {
+  if (!c || slot < 0 || slot > 1) return fail(c, BTF_EINVAL, "criteria slot must be 0 or 1");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // (a criteria call still reading the old counts)
+  if (!Y) {
+    if (c->crit_Y[slot]) (void)hipFree(c->crit_Y[slot]);
+    c->crit_Y[slot] = nullptr; c->crit_nreps[slot] = 0;
+    return BTF_OK;
+  }
+  if (nreps < 1) return fail(c, BTF_EINVAL, "btf_crit_set_counts: nreps >= 1");
+  if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, "btf_crit_set_counts: no statistics in this slot (btf_crit_set_data first)");
+  // [N][M][T][nreps] -> [M][T * nreps][N]: one lane per row, so that the kernel's loads coalesce
+  const size_t N = (size_t)c->N, MF = (size_t)c->M * c->T * nreps;
+  std::vector<double> yt(N * MF);
+  for (size_t i = 0; i < N; ++i)
+    for (size_t f = 0; f < MF; ++f) {
+      const double y = Y[i * MF + f];
+      if (y < 0.0 || std::isinf(y)) return fail(c, BTF_EINVAL, "btf_crit_set_counts: an observed count must be finite and >= 0");
+      yt[f * N + i] = y;
+    }
+  int rc;
+  if ((rc = dev_alloc(c, &c->crit_Y[slot], yt.size()))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->crit_Y[slot], yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->crit_nreps[slot] = nreps;
+  return BTF_OK;
+}
+
 namespace {
+// the rates of a Negative-Binomial criteria call (btf_nb_crit_eval / btf_nb_crit_loo): (S + 1, extent) on the host
+struct NbIn { const double* rates; int aux_flags; };
+
 // families 0..4 of FAM_SWITCH, or the gamma-grid family of btf_gg_criteria.h
 bool crit_family_ok(int family) { return (family >= 0 && family < CRIT_FAM_COUNT) || family == CRIT_FAM_GAMMA_GRID; }
 
@@ -199,8 +233,10 @@ struct CritRun {
 
 // Checks the arguments that btf_crit_eval and btf_crit_loo share, uploads the states and queues crit_kernel (with
 // `reduce` also the plug-in and per-sample-total kernels) on the context's stream.  `who` names the caller in messages.
+// nb: the Negative-Binomial model's sampled rates (btf_nb_criteria.h) - family 4's term with the rate of every sample, the
+// constant kernel ahead of it; family / param / noise are then unused.
 int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
-             const double* noise, int flags, bool pointwise, bool reduce, CritRun& r) {
+             const double* noise, int flags, bool pointwise, bool reduce, CritRun& r, const NbIn* nb = nullptr) {
   if (!c->crit_S1[slot]) return fail(c, BTF_ESTATE, who + ": no statistics in this slot (btf_crit_set_data)");
   if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, who + " needs an unsharded context");
   const bool current = (flags & BTF_CRIT_CURRENT) != 0, per_sample = (flags & BTF_CRIT_NOISE_PER_SAMPLE) != 0;
@@ -209,9 +245,20 @@ int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double pa
   if (!Ws && !current && !has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, who);
   if (per_sample && family != CRIT_FAM_GAUSSIAN) return fail(c, BTF_EINVAL, "per-sample noise is the Gaussian family's");
   if (per_sample && !noise && (Ws || current)) return fail(c, BTF_EINVAL, "per-sample noise of uploaded / current states: pass `noise`");
-  if (!per_sample && (family == CRIT_FAM_GAUSSIAN || family == CRIT_FAM_NEGBIN) && !(param > 0.0))
+  if (!nb && !per_sample && (family == CRIT_FAM_GAUSSIAN || family == CRIT_FAM_NEGBIN) && !(param > 0.0))
     return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
-  const bool gamma_grid = family == CRIT_FAM_GAMMA_GRID;
+  const bool gamma_grid = !nb && family == CRIT_FAM_GAMMA_GRID;
+  NbRate rt{};
+  if (nb) {
+    if (!c->crit_Y[slot]) return fail(c, BTF_ESTATE, who + ": no counts in this slot (btf_crit_set_counts)");
+    const long long n0 = (nb->aux_flags & BTF_PRED_AUX_ROWS) ? c->N : 1, n1 = (nb->aux_flags & BTF_PRED_AUX_COLS) ? c->M : 1,
+                    n2 = (nb->aux_flags & BTF_PRED_AUX_DEPTH) ? c->T : 1;
+    rt.ext = n0 * n1 * n2; rt.sr2 = n2 > 1 ? 1 : 0; rt.sr1 = n1 > 1 ? n2 : 0; rt.sr0 = n0 > 1 ? n1 * n2 : 0;
+    const size_t nr = (size_t)(nsamples + 1) * (size_t)rt.ext;
+    for (size_t q = 0; q < nr; ++q)
+      if (!(nb->rates[q] > 0.0) || !std::isfinite(nb->rates[q]))
+        return fail(c, BTF_EINVAL, who + ": every rate must be finite and > 0 (sample " + std::to_string(q / (size_t)rt.ext) + ")");
+  }
   if (gamma_grid && (!c->gg_tab || !c->crit_L[slot]))
     return fail(c, BTF_ESTATE, who + ": the gamma-grid family needs its table (btf_set_likelihood_table) and the slot's L (btf_crit_set_logsum)");
   HIPCHK(c, hipSetDevice(c->dev));
@@ -229,14 +276,45 @@ int crit_run(btf_ctx* c, const std::string& who, int slot, int family, double pa
   a.tot_part = s.alloc<double>((size_t)S * nwg); r.tot = s.alloc<double>((size_t)S);
   if (pointwise) a.pw = s.alloc<double>((size_t)S * NM);
   const GgTab gt{c->crit_L[slot], c->gg_tab, c->gg_G, c->gg_lsp};
-  if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_fn(K), grid, dim3(GGC_WAVES * WAVE), 0, a, gt);
+  const double* nbC = nullptr;      // [S + 1][M][N]: the per-sample curve constants
+  const bool nb_rows = rt.sr0 != 0;
+  if (nb) {
+    rt.R = s.upload(nb->rates, (size_t)(S + 1) * (size_t)rt.ext);
+    NbConstArgs ca{c->crit_Y[slot], c->crit_nreps[slot], S + 1, N, M, T, rt, s.alloc<double>((size_t)(S + 1) * NM)};
+    nbC = ca.C;
+    // one rate per (sample, column): the table form (an A/B switch for measurements: BTF_NB_CRIT_TABLE=0)
+    static const bool tab_ok = [] { const char* e = std::getenv("BTF_NB_CRIT_TABLE"); return !e || std::atoi(e) != 0; }();
+    const bool tabbed = tab_ok && rt.sr0 == 0 && rt.sr2 == 0;
+    launch_counted(s, BTF_K_CRITERIA, tabbed ? nb_crit_const_tab_fn() : nb_crit_const_fn(nb_rows), grid, dim3(CRIT_WAVES * WAVE), 0, ca);
+    launch_counted(s, BTF_K_CRITERIA, nb_crit_fn(K, nb_rows), grid, dim3(CRIT_WAVES * WAVE), 0, a, rt, nbC);
+  }
+  else if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_fn(K), grid, dim3(GGC_WAVES * WAVE), 0, a, gt);
   else K_SWITCH(K, FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_kernel<KT, FT>, grid, dim3(CRIT_WAVES * WAVE), 0, a)));
   if (reduce) {
-    if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_plugin_fn(), grid, dim3(WAVE), 0, a, gt);
+    if (nb) launch_counted(s, BTF_K_CRITERIA, nb_crit_plugin_fn(nb_rows), grid, dim3(WAVE), 0, a, rt, nbC);
+    else if (gamma_grid) launch_counted(s, BTF_K_CRITERIA, gg_crit_plugin_fn(), grid, dim3(WAVE), 0, a, gt);
     else FAM_SWITCH(family, launch_counted(s, BTF_K_CRITERIA, crit_plugin_kernel<FT>, grid, dim3(WAVE), 0, a));
     launch_counted(s, BTF_K_CRITERIA, crit_total_kernel, dim3((S + 255) / 256), dim3(256), 0, (const double*)a.tot_part, S, nwg, r.tot);
   }
   return s.rc();
+}
+}  // namespace
+
+namespace {
+// btf_crit_eval and btf_nb_crit_eval (nb: its rates) after their argument checks
+int crit_eval_run(btf_ctx* c, const char* who, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                  const double* noise, int flags, double* curve_out, double* total_out, double* pointwise_out, const NbIn* nb) {
+  CritRun r(c);
+  int rc = crit_run(c, who, slot, family, param, nsamples, Ws, Vs, noise, flags, pointwise_out != nullptr, true, r, nb);
+  if (rc) return rc;
+  const size_t S = (size_t)nsamples, NM = (size_t)c->N * c->M;
+  r.s.download(curve_out, r.a.curve, CRIT_OUT * NM);
+  r.s.download(total_out, r.tot, S);
+  r.s.download(pointwise_out, r.a.pw, S * NM);
+  return r.s.finish();        // (not check_status: the sampler's status word is not this call's)
+}
+bool nb_flags_ok(int aux_flags) {
+  return !(aux_flags & ~(BTF_PRED_AUX_PER_SAMPLE | BTF_PRED_AUX_ROWS | BTF_PRED_AUX_COLS | BTF_PRED_AUX_DEPTH));
 }
 }  // namespace
 
@@ -245,25 +323,27 @@ int btf_crit_eval(btf_ctx* c, int slot, int family, double param, int nsamples, 
   if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !curve_out || !total_out ||
       (flags & ~(BTF_CRIT_NOISE_PER_SAMPLE | BTF_CRIT_CURRENT)) || (!Ws) != (!Vs))
     return fail(c, BTF_EINVAL, "bad btf_crit_eval arguments");
-  CritRun r(c);
-  int rc = crit_run(c, "btf_crit_eval", slot, family, param, nsamples, Ws, Vs, noise, flags, pointwise_out != nullptr, true, r);
-  if (rc) return rc;
-  const size_t S = (size_t)nsamples, NM = (size_t)c->N * c->M;
-  r.s.download(curve_out, r.a.curve, CRIT_OUT * NM);
-  r.s.download(total_out, r.tot, S);
-  r.s.download(pointwise_out, r.a.pw, S * NM);
-  return r.s.finish();        // (not check_status: the sampler's status word is not this call's)
+  return crit_eval_run(c, "btf_crit_eval", slot, family, param, nsamples, Ws, Vs, noise, flags, curve_out, total_out, pointwise_out, nullptr);
+}
+
+int btf_nb_crit_eval(btf_ctx* c, int slot, int nsamples, const double* Ws, const double* Vs, const double* rates, int aux_flags,
+                     int flags, double* curve_out, double* total_out, double* pointwise_out) {
+  if (!c || slot < 0 || slot > 1 || nsamples < 1 || !curve_out || !total_out || !rates || !nb_flags_ok(aux_flags) ||
+      (flags & ~BTF_CRIT_CURRENT) || (!Ws) != (!Vs))
+    return fail(c, BTF_EINVAL, "bad btf_nb_crit_eval arguments");
+  const NbIn nb{rates, aux_flags};
+  return crit_eval_run(c, "btf_nb_crit_eval", slot, CRIT_FAM_NEGBIN, 0.0, nsamples, Ws, Vs, nullptr, flags, curve_out, total_out,
+                       pointwise_out, &nb);
 }
 
 // ---------------------------------------------------------- PSIS-LOO (btf_loo.h)
-int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
-                 const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
-                 double* logw_out) {
-  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !loo_out ||
-      (flags & ~BTF_CRIT_NOISE_PER_SAMPLE) || (!Ws) != (!Vs) || transform < 0 || transform > 2)
-    return fail(c, BTF_EINVAL, "bad btf_crit_loo arguments");
+namespace {
+// btf_crit_loo and btf_nb_crit_loo (nb: its rates) after their argument checks, under the name `who`
+int crit_loo_run(btf_ctx* c, const std::string& who, int slot, int family, double param, int nsamples, const double* Ws,
+                 const double* Vs, const double* noise, int flags, const double* r_eff, int transform, double* loo_out,
+                 double* mean_out, double* logw_out, const NbIn* nb) {
   if (nsamples > LOO_MAX_S)
-    return fail(c, BTF_EINVAL, "btf_crit_loo: " + std::to_string(nsamples) + " samples, at most " + std::to_string(LOO_MAX_S));
+    return fail(c, BTF_EINVAL, who + ": " + std::to_string(nsamples) + " samples, at most " + std::to_string(LOO_MAX_S));
   const int S = nsamples, N = c->N, M = c->M, T = c->T;
   const size_t NM = (size_t)N * M;
   // the tail length Mt = min(floor(0.2 S), ceil(3 sqrt(S / r_eff))) of every curve, on the host: IEEE sqrt and division
@@ -273,12 +353,12 @@ int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, c
     mt.resize(NM);
     for (size_t o = 0; o < NM; ++o) {
       if (!(r_eff[o] > 0.0) || !std::isfinite(r_eff[o]))
-        return fail(c, BTF_EINVAL, "btf_crit_loo: r_eff must be finite and > 0 (curve " + std::to_string(o) + ")");
+        return fail(c, BTF_EINVAL, who + ": r_eff must be finite and > 0 (curve " + std::to_string(o) + ")");
       mt[o] = tail(r_eff[o]);
     }
   }
   CritRun r(c);
-  int rc = crit_run(c, "btf_crit_loo", slot, family, param, nsamples, Ws, Vs, noise, flags, true, false, r);
+  int rc = crit_run(c, who, slot, family, param, nsamples, Ws, Vs, noise, flags, true, false, r, nb);
   if (rc) return rc;
   Scratch& s = r.s;
   double* dloo = s.alloc<double>(2 * NM);
@@ -302,6 +382,27 @@ int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, c
   s.download(loo_out + 2 * NM, r.a.curve, 2 * NM);
   s.download(logw_out, r.a.pw, (size_t)S * NM);
   return s.finish();
+}
+}  // namespace
+
+int btf_crit_loo(btf_ctx* c, int slot, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                 const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
+                 double* logw_out) {
+  if (!c || slot < 0 || slot > 1 || !crit_family_ok(family) || nsamples < 1 || !loo_out ||
+      (flags & ~BTF_CRIT_NOISE_PER_SAMPLE) || (!Ws) != (!Vs) || transform < 0 || transform > 2)
+    return fail(c, BTF_EINVAL, "bad btf_crit_loo arguments");
+  return crit_loo_run(c, "btf_crit_loo", slot, family, param, nsamples, Ws, Vs, noise, flags, r_eff, transform, loo_out, mean_out,
+                      logw_out, nullptr);
+}
+
+int btf_nb_crit_loo(btf_ctx* c, int slot, int nsamples, const double* Ws, const double* Vs, const double* rates, int aux_flags,
+                    const double* r_eff, int transform, double* loo_out, double* mean_out, double* logw_out) {
+  if (!c || slot < 0 || slot > 1 || nsamples < 1 || !loo_out || !rates || !nb_flags_ok(aux_flags) || (!Ws) != (!Vs) ||
+      transform < 0 || transform > 2)
+    return fail(c, BTF_EINVAL, "bad btf_nb_crit_loo arguments");
+  const NbIn nb{rates, aux_flags};
+  return crit_loo_run(c, "btf_nb_crit_loo", slot, CRIT_FAM_NEGBIN, 0.0, nsamples, Ws, Vs, nullptr, 0, r_eff, transform, loo_out,
+                      mean_out, logw_out, &nb);
 }
 
 // ---------------------------------------------------------- posterior predictive (btf_predict.h)

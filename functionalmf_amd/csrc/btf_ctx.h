@@ -125,6 +125,7 @@ struct btf_ctx {
   double* crit_S1[2] = {nullptr, nullptr}; double* crit_cnt[2] = {nullptr, nullptr};
   double* crit_c0[2] = {nullptr, nullptr}; double* crit_c1[2] = {nullptr, nullptr};
   double* crit_L[2] = {nullptr, nullptr};        // family 5: sum_r log y per cell (btf_crit_set_logsum)
+  double* crit_Y[2] = {nullptr, nullptr}; int crit_nreps[2] = {0, 0};   // Negative-Binomial: raw counts [M][T * nreps][N] (btf_crit_set_counts)
   int col_every = 0, col_slot = 0, col_count = 0;       // btf_collect_schedule: btf_gibbs_sweeps keeps every col_every-th state
   double* hyp = nullptr;        // device-resident scalars [HYP_COUNT] (nu2, sigma2, lam2, lam2_a, ...)
   bool dev_scalars = false;     // kernels read nu2 / sigma2 / lam2 from hyp instead of the host copies

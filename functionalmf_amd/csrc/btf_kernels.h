@@ -15,6 +15,7 @@
 #include "btf_device.h"
 #include "btf_eig.h"
 #include "btf_pg_exact.h"
+#include "btf_lgamma.h"
 
 namespace btf {
 
@@ -2906,41 +2907,8 @@ __device__ void sweep_lam_side(const LamSide& lm, double* red) {
 //   nb_trials_kernel: Binomial pseudo-data of the augmented model in both device layouts:
 //     trials N = S + cnt R, A = S - N/2 (S = sum of observed counts, cnt = number observed).
 // ============================================================================
-constexpr int NB_FAST_MAX = 32;    // integer counts up to here: product form when R varies inside a block
-constexpr int NB_TAB = 1024;       // integer counts below this: LDS table when R is constant inside a block
-
-// lgamma(x) for x >= NB_STIRLING_MIN by Stirling's series (truncation error < 1/(1188 x^9) = 4e-17 at x = 33)
-constexpr double NB_STIRLING_MIN = 33.0;
-__device__ __forceinline__ double lgamma_big(double x) {
-  const double ix = 1.0 / x, ix2 = ix * ix;
-  const double ser = ix * (8.3333333333333333e-2 + ix2 * (-2.7777777777777778e-3 + ix2 * (7.9365079365079365e-4 + ix2 * -5.9523809523809524e-4)));
-  return (x - 0.5) * log(x) - x + 0.91893853320467274178 + ser;
-}
-
-// lgamma(a) - lgamma(b) for a, b > 0 without libm's lgamma (which costs ~200 registers): both arguments
-// are shifted up by the same n until Stirling applies,
-//   lgamma(a) - lgamma(b) = lgamma_big(a+n) - lgamma_big(b+n) - log( prod_{k<n}(a+k) / prod_{k<n}(b+k) ).
-__device__ inline double lgamma_diff(double a, double b) {
-  const double lo = fmin(a, b);
-  if (lo >= NB_STIRLING_MIN) return lgamma_big(a) - lgamma_big(b);
-  const int n = (int)ceil(NB_STIRLING_MIN - lo);                                   // <= 33
-  double pa = 1.0, pb = 1.0;
-  for (int k = 0; k < n; ++k) { pa *= a + k; pb *= b + k; }                        // < 66^33: no overflow
-  return lgamma_big(a + n) - lgamma_big(b + n) - log(pa / pb);
-}
-
-// count part of one replicate's term: lgamma(y+c) - lgamma(c) - lgamma(y+r) + lgamma(r);
-// base = lgamma(r) - lgamma(c) (NaN: not computed yet - filled on first use)
-__device__ inline double nb_count_part(double y, double r, double c, double& base) {
-  if (y >= 0.0 && y <= (double)NB_FAST_MAX && y == floor(y)) {   // = log prod_{k<y} (c+k)/(r+k)
-    double num = 1.0, den = 1.0;
-    const int n = (int)y;
-    for (int k = 0; k < n; ++k) { num *= c + k; den *= r + k; }
-    return log(num / den);
-  }
-  if (!(base == base)) base = lgamma_diff(r, c);
-  return lgamma_diff(y + c, y + r) + base;
-}
+// NB_FAST_MAX, NB_TAB, lgamma_big, lgamma_diff and nb_count_part (product form for small integer counts, Stirling above
+// NB_STIRLING_MIN): btf_lgamma.h, shared with the Negative-Binomial criteria.
 
 // table of sum_{k<y} log((c+k)/(r+k)), y = 0..NB_TAB-1, by all 256 threads of a block (4 entries each)
 // (ymax: entries above ymax + 1 are not needed by the caller - their logarithms are skipped)

@@ -1152,8 +1152,9 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
         self._rate_key = None
 
     def _crit_family(self):
-        raise NotImplementedError("model-selection criteria for the Negative-Binomial model: its lgamma(y + R) terms depend on "
-                                  "the sampled rate R at every observation (not supported yet)")
+        raise NotImplementedError("information_criteria / loo / logprob are not available for the Negative-Binomial model, whose "
+                                  "lgamma(y + R) terms depend on the sampled rate R at every observation: negbin_criteria / "
+                                  "negbin_loo / negbin_logprob score it")
 
     def _pred_family(self):
         return 4, None, True                  # Negative-Binomial, logit link; the rate R of every sample
@@ -1173,6 +1174,93 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
 
     def _rate_shape(self):
         return tuple(1 if i in self._shared else c for i, c in enumerate((self.nrows, self.ncols, self.ndepth)))
+
+    # ---- WAIC, DIC, PSIS-LOO with the sampled rate (csrc/btf_nb_criteria.h).  Under names of their own:
+    # information_criteria / loo / logprob keep refusing this model. ----
+    def _crit_upload(self, slot, family, data, param):
+        if family != _criteria.FAMILY_NEGBIN_RATES:
+            return super()._crit_upload(slot, family, data, param)
+        return _criteria.negbin_upload(self._ctx, slot, data, (self.nrows, self.ncols, self.ndepth))
+
+    def _nb_rates(self, R, nsamples):
+        """(S + 1, extent) rates with R-bar appended, and their axis flags; R None: the current rate for every sample."""
+        if R is None:
+            R = np.broadcast_to(np.asarray(self.R, dtype=float), self._rate_shape())
+            R = np.broadcast_to(R, (nsamples,) + R.shape)
+        return _criteria.negbin_rates(R, nsamples, (self.nrows, self.ncols, self.ndepth))
+
+    def _nb_head(self, what, results, data):
+        self._unsharded(what)
+        if results is None:
+            raise RuntimeError("no samples collected on the device (the Negative-Binomial model keeps its samples on the host), "
+                               "and no results given")
+        S, Ws, Vs = self._samples(results)
+        rates, flags = self._nb_rates(results["R"] if "R" in results else None, S)
+        slot, obs = self._crit_slot(data, _criteria.FAMILY_NEGBIN_RATES, None)
+        return _criteria.negbin_head(slot, S, Ws, Vs, rates, flags), obs
+
+    def negbin_criteria(self, results, data=None, pointwise=False):
+        """WAIC and DIC of the posterior samples under the Negative-Binomial likelihood with the SAMPLED rate, on the GPU:
+        the dictionary of information_criteria (see there for data, pointwise and every key), from the per-curve
+        log-likelihood of csrc/btf_nb_criteria.h.
+
+        results: a run_gibbs result dict with W (S,N,K), V (S,M,T,K) and R (S,) + the rate shape (`rdims`); without "R"
+            the current rate is used for every sample.  This model keeps no samples on the device: None is a RuntimeError.
+        ll_s(i,j) = sum over observed (t,r) of nbinom.logpmf(y, R_s[i,j,t], 1 - ilogit(w_i^s . v_jt^s)), the linear
+        predictor not clipped; the plug-in of the DIC is Mu-bar = mean_s W_s V_s' with R-bar = mean_s R_s.
+        criteria.negbin_loglik is the written definition.  criteria.compare(a, b) takes the result beside a Poisson fit's.
+        Device memory: 16 B per cell of statistics and 8 B per replicate of raw counts; for the call 8 B per cell and
+        8 (S+1) N M bytes (the per-sample curve constants).  Out of scope: fold_in_rows for this model (it needs the
+        non-integer-count Polya-Gamma sampler inside the fold-in kernel)."""
+        head, obs = self._nb_head("negbin_criteria", results, data)
+        curve, totals, pw = _criteria.negbin_evaluate(self._ctx, head, (self.nrows, self.ncols), pointwise)
+        return _criteria.combine(curve, totals, obs, pw)
+
+    def negbin_loo(self, results, data=None, r_eff=None, mean=False, transform=None, log_weights=False):
+        """PSIS-LOO under the Negative-Binomial likelihood with the sampled rate, on the GPU: the dictionary of loo() (see
+        there for every argument and key), the pointwise matrix of negbin_criteria handed to the PSIS kernels of
+        csrc/btf_loo.h where it lies.  `lppd` is negbin_criteria's, bit for bit.  results as negbin_criteria; S <= 4096.
+        Out of scope: fold_in_rows for this model."""
+        from ._analysis import check_loo_samples, check_r_eff, transform_code
+        self._unsharded("negbin_loo")
+        code = transform_code(transform)
+        shape = (self.nrows, self.ncols, self.ndepth)
+        r_eff = check_r_eff(r_eff, shape[:2])
+        if results is not None:
+            check_loo_samples(self._samples(results)[0], "negbin_loo")
+        head, obs = self._nb_head("negbin_loo", results, data)
+        return _criteria.loo_evaluate(self._ctx, head, shape, obs, r_eff=r_eff, transform=code, mean=mean, log_weights=log_weights,
+                                      negbin=True)
+
+    def negbin_logprob(self, data, reduce="sum", W=None, V=None, R=None):
+        """Normalised Negative-Binomial log-likelihood of `data` under the current state, or under W=, V=, R= (R: a rate
+        tensor of the model's rate shape, or a scalar): the criteria kernel with one sample.  reduce="sum": a float;
+        "curve": the (N,M) per-curve values (0 for curves without observations).  logprob keeps refusing this model."""
+        if reduce not in ("sum", "curve"):
+            raise ValueError("reduce must be 'sum' or 'curve'")
+        self._unsharded("negbin_logprob")
+        rates, flags = self._nb_rates(None if R is None else np.asarray(R, dtype=float)[None], 1)
+        current = W is None and V is None and not (self._W_host_new or self._V_host_new)
+        if not current:
+            if W is None:
+                self._pull_W()
+                W = self._W
+            if V is None:
+                self._pull_V()
+                V = self._V
+            W, V = np.asarray(W, dtype=float), np.asarray(V, dtype=float)
+            if W.shape != (self.nrows, self.nembeds) or V.shape != (self.ncols, self.ndepth, self.nembeds):
+                raise ValueError("W %r / V %r do not match the model" % (W.shape, V.shape))
+            W, V = W[None], V[None]
+        slot, obs = self._crit_slot(data, _criteria.FAMILY_NEGBIN_RATES, None)
+        head = _criteria.negbin_head(slot, 1, W, V, rates, flags)
+        curve, totals, _ = _criteria.negbin_evaluate(self._ctx, head, (self.nrows, self.ncols), current=current)
+        if reduce == "sum":
+            return float(totals[0])
+        return np.where(obs, curve[2], 0.0)
+
+    def _dic_score(self, results):
+        return self.negbin_criteria(results)["dic"]
 
     # R: host array, refreshed from the GPU when the device-side MH loop (rng="device") moved it
     @property

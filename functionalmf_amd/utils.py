@@ -180,6 +180,56 @@ def gamma_grid_loo(Ws, Vs, Y, likelihood, r_eff=None, mean=False, transform=None
         ctx.close()
 
 
+def _negbin_context(Ws, Vs, Rs, Y, device):
+    """A context for one model-free Negative-Binomial criteria call: the statistics and counts of Y in slot 0.  Returns
+    (ctx, head of btf_nb_crit_eval / btf_nb_crit_loo, (N,M,T), observed-curve mask); the caller closes ctx."""
+    from . import _analysis, _native, criteria
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    rates, flags = criteria.negbin_rates(Rs, S, shape)              # (bad rates raise before any device call)
+    ctx = _native.Context(N, shape[1], shape[2], K, 0, device=device)
+    try:
+        obs = criteria.negbin_upload(ctx, 0, Y, shape)
+    except Exception:
+        ctx.close()
+        raise
+    return ctx, criteria.negbin_head(0, S, Ws, Vs, rates, flags), shape, obs
+
+
+def negbin_criteria(Ws, Vs, Rs, Y, pointwise=False, device=0):
+    """WAIC and DIC of saved samples under the Negative-Binomial likelihood with a sampled rate on the GPU, without a
+    model: the stateless form of NegativeBinomialBayesianTensorFiltering.negbin_criteria (see there).
+
+    Ws (S,N,K), Vs (S,M,T,K); Rs (S,) + a shape broadcasting against (N,M,T) with every axis full or 1, or (S,);
+    Y (N,M,T) or (N,M,T,R) counts, NaN = missing.  Needs ndepth >= 2 (a context is opened for the call).  No CPU fallback."""
+    from . import criteria
+    ctx, head, shape, obs = _negbin_context(Ws, Vs, Rs, Y, device)
+    try:
+        curve, totals, pw = criteria.negbin_evaluate(ctx, head, shape[:2], pointwise)
+    finally:
+        ctx.close()
+    return criteria.combine(curve, totals, obs, pw)
+
+
+def negbin_loo(Ws, Vs, Rs, Y, r_eff=None, mean=False, transform=None, log_weights=False, device=0):
+    """PSIS-LOO of saved samples under the Negative-Binomial likelihood with a sampled rate on the GPU, without a model: the
+    stateless form of NegativeBinomialBayesianTensorFiltering.negbin_loo (see there and BayesianTensorFiltering.loo);
+    arguments as negbin_criteria.  S <= 4096."""
+    from . import _analysis, criteria
+    code = _analysis.transform_code(transform)
+    S, N = np.shape(Ws)[:2] if np.ndim(Ws) == 3 else (0, 0)
+    M = np.shape(Vs)[1] if np.ndim(Vs) == 4 else 0
+    r_eff = _analysis.check_r_eff(r_eff, (N, M))
+    _analysis.check_loo_samples(S, "negbin_loo")
+    ctx, head, shape, obs = _negbin_context(Ws, Vs, Rs, Y, device)
+    try:
+        return criteria.loo_evaluate(ctx, head, shape, obs, r_eff=r_eff, transform=code, mean=mean, log_weights=log_weights,
+                                     negbin=True)
+    finally:
+        ctx.close()
+
+
 def gamma_grid_predictive(Ws, Vs, likelihood, data=None, q=(2.5, 97.5), draws_per_sample=1, seed=0, cells=None, device=0):
     """Posterior predictive of the observations under the gamma-grid likelihood on the GPU, without a model: the stateless
     form of NonconjugateBayesianTensorFiltering.gamma_grid_predictive (see there, and posterior_predictive for the outputs),

@@ -839,6 +839,30 @@ int btf_crit_loo(btf_ctx* ctx, int slot, int family, double param, int nsamples,
                  const double* noise, int flags, const double* r_eff, int transform, double* loo_out, double* mean_out,
                  double* logw_out);
 
+/* ---- the same two for the conjugate Negative-Binomial model, whose rate R is SAMPLED (csrc/btf_nb_criteria.h) ------------
+ * Family 4 of btf_crit_eval has one known rate; here every kept sample s has a rate tensor R_s that is full or shared
+ * along each of rows, columns and depth, so lgamma(y + R_s) - lgamma(R_s) is summed per (sample, curve) by a kernel of its
+ * own from the raw counts.  Not a family of btf_crit_eval (family 6 there stays BTF_EINVAL).
+ * btf_crit_set_counts: the raw counts Y [N][M][T][nreps] (NaN = missing, otherwise finite and >= 0: BTF_EINVAL) of a
+ *   slot, after btf_crit_set_data on it (S1, cnt as there; curve_c0 = - sum lgamma(y+1), curve_c1 unused), else BTF_ESTATE.
+ *   NULL frees them; btf_crit_set_data on the slot, or freeing the slot, drops them.  8 nreps bytes per cell more on the
+ *   device.  Synchronises.
+ * btf_nb_crit_eval / btf_nb_crit_loo: slot, states and outputs as btf_crit_eval / btf_crit_loo (flags: BTF_CRIT_CURRENT
+ *   or 0).  rates: (nsamples + 1, extent) on the host, rate tensor nsamples being the plug-in's R-bar (the mean over the
+ *   samples); aux_flags: the BTF_PRED_AUX_ROWS / _COLS / _DEPTH bits of btf_predict_eval say along which axes the tensor
+ *   is full (extent = the product of those axes' lengths, C order; BTF_PRED_AUX_PER_SAMPLE is accepted and implied).
+ *   ll_s(i,j) = sum over observed (t,r) of lgamma(y+R) - lgamma(R) - lgamma(y+1) + y eta - (y+R) softplus(eta), eta not
+ *   clipped; a curve without observations counts exactly 0.  BTF_ESTATE without counts on the slot; BTF_EINVAL for a rate
+ *   that is not finite and > 0, and (btf_nb_crit_loo) nsamples > 4096.  Device scratch for the call's duration, beside
+ *   what btf_crit_eval / btf_crit_loo take: 8 (nsamples + 1) N M bytes (the per-sample curve constants) and the rates.
+ *   Counted under BTF_K_CRITERIA.  No floating-point atomics: two calls return identical bits.  Touches none of the
+ *   sampler's state.  Unsharded contexts.  Synchronises.                                                              */
+int btf_crit_set_counts(btf_ctx* ctx, int slot, const double* Y, int nreps);
+int btf_nb_crit_eval(btf_ctx* ctx, int slot, int nsamples, const double* Ws, const double* Vs, const double* rates, int aux_flags,
+                     int flags, double* curve_out, double* total_out, double* pointwise_out);
+int btf_nb_crit_loo(btf_ctx* ctx, int slot, int nsamples, const double* Ws, const double* Vs, const double* rates, int aux_flags,
+                    const double* r_eff, int transform, double* loo_out, double* mean_out, double* logw_out);
+
 /* ---- posterior predictive of the observations (flutrends/benchmark.py:60-75, :129-134; politics/benchmark.py:147-172) ----
  * Replicated observations y_rep ~ p(y | theta_s) for every cell and kept sample, reduced on the device to moments, order
  * statistics and comparisons with data (csrc/btf_predict.h); the (S,N,M,T) draws never leave the chip.  Touches none of
