@@ -7,8 +7,8 @@ and the feature modules (predictive.py, functionals.py, fold_in.py, diagnostics.
 the mixin BayesianTensorFiltering inherits its analysis methods from: each method refuses what it cannot do in a fixed order
 (`_unsharded`, the family hook of the model, its own arguments), resolves its samples in one place (`_samples`: the
 device-collected ones, or an uploaded run_gibbs result dict) and hands over to the `evaluate` of its feature module, the one
-caller of the C entry point.  The hooks that differ by likelihood (_crit_family, _pred_family, _pred_aux, _fold_family)
-stay with the models in factor.py.
+caller of the C entry point.  The hooks that differ by likelihood (_crit_family, _pred_family, _pred_aux, _fold_family,
+_fold_cols_family) stay with the models in factor.py.
 """
 import numpy as np
 
@@ -426,8 +426,8 @@ class PosteriorAnalysis:
         on the device-resident W and V (transform as posterior_summary; at most 16384 samples); nsamples.  out["W"] together
         with results["V"] goes straight into utils.posterior_summary, utils.posterior_predictive and
         utils.posterior_functionals.  The sampler's state is not touched: a chain continued after the call walks the same
-        path.  Unsharded models.  Folding in new COLUMNS is out of scope: it needs the horseshoe local scales of a column
-        nobody has sampled."""
+        path.  Unsharded models.  New COLUMNS are folded in by fold_in_cols, which samples the horseshoe local scales of
+        the new column in a short chain of its own."""
         from . import fold_in as _fold
         family = self._fold_family()
         self._unsharded("fold_in_rows")
@@ -444,6 +444,66 @@ class PosteriorAnalysis:
             seed = self._next_seed() if z is None else 0
         return _fold.evaluate(family, S, R, M, T, K, weights, sums, z=z, seed=seed, summary=summary, q=q, transform=transform,
                               inner_sweeps=inner_sweeps, ctx=self._ctx, Vs=Vs, nu2=nu2, sigma2=sigma2, device=self._ctx.device)
+
+    # ---- folding new columns in (functionalmf_amd/fold_in_cols.py, csrc/btf_fold_in_cols.h) ----
+    def fold_in_cols(self, Y_new, results=None, seed=None, draws=None, sweeps=None, summary=True, q=(5, 95), transform=None,
+                     trials=None, first_sample=0):
+        """Curves of columns the chain never saw (a new drug tested on a handful of the fitted cell lines) for every row,
+        with uncertainty, on the GPU (csrc/btf_fold_in_cols.h).  Given W the columns of V are conditionally independent
+        (factor.py:378), and given a kept sample's W_s, nu2_s and lam2_s the new column's curve and its horseshoe+ levels
+        form a small Gibbs chain: `sweeps` rounds (default: functionalmf_amd.fold_in_cols.DEFAULT_SWEEPS) of the
+        conditionals of _resample_V (factor.py:378-409) and _resample_Tau2 (factor.py:136-141) for that one column, from
+        the prior draw of the levels.  One chain per (kept sample, new column); its last state is a draw from
+        p(V_c | y_c, W_s, nu2_s, lam2_s) up to the chain's finite length.  As in fold_in_rows the new data does not inform
+        W or the hyper-parameters.  The Binomial model opens every round with Polya-Gamma draws from the current curve,
+        starting at v = 0 (factor.py:437-460).  functionalmf_amd.fold_in_cols.chain is the definition in numpy.
+
+        Y_new: (C,N,T) or (C,N,T,nreps), NaN = missing; Binomial: the (Y, N) pair, or Y with trials= (default 1), counts
+            up to 32.  A column with no observation at all is allowed: its chain is the prior's.
+        results: a run_gibbs result dict (W (S,N,K), lam2 one value per sample, Gaussian nu2 likewise), uploaded; None: the
+            samples the last device-collecting run_gibbs left on the device - no upload of W, and nu2_s, lam2_s are read
+            from the collected scalars.
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        draws: optional (S,C,4 nD + sweeps (T K + 4 nD)) variates replacing the device generator (Gaussian only), per chain
+            in the layout of fold_in_cols.chain (fold_in_cols.random_draws builds one).
+        first_sample: the index of the first sample among the kept ones - with it a call over a slice of the samples
+            returns the bits of the whole call.
+
+        Returns a dict: V (S,C,T,K) one draw per kept sample; V_mean (S,C,T,K) the last conditional means (Gaussian only);
+        Tau2 (S,C,nD) the last local scales; with summary=True, mean (N,C,T) and quantiles (len(q),N,C,T) of
+        f(w_i^s . v_ct^s) from the summary kernel on the device-resident W and new V (transform as posterior_summary; at
+        most 16384 samples); nsamples.  results["W"] together with out["V"] goes straight into utils.posterior_summary,
+        utils.posterior_predictive and utils.posterior_functionals.  The sampler's state is not touched: a chain continued
+        after the call walks the same path.  Unsharded models.  A band of Q beyond one workgroup's LDS
+        (fold_in_cols.lds_bytes > LDS_LIMIT) is refused with ValueError."""
+        from . import fold_in_cols as _fc
+        family = self._fold_cols_family()
+        self._unsharded("fold_in_cols")
+        N, T, K = self.nrows, self.ndepth, self.nembeds
+        C, weights, sums = _fc.column_statistics(Y_new, family, N, T, trials=trials)
+        S, Ws, _ = self._samples(results, need=("W", "V")) if results is None else self._fold_cols_W(results)
+        _fc.check_args(family, S, C, T, K, self.tf_order, draws, sweeps, summary, q, transform, first_sample)
+        nu2 = lam2 = None
+        if results is not None:
+            lam2 = check_scalars("results: lam2", results.get("lam2"), S)
+            if _fc.FAMILIES[family] == _fc.FAMILIES["gaussian"]:
+                nu2 = check_scalars("results: nu2", results.get("nu2"), S)
+        if seed is None:
+            seed = self._next_seed() if draws is None else 0
+        return _fc.evaluate(family, S, C, N, T, K, self.tf_order, weights, sums, draws=draws, seed=seed, sweeps=sweeps,
+                            summary=summary, q=q, transform=transform, first_sample=first_sample, stability=float(self.stability),
+                            ctx=self._ctx, Ws=Ws, nu2=nu2, lam2=lam2, device=self._ctx.device)
+
+    def _fold_cols_W(self, results):
+        """(S, Ws, None) of a result dict for fold_in_cols: W alone is needed, checked against the model."""
+        try:
+            Ws = _native.as_f64(results["W"])
+        except (KeyError, TypeError):
+            raise ValueError("results must be a run_gibbs result dict with W (S,N,K)")
+        if Ws.ndim != 3 or Ws.shape[0] < 1 or Ws.shape[1:] != (self.nrows, self.nembeds):
+            raise ValueError("results: Ws must be (S,%d,%d), got %r" % (self.nrows, self.nembeds, Ws.shape))
+        return Ws.shape[0], Ws, None
 
     def logprob(self, data, reduce="sum", **state):
         """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,

@@ -126,6 +126,18 @@ void stencil_csr(int T, int tf, const std::vector<double>& Delta, int nD, std::v
       ptr[t * D1 + d + 1] = (int)row.size();
     }
 }
+}  // namespace
+
+namespace btf {
+// the two above for btf_analysis.hip (fold_in_cols builds its penalty without a context)
+void penalty_stencil(int T, int tf, std::vector<double>& Delta, int& nD, std::vector<int>& ptr, std::vector<int>& row,
+                     std::vector<double>& coef) {
+  build_delta_dense(T, tf, Delta, nD);
+  stencil_csr(T, tf, Delta, nD, ptr, row, coef);
+}
+}  // namespace btf
+
+namespace {
 int build_stencil(btf_ctx* c) {
   const int T = c->T, tf = c->TF, D1 = tf + 2;
   std::vector<double> Delta;

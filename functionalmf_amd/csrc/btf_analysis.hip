@@ -1,5 +1,5 @@
 // The posterior analyses behind the C ABI (include/btf.h): summaries, criteria, PSIS-LOO, predictive, functionals, ranking,
-// association, monotone projection, fold-in (conjugate and slice-sampled), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
+// association, monotone projection, fold-in (rows: conjugate and slice-sampled; columns), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
 #include "btf_ctx.h"            // struct btf_ctx, fail, Scratch, launch_counted, K_SWITCH / FAM_SWITCH
 #include "btf_diag.h"           // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
@@ -14,6 +14,7 @@
 #include "btf_monotone.h"       // monotone projection of the posterior (kernel in btf_monotone.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_slice_fold.h"     // the same for the slice-sampled models (kernels in btf_slice_fold.hip)
+#include "btf_fold_in_cols.h"   // folding new columns in (kernel in btf_fold_in_cols.hip)
 
 #include <algorithm>
 #include <climits>
@@ -1245,6 +1246,178 @@ int btf_collect_slice_fold(btf_ctx* c, int family, int nsamples, int nrows_new, 
   Scratch s(c, c->stream); States st;
   if (int rc = resolve_pair(s, 0, "btf_collect_slice_fold", BTF_ESTATE, nsamples, 0, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
   return slice_fold_run(s, st.V, st.W, c->N, c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, c->gg_tab, c->gg_G, c->gg_lsp, f);
+}
+
+// ---------------------------------------------------------------- folding new columns in (btf_fold_in_cols.h)
+namespace {
+struct FoldCols {
+  int family, S, C, N, T, K, tf;
+  const double *count, *ysum, *trials, *draws;
+  unsigned long long seed;
+  int sweeps;
+  long long sample0;
+  double stability;
+  double *V_out, *Vmean_out, *Tau2_out;
+  int transform;
+  const double* q; int nq;
+  double *mean_out, *q_out;
+};
+
+// the penalty rows on the host: Delta, its CSR stencil, and every row as (first depth, tf + 2 coefficients from there on)
+struct FoldColsPenalty {
+  int nD = 0;
+  std::vector<double> Delta, coef, rcoef;
+  std::vector<int> ptr, row, rcol0;
+};
+
+// everything that can be refused without a device; fills the penalty
+int fold_cols_check(btf_ctx* c, const FoldCols& f, FoldColsPenalty& p) {
+  if (f.family < FOLDC_GAUSSIAN || f.family > FOLDC_BINOMIAL || f.S < 1 || f.C < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 ||
+      f.T < 2 || !f.ysum || !f.V_out || !f.Vmean_out || !f.Tau2_out || f.sample0 < 0 || f.nq < 0 ||
+      (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2 || !(f.stability > 0.0 && f.stability <= 1.0))
+    return fail(c, BTF_EINVAL, "bad fold_in_cols arguments");
+  if (f.family == FOLDC_GAUSSIAN && !f.count) return fail(c, BTF_EINVAL, "fold_in_cols: the Gaussian family needs count");
+  if (f.family == FOLDC_BINOMIAL && (!f.trials || f.draws))
+    return fail(c, BTF_EINVAL, "fold_in_cols: the Binomial family needs trials and takes no draws");
+  if (f.sweeps < 1 || (unsigned long long)f.sweeps >= FOLDC_PG_SLOT) return fail(c, BTF_EINVAL, "fold_in_cols: sweeps must be in 1..2^20 - 2");
+  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "fold_in_cols: the half bandwidth (tf_order + 1) nembeds must stay below 64");
+  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "fold_in_cols: the summary stage takes at most 16384 samples");
+  if ((double)(f.sample0 + f.S) * f.C >= 2147483647.0 || (double)f.C * f.N * f.T >= 2147483647.0 ||
+      (double)f.sweeps * f.N * f.T >= 9.0e15)
+    return fail(c, BTF_EINVAL, "fold_in_cols: (sample0 + nsamples) * ncols_new and ncols_new * nrows * ndepth must stay below 2^31");
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  penalty_stencil(f.T, f.tf, p.Delta, p.nD, p.ptr, p.row, p.coef);
+  const size_t lds = foldc_lds_bytes(f.T, f.K, f.tf, p.nD);
+  if (lds > FOLDC_LDS_LIMIT)
+    return fail(c, BTF_EINVAL, "fold_in_cols: the band of a column needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
+                                   std::to_string(FOLDC_LDS_LIMIT));
+  const int D1 = f.tf + 2;
+  p.rcol0.assign(p.nD, 0); p.rcoef.assign((size_t)p.nD * D1, 0.0);
+  for (int r = 0; r < p.nD; ++r) {
+    int lo = f.T, hi = -1;
+    for (int t = 0; t < f.T; ++t)
+      if (p.Delta[(size_t)r * f.T + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
+    if (hi < 0 || hi - lo >= D1) return fail(c, BTF_EINVAL, "fold_in_cols: penalty row wider than the band");
+    p.rcol0[r] = lo;
+    for (int t = lo; t <= hi; ++t) p.rcoef[(size_t)r * D1 + (t - lo)] = p.Delta[(size_t)r * f.T + t];
+  }
+  const size_t ncell = (size_t)f.C * f.N * f.T;
+  const double* cw = f.family == FOLDC_GAUSSIAN ? f.count : f.trials;
+  for (size_t e = 0; e < ncell; ++e) {
+    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(f.ysum[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, "fold_in_cols: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
+    if (f.family == FOLDC_BINOMIAL && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLDC_MAX_TRIALS))
+      return fail(c, BTF_EINVAL, "fold_in_cols: Binomial trial counts must be integers up to " + std::to_string(FOLDC_MAX_TRIALS));
+  }
+  if (f.draws) {
+    const size_t n = (size_t)f.T * f.K, per = n + 4 * (size_t)p.nD, L = 4 * (size_t)p.nD + (size_t)f.sweeps * per;
+    for (size_t ch = 0; ch < (size_t)f.S * f.C; ++ch) {
+      const double* d = f.draws + ch * L;
+      for (size_t e = 0; e < L; ++e) {
+        const bool normal = e >= 4 * (size_t)p.nD && (e - 4 * (size_t)p.nD) % per < n;
+        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)))
+          return fail(c, BTF_EINVAL, "fold_in_cols: draws must be finite, its gamma variates positive");
+      }
+    }
+  }
+  return BTF_OK;
+}
+
+// The launches on device states dW (S,N,K) and per-sample scalars on the device (noise null: the Binomial family).  The
+// scratch's context may be null (the stateless form).  The new V stays on the device between the chains and the summary.
+int fold_cols_run(Scratch& s, const double* dW, const double* dnoise, int nstride, const double* dlam, int lstride, const FoldCols& f,
+                  const FoldColsPenalty& p) {
+  btf_ctx* c = s.ctx();
+  const int S = f.S, C = f.C, N = f.N, T = f.T, K = f.K, nD = p.nD;
+  FoldColsKernel kern = fold_cols_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, "fold_in_cols: nembeds must be 1..10 and family 0..1");
+  // column statistics in the kernel's [column][depth][row] layout; Binomial: kappa = successes - trials / 2
+  const size_t ncell = (size_t)C * N * T;
+  std::vector<double> hc(ncell), hy(ncell);
+  const double* cw = f.family == FOLDC_GAUSSIAN ? f.count : f.trials;
+  for (int j = 0; j < C; ++j)
+    for (int i = 0; i < N; ++i)
+      for (int t = 0; t < T; ++t) {
+        const size_t src = ((size_t)j * N + i) * T + t, dst = ((size_t)j * T + t) * N + i;
+        const double cv = cw[src], yv = f.ysum[src];
+        hc[dst] = cv;
+        hy[dst] = f.family == FOLDC_BINOMIAL ? (cv > 0.0 ? yv - 0.5 * cv : 0.0) : (cv > 0.0 ? yv : 0.0);
+      }
+  const size_t nV = (size_t)S * C * T * K, nT = (size_t)S * C * nD;
+  const size_t L = 4 * (size_t)nD + (size_t)f.sweeps * ((size_t)T * K + 4 * (size_t)nD);
+  const int stat0[2] = {0, INT_MAX};
+  FoldColsArgs a = {};
+  a.W = dW; a.noise = dnoise; a.lam2 = dlam; a.nstride = nstride; a.lstride = lstride;
+  a.cnt = s.upload(hc.data(), ncell); a.ysum = s.upload(hy.data(), ncell);
+  if (f.draws) a.draws = s.upload(f.draws, (size_t)S * C * L);
+  a.rcol0 = s.upload(p.rcol0.data(), p.rcol0.size()); a.rcoef = s.upload(p.rcoef.data(), p.rcoef.size());
+  a.st_ptr = s.upload(p.ptr.data(), p.ptr.size());
+  a.st_row = s.upload(p.row.data(), p.row.size()); a.st_coef = s.upload(p.coef.data(), p.coef.size());
+  a.V = s.alloc<double>(nV); a.Vmean = s.alloc<double>(nV); a.Tau2 = s.alloc<double>(nT);
+  a.status = s.upload(stat0, 2);
+  a.seed = f.seed; a.sample0 = f.sample0; a.lo = f.stability; a.hi = 1.0 / f.stability;
+  a.S = S; a.C = C; a.N = N; a.T = T; a.tf = f.tf; a.nD = nD; a.sweeps = f.sweeps;
+  const size_t lds = foldc_lds_bytes(T, K, f.tf, nD);
+  allow_lds(s, kern, lds);
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3((unsigned)((size_t)S * C)), dim3(WAVE), lds, a);
+  // the summary stage reads the device-resident W (S,N,K) and the new V (S,C*T,K)
+  if (f.mean_out) summary_stage(s, dW, a.V, S, N, C * T, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
+  int stat[2] = {0, INT_MAX};
+  s.download(stat, a.status, 2);
+  s.download(f.V_out, a.V, nV);
+  s.download(f.Vmean_out, a.Vmean, nV);
+  s.download(f.Tau2_out, a.Tau2, nT);
+  const int rc = s.finish();
+  if (rc) return rc;
+  if (stat[0]) {
+    if (c) c->fail_index = stat[1];
+    g_fold_fail_index = stat[1];
+    return fail(c, BTF_ESTATE, "fold_in_cols: the precision of (sample, column) index " + std::to_string(stat[1]) +
+                                   " = sample * ncols_new + column is not positive definite (or W / nu2 / lam2 not finite); its outputs are nan");
+  }
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_fold_in_cols(int device, int family, int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order,
+                     const double* Ws, const double* noise, const double* lam2, const double* count, const double* ysum,
+                     const double* trials, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                     double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q, int nq,
+                     double* mean_out, double* q_out) {
+  const FoldCols f = {family, nsamples, ncols_new, nrows, ndepth, nembeds, tf_order, count, ysum, trials, draws, seed, sweeps, sample0,
+                      stability, V_out, Vmean_out, Tau2_out, transform, q, nq, mean_out, q_out};
+  g_fold_fail_index = -1;
+  if (!Ws || !lam2 || (family == FOLDC_GAUSSIAN && !noise)) return fail(nullptr, BTF_EINVAL, "bad fold_in_cols arguments");
+  FoldColsPenalty p;
+  if (int rc = fold_cols_check(nullptr, f, p)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(lam2[s] > 0.0 && lam2[s] < INFINITY) || (family == FOLDC_GAUSSIAN && !(noise[s] > 0.0 && noise[s] < INFINITY)))
+      return fail(nullptr, BTF_EINVAL, "fold_in_cols: nu2 and lam2 must be finite and positive");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dl = s.upload(lam2, (size_t)nsamples);
+  const double* dn = family == FOLDC_GAUSSIAN ? s.upload(noise, (size_t)nsamples) : nullptr;
+  return fold_cols_run(s, dW, dn, 1, dl, 1, f, p);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload): W from the sample slots, nu2_s and
+// lam2_s from the collected scalars
+int btf_collect_fold_in_cols(btf_ctx* c, int family, int nsamples, int ncols_new, const double* count, const double* ysum,
+                             const double* trials, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                             double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
+                             int nq, double* mean_out, double* q_out) {
+  if (!c) return fail(c, BTF_EINVAL, "bad fold_in_cols arguments");
+  const FoldCols f = {family, nsamples, ncols_new, c->N, c->T, c->K, c->TF, count, ysum, trials, draws, seed, sweeps, sample0,
+                      stability, V_out, Vmean_out, Tau2_out, transform, q, nq, mean_out, q_out};
+  FoldColsPenalty p;
+  if (int rc = fold_cols_check(c, f, p)) return rc;
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_collect_fold_in_cols needs an unsharded context");
+  if (!has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, "btf_collect_fold_in_cols");
+  HIPCHK(c, hipSetDevice(c->dev));
+  Scratch s(c, c->stream);
+  return fold_cols_run(s, c->smp_W, family == FOLDC_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT, c->smp_s + HYP_LAM2,
+                       (int)HYP_COUNT, f, p);
 }
 
 // ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)

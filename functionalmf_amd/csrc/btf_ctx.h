@@ -215,6 +215,9 @@ inline int dev_alloc(btf_ctx* c, T** p, size_t n) {
 
 void launch_summary(Scratch& s, const double* W, const double* V, int S, int rows, int MT, int K, int transform, const double* dq,
                     int nq, double* mean, double* quant);      // (btf_abi.hip, beside the kernel)
+// Delta (nD,T) dense, rebuilt from its definition, and the CSR of the Delta' Delta stencil per (t, d), d = 0..tf+1 (btf_abi.hip)
+void penalty_stencil(int T, int tf, std::vector<double>& Delta, int& nD, std::vector<int>& ptr, std::vector<int>& row,
+                     std::vector<double>& coef);
 // btf_fail_index(NULL): the failing (sample, row) of this thread's last stateless fold-in (btf_analysis.hip)
 int fold_fail_index();
 // the device of a stateless entry point

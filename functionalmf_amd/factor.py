@@ -688,6 +688,10 @@ class BayesianTensorFiltering(PosteriorAnalysis, _BayesianModel):
         """Family name of fold_in_rows for this model's likelihood."""
         raise NotImplementedError("%s: fold_in_rows needs a conjugate row conditional (Gaussian and Binomial models)" % type(self).__name__)
 
+    def _fold_cols_family(self):
+        """Family name of fold_in_cols for this model's likelihood."""
+        raise NotImplementedError("%s: fold_in_cols needs a conjugate column conditional (Gaussian and Binomial models)" % type(self).__name__)
+
     # ---- the two half-sweeps (device) ----------------------------------------------
     def _w_normals(self):
         if self.rng != "host":
@@ -855,6 +859,9 @@ class GaussianBayesianTensorFiltering(BayesianTensorFiltering):
         return _criteria.FAMILY_GAUSSIAN, None, True        # variance: the sampled nu2
 
     def _fold_family(self):
+        return "gaussian"
+
+    def _fold_cols_family(self):
         return "gaussian"
 
     def _upload(self, Y):
@@ -1101,6 +1108,9 @@ class BinomialBayesianTensorFiltering(GaussianBayesianTensorFiltering):
     def _fold_family(self):
         return "binomial"
 
+    def _fold_cols_family(self):
+        return "binomial"
+
     def _set_noise(self):
         if getattr(self, "_omega_host_new", False) and np.ndim(self._nu2) == 3:
             with np.errstate(divide='ignore'):
@@ -1162,6 +1172,10 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
     def _fold_family(self):
         raise NotImplementedError("fold_in_rows for the Negative-Binomial model: the pseudo-trial counts y + R of a new row depend "
                                   "on the sampled rate R (not supported yet)")
+
+    def _fold_cols_family(self):
+        raise NotImplementedError("fold_in_cols for the Negative-Binomial model: the pseudo-trial counts y + R of a new column depend "
+                                  "on the sampled rate R, which this call does not read (not supported yet)")
 
     def _pred_aux(self, results, nsamples):
         """The rate tensor of every sample: results['R'] (S,) + rate shape, else the current R for all of them."""
@@ -1551,6 +1565,10 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         raise NotImplementedError("%s: fold_in_rows needs a conjugate row conditional (Gaussian and Binomial models); "
                                   "slice_fold_in_rows folds rows into this model" % type(self).__name__)
 
+    def _fold_cols_family(self):
+        raise NotImplementedError("%s: fold_in_cols needs the conjugate column conditional of the Gaussian and Binomial models; "
+                                  "a slice-sampled column has no closed-form draw (not supported yet)" % type(self).__name__)
+
     def _slice_fold_restrictions(self, row_features, R, results, S):
         """(Constraints, Row_constraints, codes (R,F) or None, Us (S,F,K) or None) of a slice_fold_in_rows call."""
         if row_features is not None:
@@ -1591,7 +1609,8 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         device-resident W and V (transform as posterior_summary; at most 16384 samples); nsamples.  out["W"] together with
         results["V"] goes straight into utils.posterior_summary, posterior_functionals, posterior_ranking and
         gamma_grid_predictive.  The sampler's state is not touched.  Unsharded models, device likelihoods, nembeds <= 10.
-        The Negative-Binomial model (its rate is sampled) and new columns are out of scope."""
+        The Negative-Binomial model (its rate is sampled) is out of scope; new columns are folded in by fold_in_cols, for
+        the Gaussian and Binomial models only."""
         from . import slice_fold_in as _sf
         from ._analysis import check_scalars
         self._unsharded("slice_fold_in_rows")

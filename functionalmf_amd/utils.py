@@ -387,6 +387,37 @@ def fold_in_rows(Y_new, Vs, family, nu2=None, sigma2=None, seed=0, z=None, summa
                             inner_sweeps=inner_sweeps, first_sample=first_sample, Vs=Vs, nu2=nu2, sigma2=sigma2, device=device)
 
 
+def fold_in_cols(Y_new, Ws, family, nu2=None, lam2=None, tf_order=2, seed=0, draws=None, sweeps=None, summary=True, q=(5, 95),
+                 transform=None, trials=None, first_sample=0, stability=1e-6, device=0):
+    """Curves of columns the chain never saw, one short Gibbs chain per (kept sample, new column), on the GPU, without a
+    model: the stateless form of BayesianTensorFiltering.fold_in_cols (see there for the method and the outputs).
+
+    Ws (S,N,K); family "gaussian" (nu2 and lam2: one value per sample) or "binomial" (lam2); tf_order and stability as the
+    model was built with.  Y_new: (C,N,T) or (C,N,T,nreps) with NaN = missing; Binomial: a (Y, N) pair of (C,N,T) arrays,
+    or Y with trials= (default 1), counts up to 32.  draws: optional (S,C,4 nD + sweeps (T K + 4 nD)) variates in the place
+    of the device generator (Gaussian only).  first_sample: the index of Ws[0] among the kept samples - with it a call over
+    a slice of the samples returns the bits of the whole call.  Ws and out["V"] go straight into posterior_summary,
+    posterior_predictive and posterior_functionals.  functionalmf_amd.fold_in_cols.chain is the definition in numpy.
+    There is no CPU fallback."""
+    from . import _analysis, _native, fold_in_cols as _fc
+    code = _fc.family_code(family)
+    Ws = _native.as_f64(Ws)
+    if Ws.ndim != 3 or Ws.shape[0] < 1:
+        raise ValueError("Ws must be (S,N,K), got %r" % (Ws.shape,))
+    S, N, K = Ws.shape
+    Yshape = np.shape(Y_new[0] if isinstance(Y_new, (tuple, list)) and len(Y_new) else Y_new)
+    T = Yshape[2] if len(Yshape) >= 3 else -1
+    C, weights, sums = _fc.column_statistics(Y_new, family, N, T, trials=trials)
+    _fc.check_args(family, S, C, T, K, tf_order, draws, sweeps, summary, q, transform, first_sample)
+    lam2 = _analysis.check_scalars("lam2", lam2, S)
+    nu2 = _analysis.check_scalars("nu2", nu2, S) if code == _fc.FAMILIES["gaussian"] else None
+    if not 0 < float(stability) <= 1:
+        raise ValueError("stability must lie in (0, 1]")
+    return _fc.evaluate(family, S, C, N, T, K, tf_order, weights, sums, draws=draws, seed=seed, sweeps=sweeps, summary=summary,
+                        q=q, transform=transform, first_sample=first_sample, stability=stability, Ws=Ws, nu2=nu2, lam2=lam2,
+                        device=device)
+
+
 def slice_fold_in_rows(Y_new, Vs, family, sigma2=None, Ws=None, likelihood_param=None, Constraints=None, Row_constraints=None,
                        row_features=None, Us=None, start=None, seed=0, draws=None, sweeps=None, max_rounds=40, summary=True,
                        q=(5, 95), transform=None, first_sample=0, device=0):

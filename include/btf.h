@@ -758,6 +758,34 @@ int btf_collect_slice_fold(btf_ctx* ctx, int family, int nsamples, int nrows_new
                            long long sample0, double* W_out, double* Wstart_out, int* rounds_out, int* unfinished_out,
                            int transform, const double* q, int nq, double* mean_out, double* q_out);
 
+/* ---- folding new columns into a fitted posterior (csrc/btf_fold_in_cols.h) --------------------------------------------
+ * The curves of ncols_new columns the chain never saw, one short Gibbs chain per (kept sample s, new column c) over the
+ * column's curve v (T,K) and its horseshoe+ levels, given W_s, nu2_s and lam2_s: `sweeps` rounds of the conditionals of
+ * _resample_V for one column (factor.py:378-409) and of _resample_Tau2 for one column (factor.py:136-141) from the prior
+ * draw of the levels; functionalmf_amd/fold_in_cols.py (`chain`) is the definition.  family 0 (Gaussian: count, ysum
+ * (C,N,T) = observed replicates and their sum, noise (S,) = nu2_s) or 1 (Binomial: trials, ysum = successes (C,N,T),
+ * integer counts up to 32, 0 = missing; Polya-Gamma rounds from v = 0 as in btf_fold_in_rows).  Ws (S,N,K), lam2 (S,).
+ * draws (S,C,4 nD + sweeps (T K + 4 nD)), Gaussian only: every variate of every chain - the start's unit Gamma(1/2)
+ * variates (4,nD), then per sweep T K standard normals and (4,nD) unit gammas - or NULL: Philox keyed (seed,
+ * (sample0 + s) << 32 | c, slot, element), so splitting the samples over calls or folding columns one at a time returns
+ * identical bits.  stability: the clip of the level updates.  V_out, Vmean_out (S,C,T,K): the last state and the last
+ * conditional mean; Tau2_out (S,C,nD).  mean_out non-NULL adds the summary stage on the device-resident W and new V:
+ * mean (N,C,T) and q_out (nq,N,C,T) of f(w_i^s . v_ct^s) exactly as btf_posterior_summary (nsamples <= 16384 then).  The
+ * band of a column and its side arrays must fit one workgroup's LDS: BTF_EINVAL otherwise, before any device call.  A
+ * non-positive pivot: that chain's outputs are nan, the call returns BTF_ESTATE, and btf_fail_index (ctx, or NULL after
+ * the stateless call) = (sample0 + s) * ncols_new + c of the first such chain.  fp64, no floating-point atomics, every sum
+ * in a fixed order.  btf_collect_fold_in_cols reads W, nu2_s and lam2_s of the first nsamples collected slots without an
+ * upload and touches none of the sampler's state; its launches are counted under BTF_K_CRITERIA.  Synchronous.          */
+int btf_fold_in_cols(int device, int family, int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order,
+                     const double* Ws, const double* noise, const double* lam2, const double* count, const double* ysum,
+                     const double* trials, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                     double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q, int nq,
+                     double* mean_out, double* q_out);
+int btf_collect_fold_in_cols(btf_ctx* ctx, int family, int nsamples, int ncols_new, const double* count, const double* ysum,
+                             const double* trials, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                             double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
+                             int nq, double* mean_out, double* q_out);
+
 /* ---- convergence diagnostics (csrc/btf_diag.h) ----------------------------------------------------------------------
  * Split R-hat (rank-normalised, max of bulk and folded), bulk ESS, tail ESS (min over the 5 % / 95 % indicators), MCSE of
  * the mean and the mean, per cell of f(W V') over nchains chains of nsamples draws (Vehtari et al. 2021; one chain: its
