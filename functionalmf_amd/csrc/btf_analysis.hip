@@ -1,5 +1,5 @@
 // The posterior analyses behind the C ABI (include/btf.h): summaries, criteria, PSIS-LOO, predictive, functionals, ranking,
-// association, monotone projection, fold-in (rows: conjugate and slice-sampled; columns), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
+// association, monotone projection, fold-in (rows and columns: conjugate and slice-sampled), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
 #include "btf_ctx.h"            // struct btf_ctx, fail, Scratch, launch_counted, K_SWITCH / FAM_SWITCH
 #include "btf_diag.h"           // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
@@ -15,6 +15,7 @@
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_slice_fold.h"     // the same for the slice-sampled models (kernels in btf_slice_fold.hip)
 #include "btf_fold_in_cols.h"   // folding new columns in (kernel in btf_fold_in_cols.hip)
+#include "btf_slice_fold_cols.h"   // the same for the slice-sampled models (kernels in btf_slice_fold_cols.hip)
 
 #include <algorithm>
 #include <climits>
@@ -1421,6 +1422,244 @@ int btf_collect_fold_in_cols(btf_ctx* c, int family, int nsamples, int ncols_new
 }
 
 // ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)
+// ---------------------------------------------------------------- folding new columns into a slice-sampled fit (btf_slice_fold_cols.h)
+namespace {
+struct SliceFoldCols {
+  int family; double param;
+  int S, C, N, T, K, tf;
+  const double *start, *S1, *cnt, *L, *fa, *fb;
+  const double* cons; int J;
+  const double *tau2, *draws;
+  unsigned long long seed;
+  int sweeps, max_rounds;
+  long long sample0;
+  double stability;
+  double *V_out, *Vstart_out, *Tau2_out; int *rounds_out, *unf_out;
+  int transform;
+  const double* q; int nq;
+  double *mean_out, *q_out;
+};
+
+// everything that can be refused without a device; fills the penalty (its rows as fold_cols_check does)
+int slice_fold_cols_check(btf_ctx* c, const SliceFoldCols& f, FoldColsPenalty& p) {
+  if (f.family < 0 || f.family >= ESS_FAM_COUNT || f.S < 1 || f.C < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 || f.T < 2 ||
+      !f.S1 || !f.cnt || !f.fa || !f.fb || !f.V_out || !f.Tau2_out || !f.rounds_out || !f.unf_out || f.sample0 < 0 || f.nq < 0 ||
+      (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2 || f.J < 0 || (f.J > 0 && !f.cons) ||
+      !(f.stability > 0.0 && f.stability <= 1.0))
+    return fail(c, BTF_EINVAL, "bad slice_fold_cols arguments");
+  if (f.sweeps < 1 || f.sweeps >= (1 << 20) - 1 || f.max_rounds < 1 || f.max_rounds > 65536)
+    return fail(c, BTF_EINVAL, "slice_fold_cols: sweeps in 1..2^20 - 2 and max_rounds in 1..65536");
+  if (f.family == ESS_FAM_GAMMA_GRID && !f.L) return fail(c, BTF_EINVAL, "slice_fold_cols: the gamma-grid family needs logsum");
+  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "slice_fold_cols: the half bandwidth (tf_order + 1) nembeds must stay below 64");
+  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "slice_fold_cols: the summary stage takes at most 16384 samples");
+  if ((double)(f.sample0 + f.S) * f.C >= 2147483647.0 || (double)f.C * f.N * f.T >= 2147483647.0)
+    return fail(c, BTF_EINVAL, "slice_fold_cols: (sample0 + nsamples) * ncols_new and ncols_new * nrows * ndepth must stay below 2^31");
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  penalty_stencil(f.T, f.tf, p.Delta, p.nD, p.ptr, p.row, p.coef);
+  if ((double)f.T * f.K + 1.0 + f.max_rounds + 4.0 * p.nD >= 2147483647.0)
+    return fail(c, BTF_EINVAL, "slice_fold_cols: the record of a sweep must stay below 2^31 numbers");
+  const size_t lds = scols_lds_bytes(f.T, f.K, f.tf, p.nD);
+  if (lds > SCOLS_LDS_LIMIT)
+    return fail(c, BTF_EINVAL, "slice_fold_cols: the band of a column needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
+                                   std::to_string(SCOLS_LDS_LIMIT));
+  const int D1 = f.tf + 2;
+  p.rcol0.assign(p.nD, 0); p.rcoef.assign((size_t)p.nD * D1, 0.0);
+  for (int r = 0; r < p.nD; ++r) {
+    int lo = f.T, hi = -1;
+    for (int t = 0; t < f.T; ++t)
+      if (p.Delta[(size_t)r * f.T + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
+    if (hi < 0 || hi - lo >= D1) return fail(c, BTF_EINVAL, "slice_fold_cols: penalty row wider than the band");
+    p.rcol0[r] = lo;
+    for (int t = lo; t <= hi; ++t) p.rcoef[(size_t)r * D1 + (t - lo)] = p.Delta[(size_t)r * f.T + t];
+  }
+  const size_t ncell = (size_t)f.C * f.N * f.T;
+  for (size_t e = 0; e < ncell; ++e)
+    if (!(f.cnt[e] >= 0.0 && f.cnt[e] < 1e15) || !(std::fabs(f.S1[e]) < INFINITY) || (f.L && !(std::fabs(f.L[e]) < INFINITY)) ||
+        !(f.fa[e] >= 0.0 && f.fa[e] < INFINITY) || !(std::fabs(f.fb[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, "slice_fold_cols: counts and fit weights must be finite and non-negative, sums finite (0 where there is nothing)");
+  if (!all_finite(f.cons, (size_t)f.J * (f.T + 1))) return fail(c, BTF_EINVAL, "slice_fold_cols: constraints must be finite");
+  if (f.start && !all_finite(f.start, (size_t)f.S * f.C * f.T * f.K)) return fail(c, BTF_EINVAL, "slice_fold_cols: start must be finite");
+  if (f.tau2)
+    for (size_t e = 0; e < (size_t)f.S * f.C * p.nD; ++e)
+      if (!(f.tau2[e] > 0.0 && f.tau2[e] < INFINITY)) return fail(c, BTF_EINVAL, "slice_fold_cols: tau2 must be finite and positive");
+  if (f.draws) {
+    const size_t n = (size_t)f.T * f.K, nu = 1 + (size_t)f.max_rounds, per = n + nu + 4 * (size_t)p.nD, head = 4 * (size_t)p.nD;
+    const size_t L = head + (size_t)f.sweeps * per;
+    for (size_t ch = 0; ch < (size_t)f.S * f.C; ++ch) {
+      const double* d = f.draws + ch * L;
+      for (size_t e = 0; e < L; ++e) {
+        const size_t pos = e < head ? per : (e - head) % per;         // (per: a start gamma)
+        const bool normal = pos < n, uniform = pos >= n && pos < n + nu;
+        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)) || (uniform && !(d[e] < 1.0)))
+          return fail(c, BTF_EINVAL, "slice_fold_cols: draws must be finite, its uniforms inside (0, 1), its gamma variates positive");
+      }
+    }
+  }
+  return BTF_OK;
+}
+
+// The launches on device states dW (S,N,K), dV (S,M,T,K; read when the call has no start) and per-sample lam2 on the
+// device; dgg: the gamma-grid table on the device (family 5).  The scratch's context may be null (the stateless form).
+// The new V stays on the device between the chains and the summary.
+int slice_fold_cols_run(Scratch& s, const double* dW, const double* dV, int M, const double* dlam, int lstride, const GgComp* dgg,
+                        int G, double lsp, const SliceFoldCols& f, const FoldColsPenalty& p) {
+  btf_ctx* c = s.ctx();
+  const int S = f.S, C = f.C, N = f.N, T = f.T, K = f.K, nD = p.nD;
+  SliceFoldColsKernel kern = slice_fold_cols_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, "slice_fold_cols: nembeds must be 1..10 and family 0..5");
+  // column statistics and the fit in the kernel's [column][depth][row] layout; per column the rows with any observed or
+  // fitted cell, ascending
+  const size_t ncell = (size_t)C * N * T;
+  std::vector<double> h1(ncell), hc(ncell), hl(f.L ? ncell : 0), ha(ncell), hb(ncell);
+  std::vector<int> rptr(1, 0), ridx;
+  for (int j = 0; j < C; ++j) {
+    for (int i = 0; i < N; ++i) {
+      bool any = false;
+      for (int t = 0; t < T; ++t) {
+        const size_t src = ((size_t)j * N + i) * T + t, dst = ((size_t)j * T + t) * N + i;
+        const double cv = f.cnt[src], av = f.fa[src];
+        hc[dst] = cv; h1[dst] = cv > 0.0 ? f.S1[src] : 0.0;
+        if (f.L) hl[dst] = cv > 0.0 ? f.L[src] : 0.0;
+        ha[dst] = av; hb[dst] = av > 0.0 ? f.fb[src] : 0.0;
+        any = any || cv > 0.0 || av > 0.0;
+      }
+      if (any) ridx.push_back(i);
+    }
+    rptr.push_back((int)ridx.size());
+  }
+  if (ridx.empty()) ridx.push_back(0);                       // (never read)
+  // Constraints_A by its non-zeros (CSR over the constraints), the bounds beside it
+  std::vector<int> cptr(1, 0), cidx;
+  std::vector<double> cval, cc;
+  for (int q = 0; q < f.J; ++q) {
+    for (int t = 0; t < T; ++t)
+      if (f.cons[(size_t)q * (T + 1) + t] != 0.0) { cidx.push_back(t); cval.push_back(f.cons[(size_t)q * (T + 1) + t]); }
+    cptr.push_back((int)cidx.size());
+    cc.push_back(f.cons[(size_t)q * (T + 1) + T]);
+  }
+  if (cidx.empty()) { cidx.push_back(0); cval.push_back(0.0); }
+  if (cc.empty()) cc.push_back(0.0);
+  const size_t n = (size_t)T * K, nV = (size_t)S * C * n, nT = (size_t)S * C * nD, nch = (size_t)S * C;
+  const size_t LD = 4 * (size_t)nD + (size_t)f.sweeps * (n + 1 + (size_t)f.max_rounds + 4 * (size_t)nD);
+  const int stat0[4] = {0, INT_MAX, 0, INT_MAX};
+  SliceFoldColsArgs a = {};
+  a.W = dW; a.lam2 = dlam; a.lstride = lstride;
+  a.S1 = s.upload(h1.data(), ncell); a.cnt = s.upload(hc.data(), ncell);
+  if (f.L) a.L = s.upload(hl.data(), ncell);
+  a.fa = s.upload(ha.data(), ncell); a.fb = s.upload(hb.data(), ncell);
+  a.rptr = s.upload(rptr.data(), rptr.size()); a.ridx = s.upload(ridx.data(), ridx.size());
+  a.cs_ptr = s.upload(cptr.data(), cptr.size()); a.cs_idx = s.upload(cidx.data(), cidx.size());
+  a.cs_val = s.upload(cval.data(), cval.size()); a.Cc = s.upload(cc.data(), cc.size()); a.J = f.J;
+  if (f.tau2) a.tau2 = s.upload(f.tau2, nT);
+  if (f.draws) a.draws = s.upload(f.draws, nch * LD);
+  a.rcol0 = s.upload(p.rcol0.data(), p.rcol0.size()); a.rcoef = s.upload(p.rcoef.data(), p.rcoef.size());
+  a.st_ptr = s.upload(p.ptr.data(), p.ptr.size());
+  a.st_row = s.upload(p.row.data(), p.row.size()); a.st_coef = s.upload(p.coef.data(), p.coef.size());
+  a.gg = dgg; a.G = G; a.lsp = lsp; a.fam = f.family; a.par = f.param;
+  double* dmean = nullptr;
+  if (f.start) { a.start = s.upload(f.start, nV); a.st_s = (long long)C * (long long)n; a.st_c = (long long)n; }
+  else {
+    dmean = s.alloc<double>((size_t)S * n);
+    const int nb = (int)(((size_t)S * n + 255) / 256);
+    launch_counted(s, BTF_K_CRITERIA, slice_fold_cols_mean_fn(), dim3(nb), dim3(256), 0, dV, S, M, (int)n, dmean);
+    a.start = dmean; a.st_s = (long long)n; a.st_c = 0;
+  }
+  a.V = s.alloc<double>(nV); a.Tau2 = s.alloc<double>(nT);
+  a.rounds = s.alloc<int>(nch); a.unfinished = s.alloc<int>(nch); a.status = s.upload(stat0, 4);
+  a.seed = f.seed; a.sample0 = f.sample0; a.lo = f.stability; a.hi = 1.0 / f.stability;
+  a.S = S; a.C = C; a.N = N; a.T = T; a.tf = f.tf; a.nD = nD; a.sweeps = f.sweeps; a.max_rounds = f.max_rounds;
+  const size_t lds = scols_dyn_lds_bytes(T, K, f.tf, nD);
+  allow_lds(s, kern, lds);
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3((unsigned)nch), dim3(WAVE), lds, a);
+  // the summary stage reads the device-resident W (S,N,K) and the new V (S,C*T,K)
+  if (f.mean_out) summary_stage(s, dW, a.V, S, N, C * T, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
+  int stat[4] = {0, INT_MAX, 0, INT_MAX};
+  std::vector<double> hmean(dmean ? (size_t)S * n : 0);
+  s.download(stat, (const int*)a.status, 4);
+  s.download(f.V_out, (const double*)a.V, nV);
+  s.download(f.Tau2_out, (const double*)a.Tau2, nT);
+  s.download(f.rounds_out, (const int*)a.rounds, nch);
+  s.download(f.unf_out, (const int*)a.unfinished, nch);
+  if (dmean && f.Vstart_out) s.download(hmean.data(), (const double*)dmean, hmean.size());
+  const int rc = s.finish();
+  if (rc) return rc;
+  if (f.Vstart_out) {
+    if (f.start) std::copy(f.start, f.start + nV, f.Vstart_out);
+    else
+      for (size_t e = 0; e < nV; ++e) f.Vstart_out[e] = hmean[(e / ((size_t)C * n)) * n + e % n];
+  }
+  if (stat[0]) {
+    if (c) c->fail_index = stat[1];
+    g_fold_fail_index = stat[1];
+    const long long sg = stat[1] / C;
+    return fail(c, BTF_ESTATE, "slice_fold_cols: the start of (sample " + std::to_string(sg) + ", column " + std::to_string(stat[1] - sg * C) +
+                                   ") is infeasible or has a non-finite likelihood (index " + std::to_string(stat[1]) +
+                                   " = sample * ncols_new + column)");
+  }
+  if (stat[2]) {
+    if (c) c->fail_index = stat[3];
+    g_fold_fail_index = stat[3];
+    return fail(c, BTF_ESTATE, "slice_fold_cols: the precision of (sample, column) index " + std::to_string(stat[3]) +
+                                   " = sample * ncols_new + column is not positive definite (or W / lam2 / the fit not finite); its outputs are nan");
+  }
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_slice_fold_cols(int device, int family, double param, const double* shape, const double* scale, const double* prob, int G,
+                        int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order, const double* Ws,
+                        const double* Vs, int nfit_cols, const double* lam2, const double* start, const double* S1,
+                        const double* cnt, const double* logsum, const double* fit_a, const double* fit_b,
+                        const double* constraints, int ncons, const double* tau2, const double* draws, unsigned long long seed,
+                        int sweeps, int max_rounds, long long sample0, double stability, double* V_out, double* Vstart_out,
+                        double* Tau2_out, int* rounds_out, int* unfinished_out, int transform, const double* q, int nq,
+                        double* mean_out, double* q_out) {
+  const SliceFoldCols f = {family, param, nsamples, ncols_new, nrows, ndepth, nembeds, tf_order, start, S1, cnt, logsum, fit_a, fit_b,
+                           constraints, ncons, tau2, draws, seed, sweeps, max_rounds, sample0, stability, V_out, Vstart_out, Tau2_out,
+                           rounds_out, unfinished_out, transform, q, nq, mean_out, q_out};
+  g_fold_fail_index = -1;
+  if (!Ws || !lam2 || (!start && (!Vs || nfit_cols < 1))) return fail(nullptr, BTF_EINVAL, "bad slice_fold_cols arguments");
+  FoldColsPenalty p;
+  if (int rc = slice_fold_cols_check(nullptr, f, p)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(lam2[s] > 0.0 && lam2[s] < INFINITY)) return fail(nullptr, BTF_EINVAL, "slice_fold_cols: lam2 must be finite and positive");
+  if ((family == ESS_FAM_GAUSSIAN || family == ESS_FAM_NEGBIN_LOGIT) && !(param > 0.0 && param < INFINITY))
+    return fail(nullptr, BTF_EINVAL, "slice_fold_cols: the parameter must be positive");
+  std::vector<GgComp> tab;
+  double lsp = 0.0;
+  if (family == ESS_FAM_GAMMA_GRID && gg_comp_table(shape, scale, prob, G, tab, lsp) != 0)
+    return fail(nullptr, BTF_EINVAL, "slice_fold_cols: the gamma grid has 1..128 components with finite shape > 0, scale > 0, weight >= 0, not all zero");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dV = start ? nullptr : s.upload(Vs, (size_t)nsamples * nfit_cols * ndepth * nembeds);
+  const double* dl = s.upload(lam2, (size_t)nsamples);
+  const GgComp* dgg = tab.empty() ? nullptr : s.upload(tab.data(), tab.size());
+  return slice_fold_cols_run(s, dW, dV, nfit_cols, dl, 1, dgg, (int)tab.size(), lsp, f, p);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload): W and V from the sample slots,
+// lam2_s from the collected scalars, the likelihood's parameter or table from the context
+int btf_collect_slice_fold_cols(btf_ctx* c, int family, int nsamples, int ncols_new, const double* start, const double* S1,
+                                const double* cnt, const double* logsum, const double* fit_a, const double* fit_b,
+                                const double* constraints, int ncons, const double* tau2, const double* draws,
+                                unsigned long long seed, int sweeps, int max_rounds, long long sample0, double stability,
+                                double* V_out, double* Vstart_out, double* Tau2_out, int* rounds_out, int* unfinished_out,
+                                int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  if (!c || family < 0 || family >= ESS_FAM_COUNT) return fail(c, BTF_EINVAL, "bad slice_fold_cols arguments");
+  const SliceFoldCols f = {family, c->lik_par[family], nsamples, ncols_new, c->N, c->T, c->K, c->TF, start, S1, cnt, logsum, fit_a,
+                           fit_b, constraints, ncons, tau2, draws, seed, sweeps, max_rounds, sample0, stability, V_out, Vstart_out,
+                           Tau2_out, rounds_out, unfinished_out, transform, q, nq, mean_out, q_out};
+  FoldColsPenalty p;
+  if (int rc = slice_fold_cols_check(c, f, p)) return rc;
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_collect_slice_fold_cols needs an unsharded context");
+  if (family == ESS_FAM_GAMMA_GRID && !c->gg_tab)
+    return fail(c, BTF_ESTATE, "btf_collect_slice_fold_cols: the gamma-grid family needs its table (btf_set_likelihood_table)");
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_slice_fold_cols", BTF_ESTATE, nsamples, 0, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  return slice_fold_cols_run(s, st.W, st.V, c->M, c->smp_s + HYP_LAM2, (int)HYP_COUNT, c->gg_tab, c->gg_G, c->gg_lsp, f, p);
+}
+
 int btf_diag_eval(int device, int nchains, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* const* Ws,
                   const double* const* Vs, btf_ctx* const* ctxs, int transform, double* out) {
   if (nchains < 1 || nchains > DIAG_MAX_CHAINS || nsamples < 4 || (long long)nchains * nsamples > DIAG_MAX_DRAWS || nrows < 1 ||

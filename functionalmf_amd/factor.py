@@ -1567,7 +1567,7 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
 
     def _fold_cols_family(self):
         raise NotImplementedError("%s: fold_in_cols needs the conjugate column conditional of the Gaussian and Binomial models; "
-                                  "a slice-sampled column has no closed-form draw (not supported yet)" % type(self).__name__)
+                                  "a slice-sampled column has no closed-form draw: slice_fold_in_cols folds columns into this model" % type(self).__name__)
 
     def _slice_fold_restrictions(self, row_features, R, results, S):
         """(Constraints, Row_constraints, codes (R,F) or None, Us (S,F,K) or None) of a slice_fold_in_rows call."""
@@ -1609,8 +1609,8 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         device-resident W and V (transform as posterior_summary; at most 16384 samples); nsamples.  out["W"] together with
         results["V"] goes straight into utils.posterior_summary, posterior_functionals, posterior_ranking and
         gamma_grid_predictive.  The sampler's state is not touched.  Unsharded models, device likelihoods, nembeds <= 10.
-        The Negative-Binomial model (its rate is sampled) is out of scope; new columns are folded in by fold_in_cols, for
-        the Gaussian and Binomial models only."""
+        The Negative-Binomial model (its rate is sampled) is out of scope; new columns are folded in by fold_in_cols
+        (Gaussian and Binomial models) and slice_fold_in_cols (this model)."""
         from . import slice_fold_in as _sf
         from ._analysis import check_scalars
         self._unsharded("slice_fold_in_rows")
@@ -1632,6 +1632,71 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
         return _sf.evaluate(family, param, S, R, M, T, K, S1, cnt, L, start=start, Constraints=cons, Row_constraints=rcons, Us=Us,
                             codes=codes, draws=draws, seed=seed, sweeps=sweeps, max_rounds=max_rounds, summary=summary, q=q,
                             transform=transform, ctx=self._ctx, Vs=Vs, Ws=Ws, sigma2=sigma2, device=self._ctx.device)
+
+    # ---- folding new columns in (functionalmf_amd/slice_fold_in_cols.py, csrc/btf_slice_fold_cols.h) ----
+    def _slice_fold_col_constraints(self):
+        """The curve constraints (J,T+1) a new column has to satisfy for every fitted row, or None."""
+        return None
+
+    def slice_fold_in_cols(self, Y_new, results=None, fit=None, start=None, tau2=None, seed=None, draws=None, sweeps=None,
+                           max_rounds=40, summary=True, q=(5, 95), transform=None):
+        """Curves of columns the chain never saw (a new drug tested on a handful of the fitted cell lines) for every row,
+        with uncertainty, for the slice-sampled models, on the GPU (csrc/btf_slice_fold_cols.h): fold_in_cols for the
+        likelihoods without a conjugate column conditional.  Given a kept sample's W_s and lam2_s the new column's curve
+        and its horseshoe+ levels form a small chain: `sweeps` rounds (default:
+        functionalmf_amd.slice_fold_in_cols.DEFAULT_SWEEPS) of one elliptical slice update of the curve - on an ellipse
+        centred on a per-cell Gaussian fit of the likelihood, each with at most max_rounds proposals - and the level update
+        of fold_in_cols, all in one launch.  Every restriction on the column is linear given W_s (a constrained model:
+        sum_t A[q,t] (w_i . v_t) >= C[q] for EVERY fitted row i), so the feasible set is convex; Row_constraints and row
+        features do not touch a column.  As in fold_in_cols the new data does not inform W or the hyper-parameters.
+        functionalmf_amd.slice_fold_in_cols.chain is the definition in numpy.
+
+        Y_new: (C,N,T) or (C,N,T,nreps), NaN = missing; a column with no observation at all is allowed.
+        results: a run_gibbs result dict (W (S,N,K), lam2 one value per sample, V (S,M,T,K) - read for the default start
+            only), uploaded; None: the samples the last device-collecting run_gibbs left on the device - no upload of W
+            and V, and lam2_s is read from the collected scalars.
+        fit: None: slice_fold_in_cols.gaussian_fit(Y_new, ...), a per-cell delta-method fit; (Mu_fit, Sigma_fit), each
+            (C,N,T), nan or a non-positive sd = the cell carries no fit; False: no fit at all, the plain prior ellipse
+            (valid, and slow: thousands of sweeps).  The fit changes only the mixing, never the target.
+        start: (T,K), (C,T,K) or (S,C,T,K); default: the mean over the fitted columns of V_s, which lies in the convex
+            feasible set.  A start that is infeasible or has a non-finite likelihood raises RuntimeError naming (sample,
+            column).
+        tau2: (C,nD) or (S,C,nD) holds the local scales of the new columns fixed (no level update).
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        draws: optional (S,C,slice_fold_in_cols.record_length(...)) replacing the device generator.
+
+        Returns a dict: V (S,C,T,K) the last state of every chain, one draw per kept sample; V_start (S,C,T,K); Tau2
+        (S,C,nD); rounds (S,C) likelihood evaluations; unfinished (S,C) sweeps that used all max_rounds proposals (they
+        keep their state); with summary=True, mean (N,C,T) and quantiles (len(q),N,C,T) of f(w_i^s . v_ct^s) from the
+        summary kernel (transform as posterior_summary; at most 16384 samples); nsamples.  results["W"] together with
+        out["V"] goes straight into utils.posterior_summary, posterior_functionals, posterior_ranking,
+        gamma_grid_predictive and posterior_monotone.  The sampler's state is not touched.  Unsharded models, device
+        likelihoods, nembeds <= 10; a band of Q beyond one workgroup's LDS is refused with ValueError.  The
+        Negative-Binomial model (its rate is sampled) is out of scope."""
+        from . import slice_fold_in_cols as _sc
+        from ._analysis import check_scalars
+        self._unsharded("slice_fold_in_cols")
+        if self._callback:
+            raise NotImplementedError("slice_fold_in_cols needs a device likelihood: a Python-callable loglikelihood is "
+                                      "evaluated on the host only")
+        N, T, K = self.nrows, self.ndepth, self.nembeds
+        family = self.loglikelihood
+        param = self._gg_table if self._link == 5 else self.likelihood_param
+        C, S1, cnt, L = _sc.column_statistics(Y_new, family, N, T)
+        S, Ws, Vs = self._samples(results, need=("W", "V"))
+        cons = self._slice_fold_col_constraints()
+        _sc.check_args(family, param, S, C, N, T, K, self.tf_order, start, tau2, draws, sweeps, max_rounds, summary, q, transform, 0)
+        if fit is None:
+            fit = _sc.gaussian_fit(Y_new, family, param)
+        weights, sums = _sc.fit_weights(fit, C, N, T)
+        lam2 = check_scalars("results: lam2", results.get("lam2"), S) if results is not None else None
+        if seed is None:
+            seed = self._next_seed() if draws is None else 0
+        return _sc.evaluate(family, param, S, C, N, T, K, self.tf_order, S1, cnt, L, weights, sums, start=start, Constraints=cons,
+                            tau2=tau2, draws=draws, seed=seed, sweeps=sweeps, max_rounds=max_rounds, summary=summary, q=q,
+                            transform=transform, stability=float(self.stability), ctx=self._ctx, Ws=Ws, Vs=Vs, lam2=lam2,
+                            device=self._ctx.device)
 
     def run_gibbs(self, data, nburn=1000, nthin=1, nsamples=1000, verbose=True, print_freq=100, callback=None, **kwargs):
         """genlasso.py:37-66, the result dict gathered as before.  A gamma_grid model with rng="device" also keeps every
@@ -1927,6 +1992,9 @@ class ConstrainedNonconjugateBayesianTensorFiltering(NonconjugateBayesianTensorF
             i, f = np.unravel_index(np.argmax(np.where(np.isnan(viol), np.inf, viol)), viol.shape)
             raise ValueError("invalid starting point: w_%d . u_%d = %r is outside [0, 1] (row %d, feature %d is the worst pair)"
                              % (i, f, float(P[i, f]), i, f))
+
+    def _slice_fold_col_constraints(self):
+        return self._cons
 
     def _slice_fold_restrictions(self, row_features, R, results, S):
         """The model's Constraints and Row_constraints, and - with row_features of the new rows - their codes and the

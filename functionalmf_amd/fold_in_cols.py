@@ -88,14 +88,20 @@ def _column(Y_col):
 
 def _system(weights, sums, W, lam2, tau2, tf_order):
     """(mean, Q) from per-cell weights and weighted sums (N,T): A_t = sum_i weights_it w_i w_i', b_t = sum_i sums_it w_i."""
-    N, K = W.shape
-    T = weights.shape[1]
-    if weights.shape[0] != N:
+    return _system_of_blocks(*_blocks(weights, sums, W), lam2, tau2, tf_order)
+
+
+def _blocks(weights, sums, W):
+    """(A (T,K,K), b (T K,)) of _system: what does not depend on the levels."""
+    if weights.shape[0] != W.shape[0]:
         raise ValueError("the column %r does not match W %r" % (weights.shape, W.shape))
+    return np.einsum("it,ik,il->tkl", weights, W, W), sums.T.dot(W).reshape(-1)
+
+
+def _system_of_blocks(A, b, lam2, tau2, tf_order):
+    T, K = A.shape[:2]
     D = penalty(T, tf_order)
     P = D.T.dot(D / (float(lam2) * np.asarray(tau2, dtype=float))[:, None])
-    A = np.einsum("it,ik,il->tkl", weights, W, W)
-    b = sums.T.dot(W).reshape(-1)
     Q = np.kron(P, np.eye(K))
     for t in range(T):
         Q[t * K:(t + 1) * K, t * K:(t + 1) * K] += A[t]

@@ -104,10 +104,17 @@ def loglik(family, param, stats_of_row, V, w):
     """Log-likelihood of one row at w, the families of btf_ess.h:25-37 without their state-independent terms (the gamma
     grid: complete).  stats_of_row = (S1, cnt, L) of the row, each (M,T) (L None unless gamma grid); V (M,T,K); param: the
     variance (3), the rate (4) or the table (shape, scale, prob) of likelihoods.gamma_grid_table (5)."""
-    code = family if isinstance(family, int) else family_code(family)
-    S1, cnt, L = stats_of_row
     K = np.shape(V)[-1]
     eta = np.asarray(V, dtype=float).reshape(-1, K).dot(np.asarray(w, dtype=float))
+    return loglik_eta(family, param, stats_of_row, eta)
+
+
+def loglik_eta(family, param, stats, eta):
+    """The same from the linear predictors: stats = (S1, cnt, L) and eta hold one value per cell, in any common shape
+    (slice_fold_in_cols evaluates a column's cells with eta_it = w_i . v_t through this)."""
+    code = family if isinstance(family, int) else family_code(family)
+    S1, cnt, L = stats
+    eta = np.reshape(eta, -1)
     S1, cnt = np.reshape(S1, -1), np.reshape(cnt, -1)
     obs = cnt > 0
     if not obs.any() and code != GAMMA_GRID:

@@ -449,6 +449,51 @@ def slice_fold_in_rows(Y_new, Vs, family, sigma2=None, Ws=None, likelihood_param
                         sigma2=sigma2, device=device)
 
 
+def slice_fold_in_cols(Y_new, Ws, family, lam2=None, Vs=None, likelihood_param=None, Constraints=None, tf_order=2, fit=None,
+                       start=None, tau2=None, seed=0, draws=None, sweeps=None, max_rounds=40, summary=True, q=(5, 95),
+                       transform=None, first_sample=0, stability=1e-6, device=0):
+    """Curves of columns the chain never saw for a slice-sampled fit, one draw per kept sample, on the GPU, without a
+    model: the stateless form of NonconjugateBayesianTensorFiltering.slice_fold_in_cols (see there for the method, the
+    arguments and the outputs).
+
+    Ws (S,N,K); lam2 one value per sample; family: a device likelihood name ("poisson", "poisson_identity",
+    "bernoulli_logit", "gaussian", "negbin_logit", "gamma_grid") with likelihood_param as the model class takes it;
+    tf_order and stability as the model was built with.  Vs (S,M,T,K): the fitted columns, read for the default start
+    (their mean per sample) only; start= replaces it.  Constraints (J,T+1) as
+    ConstrainedNonconjugateBayesianTensorFiltering takes them: they hold for every fitted row.  first_sample: the index
+    of Ws[0] among the kept samples - with it a call over a slice of the samples returns the bits of the whole call.
+    functionalmf_amd.slice_fold_in_cols.chain is the definition in numpy.  There is no CPU fallback."""
+    from . import _analysis, _native, slice_fold_in as _sf, slice_fold_in_cols as _sc
+    _sf.family_code(family)
+    Ws = _native.as_f64(Ws)
+    if Ws.ndim != 3 or Ws.shape[0] < 1:
+        raise ValueError("Ws must be (S,N,K), got %r" % (Ws.shape,))
+    S, N, K = Ws.shape
+    Yshape = np.shape(Y_new)
+    T = Yshape[2] if len(Yshape) >= 3 else -1
+    param = _sf.check_param(family, likelihood_param)
+    C, S1, cnt, L = _sc.column_statistics(Y_new, family, N, T)
+    if start is None and Vs is not None:
+        Vs = _native.as_f64(Vs)
+        if Vs.ndim != 4 or Vs.shape[0] != S or Vs.shape[1] < 1 or Vs.shape[2:] != (T, K):
+            raise ValueError("Vs must be (S,M,T,K) = (%d,M,%d,%d), got %r" % (S, T, K, Vs.shape))
+    else:
+        Vs = None
+    _sc.check_args(family, param, S, C, N, T, K, tf_order, start, tau2, draws, sweeps, max_rounds, summary, q, transform,
+                   first_sample, have_V=Vs is not None)
+    _sf.check_constraints(Constraints, None, T, K)
+    if fit is None:
+        fit = _sc.gaussian_fit(Y_new, family, param)
+    weights, sums = _sc.fit_weights(fit, C, N, T)
+    lam2 = _analysis.check_scalars("lam2", lam2, S)
+    if not 0 < float(stability) <= 1:
+        raise ValueError("stability must lie in (0, 1]")
+    return _sc.evaluate(family, param, S, C, N, T, K, tf_order, S1, cnt, L, weights, sums, start=start, Constraints=Constraints,
+                        tau2=tau2, draws=draws, seed=seed, sweeps=sweeps, max_rounds=max_rounds, summary=summary, q=q,
+                        transform=transform, first_sample=first_sample, stability=stability, Ws=Ws, Vs=Vs, lam2=lam2,
+                        device=device)
+
+
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
 from .nmf import bounded_tensor_nmf, factor_pav, tensor_nmf  # noqa: E402,F401
 

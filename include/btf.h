@@ -786,6 +786,40 @@ int btf_collect_fold_in_cols(btf_ctx* ctx, int family, int nsamples, int ncols_n
                              double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
                              int nq, double* mean_out, double* q_out);
 
+/* ---- folding new columns into a slice-sampled fit (csrc/btf_slice_fold_cols.h) ---------------------------------------
+ * The same for the slice-sampled models: one chain per (kept sample s, new column c) over the column's curve v (T,K) and
+ * its horseshoe+ levels given W_s and lam2_s, the curve updated by elliptical slice sampling on an ellipse centred on a
+ * per-cell Gaussian fit of the likelihood; functionalmf_amd/slice_fold_in_cols.py (`chain`) is the definition.  family and
+ * param / the table as btf_slice_fold_rows.  Ws (S,N,K), lam2 (S,); start (S,C,T,K), or NULL: the mean over the nfit_cols
+ * fitted columns of Vs (S,nfit_cols,T,K).  S1, cnt, logsum (C,N,T): the per-cell statistics of the new columns
+ * (cnt = 0: missing; logsum: gamma grid only); fit_a, fit_b (C,N,T): 1 / Sigma_fit^2 and Mu_fit / Sigma_fit^2 (0, 0: the
+ * cell carries no fit; the fit changes the mixing, never the target).  constraints (ncons, T + 1): sum_t A[q,t] (w_i . v_t)
+ * >= C[q] for every fitted row i.  tau2 (S,C,nD) holds the local scales fixed (NULL: sampled).  draws
+ * (S,C,4 nD + sweeps (T K + 1 + max_rounds + 4 nD)): the start's (4,nD) unit Gamma(1/2) variates, then per sweep T K
+ * normals, u_h, u_a, max_rounds - 1 shrink uniforms and (4,nD) unit gammas - or NULL: Philox keyed (seed,
+ * (sample0 + s) << 32 | c, slot, element).  V_out, Vstart_out (S,C,T,K), Tau2_out (S,C,nD), rounds_out, unfinished_out
+ * (S,C); mean_out non-NULL adds the summary stage as in btf_fold_in_cols.  The band of a column, its side arrays and the
+ * likelihood tables must fit one workgroup's LDS: BTF_EINVAL otherwise, before any device call.  A start that is infeasible
+ * or has a non-finite likelihood, or a non-positive pivot: that chain's outputs are nan, the call returns BTF_ESTATE and
+ * btf_fail_index (ctx, or NULL after the stateless call) = (sample0 + s) * ncols_new + c of the first such chain.  fp64,
+ * no floating-point atomics, every sum in a fixed order.  btf_collect_slice_fold_cols reads W, V and lam2_s of the first
+ * nsamples collected slots without an upload, takes param / the table from the context and touches none of the sampler's
+ * state.  Launches are counted under BTF_K_CRITERIA.  Synchronous.                                                      */
+int btf_slice_fold_cols(int device, int family, double param, const double* shape, const double* scale, const double* prob, int G,
+                        int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order, const double* Ws,
+                        const double* Vs, int nfit_cols, const double* lam2, const double* start, const double* S1,
+                        const double* cnt, const double* logsum, const double* fit_a, const double* fit_b,
+                        const double* constraints, int ncons, const double* tau2, const double* draws, unsigned long long seed,
+                        int sweeps, int max_rounds, long long sample0, double stability, double* V_out, double* Vstart_out,
+                        double* Tau2_out, int* rounds_out, int* unfinished_out, int transform, const double* q, int nq,
+                        double* mean_out, double* q_out);
+int btf_collect_slice_fold_cols(btf_ctx* ctx, int family, int nsamples, int ncols_new, const double* start, const double* S1,
+                                const double* cnt, const double* logsum, const double* fit_a, const double* fit_b,
+                                const double* constraints, int ncons, const double* tau2, const double* draws,
+                                unsigned long long seed, int sweeps, int max_rounds, long long sample0, double stability,
+                                double* V_out, double* Vstart_out, double* Tau2_out, int* rounds_out, int* unfinished_out,
+                                int transform, const double* q, int nq, double* mean_out, double* q_out);
+
 /* ---- convergence diagnostics (csrc/btf_diag.h) ----------------------------------------------------------------------
  * Split R-hat (rank-normalised, max of bulk and folded), bulk ESS, tail ESS (min over the 5 % / 95 % indicators), MCSE of
  * the mean and the mean, per cell of f(W V') over nchains chains of nsamples draws (Vehtari et al. 2021; one chain: its
