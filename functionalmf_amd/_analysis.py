@@ -346,6 +346,27 @@ class PosteriorAnalysis:
         return _rank.evaluate(shape, self.nembeds, S, which=which, along=along, order=order, top=top, transform=transform, x=x,
                               level=level, pairs=pairs, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
 
+    # ---- posterior similarity: which rows or columns are alike (functionalmf_amd/similarity.py) ----
+    def posterior_similarity(self, results=None, along="rows", metric="rms", over=None, q=(5, 95), nearest=(1, 5), pairs=None,
+                             pointwise=False, _scratch_bytes=0):
+        """The distance between the fitted surfaces of every two rows (along="rows") or columns (along="cols") per kept
+        sample, summarised over the samples, and every entity's neighbours with their probabilities, on the GPU
+        (csrc/btf_similarity.h).  The posterior form of the embedding scatter of doseresponse/plot_embeddings.py: invariant
+        under the K x K map the embeddings are identified up to.
+
+        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device (no upload).
+        The other arguments and the returned dict: functionalmf_amd.utils.posterior_similarity.  The sampler's state is not
+        touched: a chain continued after the call walks the same path.  Unsharded models."""
+        from . import similarity as _sim
+        self._unsharded("posterior similarity")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        _sim.check_args(along, metric, over, q, nearest, pairs, False, 1, *shape, self.nembeds)
+        S, Ws, Vs = self._samples(results)
+        return _sim.evaluate(shape, self.nembeds, S, along=along, metric=metric, over=over, q=q, nearest=nearest, pairs=pairs,
+                             pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device,
+                             _scratch_bytes=_scratch_bytes)
+
     # ---- posterior feature association: which biomarker goes with which drug (functionalmf_amd/association.py) ----
     def posterior_feature_association(self, U=None, results=None, which="auc", stats=("r",), q=(5, 95), transform=None, x=None,
                                       level=None, pairs=None, of_means=True):

@@ -21,7 +21,8 @@ UNITS = [(os.path.join(CSRC, "btf_%s.hip" % name), suffix) for name, suffix in [
     ("gamma_grid", "_gamma_grid.o"), ("diag", "_diag.o"), ("predict", "_predict.o"), ("functionals", "_functionals.o"),
     ("fold_in", "_fold_in.o"), ("loo", "_loo.o"), ("ranking", "_ranking.o"), ("assoc", "_assoc.o"), ("monotone", "_monotone.o"),
     ("gg_criteria", "_gg_criteria.o"), ("gg_predict", "_gg_predict.o"), ("slice_fold", "_slice_fold.o"),
-    ("nb_criteria", "_nb_criteria.o"), ("fold_in_cols", "_fold_in_cols.o"), ("slice_fold_cols", "_slice_fold_cols.o")]]
+    ("nb_criteria", "_nb_criteria.o"), ("fold_in_cols", "_fold_in_cols.o"), ("slice_fold_cols", "_slice_fold_cols.o"),
+    ("similarity", "_similarity.o")]]
 SOURCES = [src for src, _ in UNITS]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
@@ -101,6 +102,10 @@ SIGNATURES = {
                                         _c_ip, C.c_int, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_dp, C.c_longlong]),
     "btf_collect_ranking": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _c_dp, C.c_double, C.c_int, C.c_int, _c_ip, C.c_int, _c_ip, C.c_int,
                                       _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_dp, C.c_longlong]),
+    "btf_posterior_similarity": (C.c_int, [C.c_int] * 6 + [_c_dp, _c_dp, C.c_int, C.c_int, _c_ip, C.c_int, _c_dp, C.c_int, _c_ip, C.c_int,
+                                           _c_ip, C.c_int] + [_c_dp] * 8 + [C.c_longlong]),
+    "btf_collect_similarity": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _c_ip, C.c_int, _c_dp, C.c_int, _c_ip, C.c_int, _c_ip, C.c_int] +
+                               [_c_dp] * 8 + [C.c_longlong]),
     "btf_posterior_association": (C.c_int, [C.c_int] * 7 + [_c_dp, _c_dp, _c_dp, C.c_int, C.c_int, _c_dp, C.c_double, _c_ip, C.c_int, _c_dp,
                                             C.c_int, _c_ip, C.c_int] + [_c_dp] * 10 + [C.c_longlong]),
     "btf_collect_association": (C.c_int, [_ctx, C.c_int, C.c_int, _c_dp, C.c_int, C.c_int, _c_dp, C.c_double, _c_ip, C.c_int, _c_dp, C.c_int,

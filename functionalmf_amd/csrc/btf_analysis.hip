@@ -1,5 +1,5 @@
 // The posterior analyses behind the C ABI (include/btf.h): summaries, criteria, PSIS-LOO, predictive, functionals, ranking,
-// association, monotone projection, fold-in (rows and columns: conjugate and slice-sampled), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
+// similarity, association, monotone projection, fold-in (rows and columns: conjugate and slice-sampled), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
 #include "btf_ctx.h"            // struct btf_ctx, fail, Scratch, launch_counted, K_SWITCH / FAM_SWITCH
 #include "btf_diag.h"           // convergence diagnostics (instances in btf_diag.hip)
 #include "btf_criteria.h"       // model-selection criteria (instances in btf_criteria.hip)
@@ -10,6 +10,7 @@
 #include "btf_gg_predict.h"     // the same for the gamma-grid likelihood (kernels in btf_gg_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
 #include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
+#include "btf_similarity.h"     // posterior similarity (kernels in btf_similarity.hip)
 #include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
 #include "btf_monotone.h"       // monotone projection of the posterior (kernel in btf_monotone.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
@@ -773,6 +774,159 @@ int btf_collect_ranking(btf_ctx* c, int nsamples, int transform, int which, cons
   if (int rc = resolve_pair(s, 0, "btf_collect_ranking", BTF_ESTATE, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
   return ranking_run(s, st.W, st.V, nsamples, c->N, c->M, c->T, c->K, transform, which, x, level, along, descending, top, ntop,
                      pairs, npairs, o, scratch_bytes);
+}
+
+// ---------------------------------------------------------------- posterior similarity (btf_similarity.h)
+namespace {
+struct SimOut { double *mean, *var, *quant, *expected, *rank_var, *pnear, *pair_values, *dist; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): the metric of every sample, then per tile of entities
+// the keys of every (partner, sample, entity) into the stage, the unchanged rank kernel on them, the keys to distances in
+// place, the unchanged sort kernel's reductions over the samples, and the tile's rows of the outputs.  scratch_bytes caps
+// the stage (0: FUNC_SCRATCH_BYTES; one entity is the least a tile holds).
+int sim_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int along, int metric, const int* over,
+            int nover, const double* q, int nq, const int* nearest, int nnearest, const int* pairs, int npairs, const SimOut& o,
+            long long scratch_bytes) {
+  const bool cols = along == 1, cosine = metric == 1;
+  const int E = cols ? M : N, YN = cols ? N : M;
+  std::vector<int> all;
+  if (!over) { all.resize(YN); for (int k = 0; k < YN; ++k) all[k] = k; over = all.data(); nover = YN; }
+  SimKernel metric_k = sim_metric_fn(K), dist_k = sim_dist_fn(K, cosine);
+  if (!metric_k || !dist_k) return fail(s.ctx(), BTF_EINVAL, "posterior similarity: nembeds must be 1..10");
+  const size_t EE = (size_t)E * E, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
+  const int ne_max = (int)std::max<size_t>(1, std::min<size_t>(E, cap / ((size_t)S * E * sizeof(double))));
+  const size_t tile_max = (size_t)ne_max * E;
+  SimArgs a = {};
+  a.X = cols ? dV : dW; a.Y = cols ? dW : dV; a.over = s.upload(over, (size_t)nover);
+  a.S = S; a.E = E; a.TT = cols ? T : 1; a.YN = YN; a.mt = cols ? 1 : T; a.nmem = nover * a.mt;
+  a.ncells = (double)nover * T; a.rms = cosine ? 0 : 1; a.ntop = nnearest; a.nq = nq; a.P = npairs;
+  a.metric = s.alloc<double>((size_t)S * K * K);
+  if (cosine) a.norms = s.alloc<double>((size_t)S * E);
+  a.stage = s.alloc<double>((size_t)S * tile_max);
+  if (o.dist) a.dist = s.alloc<double>((size_t)S * EE);
+  if (npairs) { a.pairs = s.upload(pairs, (size_t)2 * npairs); a.pair_values = s.alloc<double>((size_t)S * npairs); }
+  unsigned long long* dA = s.alloc<unsigned long long>(tile_max);
+  unsigned long long* dB = s.alloc<unsigned long long>(tile_max);
+  unsigned int* dC = s.alloc<unsigned int>((size_t)nnearest * tile_max);
+  double* dqt = s.alloc<double>((size_t)nq * tile_max);
+  a.A = dA; a.B = dB; a.C = dC; a.qtmp = dqt;
+  a.expected = s.alloc<double>(EE); a.rank_var = s.alloc<double>(EE); a.pnear = s.alloc<double>((size_t)nnearest * EE);
+  a.quant = s.alloc<double>((size_t)nq * EE);
+  double* dmean = s.alloc<double>(EE);
+  double* dvar = s.alloc<double>(EE);
+  // the two borrowed kernels: the sort reduces column = partner, row = local entity; the rank kernel ranks the E partners
+  // (along 0: the "columns") of every (sample, local entity)
+  FuncArgs f = {};
+  f.S = S; f.M = E; f.j0 = 0; f.jc = E; f.nslots = 1; f.nq = nq; f.exceed = std::nan("");
+  for (int k = 0; k < FUNC_COUNT; ++k) f.slot[k] = -1;
+  f.slot[FUNC_AUC] = 0; f.code[0] = FUNC_AUC;            // (any functional but the crossing: no value is censored)
+  f.q = nq ? s.upload(q, (size_t)nq) : nullptr;
+  const SortGeom g = sort_geom(S, FUNC_SORT_LDS, FUNC_SORT_CELLS);
+  f.P = g.P; f.cells = g.cells;
+  FuncKernel sort = func_sort_fn();
+  allow_lds(s, sort, g.lds);
+  RankArgs r = {};
+  r.S = S; r.M = E; r.along = 0; r.ntop = nnearest; r.s0 = 0; r.sc = S; r.L = E;
+  for (int k = 0; k < nnearest; ++k) r.top[k] = std::min(nearest[k], RANK_MAX_L + 1);      // (a rank never exceeds RANK_MAX_L)
+  while ((1 << r.lshift) < r.L) ++r.lshift;
+  r.Lp = 1 << r.lshift;
+  r.A = dA; r.B = dB; r.C = dC;
+  RankKernel rank = rank_fn(false);
+  launch_counted(s, BTF_K_CRITERIA, metric_k, dim3(S), dim3(SIM_THREADS), 0, a);
+  const int fblocks = (E + SIM_FBLK - 1) / SIM_FBLK;
+  for (int e0 = 0; e0 < E; e0 += ne_max) {
+    const int ne = std::min(ne_max, E - e0);
+    const size_t tile = (size_t)ne * E;
+    a.e0 = e0; a.ne = ne;
+    // sample slices: enough workgroups to fill the chip when entity blocks x partner blocks alone do not (geometry only)
+    const int eblocks = (ne + WAVE - 1) / WAVE;
+    const int zs = std::max(1, std::min(S, (2048 + eblocks * fblocks - 1) / (eblocks * fblocks)));
+    launch_counted(s, BTF_K_CRITERIA, dist_k, dim3(eblocks, fblocks, zs), dim3(SIM_THREADS), sim_dist_lds_bytes(K), a);
+    // ---- neighbours: the ranks of the E partners of every (sample, entity) on the keys; the entity itself (nan) last
+    s.zero(dA, tile * sizeof(unsigned long long)); s.zero(dB, tile * sizeof(unsigned long long));
+    s.zero(dC, (size_t)nnearest * tile * sizeof(unsigned int));
+    r.vals = a.stage; r.N = ne;
+    r.G = std::max(1, std::min(ne, std::min(RANK_MAX_L / r.Lp, RANK_MAX_GROUPS)));
+    const int rtiles = (ne + r.G - 1) / r.G;
+    launch_counted(s, BTF_K_CRITERIA, rank, dim3(rtiles, std::max(1, std::min(S, (1024 + rtiles - 1) / rtiles))), dim3(RANK_THREADS),
+                   rank_lds_bytes(r.G, r.Lp), r);
+    // ---- keys to distances, the pointwise output and the pairs
+    launch_counted(s, BTF_K_CRITERIA, sim_root_fn(), dim3((unsigned)(((size_t)S * tile + 255) / 256)), dim3(256), 0, a);
+    if (npairs) launch_counted(s, BTF_K_CRITERIA, sim_pairs_fn(), dim3(npairs), dim3(256), 0, a);
+    // ---- mean, variance and percentiles over the samples; mean and variance land in their rows directly
+    f.vals = a.stage; f.N = ne; f.mean = dmean + (size_t)e0 * E; f.var = dvar + (size_t)e0 * E; f.quant = dqt;
+    launch_counted(s, BTF_K_CRITERIA, sort, dim3((ne + f.cells - 1) / f.cells, E, 1), dim3(256), g.lds, f);
+    launch_counted(s, BTF_K_CRITERIA, sim_finish_fn(), dim3((unsigned)((tile + 255) / 256)), dim3(256), 0, a);
+  }
+  s.download(o.mean, dmean, EE);
+  s.download(o.var, dvar, EE);
+  if (nq) s.download(o.quant, a.quant, (size_t)nq * EE);
+  s.download(o.expected, a.expected, EE);
+  s.download(o.rank_var, a.rank_var, EE);
+  s.download(o.pnear, a.pnear, (size_t)nnearest * EE);
+  if (npairs) s.download(o.pair_values, a.pair_values, (size_t)S * npairs);
+  s.download(o.dist, a.dist, (size_t)S * EE);
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int sim_check(btf_ctx* c, int S, int N, int M, int T, int K, int along, int metric, const int* over, int nover, const double* q, int nq,
+              const int* nearest, int nnearest, const int* pairs, int npairs, const SimOut& o, long long scratch_bytes) {
+  if (S < 1 || N < 1 || M < 1 || T < 1 || K < 1 || K > MAX_K || along < 0 || along > 1 || metric < 0 || metric > 1 || nover < 0 ||
+      (over && nover < 1) || (!over && nover > 0) || nq < 0 || (nq > 0 && (!q || !o.quant)) || !nearest || nnearest < 1 ||
+      nnearest > SIM_MAX_NEAREST || npairs < 0 || (npairs > 0 && (!pairs || !o.pair_values)) || scratch_bytes < 0)
+    return fail(c, BTF_EINVAL, "bad posterior similarity arguments");
+  if (S > FUNC_MAX_S) return fail(c, BTF_EINVAL, "posterior similarity: at most " + std::to_string(FUNC_MAX_S) + " samples");
+  const int E = along ? M : N, YN = along ? N : M;
+  if (E > SIM_MAX_E)
+    return fail(c, BTF_EINVAL, "posterior similarity: at most " + std::to_string(SIM_MAX_E) + " entities (a neighbour group is sorted in LDS)");
+  if (int rc = check_percentiles(c, q, nq)) return rc;
+  for (int k = 0; k < nnearest; ++k) {
+    if (nearest[k] < 1) return fail(c, BTF_EINVAL, "posterior similarity: nearest must hold integers >= 1");
+    for (int l = 0; l < k; ++l)
+      if (nearest[l] == nearest[k]) return fail(c, BTF_EINVAL, "posterior similarity: nearest must hold distinct integers");
+  }
+  if (over) {
+    std::vector<char> seen((size_t)YN, 0);
+    for (int k = 0; k < nover; ++k) {
+      if (over[k] < 0 || over[k] >= YN || seen[over[k]]) return fail(c, BTF_EINVAL, "posterior similarity: over must hold distinct indices in range");
+      seen[over[k]] = 1;
+    }
+  }
+  for (int k = 0; k < 2 * npairs; ++k)
+    if (pairs[k] < 0 || pairs[k] >= E) return fail(c, BTF_EINVAL, "posterior similarity: pair index out of range");
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_posterior_similarity(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                             int along, int metric, const int* over, int nover, const double* q, int nq, const int* nearest,
+                             int nnearest, const int* pairs, int npairs, double* mean_out, double* var_out, double* q_out,
+                             double* expected_out, double* rank_var_out, double* pnear_out, double* pair_out, double* dist_out,
+                             long long scratch_bytes) {
+  const SimOut o = {mean_out, var_out, q_out, expected_out, rank_var_out, pnear_out, pair_out, dist_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior similarity arguments");
+  if (int rc = sim_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, along, metric, over, nover, q, nq, nearest, nnearest, pairs,
+                         npairs, o, scratch_bytes)) return rc;
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, nrows, ncols * ndepth, nembeds, Ws, Vs, st)) return rc;
+  return sim_run(s, st.W, st.V, nsamples, nrows, ncols, ndepth, nembeds, along, metric, over, nover, q, nq, nearest, nnearest, pairs,
+                 npairs, o, scratch_bytes);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload)
+int btf_collect_similarity(btf_ctx* c, int nsamples, int along, int metric, const int* over, int nover, const double* q, int nq,
+                           const int* nearest, int nnearest, const int* pairs, int npairs, double* mean_out, double* var_out,
+                           double* q_out, double* expected_out, double* rank_var_out, double* pnear_out, double* pair_out,
+                           double* dist_out, long long scratch_bytes) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior similarity arguments");
+  const SimOut o = {mean_out, var_out, q_out, expected_out, rank_var_out, pnear_out, pair_out, dist_out};
+  if (int rc = sim_check(c, nsamples, c->N, c->M, c->T, c->K, along, metric, over, nover, q, nq, nearest, nnearest, pairs, npairs, o,
+                         scratch_bytes)) return rc;
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_similarity", BTF_ESTATE, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  return sim_run(s, st.W, st.V, nsamples, c->N, c->M, c->T, c->K, along, metric, over, nover, q, nq, nearest, nnearest, pairs, npairs, o,
+                 scratch_bytes);
 }
 
 // ---------------------------------------------------------------- posterior feature association (btf_assoc.h)

@@ -310,6 +310,38 @@ def posterior_ranking(Ws, Vs, which="auc", along="cols", order="ascending", top=
                             pairs=pairs, pointwise=pointwise, Ws=Ws, Vs=Vs, device=device, _scratch_bytes=_scratch_bytes)
 
 
+def posterior_similarity(Ws, Vs, along="rows", metric="rms", over=None, q=(5, 95), nearest=(1, 5), pairs=None, pointwise=False,
+                         device=0, _scratch_bytes=0):
+    """Which rows (or columns) are alike: the distance between their fitted surfaces W V' per kept sample, summarised over
+    the samples, and every entity's neighbours with their probabilities, on the GPU, without a model: the stateless form of
+    BayesianTensorFiltering.posterior_similarity, next to posterior_ranking.
+
+    The embeddings themselves are identified only up to an invertible K x K map that differs from sample to sample; the
+    distance between two surfaces does not depend on it.  On the host this takes the quadratic form per sample, an (S,E,E)
+    array, np.percentile and an argsort per sample (functionalmf_amd.similarity.reference is exactly that, in numpy).
+
+    along="rows": the E = N rows are compared, each by its surface over the columns `over` (default: all) and all depths;
+    along="cols": the E = M columns, over the rows `over`.  metric="rms": the root-mean-square gap between the two surfaces
+    of the linear predictor w_i . v_jt; "cosine": 1 - the cosine of the angle between them (a zero surface is at distance 1
+    from everything but itself).  No transform= is offered: under a non-linear transform the distance is no quadratic form
+    in the embeddings any more.  Identical embeddings are at exactly 0, the result is symmetric bit for bit, the diagonal 0.
+    nearest: 1 to 8 distinct integers k >= 1.
+
+    Returns a dict: mean, var (E,E; ddof 1, nan for a single sample) and quantiles (len(q),E,E) of the distance over the
+    samples; expected_rank, rank_var (E,E) and p_nearest (len(nearest),E,E): out["p_nearest"][k, e, f] is the share of
+    samples in which f is among the nearest[k] nearest neighbours of e (ties to the smaller index, e itself last); along,
+    metric, nearest, nsamples, ncells.  pairs: a (P,2) integer array of (e, f) adds pair_values (S,P), the distances in
+    sample order; pointwise=True adds distances (S,E,E), refused above 1 GiB (use pairs=).  At most 8192 samples, 4096
+    entities and nembeds 10.  functionalmf_amd.similarity.embed(out) gives multidimensional-scaling coordinates.  There is
+    no CPU fallback."""
+    from . import _analysis, similarity
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    return similarity.evaluate(shape, K, S, along=along, metric=metric, over=over, q=q, nearest=nearest, pairs=pairs,
+                               pointwise=pointwise, Ws=Ws, Vs=Vs, device=device, _scratch_bytes=_scratch_bytes)
+
+
 def posterior_feature_association(Ws, Vs, Us, which="auc", stats=("r",), q=(5, 95), transform=None, x=None, level=None, pairs=None,
                                   of_means=True, device=0, _scratch_bytes=0):
     """Which row feature (biomarker) goes with which column's curve functional (drug sensitivity), with uncertainty, on the

@@ -641,6 +641,34 @@ int btf_collect_ranking(btf_ctx* ctx, int nsamples, int transform, int which, co
                         double* var_out, double* ptop_out, int* ranks_out, double* prob_less_out, double* prob_defined_out,
                         long long scratch_bytes);
 
+/* ---- posterior similarity (csrc/btf_similarity.h) ------------------------------------------------------------------------
+ * The distance between the fitted surfaces mu = W V' of two rows (along 0: E = nrows entities, each compared over the
+ * columns `over` and every depth) or two columns (along 1: E = ncols, over the rows `over`), per kept sample, and every
+ * entity's neighbours.  over: nover distinct indices, or NULL with nover 0 for all; n = (members of over) x ndepth cells.
+ * metric 0 (rms): d = sqrt(d2), n d2(e,f) = sum_t delta_t' Q delta_t with Q the K x K sum of the members' outer products
+ * and delta the difference of the entities' embeddings - the difference first, so identical embeddings give exactly 0, and
+ * d2 is clamped at 0.  metric 1 (cosine): d = 1 - <e,f> / sqrt(|e|^2 |f|^2), the ratio clamped to [-1, 1] and taken as 0
+ * where the product of the squared norms is 0.  d(e,f) and d(f,e) are the same bits and d(e,e) = 0 with both metrics.
+ * Over the samples: mean_out, var_out (E,E; ddof 1, nan when nsamples = 1) and q_out (nq,E,E), numpy's linear percentiles,
+ * of d.  Neighbours: within every (sample, e) the E entities are ranked by ascending key - d2 for rms, d for cosine - ties
+ * to the smaller index, e itself last; expected_out, rank_var_out (E,E) and pnear_out (nnearest,E,E) are the integer
+ * summaries of btf_posterior_ranking with nearest (1..8 distinct integers >= 1) in the place of top.  pairs: npairs (e,f)
+ * rows; pair_out (nsamples,npairs) their distances.  dist_out (nsamples,E,E) or NULL: every distance.  nembeds 1..10,
+ * E <= 4096 and nsamples <= 8192 (BTF_EINVAL beyond).  scratch_bytes: the cap of the staging buffer, which holds whole
+ * entities with all samples and partners (0: the default of the functionals; at least one entity is staged); the tiling
+ * cannot change a bit.  fp64, no floating-point atomics, every sum in a fixed order.  btf_collect_similarity reads the
+ * first nsamples collected slots without an upload and touches none of the sampler's state; its launches are counted under
+ * BTF_K_CRITERIA.  Synchronous.                                                                                          */
+int btf_posterior_similarity(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws,
+                             const double* Vs, int along, int metric, const int* over, int nover, const double* q, int nq,
+                             const int* nearest, int nnearest, const int* pairs, int npairs, double* mean_out, double* var_out,
+                             double* q_out, double* expected_out, double* rank_var_out, double* pnear_out, double* pair_out,
+                             double* dist_out, long long scratch_bytes);
+int btf_collect_similarity(btf_ctx* ctx, int nsamples, int along, int metric, const int* over, int nover, const double* q,
+                           int nq, const int* nearest, int nnearest, const int* pairs, int npairs, double* mean_out,
+                           double* var_out, double* q_out, double* expected_out, double* rank_var_out, double* pnear_out,
+                           double* pair_out, double* dist_out, long long scratch_bytes);
+
 /* ---- posterior feature association (csrc/btf_assoc.h) -------------------------------------------------------------------
  * The association between a row feature's probability and ONE curve functional across the rows, per kept sample: what
  * doseresponse/feature_importance.py:39-54 computes on posterior means only.  For kept sample s, feature f (Us (S,F,K):
