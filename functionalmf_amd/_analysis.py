@@ -8,7 +8,7 @@ the mixin BayesianTensorFiltering inherits its analysis methods from: each metho
 (`_unsharded`, the family hook of the model, its own arguments), resolves its samples in one place (`_samples`: the
 device-collected ones, or an uploaded run_gibbs result dict) and hands over to the `evaluate` of its feature module, the one
 caller of the C entry point.  The hooks that differ by likelihood (_crit_family, _pred_family, _pred_aux, _fold_family,
-_fold_cols_family) stay with the models in factor.py.
+_fold_cols_family, _fold_depth_family) stay with the models in factor.py.
 """
 import numpy as np
 
@@ -525,6 +525,61 @@ class PosteriorAnalysis:
         if Ws.ndim != 3 or Ws.shape[0] < 1 or Ws.shape[1:] != (self.nrows, self.nembeds):
             raise ValueError("results: Ws must be (S,%d,%d), got %r" % (self.nrows, self.nembeds, Ws.shape))
         return Ws.shape[0], Ws, None
+
+    # ---- folding new depth slices in (functionalmf_amd/fold_in_depth.py, csrc/btf_fold_in_depth.h) ----
+    def fold_in_depth(self, Y_new, horizon=None, results=None, seed=None, draws=None, sweeps=None, summary=True, q=(5, 95),
+                      transform=None, trials=None, first_sample=0):
+        """Curves of every fitted column at depths the chain never saw (new weeks of a series, a new dose), for every row,
+        with uncertainty, on the GPU (csrc/btf_fold_in_depth.h) and without another burn-in.  The trend-filtering prior
+        couples a new depth with the last tf_order + 1 kept depths of its column through penalty rows whose horseshoe+
+        local scales nobody has sampled; given a kept sample's W_s, V_s[j], nu2_s and lam2_s the H new depths of column j
+        and the scales of those rows form a small Gibbs chain: `sweeps` rounds (default:
+        functionalmf_amd.fold_in_depth.DEFAULT_SWEEPS) from the prior draw of the levels, one chain per (kept sample,
+        fitted column).  functionalmf_amd.fold_in_depth.chain is the definition in numpy.  The new data does not inform W,
+        the kept depths (the past is not smoothed) or the hyper-parameters; the new depths continue the fitted grid at
+        its spacing.  The Binomial model opens every round with Polya-Gamma draws from the current curve, starting at the
+        last kept depth.
+
+        Y_new: (N,M,H) or (N,M,H,nreps), NaN = missing; Binomial: the (Y, N) pair, or Y with trials= (default 1), counts
+            up to 32.  A column slice with no observation at all is allowed.  Y_new=None with horizon=H is the model's
+            FORECAST: no data at all, every chain runs on the prior given the kept curve (sweeps=1 is then an exact draw).
+            The forecast is honest but weak - fresh local scales on the low-order rows shrink the continuation towards
+            flat, and its curves are heavy-tailed: folding in even a few observed rows is what the call is for.
+        results: a run_gibbs result dict (W (S,N,K), V (S,M,T,K), lam2 one value per sample, Gaussian nu2 likewise),
+            uploaded (of V only the last min(T, tf_order + 1) depths); None: the samples the last device-collecting
+            run_gibbs left on the device - nothing but the new data is uploaded.
+        seed: None takes the model's next device seed (the model's draw counter moves on by one, as for any device draw);
+            an integer leaves the model untouched, and two calls with it return identical bits.
+        draws: optional (S,M,4 nR + sweeps (H K + 4 nR)) variates replacing the device generator (Gaussian only), per chain
+            in the layout of fold_in_depth.chain (fold_in_depth.random_draws builds one).
+        first_sample: the index of the first sample among the kept ones - with it a call over a slice of the samples
+            returns the bits of the whole call.
+
+        Returns a dict: V (S,M,H,K) one draw per kept sample; V_mean (S,M,H,K) the last conditional means (Gaussian only);
+        Tau2 (S,M,nR) the last local scales of the new penalty rows; with summary=True, mean (N,M,H) and quantiles
+        (len(q),N,M,H) of f(w_i^s . v_jt^s) from the summary kernel on the device-resident W and new V (transform as
+        posterior_summary; at most 16384 samples); nsamples.  np.concatenate([results["V"], out["V"]], axis=2) with
+        results["W"] goes straight into utils.posterior_summary, utils.posterior_predictive and
+        utils.posterior_functionals.  The sampler's state is not touched: a chain continued after the call walks the same
+        path.  Unsharded models.  A band beyond one workgroup's LDS (fold_in_depth.lds_bytes > LDS_LIMIT) is refused with
+        ValueError."""
+        from . import fold_in_depth as _fd
+        family = self._fold_depth_family()
+        self._unsharded("fold_in_depth")
+        N, M, T, K = self.nrows, self.ncols, self.ndepth, self.nembeds
+        H, weights, sums = _fd.slice_statistics(Y_new, family, N, M, trials=trials, horizon=horizon)
+        S, Ws, Vs = self._samples(results)
+        _fd.check_args(family, S, M, T, H, K, self.tf_order, draws, sweeps, summary, q, transform, first_sample)
+        nu2 = lam2 = None
+        if results is not None:
+            lam2 = check_scalars("results: lam2", results.get("lam2"), S)
+            if _fd.FAMILIES[family] == _fd.FAMILIES["gaussian"]:
+                nu2 = check_scalars("results: nu2", results.get("nu2"), S)
+        if seed is None:
+            seed = self._next_seed() if draws is None else 0
+        return _fd.evaluate(family, S, N, M, T, H, K, self.tf_order, weights, sums, draws=draws, seed=seed, sweeps=sweeps,
+                            summary=summary, q=q, transform=transform, first_sample=first_sample, stability=float(self.stability),
+                            ctx=self._ctx, Ws=Ws, Vs=Vs, nu2=nu2, lam2=lam2, device=self._ctx.device)
 
     def logprob(self, data, reduce="sum", **state):
         """Normalised log-likelihood of `data` under the current state, or under the state in W=, V= (and, Gaussian,

@@ -16,6 +16,7 @@
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
 #include "btf_slice_fold.h"     // the same for the slice-sampled models (kernels in btf_slice_fold.hip)
 #include "btf_fold_in_cols.h"   // folding new columns in (kernel in btf_fold_in_cols.hip)
+#include "btf_fold_in_depth.h"  // folding new depth slices in (kernel in btf_fold_in_depth.hip)
 #include "btf_slice_fold_cols.h"   // the same for the slice-sampled models (kernels in btf_slice_fold_cols.hip)
 
 #include <algorithm>
@@ -1573,6 +1574,203 @@ int btf_collect_fold_in_cols(btf_ctx* c, int family, int nsamples, int ncols_new
   Scratch s(c, c->stream);
   return fold_cols_run(s, c->smp_W, family == FOLDC_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT, c->smp_s + HYP_LAM2,
                        (int)HYP_COUNT, f, p);
+}
+
+// ---------------------------------------------------------------- folding new depth slices in (btf_fold_in_depth.h)
+namespace {
+struct FoldDepth {
+  int family, S, N, M, T, H, K, tf;
+  const double *count, *ysum, *trials, *draws;
+  unsigned long long seed;
+  int sweeps;
+  long long sample0;
+  double stability;
+  double *V_out, *Vmean_out, *Tau2_out;
+  int transform;
+  const double* q; int nq;
+  double *mean_out, *q_out;
+};
+
+// the new rows of the penalty on T + H points on the host: every row as (first depth counted from the first new one,
+// tf + 2 coefficients from there on), and the D_n' D_n stencil per (t, d) as CSR over the new rows
+struct FoldDepthPenalty {
+  int nR = 0, L = 0;
+  std::vector<double> rcoef, coef;
+  std::vector<int> rcol0, ptr, row;
+};
+
+// everything that can be refused without a device; fills the penalty
+int fold_depth_check(btf_ctx* c, const FoldDepth& f, FoldDepthPenalty& p) {
+  if (f.family < FOLDD_GAUSSIAN || f.family > FOLDD_BINOMIAL || f.S < 1 || f.M < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 ||
+      f.T < 2 || f.H < 1 || !f.ysum || !f.V_out || !f.Vmean_out || !f.Tau2_out || f.sample0 < 0 || f.nq < 0 ||
+      (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2 || !(f.stability > 0.0 && f.stability <= 1.0))
+    return fail(c, BTF_EINVAL, "bad fold_in_depth arguments");
+  if (f.family == FOLDD_GAUSSIAN && !f.count) return fail(c, BTF_EINVAL, "fold_in_depth: the Gaussian family needs count");
+  if (f.family == FOLDD_BINOMIAL && (!f.trials || f.draws))
+    return fail(c, BTF_EINVAL, "fold_in_depth: the Binomial family needs trials and takes no draws");
+  if (f.sweeps < 1 || (unsigned long long)f.sweeps >= FOLDD_PG_SLOT) return fail(c, BTF_EINVAL, "fold_in_depth: sweeps must be in 1..2^20 - 2");
+  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "fold_in_depth: the half bandwidth (tf_order + 1) nembeds must stay below 64");
+  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "fold_in_depth: the summary stage takes at most 16384 samples");
+  if ((double)(f.sample0 + f.S) * f.M >= 2147483647.0 || (double)f.M * f.N * f.H >= 2147483647.0 ||
+      (double)f.sweeps * f.N * f.H >= 9.0e15)
+    return fail(c, BTF_EINVAL, "fold_in_depth: (sample0 + nsamples) * ncols and ncols * nrows * horizon must stay below 2^31");
+  if ((double)f.T + f.H > (double)FOLDD_MAX_GRID)        // (the penalty on the extended grid is built dense on the host)
+    return fail(c, BTF_EINVAL, "fold_in_depth: ndepth + horizon must stay within " + std::to_string(FOLDD_MAX_GRID));
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  // a band this wide is refused whatever the rows are (3 H + 2 bounds them from above only for tf <= 2: count them below)
+  if (foldd_lds_bytes(f.H, f.K, f.tf, f.H, 1) > FOLDD_LDS_LIMIT)
+    return fail(c, BTF_EINVAL, "fold_in_depth: the band of the new depths needs more than the LDS limit of " + std::to_string(FOLDD_LDS_LIMIT) + " bytes");
+  const int TH = f.T + f.H, D1 = f.tf + 2;
+  std::vector<double> Delta; std::vector<int> ptr0, row0; std::vector<double> coef0; int nD = 0;
+  penalty_stencil(TH, f.tf, Delta, nD, ptr0, row0, coef0);
+  p.L = std::min(f.T, f.tf + 1);
+  p.rcol0.clear(); p.rcoef.clear();
+  for (int r = 0; r < nD; ++r) {
+    int lo = TH, hi = -1;
+    for (int t = 0; t < TH; ++t)
+      if (Delta[(size_t)r * TH + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
+    if (hi < f.T) continue;                                      // a row on kept depths alone (or an empty one)
+    if (hi - lo >= D1 || lo < f.T - p.L) return fail(c, BTF_EINVAL, "fold_in_depth: penalty row wider than the band");
+    p.rcol0.push_back(lo - f.T);
+    for (int e = 0; e < D1; ++e) p.rcoef.push_back(lo + e <= hi ? Delta[(size_t)r * TH + lo + e] : 0.0);
+  }
+  p.nR = (int)p.rcol0.size();
+  if (p.nR < 1) return fail(c, BTF_EINVAL, "fold_in_depth: no penalty row touches the new depths");
+  const size_t lds = foldd_lds_bytes(f.H, f.K, f.tf, p.nR, p.L);
+  if (lds > FOLDD_LDS_LIMIT)
+    return fail(c, BTF_EINVAL, "fold_in_depth: the band of the new depths needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
+                                   std::to_string(FOLDD_LDS_LIMIT));
+  // D_n[r][t] = rcoef[r][t - rcol0[r]] inside the row's window
+  auto dn = [&](int r, int t) {
+    const int e = t - p.rcol0[r];
+    return e >= 0 && e < D1 ? p.rcoef[(size_t)r * D1 + e] : 0.0;
+  };
+  p.ptr.assign((size_t)f.H * D1 + 1, 0); p.row.clear(); p.coef.clear();
+  for (int t = 0; t < f.H; ++t)
+    for (int d = 0; d < D1; ++d) {
+      if (t + d < f.H)
+        for (int r = 0; r < p.nR; ++r) {
+          const double pr = dn(r, t) * dn(r, t + d);
+          if (pr != 0.0) { p.row.push_back(r); p.coef.push_back(pr); }
+        }
+      p.ptr[(size_t)t * D1 + d + 1] = (int)p.row.size();
+    }
+  const size_t ncell = (size_t)f.M * f.H * f.N;
+  const double* cw = f.family == FOLDD_GAUSSIAN ? f.count : f.trials;
+  for (size_t e = 0; e < ncell; ++e) {
+    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(f.ysum[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, "fold_in_depth: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
+    if (f.family == FOLDD_BINOMIAL && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLDD_MAX_TRIALS))
+      return fail(c, BTF_EINVAL, "fold_in_depth: Binomial trial counts must be integers up to " + std::to_string(FOLDD_MAX_TRIALS));
+  }
+  if (f.draws) {
+    const size_t n = (size_t)f.H * f.K, per = n + 4 * (size_t)p.nR, L = 4 * (size_t)p.nR + (size_t)f.sweeps * per;
+    for (size_t ch = 0; ch < (size_t)f.S * f.M; ++ch) {
+      const double* d = f.draws + ch * L;
+      for (size_t e = 0; e < L; ++e) {
+        const bool normal = e >= 4 * (size_t)p.nR && (e - 4 * (size_t)p.nR) % per < n;
+        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)))
+          return fail(c, BTF_EINVAL, "fold_in_depth: draws must be finite, its gamma variates positive");
+      }
+    }
+  }
+  return BTF_OK;
+}
+
+// The launches on device states dW (S,N,K), the kept tails (tail of (s, j) at dVt[(s M + j) vstride], L x K) and per-sample
+// scalars on the device (noise null: the Binomial family).  The scratch's context may be null (the stateless form).  The new
+// V stays on the device between the chains and the summary.
+int fold_depth_run(Scratch& s, const double* dW, const double* dVt, long long vstride, const double* dnoise, int nstride,
+                   const double* dlam, int lstride, const FoldDepth& f, const FoldDepthPenalty& p) {
+  btf_ctx* c = s.ctx();
+  const int S = f.S, M = f.M, N = f.N, H = f.H, K = f.K, nR = p.nR;
+  FoldDepthKernel kern = fold_depth_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, "fold_in_depth: nembeds must be 1..10 and family 0..1");
+  // the slice statistics lie [column][depth][row] as the kernel reads them; Binomial: kappa = successes - trials / 2
+  const size_t ncell = (size_t)M * H * N;
+  const double* cw = f.family == FOLDD_GAUSSIAN ? f.count : f.trials;
+  std::vector<double> hy(ncell);
+  for (size_t e = 0; e < ncell; ++e)
+    hy[e] = cw[e] > 0.0 ? (f.family == FOLDD_BINOMIAL ? f.ysum[e] - 0.5 * cw[e] : f.ysum[e]) : 0.0;
+  const size_t nV = (size_t)S * M * H * K, nT = (size_t)S * M * nR;
+  const size_t LD = 4 * (size_t)nR + (size_t)f.sweeps * ((size_t)H * K + 4 * (size_t)nR);
+  const int stat0[2] = {0, INT_MAX};
+  FoldDepthArgs a = {};
+  a.W = dW; a.Vtail = dVt; a.vstride = vstride; a.noise = dnoise; a.lam2 = dlam; a.nstride = nstride; a.lstride = lstride;
+  a.cnt = s.upload(cw, ncell); a.ysum = s.upload(hy.data(), ncell);
+  if (f.draws) a.draws = s.upload(f.draws, (size_t)S * M * LD);
+  a.rcol0 = s.upload(p.rcol0.data(), p.rcol0.size()); a.rcoef = s.upload(p.rcoef.data(), p.rcoef.size());
+  a.st_ptr = s.upload(p.ptr.data(), p.ptr.size());
+  // (a prior that couples nothing - H = 1 rows only - still has its diagonal entries: row and coef are never empty)
+  a.st_row = s.upload(p.row.data(), p.row.size()); a.st_coef = s.upload(p.coef.data(), p.coef.size());
+  a.V = s.alloc<double>(nV); a.Vmean = s.alloc<double>(nV); a.Tau2 = s.alloc<double>(nT);
+  a.status = s.upload(stat0, 2);
+  a.seed = f.seed; a.sample0 = f.sample0; a.lo = f.stability; a.hi = 1.0 / f.stability;
+  a.S = S; a.M = M; a.N = N; a.H = H; a.L = p.L; a.tf = f.tf; a.nR = nR; a.sweeps = f.sweeps;
+  const size_t lds = foldd_lds_bytes(H, K, f.tf, nR, p.L);
+  allow_lds(s, kern, lds);
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3((unsigned)((size_t)S * M)), dim3(WAVE), lds, a);
+  // the summary stage reads the device-resident W (S,N,K) and the new V (S,M*H,K)
+  if (f.mean_out) summary_stage(s, dW, a.V, S, N, M * H, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
+  int stat[2] = {0, INT_MAX};
+  s.download(stat, a.status, 2);
+  s.download(f.V_out, a.V, nV);
+  s.download(f.Vmean_out, a.Vmean, nV);
+  s.download(f.Tau2_out, a.Tau2, nT);
+  const int rc = s.finish();
+  if (rc) return rc;
+  if (stat[0]) {
+    if (c) c->fail_index = stat[1];
+    g_fold_fail_index = stat[1];
+    return fail(c, BTF_ESTATE, "fold_in_depth: the precision of (sample, column) index " + std::to_string(stat[1]) +
+                                   " = sample * ncols + column is not positive definite (or W / V / nu2 / lam2 not finite); its outputs are nan");
+  }
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_fold_in_depth(int device, int family, int nsamples, int nrows, int ncols, int ndepth, int horizon, int nembeds,
+                      int tf_order, const double* Ws, const double* Vtail, const double* noise, const double* lam2,
+                      const double* count, const double* ysum, const double* trials, const double* draws, unsigned long long seed,
+                      int sweeps, long long sample0, double stability, double* V_out, double* Vmean_out, double* Tau2_out,
+                      int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  const FoldDepth f = {family, nsamples, nrows, ncols, ndepth, horizon, nembeds, tf_order, count, ysum, trials, draws, seed, sweeps,
+                       sample0, stability, V_out, Vmean_out, Tau2_out, transform, q, nq, mean_out, q_out};
+  g_fold_fail_index = -1;
+  if (!Ws || !Vtail || !lam2 || (family == FOLDD_GAUSSIAN && !noise)) return fail(nullptr, BTF_EINVAL, "bad fold_in_depth arguments");
+  FoldDepthPenalty p;
+  if (int rc = fold_depth_check(nullptr, f, p)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(lam2[s] > 0.0 && lam2[s] < INFINITY) || (family == FOLDD_GAUSSIAN && !(noise[s] > 0.0 && noise[s] < INFINITY)))
+      return fail(nullptr, BTF_EINVAL, "fold_in_depth: nu2 and lam2 must be finite and positive");
+  const size_t ntail = (size_t)nsamples * ncols * p.L * nembeds;
+  if (!all_finite(Vtail, ntail)) return fail(nullptr, BTF_EINVAL, "fold_in_depth: the kept curves must be finite");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dVt = s.upload(Vtail, ntail);
+  const double* dl = s.upload(lam2, (size_t)nsamples);
+  const double* dn = family == FOLDD_GAUSSIAN ? s.upload(noise, (size_t)nsamples) : nullptr;
+  return fold_depth_run(s, dW, dVt, (long long)p.L * nembeds, dn, 1, dl, 1, f, p);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload): W and the last depths of V from the
+// sample slots, nu2_s and lam2_s from the collected scalars
+int btf_collect_fold_in_depth(btf_ctx* c, int family, int nsamples, int horizon, const double* count, const double* ysum,
+                              const double* trials, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                              double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
+                              int nq, double* mean_out, double* q_out) {
+  if (!c) return fail(c, BTF_EINVAL, "bad fold_in_depth arguments");
+  const FoldDepth f = {family, nsamples, c->N, c->M, c->T, horizon, c->K, c->TF, count, ysum, trials, draws, seed, sweeps, sample0,
+                       stability, V_out, Vmean_out, Tau2_out, transform, q, nq, mean_out, q_out};
+  FoldDepthPenalty p;
+  if (int rc = fold_depth_check(c, f, p)) return rc;
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_collect_fold_in_depth needs an unsharded context");
+  if (!has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, "btf_collect_fold_in_depth");
+  HIPCHK(c, hipSetDevice(c->dev));
+  Scratch s(c, c->stream);
+  return fold_depth_run(s, c->smp_W, c->smp_V + (size_t)(c->T - p.L) * c->K, (long long)c->T * c->K,
+                        family == FOLDD_GAUSSIAN ? c->smp_s + HYP_NU2 : nullptr, (int)HYP_COUNT, c->smp_s + HYP_LAM2, (int)HYP_COUNT, f, p);
 }
 
 // ---------------------------------------------------------------- convergence diagnostics (btf_diag.h)

@@ -692,6 +692,10 @@ class BayesianTensorFiltering(PosteriorAnalysis, _BayesianModel):
         """Family name of fold_in_cols for this model's likelihood."""
         raise NotImplementedError("%s: fold_in_cols needs a conjugate column conditional (Gaussian and Binomial models)" % type(self).__name__)
 
+    def _fold_depth_family(self):
+        """Family name of fold_in_depth for this model's likelihood."""
+        raise NotImplementedError("%s: fold_in_depth needs a conjugate column conditional (Gaussian and Binomial models)" % type(self).__name__)
+
     # ---- the two half-sweeps (device) ----------------------------------------------
     def _w_normals(self):
         if self.rng != "host":
@@ -862,6 +866,9 @@ class GaussianBayesianTensorFiltering(BayesianTensorFiltering):
         return "gaussian"
 
     def _fold_cols_family(self):
+        return "gaussian"
+
+    def _fold_depth_family(self):
         return "gaussian"
 
     def _upload(self, Y):
@@ -1111,6 +1118,9 @@ class BinomialBayesianTensorFiltering(GaussianBayesianTensorFiltering):
     def _fold_cols_family(self):
         return "binomial"
 
+    def _fold_depth_family(self):
+        return "binomial"
+
     def _set_noise(self):
         if getattr(self, "_omega_host_new", False) and np.ndim(self._nu2) == 3:
             with np.errstate(divide='ignore'):
@@ -1176,6 +1186,10 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
     def _fold_cols_family(self):
         raise NotImplementedError("fold_in_cols for the Negative-Binomial model: the pseudo-trial counts y + R of a new column depend "
                                   "on the sampled rate R, which this call does not read (not supported yet)")
+
+    def _fold_depth_family(self):
+        raise NotImplementedError("fold_in_depth for the Negative-Binomial model: the pseudo-trial counts y + R of a new depth slice "
+                                  "depend on the sampled rate R, which this call does not read (not supported yet)")
 
     def _pred_aux(self, results, nsamples):
         """The rate tensor of every sample: results['R'] (S,) + rate shape, else the current R for all of them."""
@@ -1568,6 +1582,14 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
     def _fold_cols_family(self):
         raise NotImplementedError("%s: fold_in_cols needs the conjugate column conditional of the Gaussian and Binomial models; "
                                   "a slice-sampled column has no closed-form draw: slice_fold_in_cols folds columns into this model" % type(self).__name__)
+
+    def _fold_depth_family(self):
+        if self._callback:
+            raise NotImplementedError("%s: fold_in_depth needs a device likelihood with a conjugate column conditional; a "
+                                      "Python-callable loglikelihood is evaluated on the host only" % type(self).__name__)
+        raise NotImplementedError("%s: fold_in_depth needs the conjugate column conditional of the Gaussian and Binomial models; "
+                                  "new depths of a slice-sampled model have no closed-form draw (a slice_fold_in_depth is not "
+                                  "written yet)" % type(self).__name__)
 
     def _slice_fold_restrictions(self, row_features, R, results, S):
         """(Constraints, Row_constraints, codes (R,F) or None, Us (S,F,K) or None) of a slice_fold_in_rows call."""

@@ -450,6 +450,38 @@ def fold_in_cols(Y_new, Ws, family, nu2=None, lam2=None, tf_order=2, seed=0, dra
                         device=device)
 
 
+def fold_in_depth(Y_new, Ws, Vs, family, horizon=None, nu2=None, lam2=None, tf_order=2, seed=0, draws=None, sweeps=None, summary=True,
+                  q=(5, 95), transform=None, trials=None, first_sample=0, stability=1e-6, device=0):
+    """Curves of every fitted column at depths the chain never saw, one short Gibbs chain per (kept sample, fitted column),
+    on the GPU, without a model: the stateless form of BayesianTensorFiltering.fold_in_depth (see there for the method and
+    the outputs).
+
+    Ws (S,N,K) and Vs (S,M,T,K): the kept samples (of Vs only the last min(T, tf_order + 1) depths are uploaded); family
+    "gaussian" (nu2 and lam2: one value per sample) or "binomial" (lam2); tf_order and stability as the model was built
+    with.  Y_new: (N,M,H) or (N,M,H,nreps) with NaN = missing; Binomial: a (Y, N) pair of (N,M,H) arrays, or Y with trials=
+    (default 1), counts up to 32; None with horizon=H: the forecast (no data).  draws: optional (S,M,4 nR + sweeps (H K +
+    4 nR)) variates in the place of the device generator (Gaussian only).  first_sample: the index of Ws[0] among the kept
+    samples - with it a call over a slice of the samples returns the bits of the whole call.  Ws with
+    np.concatenate([Vs, out["V"]], axis=2) goes straight into posterior_summary, posterior_predictive and
+    posterior_functionals.  functionalmf_amd.fold_in_depth.chain is the definition in numpy.  There is no CPU fallback."""
+    from . import _analysis, fold_in_depth as _fd
+    code = _fd.family_code(family)
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, M, T, K = Vs.shape
+    N = Ws.shape[1]
+    H, weights, sums = _fd.slice_statistics(Y_new, family, N, M, trials=trials, horizon=horizon)
+    _fd.check_args(family, S, M, T, H, K, tf_order, draws, sweeps, summary, q, transform, first_sample)
+    lam2 = _analysis.check_scalars("lam2", lam2, S)
+    nu2 = _analysis.check_scalars("nu2", nu2, S) if code == _fd.FAMILIES["gaussian"] else None
+    if not 0 < float(stability) <= 1:
+        raise ValueError("stability must lie in (0, 1]")
+    if not np.all(np.isfinite(Vs[:, :, T - _fd.tail_depths(T, tf_order):])):
+        raise ValueError("Vs must be finite at the last kept depths")
+    return _fd.evaluate(family, S, N, M, T, H, K, tf_order, weights, sums, draws=draws, seed=seed, sweeps=sweeps, summary=summary,
+                        q=q, transform=transform, first_sample=first_sample, stability=stability, Ws=Ws, Vs=Vs, nu2=nu2, lam2=lam2,
+                        device=device)
+
+
 def slice_fold_in_rows(Y_new, Vs, family, sigma2=None, Ws=None, likelihood_param=None, Constraints=None, Row_constraints=None,
                        row_features=None, Us=None, start=None, seed=0, draws=None, sweeps=None, max_rounds=40, summary=True,
                        q=(5, 95), transform=None, first_sample=0, device=0):

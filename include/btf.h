@@ -814,6 +814,35 @@ int btf_collect_fold_in_cols(btf_ctx* ctx, int family, int nsamples, int ncols_n
                              double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
                              int nq, double* mean_out, double* q_out);
 
+/* ---- folding new depth slices into a fitted posterior (csrc/btf_fold_in_depth.h) ---------------------------------------
+ * The curves of every fitted column at `horizon` depths the chain never saw, one short Gibbs chain per (kept sample s,
+ * fitted column j) over the new depths v (H,K) and the horseshoe+ levels of the nR rows of the penalty on ndepth + horizon
+ * points that touch a new depth, given W_s, the last min(ndepth, tf_order + 1) depths of V_s[j], nu2_s and lam2_s;
+ * functionalmf_amd/fold_in_depth.py (`chain`) is the definition.  family 0 (Gaussian: count, ysum = observed replicates and
+ * their sum, noise (S,) = nu2_s) or 1 (Binomial: trials, ysum = successes, integer counts up to 32, 0 = missing;
+ * Polya-Gamma rounds from v_t = V_s[j, ndepth - 1]).  The new data lies [column][depth][row]: (M,H,N); a slice of all
+ * zeros is the model's forecast.  Ws (S,N,K); Vtail (S,M,min(ndepth, tf_order + 1),K): the last kept depths; lam2 (S,).
+ * draws (S,M,4 nR + sweeps (H K + 4 nR)), Gaussian only: every variate of every chain - the start's unit Gamma(1/2)
+ * variates (4,nR), then per sweep H K standard normals and (4,nR) unit gammas - or NULL: Philox keyed (seed,
+ * (sample0 + s) << 32 | j, slot, element), so splitting the samples over calls returns identical bits.  stability: the
+ * clip of the level updates.  V_out, Vmean_out (S,M,H,K): the last state and the last conditional mean; Tau2_out
+ * (S,M,nR).  mean_out non-NULL adds the summary stage on the device-resident W and new V: mean (N,M,H) and q_out
+ * (nq,N,M,H) of f(w_i^s . v_jt^s) exactly as btf_posterior_summary (nsamples <= 16384 then).  The band of the H K wide
+ * system and its side arrays must fit one workgroup's LDS: BTF_EINVAL otherwise, before any device call.  A non-positive
+ * pivot: that chain's outputs are nan, the call returns BTF_ESTATE, and btf_fail_index (ctx, or NULL after the stateless
+ * call) = (sample0 + s) * ncols + j of the first such chain.  fp64, no floating-point atomics, every sum in a fixed order.
+ * btf_collect_fold_in_depth reads W, the tail of V, nu2_s and lam2_s of the first nsamples collected slots without an
+ * upload and touches none of the sampler's state; its launches are counted under BTF_K_CRITERIA.  Synchronous.          */
+int btf_fold_in_depth(int device, int family, int nsamples, int nrows, int ncols, int ndepth, int horizon, int nembeds,
+                      int tf_order, const double* Ws, const double* Vtail, const double* noise, const double* lam2,
+                      const double* count, const double* ysum, const double* trials, const double* draws, unsigned long long seed,
+                      int sweeps, long long sample0, double stability, double* V_out, double* Vmean_out, double* Tau2_out,
+                      int transform, const double* q, int nq, double* mean_out, double* q_out);
+int btf_collect_fold_in_depth(btf_ctx* ctx, int family, int nsamples, int horizon, const double* count, const double* ysum,
+                              const double* trials, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                              double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
+                              int nq, double* mean_out, double* q_out);
+
 /* ---- folding new columns into a slice-sampled fit (csrc/btf_slice_fold_cols.h) ---------------------------------------
  * The same for the slice-sampled models: one chain per (kept sample s, new column c) over the column's curve v (T,K) and
  * its horseshoe+ levels given W_s and lam2_s, the curve updated by elliptical slice sampling on an ellipse centred on a
