@@ -22,7 +22,7 @@ UNITS = [(os.path.join(CSRC, "btf_%s.hip" % name), suffix) for name, suffix in [
     ("fold_in", "_fold_in.o"), ("loo", "_loo.o"), ("ranking", "_ranking.o"), ("assoc", "_assoc.o"), ("monotone", "_monotone.o"),
     ("gg_criteria", "_gg_criteria.o"), ("gg_predict", "_gg_predict.o"), ("slice_fold", "_slice_fold.o"),
     ("nb_criteria", "_nb_criteria.o"), ("fold_in_cols", "_fold_in_cols.o"), ("slice_fold_cols", "_slice_fold_cols.o"),
-    ("similarity", "_similarity.o"), ("fold_in_depth", "_fold_in_depth.o")]]
+    ("similarity", "_similarity.o"), ("fold_in_depth", "_fold_in_depth.o"), ("slice_fold_depth", "_slice_fold_depth.o")]]
 SOURCES = [src for src, _ in UNITS]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
     [os.path.join(ROOT, "include", "btf.h")]
@@ -141,6 +141,13 @@ SIGNATURES = {
                                                                                                C.c_int, C.c_int64, C.c_double, _c_dp, _c_dp,
                                                                                                _c_dp, _c_ip, _c_ip, C.c_int, _c_dp, C.c_int,
                                                                                                _c_dp, _c_dp]),
+    "btf_slice_fold_depth": (C.c_int, [C.c_int, C.c_int, C.c_double, _c_dp, _c_dp, _c_dp] + [C.c_int] * 8 + [_c_dp] * 10 +
+                             [C.c_int, C.c_int, _c_dp, _c_dp, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_double, _c_dp, _c_dp, _c_dp,
+                              _c_ip, _c_ip, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),
+    "btf_collect_slice_fold_depth": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [_c_dp] * 7 + [C.c_int, C.c_int, _c_dp, _c_dp, C.c_uint64,
+                                                                                                C.c_int, C.c_int, C.c_int64, C.c_double,
+                                                                                                _c_dp, _c_dp, _c_dp, _c_ip, _c_ip, C.c_int,
+                                                                                                _c_dp, C.c_int, _c_dp, _c_dp]),
     "btf_diag_eval": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_c_dp), C.POINTER(_c_dp),
                                 C.POINTER(_ctx), C.c_int, _c_dp]),
     "btf_collect_begin": (C.c_int, [_ctx, C.c_int]),

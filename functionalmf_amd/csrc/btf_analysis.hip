@@ -18,6 +18,7 @@
 #include "btf_fold_in_cols.h"   // folding new columns in (kernel in btf_fold_in_cols.hip)
 #include "btf_fold_in_depth.h"  // folding new depth slices in (kernel in btf_fold_in_depth.hip)
 #include "btf_slice_fold_cols.h"   // the same for the slice-sampled models (kernels in btf_slice_fold_cols.hip)
+#include "btf_slice_fold_depth.h"  // new depth slices for the slice-sampled models (kernels in btf_slice_fold_depth.hip)
 
 #include <algorithm>
 #include <climits>
@@ -1599,6 +1600,42 @@ struct FoldDepthPenalty {
   std::vector<int> rcol0, ptr, row;
 };
 
+// fills the penalty of H new depths behind T kept ones (shared with slice_fold_depth_check); `name` opens the messages
+int fold_depth_rows(btf_ctx* c, const char* name, int T, int H, int tf, FoldDepthPenalty& p) {
+  const int TH = T + H, D1 = tf + 2;
+  std::vector<double> Delta; std::vector<int> ptr0, row0; std::vector<double> coef0; int nD = 0;
+  penalty_stencil(TH, tf, Delta, nD, ptr0, row0, coef0);
+  p.L = std::min(T, tf + 1);
+  p.rcol0.clear(); p.rcoef.clear();
+  for (int r = 0; r < nD; ++r) {
+    int lo = TH, hi = -1;
+    for (int t = 0; t < TH; ++t)
+      if (Delta[(size_t)r * TH + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
+    if (hi < T) continue;                                        // a row on kept depths alone (or an empty one)
+    if (hi - lo >= D1 || lo < T - p.L) return fail(c, BTF_EINVAL, std::string(name) + ": penalty row wider than the band");
+    p.rcol0.push_back(lo - T);
+    for (int e = 0; e < D1; ++e) p.rcoef.push_back(lo + e <= hi ? Delta[(size_t)r * TH + lo + e] : 0.0);
+  }
+  p.nR = (int)p.rcol0.size();
+  if (p.nR < 1) return fail(c, BTF_EINVAL, std::string(name) + ": no penalty row touches the new depths");
+  // D_n[r][t] = rcoef[r][t - rcol0[r]] inside the row's window
+  auto dn = [&](int r, int t) {
+    const int e = t - p.rcol0[r];
+    return e >= 0 && e < D1 ? p.rcoef[(size_t)r * D1 + e] : 0.0;
+  };
+  p.ptr.assign((size_t)H * D1 + 1, 0); p.row.clear(); p.coef.clear();
+  for (int t = 0; t < H; ++t)
+    for (int d = 0; d < D1; ++d) {
+      if (t + d < H)
+        for (int r = 0; r < p.nR; ++r) {
+          const double pr = dn(r, t) * dn(r, t + d);
+          if (pr != 0.0) { p.row.push_back(r); p.coef.push_back(pr); }
+        }
+      p.ptr[(size_t)t * D1 + d + 1] = (int)p.row.size();
+    }
+  return BTF_OK;
+}
+
 // everything that can be refused without a device; fills the penalty
 int fold_depth_check(btf_ctx* c, const FoldDepth& f, FoldDepthPenalty& p) {
   if (f.family < FOLDD_GAUSSIAN || f.family > FOLDD_BINOMIAL || f.S < 1 || f.M < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 ||
@@ -1620,41 +1657,11 @@ int fold_depth_check(btf_ctx* c, const FoldDepth& f, FoldDepthPenalty& p) {
   // a band this wide is refused whatever the rows are (3 H + 2 bounds them from above only for tf <= 2: count them below)
   if (foldd_lds_bytes(f.H, f.K, f.tf, f.H, 1) > FOLDD_LDS_LIMIT)
     return fail(c, BTF_EINVAL, "fold_in_depth: the band of the new depths needs more than the LDS limit of " + std::to_string(FOLDD_LDS_LIMIT) + " bytes");
-  const int TH = f.T + f.H, D1 = f.tf + 2;
-  std::vector<double> Delta; std::vector<int> ptr0, row0; std::vector<double> coef0; int nD = 0;
-  penalty_stencil(TH, f.tf, Delta, nD, ptr0, row0, coef0);
-  p.L = std::min(f.T, f.tf + 1);
-  p.rcol0.clear(); p.rcoef.clear();
-  for (int r = 0; r < nD; ++r) {
-    int lo = TH, hi = -1;
-    for (int t = 0; t < TH; ++t)
-      if (Delta[(size_t)r * TH + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
-    if (hi < f.T) continue;                                      // a row on kept depths alone (or an empty one)
-    if (hi - lo >= D1 || lo < f.T - p.L) return fail(c, BTF_EINVAL, "fold_in_depth: penalty row wider than the band");
-    p.rcol0.push_back(lo - f.T);
-    for (int e = 0; e < D1; ++e) p.rcoef.push_back(lo + e <= hi ? Delta[(size_t)r * TH + lo + e] : 0.0);
-  }
-  p.nR = (int)p.rcol0.size();
-  if (p.nR < 1) return fail(c, BTF_EINVAL, "fold_in_depth: no penalty row touches the new depths");
+  if (int rc = fold_depth_rows(c, "fold_in_depth", f.T, f.H, f.tf, p)) return rc;
   const size_t lds = foldd_lds_bytes(f.H, f.K, f.tf, p.nR, p.L);
   if (lds > FOLDD_LDS_LIMIT)
     return fail(c, BTF_EINVAL, "fold_in_depth: the band of the new depths needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
                                    std::to_string(FOLDD_LDS_LIMIT));
-  // D_n[r][t] = rcoef[r][t - rcol0[r]] inside the row's window
-  auto dn = [&](int r, int t) {
-    const int e = t - p.rcol0[r];
-    return e >= 0 && e < D1 ? p.rcoef[(size_t)r * D1 + e] : 0.0;
-  };
-  p.ptr.assign((size_t)f.H * D1 + 1, 0); p.row.clear(); p.coef.clear();
-  for (int t = 0; t < f.H; ++t)
-    for (int d = 0; d < D1; ++d) {
-      if (t + d < f.H)
-        for (int r = 0; r < p.nR; ++r) {
-          const double pr = dn(r, t) * dn(r, t + d);
-          if (pr != 0.0) { p.row.push_back(r); p.coef.push_back(pr); }
-        }
-      p.ptr[(size_t)t * D1 + d + 1] = (int)p.row.size();
-    }
   const size_t ncell = (size_t)f.M * f.H * f.N;
   const double* cw = f.family == FOLDD_GAUSSIAN ? f.count : f.trials;
   for (size_t e = 0; e < ncell; ++e) {
@@ -2010,6 +2017,235 @@ int btf_collect_slice_fold_cols(btf_ctx* c, int family, int nsamples, int ncols_
   Scratch s(c, c->stream); States st;
   if (int rc = resolve_pair(s, 0, "btf_collect_slice_fold_cols", BTF_ESTATE, nsamples, 0, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
   return slice_fold_cols_run(s, st.W, st.V, c->M, c->smp_s + HYP_LAM2, (int)HYP_COUNT, c->gg_tab, c->gg_G, c->gg_lsp, f, p);
+}
+
+// ---------------------------------------------------------------- folding new depth slices into a slice-sampled fit (btf_slice_fold_depth.h)
+namespace {
+struct SliceFoldDepth {
+  int family; double param;
+  int S, N, M, T, H, K, tf;
+  const double *start, *S1, *cnt, *L, *fa, *fb;
+  const double* cons; int J, B;          // the reduced constraints (J, B + H + 1): B trailing kept depths, the H new ones, the bound
+  const double *tau2, *draws;
+  unsigned long long seed;
+  int sweeps, max_rounds;
+  long long sample0;
+  double stability;
+  double *V_out, *Vstart_out, *Tau2_out; int *rounds_out, *unf_out;
+  int transform;
+  const double* q; int nq;
+  double *mean_out, *q_out;
+};
+
+// kept depths the chain reads: the prior's min(T, tf + 1), or the B the constraints reach back
+int slice_fold_depth_tail(const SliceFoldDepth& f) { return std::max(std::min(f.T, f.tf + 1), f.B); }
+
+// everything that can be refused without a device; fills the penalty
+int slice_fold_depth_check(btf_ctx* c, const SliceFoldDepth& f, FoldDepthPenalty& p) {
+  if (f.family < 0 || f.family >= ESS_FAM_COUNT || f.S < 1 || f.M < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 || f.T < 2 ||
+      f.H < 1 || !f.S1 || !f.cnt || !f.fa || !f.fb || !f.V_out || !f.Tau2_out || !f.rounds_out || !f.unf_out || f.sample0 < 0 ||
+      f.nq < 0 || (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2 || f.J < 0 ||
+      (f.J > 0 && !f.cons) || f.B < 0 || f.B > f.T || (f.J == 0 && f.B != 0) || !(f.stability > 0.0 && f.stability <= 1.0))
+    return fail(c, BTF_EINVAL, "bad slice_fold_depth arguments");
+  if (f.sweeps < 1 || f.sweeps >= (1 << 20) - 1 || f.max_rounds < 1 || f.max_rounds > 65536)
+    return fail(c, BTF_EINVAL, "slice_fold_depth: sweeps in 1..2^20 - 2 and max_rounds in 1..65536");
+  if (f.family == ESS_FAM_GAMMA_GRID && !f.L) return fail(c, BTF_EINVAL, "slice_fold_depth: the gamma-grid family needs logsum");
+  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "slice_fold_depth: the half bandwidth (tf_order + 1) nembeds must stay below 64");
+  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "slice_fold_depth: the summary stage takes at most 16384 samples");
+  if ((double)(f.sample0 + f.S) * f.M >= 2147483647.0 || (double)f.M * f.N * f.H >= 2147483647.0)
+    return fail(c, BTF_EINVAL, "slice_fold_depth: (sample0 + nsamples) * ncols and ncols * nrows * horizon must stay below 2^31");
+  if ((double)f.T + f.H > (double)FOLDD_MAX_GRID)        // (the penalty on the extended grid is built dense on the host)
+    return fail(c, BTF_EINVAL, "slice_fold_depth: ndepth + horizon must stay within " + std::to_string(FOLDD_MAX_GRID));
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  // a band this wide is refused whatever the rows are (count them below)
+  if (sdepth_lds_bytes(f.H, f.K, f.tf, f.H, 1) > SDEPTH_LDS_LIMIT)
+    return fail(c, BTF_EINVAL, "slice_fold_depth: the band of the new depths needs more than the LDS limit of " + std::to_string(SDEPTH_LDS_LIMIT) + " bytes");
+  if (int rc = fold_depth_rows(c, "slice_fold_depth", f.T, f.H, f.tf, p)) return rc;
+  if ((double)f.H * f.K + 1.0 + f.max_rounds + 4.0 * p.nR >= 2147483647.0)
+    return fail(c, BTF_EINVAL, "slice_fold_depth: the record of a sweep must stay below 2^31 numbers");
+  const size_t lds = sdepth_lds_bytes(f.H, f.K, f.tf, p.nR, slice_fold_depth_tail(f));
+  if (lds > SDEPTH_LDS_LIMIT)
+    return fail(c, BTF_EINVAL, "slice_fold_depth: the band of the new depths needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
+                                   std::to_string(SDEPTH_LDS_LIMIT));
+  const size_t ncell = (size_t)f.M * f.N * f.H;
+  for (size_t e = 0; e < ncell; ++e)
+    if (!(f.cnt[e] >= 0.0 && f.cnt[e] < 1e15) || !(std::fabs(f.S1[e]) < INFINITY) || (f.L && !(std::fabs(f.L[e]) < INFINITY)) ||
+        !(f.fa[e] >= 0.0 && f.fa[e] < INFINITY) || !(std::fabs(f.fb[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, "slice_fold_depth: counts and fit weights must be finite and non-negative, sums finite (0 where there is nothing)");
+  if (!all_finite(f.cons, (size_t)f.J * (f.B + f.H + 1))) return fail(c, BTF_EINVAL, "slice_fold_depth: constraints must be finite");
+  const size_t n = (size_t)f.H * f.K;
+  if (f.start && !all_finite(f.start, (size_t)f.S * f.M * n)) return fail(c, BTF_EINVAL, "slice_fold_depth: start must be finite");
+  if (f.tau2)
+    for (size_t e = 0; e < (size_t)f.S * f.M * p.nR; ++e)
+      if (!(f.tau2[e] > 0.0 && f.tau2[e] < INFINITY)) return fail(c, BTF_EINVAL, "slice_fold_depth: tau2 must be finite and positive");
+  if (f.draws) {
+    const size_t nu = 1 + (size_t)f.max_rounds, per = n + nu + 4 * (size_t)p.nR, head = 4 * (size_t)p.nR;
+    const size_t L = head + (size_t)f.sweeps * per;
+    for (size_t ch = 0; ch < (size_t)f.S * f.M; ++ch) {
+      const double* d = f.draws + ch * L;
+      for (size_t e = 0; e < L; ++e) {
+        const size_t pos = e < head ? per : (e - head) % per;         // (per: a start gamma)
+        const bool normal = pos < n, uniform = pos >= n && pos < n + nu;
+        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)) || (uniform && !(d[e] < 1.0)))
+          return fail(c, BTF_EINVAL, "slice_fold_depth: draws must be finite, its uniforms inside (0, 1), its gamma variates positive");
+      }
+    }
+  }
+  return BTF_OK;
+}
+
+// The launch on device states dW (S,N,K), the kept tails (tail of (s, j) at dVt[(s M + j) vstride], Lt x K) and per-sample
+// lam2 on the device; dgg: the gamma-grid table on the device (family 5).  The scratch's context may be null (the
+// stateless form).  The new V stays on the device between the chains and the summary.
+int slice_fold_depth_run(Scratch& s, const double* dW, const double* dVt, long long vstride, const double* dlam, int lstride,
+                         const GgComp* dgg, int G, double lsp, const SliceFoldDepth& f, const FoldDepthPenalty& p) {
+  btf_ctx* c = s.ctx();
+  const int S = f.S, M = f.M, N = f.N, H = f.H, K = f.K, nR = p.nR, Lt = slice_fold_depth_tail(f), BH = f.B + H;
+  SliceFoldDepthKernel kern = slice_fold_depth_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, "slice_fold_depth: nembeds must be 1..10 and family 0..5");
+  // slice statistics and the fit, (M,N,H) as given, in the kernel's [column][depth][row] layout; per fitted column the rows
+  // with any observed or fitted new cell, ascending
+  const size_t ncell = (size_t)M * N * H;
+  std::vector<double> h1(ncell), hc(ncell), hl(f.L ? ncell : 0), ha(ncell), hb(ncell);
+  std::vector<int> rptr(1, 0), ridx;
+  for (int j = 0; j < M; ++j) {
+    for (int i = 0; i < N; ++i) {
+      bool any = false;
+      for (int h = 0; h < H; ++h) {
+        const size_t src = ((size_t)j * N + i) * H + h, dst = ((size_t)j * H + h) * N + i;
+        const double cv = f.cnt[src], av = f.fa[src];
+        hc[dst] = cv; h1[dst] = cv > 0.0 ? f.S1[src] : 0.0;
+        if (f.L) hl[dst] = cv > 0.0 ? f.L[src] : 0.0;
+        ha[dst] = av; hb[dst] = av > 0.0 ? f.fb[src] : 0.0;
+        any = any || cv > 0.0 || av > 0.0;
+      }
+      if (any) ridx.push_back(i);
+    }
+    rptr.push_back((int)ridx.size());
+  }
+  if (ridx.empty()) ridx.push_back(0);                       // (never read)
+  // the reduced constraints by their non-zeros (CSR over the constraints, local depths ascending), the bounds beside them
+  std::vector<int> cptr(1, 0), cidx;
+  std::vector<double> cval, cc;
+  for (int q = 0; q < f.J; ++q) {
+    for (int l = 0; l < BH; ++l)
+      if (f.cons[(size_t)q * (BH + 1) + l] != 0.0) { cidx.push_back(l); cval.push_back(f.cons[(size_t)q * (BH + 1) + l]); }
+    cptr.push_back((int)cidx.size());
+    cc.push_back(f.cons[(size_t)q * (BH + 1) + BH]);
+  }
+  if (cidx.empty()) { cidx.push_back(0); cval.push_back(0.0); }
+  if (cc.empty()) cc.push_back(0.0);
+  const size_t n = (size_t)H * K, nV = (size_t)S * M * n, nT = (size_t)S * M * nR, nch = (size_t)S * M;
+  const size_t LD = 4 * (size_t)nR + (size_t)f.sweeps * (n + 1 + (size_t)f.max_rounds + 4 * (size_t)nR);
+  const int stat0[4] = {0, INT_MAX, 0, INT_MAX};
+  SliceFoldDepthArgs a = {};
+  a.W = dW; a.Vtail = dVt; a.vstride = vstride; a.lam2 = dlam; a.lstride = lstride;
+  if (f.start) a.start = s.upload(f.start, nV);
+  a.S1 = s.upload(h1.data(), ncell); a.cnt = s.upload(hc.data(), ncell);
+  if (f.L) a.L = s.upload(hl.data(), ncell);
+  a.fa = s.upload(ha.data(), ncell); a.fb = s.upload(hb.data(), ncell);
+  a.rptr = s.upload(rptr.data(), rptr.size()); a.ridx = s.upload(ridx.data(), ridx.size());
+  a.cs_ptr = s.upload(cptr.data(), cptr.size()); a.cs_idx = s.upload(cidx.data(), cidx.size());
+  a.cs_val = s.upload(cval.data(), cval.size()); a.Cc = s.upload(cc.data(), cc.size()); a.J = f.J;
+  if (f.tau2) a.tau2 = s.upload(f.tau2, nT);
+  if (f.draws) a.draws = s.upload(f.draws, nch * LD);
+  a.rcol0 = s.upload(p.rcol0.data(), p.rcol0.size()); a.rcoef = s.upload(p.rcoef.data(), p.rcoef.size());
+  a.st_ptr = s.upload(p.ptr.data(), p.ptr.size());
+  a.st_row = s.upload(p.row.data(), p.row.size()); a.st_coef = s.upload(p.coef.data(), p.coef.size());
+  a.gg = dgg; a.G = G; a.lsp = lsp; a.fam = f.family; a.par = f.param;
+  a.V = s.alloc<double>(nV); a.Vstart = s.alloc<double>(nV); a.Tau2 = s.alloc<double>(nT);
+  a.rounds = s.alloc<int>(nch); a.unfinished = s.alloc<int>(nch); a.status = s.upload(stat0, 4);
+  a.seed = f.seed; a.sample0 = f.sample0; a.lo = f.stability; a.hi = 1.0 / f.stability;
+  a.S = S; a.M = M; a.N = N; a.H = H; a.Lt = Lt; a.B = f.B; a.tf = f.tf; a.nR = nR; a.sweeps = f.sweeps; a.max_rounds = f.max_rounds;
+  const size_t lds = sdepth_dyn_lds_bytes(H, K, f.tf, nR, Lt);
+  allow_lds(s, kern, lds);
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3((unsigned)nch), dim3(WAVE), lds, a);
+  // the summary stage reads the device-resident W (S,N,K) and the new V (S,M*H,K)
+  if (f.mean_out) summary_stage(s, dW, a.V, S, N, M * H, K, f.transform, f.q, f.nq, f.mean_out, f.q_out);
+  int stat[4] = {0, INT_MAX, 0, INT_MAX};
+  s.download(stat, (const int*)a.status, 4);
+  s.download(f.V_out, (const double*)a.V, nV);
+  if (f.Vstart_out) s.download(f.Vstart_out, (const double*)a.Vstart, nV);
+  s.download(f.Tau2_out, (const double*)a.Tau2, nT);
+  s.download(f.rounds_out, (const int*)a.rounds, nch);
+  s.download(f.unf_out, (const int*)a.unfinished, nch);
+  const int rc = s.finish();
+  if (rc) return rc;
+  if (stat[0]) {
+    if (c) c->fail_index = stat[1];
+    g_fold_fail_index = stat[1];
+    const long long sg = stat[1] / M;
+    return fail(c, BTF_ESTATE, "slice_fold_depth: the start of (sample " + std::to_string(sg) + ", column " + std::to_string(stat[1] - sg * M) +
+                                   ") is infeasible or has a non-finite likelihood (index " + std::to_string(stat[1]) +
+                                   " = sample * ncols + column)");
+  }
+  if (stat[2]) {
+    if (c) c->fail_index = stat[3];
+    g_fold_fail_index = stat[3];
+    return fail(c, BTF_ESTATE, "slice_fold_depth: the precision of (sample, column) index " + std::to_string(stat[3]) +
+                                   " = sample * ncols + column is not positive definite (or W / V / lam2 / the fit not finite); its outputs are nan");
+  }
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_slice_fold_depth(int device, int family, double param, const double* shape, const double* scale, const double* prob, int G,
+                         int nsamples, int nrows, int ncols, int ndepth, int horizon, int nembeds, int tf_order, const double* Ws,
+                         const double* Vtail, const double* lam2, const double* start, const double* S1, const double* cnt,
+                         const double* logsum, const double* fit_a, const double* fit_b, const double* constraints, int ncons,
+                         int nback, const double* tau2, const double* draws, unsigned long long seed, int sweeps, int max_rounds,
+                         long long sample0, double stability, double* V_out, double* Vstart_out, double* Tau2_out, int* rounds_out,
+                         int* unfinished_out, int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  const SliceFoldDepth f = {family, param, nsamples, nrows, ncols, ndepth, horizon, nembeds, tf_order, start, S1, cnt, logsum, fit_a,
+                            fit_b, constraints, ncons, nback, tau2, draws, seed, sweeps, max_rounds, sample0, stability, V_out,
+                            Vstart_out, Tau2_out, rounds_out, unfinished_out, transform, q, nq, mean_out, q_out};
+  g_fold_fail_index = -1;
+  if (!Ws || !Vtail || !lam2) return fail(nullptr, BTF_EINVAL, "bad slice_fold_depth arguments");
+  FoldDepthPenalty p;
+  if (int rc = slice_fold_depth_check(nullptr, f, p)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(lam2[s] > 0.0 && lam2[s] < INFINITY)) return fail(nullptr, BTF_EINVAL, "slice_fold_depth: lam2 must be finite and positive");
+  if ((family == ESS_FAM_GAUSSIAN || family == ESS_FAM_NEGBIN_LOGIT) && !(param > 0.0 && param < INFINITY))
+    return fail(nullptr, BTF_EINVAL, "slice_fold_depth: the parameter must be positive");
+  const int Lt = slice_fold_depth_tail(f);
+  const size_t ntail = (size_t)nsamples * ncols * Lt * nembeds;
+  if (!all_finite(Vtail, ntail)) return fail(nullptr, BTF_EINVAL, "slice_fold_depth: the kept curves must be finite");
+  std::vector<GgComp> tab;
+  double lsp = 0.0;
+  if (family == ESS_FAM_GAMMA_GRID && gg_comp_table(shape, scale, prob, G, tab, lsp) != 0)
+    return fail(nullptr, BTF_EINVAL, "slice_fold_depth: the gamma grid has 1..128 components with finite shape > 0, scale > 0, weight >= 0, not all zero");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dVt = s.upload(Vtail, ntail);
+  const double* dl = s.upload(lam2, (size_t)nsamples);
+  const GgComp* dgg = tab.empty() ? nullptr : s.upload(tab.data(), tab.size());
+  return slice_fold_depth_run(s, dW, dVt, (long long)Lt * nembeds, dl, 1, dgg, (int)tab.size(), lsp, f, p);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload): W and the last depths of V from the
+// sample slots, lam2_s from the collected scalars, the likelihood's parameter or table from the context
+int btf_collect_slice_fold_depth(btf_ctx* c, int family, int nsamples, int horizon, const double* start, const double* S1,
+                                 const double* cnt, const double* logsum, const double* fit_a, const double* fit_b,
+                                 const double* constraints, int ncons, int nback, const double* tau2, const double* draws,
+                                 unsigned long long seed, int sweeps, int max_rounds, long long sample0, double stability,
+                                 double* V_out, double* Vstart_out, double* Tau2_out, int* rounds_out, int* unfinished_out,
+                                 int transform, const double* q, int nq, double* mean_out, double* q_out) {
+  if (!c || family < 0 || family >= ESS_FAM_COUNT) return fail(c, BTF_EINVAL, "bad slice_fold_depth arguments");
+  const SliceFoldDepth f = {family, c->lik_par[family], nsamples, c->N, c->M, c->T, horizon, c->K, c->TF, start, S1, cnt, logsum,
+                            fit_a, fit_b, constraints, ncons, nback, tau2, draws, seed, sweeps, max_rounds, sample0, stability, V_out,
+                            Vstart_out, Tau2_out, rounds_out, unfinished_out, transform, q, nq, mean_out, q_out};
+  FoldDepthPenalty p;
+  if (int rc = slice_fold_depth_check(c, f, p)) return rc;
+  if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, "btf_collect_slice_fold_depth needs an unsharded context");
+  if (family == ESS_FAM_GAMMA_GRID && !c->gg_tab)
+    return fail(c, BTF_ESTATE, "btf_collect_slice_fold_depth: the gamma-grid family needs its table (btf_set_likelihood_table)");
+  if (!has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, "btf_collect_slice_fold_depth");
+  HIPCHK(c, hipSetDevice(c->dev));
+  Scratch s(c, c->stream);
+  const int Lt = slice_fold_depth_tail(f);
+  return slice_fold_depth_run(s, c->smp_W, c->smp_V + (size_t)(c->T - Lt) * c->K, (long long)c->T * c->K, c->smp_s + HYP_LAM2,
+                              (int)HYP_COUNT, c->gg_tab, c->gg_G, c->gg_lsp, f, p);
 }
 
 int btf_diag_eval(int device, int nchains, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* const* Ws,

@@ -16,7 +16,8 @@
 //   gg_logsum_kernel                              L = sum_r log y of every cell, and a flag for an observed y <= 0
 // Every sum has a fixed order (no float atomics): two calls give identical bits.
 #pragma once
-#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT) || defined(BTF_SLICE_FOLD_UNIT) || defined(BTF_SLICE_FOLD_COLS_UNIT)
+#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT) || defined(BTF_SLICE_FOLD_UNIT) || defined(BTF_SLICE_FOLD_COLS_UNIT) || \
+    defined(BTF_SLICE_FOLD_DEPTH_UNIT)
 #include "btf_gass.h"
 #else      // host code that needs the table's types alone (btf_ctx.h, btf_gg_criteria.h): no sampler kernels
 #include "btf_device.h"
@@ -105,8 +106,10 @@ GgEvalKernel gg_eval_fn(bool rows, bool ep);
 GgLogsumKernel gg_logsum_fn();
 
 // the cell term, shared by this unit's kernels, the criteria kernels of btf_gg_criteria.h (BTF_GG_CRIT_UNIT) and the
-// slice fold-in kernels of btf_slice_fold.h (BTF_SLICE_FOLD_UNIT) and btf_slice_fold_cols.h (BTF_SLICE_FOLD_COLS_UNIT)
-#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT) || defined(BTF_SLICE_FOLD_UNIT) || defined(BTF_SLICE_FOLD_COLS_UNIT)
+// slice fold-in kernels of btf_slice_fold.h (BTF_SLICE_FOLD_UNIT), btf_slice_fold_cols.h (BTF_SLICE_FOLD_COLS_UNIT) and
+// btf_slice_fold_depth.h (BTF_SLICE_FOLD_DEPTH_UNIT)
+#if defined(BTF_GAMMA_GRID_UNIT) || defined(BTF_GG_CRIT_UNIT) || defined(BTF_SLICE_FOLD_UNIT) || defined(BTF_SLICE_FOLD_COLS_UNIT) || \
+    defined(BTF_SLICE_FOLD_DEPTH_UNIT)
 // table and exp / log tables into LDS (then a barrier, by the caller)
 __device__ __forceinline__ void gg_stage(const GgTab& t, GgComp* tab, double2* ltab, double2* etab) {
   for (int g = threadIdx.x; g < t.G; g += blockDim.x) tab[g] = t.tab[g];
@@ -133,7 +136,7 @@ __device__ __forceinline__ double gg_term(double s1, double L, double cnt, doubl
   if (!(m > -INFINITY)) return -INFINITY;
   return m + log_tab(s, ltab) - L;
 }
-#endif  // BTF_GAMMA_GRID_UNIT || BTF_GG_CRIT_UNIT || BTF_SLICE_FOLD_UNIT || BTF_SLICE_FOLD_COLS_UNIT
+#endif  // BTF_GAMMA_GRID_UNIT || BTF_GG_CRIT_UNIT || BTF_SLICE_FOLD_UNIT || BTF_SLICE_FOLD_COLS_UNIT || BTF_SLICE_FOLD_DEPTH_UNIT
 
 #ifdef BTF_GAMMA_GRID_UNIT
 template <int K>

@@ -1191,6 +1191,10 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
         raise NotImplementedError("fold_in_depth for the Negative-Binomial model: the pseudo-trial counts y + R of a new depth slice "
                                   "depend on the sampled rate R, which this call does not read (not supported yet)")
 
+    def slice_fold_in_depth(self, *args, **kwargs):
+        raise NotImplementedError("slice_fold_in_depth for the Negative-Binomial model: the likelihood of a new depth slice depends "
+                                  "on the sampled rate R, which the slice fold-ins do not read (not supported yet)")
+
     def _pred_aux(self, results, nsamples):
         """The rate tensor of every sample: results['R'] (S,) + rate shape, else the current R for all of them."""
         from . import predictive as _pred
@@ -1588,8 +1592,8 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
             raise NotImplementedError("%s: fold_in_depth needs a device likelihood with a conjugate column conditional; a "
                                       "Python-callable loglikelihood is evaluated on the host only" % type(self).__name__)
         raise NotImplementedError("%s: fold_in_depth needs the conjugate column conditional of the Gaussian and Binomial models; "
-                                  "new depths of a slice-sampled model have no closed-form draw (a slice_fold_in_depth is not "
-                                  "written yet)" % type(self).__name__)
+                                  "new depths of a slice-sampled model have no closed-form draw: slice_fold_in_depth folds depths "
+                                  "into this model" % type(self).__name__)
 
     def _slice_fold_restrictions(self, row_features, R, results, S):
         """(Constraints, Row_constraints, codes (R,F) or None, Us (S,F,K) or None) of a slice_fold_in_rows call."""
@@ -1719,6 +1723,75 @@ class NonconjugateBayesianTensorFiltering(BayesianTensorFiltering):
                             tau2=tau2, draws=draws, seed=seed, sweeps=sweeps, max_rounds=max_rounds, summary=summary, q=q,
                             transform=transform, stability=float(self.stability), ctx=self._ctx, Ws=Ws, Vs=Vs, lam2=lam2,
                             device=self._ctx.device)
+
+    # ---- folding new depth slices in (functionalmf_amd/slice_fold_in_depth.py, csrc/btf_slice_fold_depth.h) ----
+    def slice_fold_in_depth(self, Y_new, horizon=None, results=None, Constraints=None, fit=None, start=None, tau2=None, seed=None,
+                            draws=None, sweeps=None, max_rounds=40, summary=True, q=(5, 95), transform=None):
+        """Curves of every fitted column at depths the chain never saw (new weeks of a count series, new and higher doses
+        of every drug), with uncertainty, for the slice-sampled models, on the GPU (csrc/btf_slice_fold_depth.h):
+        fold_in_depth for the likelihoods without a conjugate column conditional.  The prior side is fold_in_depth's - the
+        new penalty rows of the operator on ndepth + H points, offsets from the kept tail of V_s[j], fresh horseshoe+
+        levels - and the curve update is slice_fold_in_cols's: `sweeps` rounds (default:
+        functionalmf_amd.slice_fold_in_depth.DEFAULT_SWEEPS) of one elliptical slice update of the H new depths - on an
+        ellipse centred on a per-cell Gaussian fit of the likelihood, each with at most max_rounds proposals - and the
+        level update, one chain per (kept sample, fitted column), all in one launch.  The new data does not inform W, the
+        kept depths or the hyper-parameters.  functionalmf_amd.slice_fold_in_depth.chain is the definition in numpy.
+
+        Y_new: (N,M,H) or (N,M,H,nreps), NaN = missing.  None with horizon=H: the (constrained) forecast - the prior
+            continuation truncated to the feasible set.
+        results: a run_gibbs result dict (W (S,N,K), V (S,M,T,K), lam2 one value per sample), uploaded; None: the samples
+            the last device-collecting run_gibbs left on the device - no upload of W and V.
+        Constraints: (J, ndepth + H + 1) on the EXTENDED grid: sum_t A[q,t] (w_i . v_t) >= C[q] over kept and new depths,
+            for every fitted row i.  Rows on kept depths alone are dropped; a row may couple new and kept depths.  A
+            constrained model MUST be given them (its own (J, ndepth + 1) rows are never stretched silently): None raises
+            ValueError there; an array with zero rows means none.
+        fit: None: slice_fold_in_cols.gaussian_fit on the new slices; (Mu_fit, Sigma_fit), each (M,N,H) -
+            [column][row][depth] -, nan or a non-positive sd = the cell carries no fit; False: no fit at all.  The fit
+            changes only the mixing, never the target.
+        start: (H,K), (M,H,K) or (S,M,H,K); default: the last kept depth V_s[j, ndepth - 1] at every new depth, feasible
+            under positivity and monotone rows whenever the kept curve is.  A start that is infeasible or has a non-finite
+            likelihood raises RuntimeError naming (sample, column).
+        tau2: (M,nR) or (S,M,nR) holds the local scales of the new penalty rows fixed (no level update).
+        seed: None takes the model's next device seed (the model's draw counter moves on by one); an integer leaves the
+            model untouched, and two calls with it return identical bits.
+        draws: optional (S,M,slice_fold_in_depth.record_length(...)) replacing the device generator.
+
+        Returns a dict: V (S,M,H,K) the last state of every chain, one draw per kept sample; V_start (S,M,H,K); Tau2
+        (S,M,nR); rounds (S,M) likelihood evaluations; unfinished (S,M) sweeps that used all max_rounds proposals (they
+        keep their state); with summary=True, mean (N,M,H) and quantiles (len(q),N,M,H) of f(w_i^s . v_jh^s) from the
+        summary kernel (at most 16384 samples); nsamples.  results["W"] with np.concatenate([results["V"], out["V"]],
+        axis=2) goes straight into utils.posterior_summary and posterior_functionals.  The sampler's state is not touched.
+        Unsharded models, device likelihoods, nembeds <= 10, (tf_order + 1) nembeds < 64; a band beyond one workgroup's LDS
+        (slice_fold_in_depth.lds_bytes > LDS_LIMIT) is refused with ValueError.  The Negative-Binomial model (its rate is
+        sampled) is out of scope."""
+        from . import slice_fold_in_cols as _sc, slice_fold_in_depth as _sd
+        from ._analysis import check_scalars
+        self._unsharded("slice_fold_in_depth")
+        if self._callback:
+            raise NotImplementedError("slice_fold_in_depth needs a device likelihood: a Python-callable loglikelihood is "
+                                      "evaluated on the host only")
+        N, M, T, K = self.nrows, self.ncols, self.ndepth, self.nembeds
+        family = self.loglikelihood
+        param = self._gg_table if self._link == 5 else self.likelihood_param
+        H, S1, cnt, L = _sd.slice_statistics(Y_new, family, N, M, horizon=horizon)
+        if Constraints is None and self._slice_fold_col_constraints() is not None:
+            raise ValueError("slice_fold_in_depth: a constrained model needs Constraints on the extended grid, (J, ndepth + "
+                             "horizon + 1) = (J, %d); the model's own (J, %d) rows are not stretched (an array with zero "
+                             "rows: none)" % (T + H + 1, T + 1))
+        S, Ws, Vs = self._samples(results, need=("W", "V"))
+        B = _sd.reduce_constraints(Constraints, T, H)[3]
+        _sd.check_args(family, param, S, M, N, T, H, K, self.tf_order, start, tau2, draws, sweeps, max_rounds, summary, q, transform,
+                       0, B)
+        if fit is None:
+            fit = _sd.default_fit(Y_new, family, param, N, M)
+        weights, sums = _sc.fit_weights(fit, M, N, H)
+        lam2 = check_scalars("results: lam2", results.get("lam2"), S) if results is not None else None
+        if seed is None:
+            seed = self._next_seed() if draws is None else 0
+        return _sd.evaluate(family, param, S, N, M, T, H, K, self.tf_order, S1, cnt, L, weights, sums, start=start,
+                            Constraints=Constraints, tau2=tau2, draws=draws, seed=seed, sweeps=sweeps, max_rounds=max_rounds,
+                            summary=summary, q=q, transform=transform, stability=float(self.stability), ctx=self._ctx, Ws=Ws, Vs=Vs,
+                            lam2=lam2, device=self._ctx.device)
 
     def run_gibbs(self, data, nburn=1000, nthin=1, nsamples=1000, verbose=True, print_freq=100, callback=None, **kwargs):
         """genlasso.py:37-66, the result dict gathered as before.  A gamma_grid model with rng="device" also keeps every

@@ -558,6 +558,45 @@ def slice_fold_in_cols(Y_new, Ws, family, lam2=None, Vs=None, likelihood_param=N
                         device=device)
 
 
+def slice_fold_in_depth(Y_new, Ws, Vs, family, horizon=None, lam2=None, likelihood_param=None, Constraints=None, tf_order=2,
+                        fit=None, start=None, tau2=None, seed=0, draws=None, sweeps=None, max_rounds=40, summary=True, q=(5, 95),
+                        transform=None, first_sample=0, stability=1e-6, device=0):
+    """Curves of every fitted column at depths the chain never saw for a slice-sampled fit, one draw per kept sample, on
+    the GPU, without a model: the stateless form of NonconjugateBayesianTensorFiltering.slice_fold_in_depth (see there for
+    the method, the arguments and the outputs).
+
+    Ws (S,N,K) and Vs (S,M,T,K): the kept samples (of Vs only the last max(min(T, tf_order + 1), B) depths are uploaded, B
+    the kept depths the constraints reach); lam2 one value per sample; family: a device likelihood name ("poisson",
+    "poisson_identity", "bernoulli_logit", "gaussian", "negbin_logit", "gamma_grid") with likelihood_param as the model
+    class takes it; tf_order and stability as the model was built with.  Y_new (N,M,H) or (N,M,H,nreps), NaN = missing;
+    None with horizon=H: the (constrained) forecast.  Constraints (J, T + H + 1) on the extended grid: they hold for every
+    fitted row.  first_sample: the index of Ws[0] among the kept samples - with it a call over a slice of the samples
+    returns the bits of the whole call.  functionalmf_amd.slice_fold_in_depth.chain is the definition in numpy.  There is
+    no CPU fallback."""
+    from . import _analysis, slice_fold_in as _sf, slice_fold_in_cols as _sc, slice_fold_in_depth as _sd
+    _sf.family_code(family)
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, M, T, K = Vs.shape
+    N = Ws.shape[1]
+    param = _sf.check_param(family, likelihood_param)
+    H, S1, cnt, L = _sd.slice_statistics(Y_new, family, N, M, horizon=horizon)
+    B = _sd.reduce_constraints(Constraints, T, H)[3]
+    _sd.check_args(family, param, S, M, N, T, H, K, tf_order, start, tau2, draws, sweeps, max_rounds, summary, q, transform,
+                   first_sample, B)
+    if fit is None:
+        fit = _sd.default_fit(Y_new, family, param, N, M)
+    weights, sums = _sc.fit_weights(fit, M, N, H)
+    lam2 = _analysis.check_scalars("lam2", lam2, S)
+    if not 0 < float(stability) <= 1:
+        raise ValueError("stability must lie in (0, 1]")
+    if not np.all(np.isfinite(Vs[:, :, T - _sd.tail_depths(T, tf_order, B):])):
+        raise ValueError("Vs must be finite at the last kept depths")
+    return _sd.evaluate(family, param, S, N, M, T, H, K, tf_order, S1, cnt, L, weights, sums, start=start, Constraints=Constraints,
+                        tau2=tau2, draws=draws, seed=seed, sweeps=sweeps, max_rounds=max_rounds, summary=summary, q=q,
+                        transform=transform, first_sample=first_sample, stability=stability, Ws=Ws, Vs=Vs, lam2=lam2,
+                        device=device)
+
+
 # chain initialisers (utils.py:218-419): non-negative tensor factorisation and the factor PAV projection, on the GPU
 from .nmf import bounded_tensor_nmf, factor_pav, tensor_nmf  # noqa: E402,F401
 

@@ -877,6 +877,43 @@ int btf_collect_slice_fold_cols(btf_ctx* ctx, int family, int nsamples, int ncol
                                 double* V_out, double* Vstart_out, double* Tau2_out, int* rounds_out, int* unfinished_out,
                                 int transform, const double* q, int nq, double* mean_out, double* q_out);
 
+/* ---- folding new depth slices into a slice-sampled fit (csrc/btf_slice_fold_depth.h) --------------------------------
+ * btf_fold_in_depth for the slice-sampled models: one chain per (kept sample s, fitted column j) over the `horizon` new
+ * depths v (H,K) and the horseshoe+ levels of the nR new penalty rows, given W_s, the kept tail of V_s[j] and lam2_s - the
+ * prior side of btf_fold_in_depth (new rows, offsets from the kept tail, fresh levels) with the curve update of
+ * btf_slice_fold_cols (one elliptical slice update on an ellipse centred on a per-cell Gaussian fit);
+ * functionalmf_amd/slice_fold_in_depth.py (`chain`) is the definition.  family and param / the table as
+ * btf_slice_fold_rows.  Ws (S,N,K), lam2 (S,).  constraints (ncons, nback + H + 1): the rows of the constraints on the
+ * extended grid that touch a new depth, cut to the nback trailing kept depths they reach, the H new depths and the bound
+ * (slice_fold_in_depth.reduce_constraints): sum_t A[q,t] (w_i . V_s[j, T - nback + t]) + sum_h A[q,nback + h] (w_i . v_h) >=
+ * c[q] for every fitted row i; kept and new terms go through one dot product in ascending depth order, so a new depth that
+ * repeats the bits of the last kept depth ties exactly.  Vtail (S,M,Lt,K): the last Lt = max(min(ndepth, tf_order + 1),
+ * nback) kept depths.  start (S,M,H,K), or NULL: every new depth starts at V_s[j, ndepth - 1].  S1, cnt, logsum, fit_a,
+ * fit_b (M,N,H): the per-cell statistics and the fit of the new slices as in btf_slice_fold_cols (all zeros: the
+ * constrained forecast).  tau2 (S,M,nR) holds the scales fixed.  draws (S,M,4 nR + sweeps (H K + 1 + max_rounds + 4 nR)):
+ * the layout of btf_slice_fold_cols with nR and H K - or NULL: Philox keyed (seed, (sample0 + s) << 32 | j, slot, element).
+ * V_out, Vstart_out (S,M,H,K), Tau2_out (S,M,nR), rounds_out, unfinished_out (S,M); mean_out non-NULL adds the summary
+ * stage: mean (N,M,H), q_out (nq,N,M,H).  The band of the H K wide system, its side arrays, the tail and the likelihood
+ * tables must fit one workgroup's LDS, and (tf_order + 1) nembeds < 64: BTF_EINVAL otherwise, before any device call.  A
+ * start that is infeasible or has a non-finite likelihood, or a non-positive pivot: that chain's outputs are nan, the call
+ * returns BTF_ESTATE and btf_fail_index (ctx, or NULL after the stateless call) = (sample0 + s) * ncols + j of the first
+ * such chain.  fp64, no floating-point atomics, every sum in a fixed order.  btf_collect_slice_fold_depth reads W, the tail
+ * of V and lam2_s of the first nsamples collected slots without an upload, takes param / the table from the context and
+ * touches none of the sampler's state.  Launches are counted under BTF_K_CRITERIA.  Synchronous.                        */
+int btf_slice_fold_depth(int device, int family, double param, const double* shape, const double* scale, const double* prob, int G,
+                         int nsamples, int nrows, int ncols, int ndepth, int horizon, int nembeds, int tf_order, const double* Ws,
+                         const double* Vtail, const double* lam2, const double* start, const double* S1, const double* cnt,
+                         const double* logsum, const double* fit_a, const double* fit_b, const double* constraints, int ncons,
+                         int nback, const double* tau2, const double* draws, unsigned long long seed, int sweeps, int max_rounds,
+                         long long sample0, double stability, double* V_out, double* Vstart_out, double* Tau2_out, int* rounds_out,
+                         int* unfinished_out, int transform, const double* q, int nq, double* mean_out, double* q_out);
+int btf_collect_slice_fold_depth(btf_ctx* ctx, int family, int nsamples, int horizon, const double* start, const double* S1,
+                                 const double* cnt, const double* logsum, const double* fit_a, const double* fit_b,
+                                 const double* constraints, int ncons, int nback, const double* tau2, const double* draws,
+                                 unsigned long long seed, int sweeps, int max_rounds, long long sample0, double stability,
+                                 double* V_out, double* Vstart_out, double* Tau2_out, int* rounds_out, int* unfinished_out,
+                                 int transform, const double* q, int nq, double* mean_out, double* q_out);
+
 /* ---- convergence diagnostics (csrc/btf_diag.h) ----------------------------------------------------------------------
  * Split R-hat (rank-normalised, max of bulk and folded), bulk ESS, tail ESS (min over the 5 % / 95 % indicators), MCSE of
  * the mean and the mean, per cell of f(W V') over nchains chains of nsamples draws (Vehtari et al. 2021; one chain: its
