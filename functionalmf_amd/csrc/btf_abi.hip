@@ -13,6 +13,7 @@
 #include "btf_gamma_grid.h"    // the gamma-grid likelihood (instances in btf_gamma_grid.hip)
 #include "btf_fused.h"
 #include "btf_functionals.h"    // FUNC_SORT_LDS / FUNC_SORT_CELLS (btf_host_selftest walks every sort geometry)
+#include "btf_fold_chain.h"     // fold_chain_lds_bytes (btf_host_selftest checks the one LDS layout of the fold-in chains)
 #include "btf_instances.h"      // the large kernel families: extern templates, compiled in btf_instances.hip
 #include "btf_comm.h"           // RCCL, bound at run time
 #include "btf_ctx.h"            // struct btf_ctx, Scratch and the host plumbing shared with btf_analysis.hip
@@ -4191,6 +4192,16 @@ int btf_host_selftest(void) {
           }
         }
         for (int i = 0; i + 1 < 8; ++i) ST_CHECK(w_z_offset(i + 1, K) - w_z_offset(i, K) == std::min(i + 1, K));
+        // the chain core of the column and depth fold-ins: the one layout counts what the closed form counts (a column
+        // kernel: no tail; a depth kernel with tf + 1 kept depths; Gibbs: four T K vectors, slice-sampled: six)
+        for (int slice = 0; slice <= 1; ++slice)
+          for (int Lk = 0; Lk <= tf + 1; Lk += tf + 1) {
+            const int bwf = Lk ? fold_depth_bandwidth(T, K, tf) : (tf + 1) * K;
+            const size_t npairs = (size_t)bwf * (bwf + 1) / 2, tail = Lk ? (size_t)nD * K + (size_t)Lk * K : 0;
+            ST_CHECK(fold_chain_lds_bytes(T, K, tf, bwf, nD, Lk, slice != 0) ==
+                     8 * ((size_t)n * (bwf + 1) + (slice ? 6 : 4) * (size_t)n + (size_t)T * tri(K) + 5 * (size_t)nD + tail + (size_t)T * (tf + 2)) +
+                         8 * ((npairs + 3) / 4));
+          }
       }
     }
   // rows per workgroup and the split of an accumulation around a rank's own block: every row exactly once

@@ -1405,6 +1405,99 @@ int btf_collect_slice_fold(btf_ctx* c, int family, int nsamples, int nrows_new, 
   return slice_fold_run(s, st.V, st.W, c->N, c->smp_s + HYP_SIGMA2, (int)HYP_COUNT, c->gg_tab, c->gg_G, c->gg_lsp, f);
 }
 
+// ---------------------------------------------------------------- what the column and depth fold-ins share (btf_fold_chain.h)
+namespace {
+// first and last non-zero of a penalty row over T depths (hi < 0: none)
+void penalty_row_window(const double* row, int T, int& lo, int& hi) {
+  lo = T; hi = -1;
+  for (int t = 0; t < T; ++t)
+    if (row[t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
+}
+// its D1 = tf + 2 coefficients from lo on (0 past the row's end)
+void penalty_row_coefs(const double* row, int lo, int hi, int D1, std::vector<double>& rcoef) {
+  for (int e = 0; e < D1; ++e) rcoef.push_back(lo + e <= hi ? row[lo + e] : 0.0);
+}
+
+// the sweeps a chain's generator slots hold; `name` opens every message
+bool fold_sweeps_ok(int sweeps) { return sweeps >= 1 && (unsigned long long)sweeps < FOLD_CHAIN_PG_SLOT; }
+int fold_sweeps_check(btf_ctx* c, const std::string& name, int sweeps) {
+  return fold_sweeps_ok(sweeps) ? BTF_OK : fail(c, BTF_EINVAL, name + ": sweeps must be in 1..2^20 - 2");
+}
+// the same with the proposals of a slice sweep
+int slice_fold_sweeps_check(btf_ctx* c, const std::string& name, int sweeps, int max_rounds) {
+  if (fold_sweeps_ok(sweeps) && max_rounds >= 1 && max_rounds <= 65536) return BTF_OK;
+  return fail(c, BTF_EINVAL, name + ": sweeps in 1..2^20 - 2 and max_rounds in 1..65536");
+}
+// the sizes: S samples at sample0, C chains per sample (`cols`: their name), N rows, T depths (`depths`: their name) per chain;
+// pg_cells: the Polya-Gamma cell indices of a chain (sweeps * N * T, 0 for a chain without them)
+int fold_sizes_check(btf_ctx* c, const std::string& name, const char* cols, const char* depths, int S, int C, int N, int T, int K, int tf,
+                     long long sample0, bool summary, double pg_cells) {
+  if ((tf + 1) * K >= WAVE) return fail(c, BTF_EINVAL, name + ": the half bandwidth (tf_order + 1) nembeds must stay below 64");
+  if (summary && S > 16384) return fail(c, BTF_EINVAL, name + ": the summary stage takes at most 16384 samples");
+  if ((double)(sample0 + S) * C >= 2147483647.0 || (double)C * N * T >= 2147483647.0 || pg_cells >= 9.0e15)
+    return fail(c, BTF_EINVAL, name + ": (sample0 + nsamples) * " + cols + " and " + cols + " * nrows * " + depths + " must stay below 2^31");
+  return BTF_OK;
+}
+int fold_lds_check(btf_ctx* c, const std::string& name, const char* what, size_t lds) {
+  if (lds <= FOLD_CHAIN_LDS_LIMIT) return BTF_OK;
+  return fail(c, BTF_EINVAL, name + ": the band of " + what + " needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
+                                 std::to_string(FOLD_CHAIN_LDS_LIMIT));
+}
+// the cells of a Gibbs fold-in: cw the counts (Gaussian) or the trials (Binomial)
+int fold_cells_check(btf_ctx* c, const std::string& name, const double* cw, const double* ysum, size_t ncell, bool binomial) {
+  for (size_t e = 0; e < ncell; ++e) {
+    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(ysum[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, name + ": counts must be finite and non-negative, sums finite (0 where nothing was observed)");
+    if (binomial && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLD_CHAIN_MAX_TRIALS))
+      return fail(c, BTF_EINVAL, name + ": Binomial trial counts must be integers up to " + std::to_string(FOLD_CHAIN_MAX_TRIALS));
+  }
+  return BTF_OK;
+}
+// the cells of a slice-sampled fold-in: statistics and the fit (L: the gamma grid's, or null)
+int slice_fold_cells_check(btf_ctx* c, const std::string& name, const double* cnt, const double* S1, const double* L, const double* fa,
+                           const double* fb, size_t ncell) {
+  for (size_t e = 0; e < ncell; ++e)
+    if (!(cnt[e] >= 0.0 && cnt[e] < 1e15) || !(std::fabs(S1[e]) < INFINITY) || (L && !(std::fabs(L[e]) < INFINITY)) ||
+        !(fa[e] >= 0.0 && fa[e] < INFINITY) || !(std::fabs(fb[e]) < INFINITY))
+      return fail(c, BTF_EINVAL, name + ": counts and fit weights must be finite and non-negative, sums finite (0 where there is nothing)");
+  return BTF_OK;
+}
+// `draws` of nch chains: 4 nlev start gammas, then per sweep n normals, nu uniforms (0: a Gibbs chain) and 4 nlev gammas
+int fold_draws_check(btf_ctx* c, const std::string& name, const double* draws, size_t nch, size_t n, size_t nu, size_t nlev, int sweeps) {
+  if (!draws) return BTF_OK;
+  const size_t head = 4 * nlev, per = n + nu + 4 * nlev, L = head + (size_t)sweeps * per;
+  for (size_t ch = 0; ch < nch; ++ch) {
+    const double* d = draws + ch * L;
+    for (size_t e = 0; e < L; ++e) {
+      const size_t pos = e < head ? per : (e - head) % per;         // (per: a start gamma)
+      const bool normal = pos < n, uniform = pos >= n && pos < n + nu;
+      if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)) || (uniform && !(d[e] < 1.0)))
+        return fail(c, BTF_EINVAL, name + (nu ? ": draws must be finite, its uniforms inside (0, 1), its gamma variates positive"
+                                              : ": draws must be finite, its gamma variates positive"));
+    }
+  }
+  return BTF_OK;
+}
+// a chain's failure, from the kernel's status pair: the index for btf_fail_index ...
+void fold_fail_at(btf_ctx* c, int index) {
+  if (c) c->fail_index = index;
+  g_fold_fail_index = index;
+}
+// ... and the message.  `cols`: the name of the chains per sample; `inputs`: what a non-positive pivot may come from.
+int fold_pivot_fail(btf_ctx* c, const std::string& name, int index, const char* cols, const char* inputs) {
+  fold_fail_at(c, index);
+  return fail(c, BTF_ESTATE, name + ": the precision of (sample, column) index " + std::to_string(index) + " = sample * " + cols +
+                                 " + column is not positive definite (or " + inputs + " not finite); its outputs are nan");
+}
+int slice_fold_start_fail(btf_ctx* c, const std::string& name, int index, int C, const char* cols) {
+  fold_fail_at(c, index);
+  const long long sg = index / C;
+  return fail(c, BTF_ESTATE, name + ": the start of (sample " + std::to_string(sg) + ", column " + std::to_string(index - sg * C) +
+                                 ") is infeasible or has a non-finite likelihood (index " + std::to_string(index) + " = sample * " + cols +
+                                 " + column)");
+}
+}  // namespace
+
 // ---------------------------------------------------------------- folding new columns in (btf_fold_in_cols.h)
 namespace {
 struct FoldCols {
@@ -1427,6 +1520,20 @@ struct FoldColsPenalty {
   std::vector<int> ptr, row, rcol0;
 };
 
+// fills the penalty of T depths (shared with slice_fold_cols_check); `name` opens the messages
+int fold_cols_rows(btf_ctx* c, const char* name, int T, int tf, FoldColsPenalty& p) {
+  const int D1 = tf + 2;
+  p.rcol0.assign(p.nD, 0); p.rcoef.clear();
+  for (int r = 0; r < p.nD; ++r) {
+    int lo, hi;
+    penalty_row_window(&p.Delta[(size_t)r * T], T, lo, hi);
+    if (hi < 0 || hi - lo >= D1) return fail(c, BTF_EINVAL, std::string(name) + ": penalty row wider than the band");
+    p.rcol0[r] = lo;
+    penalty_row_coefs(&p.Delta[(size_t)r * T], lo, hi, D1, p.rcoef);
+  }
+  return BTF_OK;
+}
+
 // everything that can be refused without a device; fills the penalty
 int fold_cols_check(btf_ctx* c, const FoldCols& f, FoldColsPenalty& p) {
   if (f.family < FOLDC_GAUSSIAN || f.family > FOLDC_BINOMIAL || f.S < 1 || f.C < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 ||
@@ -1436,48 +1543,18 @@ int fold_cols_check(btf_ctx* c, const FoldCols& f, FoldColsPenalty& p) {
   if (f.family == FOLDC_GAUSSIAN && !f.count) return fail(c, BTF_EINVAL, "fold_in_cols: the Gaussian family needs count");
   if (f.family == FOLDC_BINOMIAL && (!f.trials || f.draws))
     return fail(c, BTF_EINVAL, "fold_in_cols: the Binomial family needs trials and takes no draws");
-  if (f.sweeps < 1 || (unsigned long long)f.sweeps >= FOLDC_PG_SLOT) return fail(c, BTF_EINVAL, "fold_in_cols: sweeps must be in 1..2^20 - 2");
-  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "fold_in_cols: the half bandwidth (tf_order + 1) nembeds must stay below 64");
-  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "fold_in_cols: the summary stage takes at most 16384 samples");
-  if ((double)(f.sample0 + f.S) * f.C >= 2147483647.0 || (double)f.C * f.N * f.T >= 2147483647.0 ||
-      (double)f.sweeps * f.N * f.T >= 9.0e15)
-    return fail(c, BTF_EINVAL, "fold_in_cols: (sample0 + nsamples) * ncols_new and ncols_new * nrows * ndepth must stay below 2^31");
+  if (int rc = fold_sweeps_check(c, "fold_in_cols", f.sweeps)) return rc;
+  if (int rc = fold_sizes_check(c, "fold_in_cols", "ncols_new", "ndepth", f.S, f.C, f.N, f.T, f.K, f.tf, f.sample0, f.mean_out != nullptr,
+                                (double)f.sweeps * f.N * f.T))
+    return rc;
   if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
   penalty_stencil(f.T, f.tf, p.Delta, p.nD, p.ptr, p.row, p.coef);
-  const size_t lds = foldc_lds_bytes(f.T, f.K, f.tf, p.nD);
-  if (lds > FOLDC_LDS_LIMIT)
-    return fail(c, BTF_EINVAL, "fold_in_cols: the band of a column needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
-                                   std::to_string(FOLDC_LDS_LIMIT));
-  const int D1 = f.tf + 2;
-  p.rcol0.assign(p.nD, 0); p.rcoef.assign((size_t)p.nD * D1, 0.0);
-  for (int r = 0; r < p.nD; ++r) {
-    int lo = f.T, hi = -1;
-    for (int t = 0; t < f.T; ++t)
-      if (p.Delta[(size_t)r * f.T + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
-    if (hi < 0 || hi - lo >= D1) return fail(c, BTF_EINVAL, "fold_in_cols: penalty row wider than the band");
-    p.rcol0[r] = lo;
-    for (int t = lo; t <= hi; ++t) p.rcoef[(size_t)r * D1 + (t - lo)] = p.Delta[(size_t)r * f.T + t];
-  }
-  const size_t ncell = (size_t)f.C * f.N * f.T;
-  const double* cw = f.family == FOLDC_GAUSSIAN ? f.count : f.trials;
-  for (size_t e = 0; e < ncell; ++e) {
-    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(f.ysum[e]) < INFINITY))
-      return fail(c, BTF_EINVAL, "fold_in_cols: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
-    if (f.family == FOLDC_BINOMIAL && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLDC_MAX_TRIALS))
-      return fail(c, BTF_EINVAL, "fold_in_cols: Binomial trial counts must be integers up to " + std::to_string(FOLDC_MAX_TRIALS));
-  }
-  if (f.draws) {
-    const size_t n = (size_t)f.T * f.K, per = n + 4 * (size_t)p.nD, L = 4 * (size_t)p.nD + (size_t)f.sweeps * per;
-    for (size_t ch = 0; ch < (size_t)f.S * f.C; ++ch) {
-      const double* d = f.draws + ch * L;
-      for (size_t e = 0; e < L; ++e) {
-        const bool normal = e >= 4 * (size_t)p.nD && (e - 4 * (size_t)p.nD) % per < n;
-        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)))
-          return fail(c, BTF_EINVAL, "fold_in_cols: draws must be finite, its gamma variates positive");
-      }
-    }
-  }
-  return BTF_OK;
+  if (int rc = fold_lds_check(c, "fold_in_cols", "a column", foldc_lds_bytes(f.T, f.K, f.tf, p.nD))) return rc;
+  if (int rc = fold_cols_rows(c, "fold_in_cols", f.T, f.tf, p)) return rc;
+  if (int rc = fold_cells_check(c, "fold_in_cols", f.family == FOLDC_GAUSSIAN ? f.count : f.trials, f.ysum, (size_t)f.C * f.N * f.T,
+                                f.family == FOLDC_BINOMIAL))
+    return rc;
+  return fold_draws_check(c, "fold_in_cols", f.draws, (size_t)f.S * f.C, (size_t)f.T * f.K, 0, (size_t)p.nD, f.sweeps);
 }
 
 // The launches on device states dW (S,N,K) and per-sample scalars on the device (noise null: the Binomial family).  The
@@ -1526,13 +1603,7 @@ int fold_cols_run(Scratch& s, const double* dW, const double* dnoise, int nstrid
   s.download(f.Tau2_out, a.Tau2, nT);
   const int rc = s.finish();
   if (rc) return rc;
-  if (stat[0]) {
-    if (c) c->fail_index = stat[1];
-    g_fold_fail_index = stat[1];
-    return fail(c, BTF_ESTATE, "fold_in_cols: the precision of (sample, column) index " + std::to_string(stat[1]) +
-                                   " = sample * ncols_new + column is not positive definite (or W / nu2 / lam2 not finite); its outputs are nan");
-  }
-  return BTF_OK;
+  return stat[0] ? fold_pivot_fail(c, "fold_in_cols", stat[1], "ncols_new", "W / nu2 / lam2") : BTF_OK;
 }
 }  // namespace
 
@@ -1608,13 +1679,12 @@ int fold_depth_rows(btf_ctx* c, const char* name, int T, int H, int tf, FoldDept
   p.L = std::min(T, tf + 1);
   p.rcol0.clear(); p.rcoef.clear();
   for (int r = 0; r < nD; ++r) {
-    int lo = TH, hi = -1;
-    for (int t = 0; t < TH; ++t)
-      if (Delta[(size_t)r * TH + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
+    int lo, hi;
+    penalty_row_window(&Delta[(size_t)r * TH], TH, lo, hi);
     if (hi < T) continue;                                        // a row on kept depths alone (or an empty one)
     if (hi - lo >= D1 || lo < T - p.L) return fail(c, BTF_EINVAL, std::string(name) + ": penalty row wider than the band");
     p.rcol0.push_back(lo - T);
-    for (int e = 0; e < D1; ++e) p.rcoef.push_back(lo + e <= hi ? Delta[(size_t)r * TH + lo + e] : 0.0);
+    penalty_row_coefs(&Delta[(size_t)r * TH], lo, hi, D1, p.rcoef);
   }
   p.nR = (int)p.rcol0.size();
   if (p.nR < 1) return fail(c, BTF_EINVAL, std::string(name) + ": no penalty row touches the new depths");
@@ -1645,12 +1715,10 @@ int fold_depth_check(btf_ctx* c, const FoldDepth& f, FoldDepthPenalty& p) {
   if (f.family == FOLDD_GAUSSIAN && !f.count) return fail(c, BTF_EINVAL, "fold_in_depth: the Gaussian family needs count");
   if (f.family == FOLDD_BINOMIAL && (!f.trials || f.draws))
     return fail(c, BTF_EINVAL, "fold_in_depth: the Binomial family needs trials and takes no draws");
-  if (f.sweeps < 1 || (unsigned long long)f.sweeps >= FOLDD_PG_SLOT) return fail(c, BTF_EINVAL, "fold_in_depth: sweeps must be in 1..2^20 - 2");
-  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "fold_in_depth: the half bandwidth (tf_order + 1) nembeds must stay below 64");
-  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "fold_in_depth: the summary stage takes at most 16384 samples");
-  if ((double)(f.sample0 + f.S) * f.M >= 2147483647.0 || (double)f.M * f.N * f.H >= 2147483647.0 ||
-      (double)f.sweeps * f.N * f.H >= 9.0e15)
-    return fail(c, BTF_EINVAL, "fold_in_depth: (sample0 + nsamples) * ncols and ncols * nrows * horizon must stay below 2^31");
+  if (int rc = fold_sweeps_check(c, "fold_in_depth", f.sweeps)) return rc;
+  if (int rc = fold_sizes_check(c, "fold_in_depth", "ncols", "horizon", f.S, f.M, f.N, f.H, f.K, f.tf, f.sample0, f.mean_out != nullptr,
+                                (double)f.sweeps * f.N * f.H))
+    return rc;
   if ((double)f.T + f.H > (double)FOLDD_MAX_GRID)        // (the penalty on the extended grid is built dense on the host)
     return fail(c, BTF_EINVAL, "fold_in_depth: ndepth + horizon must stay within " + std::to_string(FOLDD_MAX_GRID));
   if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
@@ -1658,30 +1726,11 @@ int fold_depth_check(btf_ctx* c, const FoldDepth& f, FoldDepthPenalty& p) {
   if (foldd_lds_bytes(f.H, f.K, f.tf, f.H, 1) > FOLDD_LDS_LIMIT)
     return fail(c, BTF_EINVAL, "fold_in_depth: the band of the new depths needs more than the LDS limit of " + std::to_string(FOLDD_LDS_LIMIT) + " bytes");
   if (int rc = fold_depth_rows(c, "fold_in_depth", f.T, f.H, f.tf, p)) return rc;
-  const size_t lds = foldd_lds_bytes(f.H, f.K, f.tf, p.nR, p.L);
-  if (lds > FOLDD_LDS_LIMIT)
-    return fail(c, BTF_EINVAL, "fold_in_depth: the band of the new depths needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
-                                   std::to_string(FOLDD_LDS_LIMIT));
-  const size_t ncell = (size_t)f.M * f.H * f.N;
-  const double* cw = f.family == FOLDD_GAUSSIAN ? f.count : f.trials;
-  for (size_t e = 0; e < ncell; ++e) {
-    if (!(cw[e] >= 0.0 && cw[e] < 1e15) || !(std::fabs(f.ysum[e]) < INFINITY))
-      return fail(c, BTF_EINVAL, "fold_in_depth: counts must be finite and non-negative, sums finite (0 where nothing was observed)");
-    if (f.family == FOLDD_BINOMIAL && (cw[e] != std::floor(cw[e]) || cw[e] > (double)FOLDD_MAX_TRIALS))
-      return fail(c, BTF_EINVAL, "fold_in_depth: Binomial trial counts must be integers up to " + std::to_string(FOLDD_MAX_TRIALS));
-  }
-  if (f.draws) {
-    const size_t n = (size_t)f.H * f.K, per = n + 4 * (size_t)p.nR, L = 4 * (size_t)p.nR + (size_t)f.sweeps * per;
-    for (size_t ch = 0; ch < (size_t)f.S * f.M; ++ch) {
-      const double* d = f.draws + ch * L;
-      for (size_t e = 0; e < L; ++e) {
-        const bool normal = e >= 4 * (size_t)p.nR && (e - 4 * (size_t)p.nR) % per < n;
-        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)))
-          return fail(c, BTF_EINVAL, "fold_in_depth: draws must be finite, its gamma variates positive");
-      }
-    }
-  }
-  return BTF_OK;
+  if (int rc = fold_lds_check(c, "fold_in_depth", "the new depths", foldd_lds_bytes(f.H, f.K, f.tf, p.nR, p.L))) return rc;
+  if (int rc = fold_cells_check(c, "fold_in_depth", f.family == FOLDD_GAUSSIAN ? f.count : f.trials, f.ysum, (size_t)f.M * f.H * f.N,
+                                f.family == FOLDD_BINOMIAL))
+    return rc;
+  return fold_draws_check(c, "fold_in_depth", f.draws, (size_t)f.S * f.M, (size_t)f.H * f.K, 0, (size_t)p.nR, f.sweeps);
 }
 
 // The launches on device states dW (S,N,K), the kept tails (tail of (s, j) at dVt[(s M + j) vstride], L x K) and per-sample
@@ -1726,13 +1775,7 @@ int fold_depth_run(Scratch& s, const double* dW, const double* dVt, long long vs
   s.download(f.Tau2_out, a.Tau2, nT);
   const int rc = s.finish();
   if (rc) return rc;
-  if (stat[0]) {
-    if (c) c->fail_index = stat[1];
-    g_fold_fail_index = stat[1];
-    return fail(c, BTF_ESTATE, "fold_in_depth: the precision of (sample, column) index " + std::to_string(stat[1]) +
-                                   " = sample * ncols + column is not positive definite (or W / V / nu2 / lam2 not finite); its outputs are nan");
-  }
-  return BTF_OK;
+  return stat[0] ? fold_pivot_fail(c, "fold_in_depth", stat[1], "ncols", "W / V / nu2 / lam2") : BTF_OK;
 }
 }  // namespace
 
@@ -1806,55 +1849,23 @@ int slice_fold_cols_check(btf_ctx* c, const SliceFoldCols& f, FoldColsPenalty& p
       (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2 || f.J < 0 || (f.J > 0 && !f.cons) ||
       !(f.stability > 0.0 && f.stability <= 1.0))
     return fail(c, BTF_EINVAL, "bad slice_fold_cols arguments");
-  if (f.sweeps < 1 || f.sweeps >= (1 << 20) - 1 || f.max_rounds < 1 || f.max_rounds > 65536)
-    return fail(c, BTF_EINVAL, "slice_fold_cols: sweeps in 1..2^20 - 2 and max_rounds in 1..65536");
+  if (int rc = slice_fold_sweeps_check(c, "slice_fold_cols", f.sweeps, f.max_rounds)) return rc;
   if (f.family == ESS_FAM_GAMMA_GRID && !f.L) return fail(c, BTF_EINVAL, "slice_fold_cols: the gamma-grid family needs logsum");
-  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "slice_fold_cols: the half bandwidth (tf_order + 1) nembeds must stay below 64");
-  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "slice_fold_cols: the summary stage takes at most 16384 samples");
-  if ((double)(f.sample0 + f.S) * f.C >= 2147483647.0 || (double)f.C * f.N * f.T >= 2147483647.0)
-    return fail(c, BTF_EINVAL, "slice_fold_cols: (sample0 + nsamples) * ncols_new and ncols_new * nrows * ndepth must stay below 2^31");
+  if (int rc = fold_sizes_check(c, "slice_fold_cols", "ncols_new", "ndepth", f.S, f.C, f.N, f.T, f.K, f.tf, f.sample0, f.mean_out != nullptr, 0.0))
+    return rc;
   if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
   penalty_stencil(f.T, f.tf, p.Delta, p.nD, p.ptr, p.row, p.coef);
   if ((double)f.T * f.K + 1.0 + f.max_rounds + 4.0 * p.nD >= 2147483647.0)
     return fail(c, BTF_EINVAL, "slice_fold_cols: the record of a sweep must stay below 2^31 numbers");
-  const size_t lds = scols_lds_bytes(f.T, f.K, f.tf, p.nD);
-  if (lds > SCOLS_LDS_LIMIT)
-    return fail(c, BTF_EINVAL, "slice_fold_cols: the band of a column needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
-                                   std::to_string(SCOLS_LDS_LIMIT));
-  const int D1 = f.tf + 2;
-  p.rcol0.assign(p.nD, 0); p.rcoef.assign((size_t)p.nD * D1, 0.0);
-  for (int r = 0; r < p.nD; ++r) {
-    int lo = f.T, hi = -1;
-    for (int t = 0; t < f.T; ++t)
-      if (p.Delta[(size_t)r * f.T + t] != 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); }
-    if (hi < 0 || hi - lo >= D1) return fail(c, BTF_EINVAL, "slice_fold_cols: penalty row wider than the band");
-    p.rcol0[r] = lo;
-    for (int t = lo; t <= hi; ++t) p.rcoef[(size_t)r * D1 + (t - lo)] = p.Delta[(size_t)r * f.T + t];
-  }
-  const size_t ncell = (size_t)f.C * f.N * f.T;
-  for (size_t e = 0; e < ncell; ++e)
-    if (!(f.cnt[e] >= 0.0 && f.cnt[e] < 1e15) || !(std::fabs(f.S1[e]) < INFINITY) || (f.L && !(std::fabs(f.L[e]) < INFINITY)) ||
-        !(f.fa[e] >= 0.0 && f.fa[e] < INFINITY) || !(std::fabs(f.fb[e]) < INFINITY))
-      return fail(c, BTF_EINVAL, "slice_fold_cols: counts and fit weights must be finite and non-negative, sums finite (0 where there is nothing)");
+  if (int rc = fold_lds_check(c, "slice_fold_cols", "a column", scols_lds_bytes(f.T, f.K, f.tf, p.nD))) return rc;
+  if (int rc = fold_cols_rows(c, "slice_fold_cols", f.T, f.tf, p)) return rc;
+  if (int rc = slice_fold_cells_check(c, "slice_fold_cols", f.cnt, f.S1, f.L, f.fa, f.fb, (size_t)f.C * f.N * f.T)) return rc;
   if (!all_finite(f.cons, (size_t)f.J * (f.T + 1))) return fail(c, BTF_EINVAL, "slice_fold_cols: constraints must be finite");
   if (f.start && !all_finite(f.start, (size_t)f.S * f.C * f.T * f.K)) return fail(c, BTF_EINVAL, "slice_fold_cols: start must be finite");
   if (f.tau2)
     for (size_t e = 0; e < (size_t)f.S * f.C * p.nD; ++e)
       if (!(f.tau2[e] > 0.0 && f.tau2[e] < INFINITY)) return fail(c, BTF_EINVAL, "slice_fold_cols: tau2 must be finite and positive");
-  if (f.draws) {
-    const size_t n = (size_t)f.T * f.K, nu = 1 + (size_t)f.max_rounds, per = n + nu + 4 * (size_t)p.nD, head = 4 * (size_t)p.nD;
-    const size_t L = head + (size_t)f.sweeps * per;
-    for (size_t ch = 0; ch < (size_t)f.S * f.C; ++ch) {
-      const double* d = f.draws + ch * L;
-      for (size_t e = 0; e < L; ++e) {
-        const size_t pos = e < head ? per : (e - head) % per;         // (per: a start gamma)
-        const bool normal = pos < n, uniform = pos >= n && pos < n + nu;
-        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)) || (uniform && !(d[e] < 1.0)))
-          return fail(c, BTF_EINVAL, "slice_fold_cols: draws must be finite, its uniforms inside (0, 1), its gamma variates positive");
-      }
-    }
-  }
-  return BTF_OK;
+  return fold_draws_check(c, "slice_fold_cols", f.draws, (size_t)f.S * f.C, (size_t)f.T * f.K, 1 + (size_t)f.max_rounds, (size_t)p.nD, f.sweeps);
 }
 
 // The launches on device states dW (S,N,K), dV (S,M,T,K; read when the call has no start) and per-sample lam2 on the
@@ -1947,21 +1958,8 @@ int slice_fold_cols_run(Scratch& s, const double* dW, const double* dV, int M, c
     else
       for (size_t e = 0; e < nV; ++e) f.Vstart_out[e] = hmean[(e / ((size_t)C * n)) * n + e % n];
   }
-  if (stat[0]) {
-    if (c) c->fail_index = stat[1];
-    g_fold_fail_index = stat[1];
-    const long long sg = stat[1] / C;
-    return fail(c, BTF_ESTATE, "slice_fold_cols: the start of (sample " + std::to_string(sg) + ", column " + std::to_string(stat[1] - sg * C) +
-                                   ") is infeasible or has a non-finite likelihood (index " + std::to_string(stat[1]) +
-                                   " = sample * ncols_new + column)");
-  }
-  if (stat[2]) {
-    if (c) c->fail_index = stat[3];
-    g_fold_fail_index = stat[3];
-    return fail(c, BTF_ESTATE, "slice_fold_cols: the precision of (sample, column) index " + std::to_string(stat[3]) +
-                                   " = sample * ncols_new + column is not positive definite (or W / lam2 / the fit not finite); its outputs are nan");
-  }
-  return BTF_OK;
+  if (stat[0]) return slice_fold_start_fail(c, "slice_fold_cols", stat[1], C, "ncols_new");
+  return stat[2] ? fold_pivot_fail(c, "slice_fold_cols", stat[3], "ncols_new", "W / lam2 / the fit") : BTF_OK;
 }
 }  // namespace
 
@@ -2047,13 +2045,10 @@ int slice_fold_depth_check(btf_ctx* c, const SliceFoldDepth& f, FoldDepthPenalty
       f.nq < 0 || (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2 || f.J < 0 ||
       (f.J > 0 && !f.cons) || f.B < 0 || f.B > f.T || (f.J == 0 && f.B != 0) || !(f.stability > 0.0 && f.stability <= 1.0))
     return fail(c, BTF_EINVAL, "bad slice_fold_depth arguments");
-  if (f.sweeps < 1 || f.sweeps >= (1 << 20) - 1 || f.max_rounds < 1 || f.max_rounds > 65536)
-    return fail(c, BTF_EINVAL, "slice_fold_depth: sweeps in 1..2^20 - 2 and max_rounds in 1..65536");
+  if (int rc = slice_fold_sweeps_check(c, "slice_fold_depth", f.sweeps, f.max_rounds)) return rc;
   if (f.family == ESS_FAM_GAMMA_GRID && !f.L) return fail(c, BTF_EINVAL, "slice_fold_depth: the gamma-grid family needs logsum");
-  if ((f.tf + 1) * f.K >= WAVE) return fail(c, BTF_EINVAL, "slice_fold_depth: the half bandwidth (tf_order + 1) nembeds must stay below 64");
-  if (f.mean_out && f.S > 16384) return fail(c, BTF_EINVAL, "slice_fold_depth: the summary stage takes at most 16384 samples");
-  if ((double)(f.sample0 + f.S) * f.M >= 2147483647.0 || (double)f.M * f.N * f.H >= 2147483647.0)
-    return fail(c, BTF_EINVAL, "slice_fold_depth: (sample0 + nsamples) * ncols and ncols * nrows * horizon must stay below 2^31");
+  if (int rc = fold_sizes_check(c, "slice_fold_depth", "ncols", "horizon", f.S, f.M, f.N, f.H, f.K, f.tf, f.sample0, f.mean_out != nullptr, 0.0))
+    return rc;
   if ((double)f.T + f.H > (double)FOLDD_MAX_GRID)        // (the penalty on the extended grid is built dense on the host)
     return fail(c, BTF_EINVAL, "slice_fold_depth: ndepth + horizon must stay within " + std::to_string(FOLDD_MAX_GRID));
   if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
@@ -2063,35 +2058,15 @@ int slice_fold_depth_check(btf_ctx* c, const SliceFoldDepth& f, FoldDepthPenalty
   if (int rc = fold_depth_rows(c, "slice_fold_depth", f.T, f.H, f.tf, p)) return rc;
   if ((double)f.H * f.K + 1.0 + f.max_rounds + 4.0 * p.nR >= 2147483647.0)
     return fail(c, BTF_EINVAL, "slice_fold_depth: the record of a sweep must stay below 2^31 numbers");
-  const size_t lds = sdepth_lds_bytes(f.H, f.K, f.tf, p.nR, slice_fold_depth_tail(f));
-  if (lds > SDEPTH_LDS_LIMIT)
-    return fail(c, BTF_EINVAL, "slice_fold_depth: the band of the new depths needs " + std::to_string(lds) + " bytes of LDS, beyond the limit of " +
-                                   std::to_string(SDEPTH_LDS_LIMIT));
-  const size_t ncell = (size_t)f.M * f.N * f.H;
-  for (size_t e = 0; e < ncell; ++e)
-    if (!(f.cnt[e] >= 0.0 && f.cnt[e] < 1e15) || !(std::fabs(f.S1[e]) < INFINITY) || (f.L && !(std::fabs(f.L[e]) < INFINITY)) ||
-        !(f.fa[e] >= 0.0 && f.fa[e] < INFINITY) || !(std::fabs(f.fb[e]) < INFINITY))
-      return fail(c, BTF_EINVAL, "slice_fold_depth: counts and fit weights must be finite and non-negative, sums finite (0 where there is nothing)");
+  if (int rc = fold_lds_check(c, "slice_fold_depth", "the new depths", sdepth_lds_bytes(f.H, f.K, f.tf, p.nR, slice_fold_depth_tail(f)))) return rc;
+  if (int rc = slice_fold_cells_check(c, "slice_fold_depth", f.cnt, f.S1, f.L, f.fa, f.fb, (size_t)f.M * f.N * f.H)) return rc;
   if (!all_finite(f.cons, (size_t)f.J * (f.B + f.H + 1))) return fail(c, BTF_EINVAL, "slice_fold_depth: constraints must be finite");
   const size_t n = (size_t)f.H * f.K;
   if (f.start && !all_finite(f.start, (size_t)f.S * f.M * n)) return fail(c, BTF_EINVAL, "slice_fold_depth: start must be finite");
   if (f.tau2)
     for (size_t e = 0; e < (size_t)f.S * f.M * p.nR; ++e)
       if (!(f.tau2[e] > 0.0 && f.tau2[e] < INFINITY)) return fail(c, BTF_EINVAL, "slice_fold_depth: tau2 must be finite and positive");
-  if (f.draws) {
-    const size_t nu = 1 + (size_t)f.max_rounds, per = n + nu + 4 * (size_t)p.nR, head = 4 * (size_t)p.nR;
-    const size_t L = head + (size_t)f.sweeps * per;
-    for (size_t ch = 0; ch < (size_t)f.S * f.M; ++ch) {
-      const double* d = f.draws + ch * L;
-      for (size_t e = 0; e < L; ++e) {
-        const size_t pos = e < head ? per : (e - head) % per;         // (per: a start gamma)
-        const bool normal = pos < n, uniform = pos >= n && pos < n + nu;
-        if (!(std::fabs(d[e]) < INFINITY) || (!normal && !(d[e] > 0.0)) || (uniform && !(d[e] < 1.0)))
-          return fail(c, BTF_EINVAL, "slice_fold_depth: draws must be finite, its uniforms inside (0, 1), its gamma variates positive");
-      }
-    }
-  }
-  return BTF_OK;
+  return fold_draws_check(c, "slice_fold_depth", f.draws, (size_t)f.S * f.M, n, 1 + (size_t)f.max_rounds, (size_t)p.nR, f.sweeps);
 }
 
 // The launch on device states dW (S,N,K), the kept tails (tail of (s, j) at dVt[(s M + j) vstride], Lt x K) and per-sample
@@ -2171,21 +2146,8 @@ int slice_fold_depth_run(Scratch& s, const double* dW, const double* dVt, long l
   s.download(f.unf_out, (const int*)a.unfinished, nch);
   const int rc = s.finish();
   if (rc) return rc;
-  if (stat[0]) {
-    if (c) c->fail_index = stat[1];
-    g_fold_fail_index = stat[1];
-    const long long sg = stat[1] / M;
-    return fail(c, BTF_ESTATE, "slice_fold_depth: the start of (sample " + std::to_string(sg) + ", column " + std::to_string(stat[1] - sg * M) +
-                                   ") is infeasible or has a non-finite likelihood (index " + std::to_string(stat[1]) +
-                                   " = sample * ncols + column)");
-  }
-  if (stat[2]) {
-    if (c) c->fail_index = stat[3];
-    g_fold_fail_index = stat[3];
-    return fail(c, BTF_ESTATE, "slice_fold_depth: the precision of (sample, column) index " + std::to_string(stat[3]) +
-                                   " = sample * ncols + column is not positive definite (or W / V / lam2 / the fit not finite); its outputs are nan");
-  }
-  return BTF_OK;
+  if (stat[0]) return slice_fold_start_fail(c, "slice_fold_depth", stat[1], M, "ncols");
+  return stat[2] ? fold_pivot_fail(c, "slice_fold_depth", stat[3], "ncols", "W / V / lam2 / the fit") : BTF_OK;
 }
 }  // namespace
 

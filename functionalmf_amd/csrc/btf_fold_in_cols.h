@@ -16,7 +16,9 @@
 // functionalmf_amd/fold_in_cols.py restates this in numpy (`conditional`, `chain`); that module is the definition.
 //
 // ONE launch, fold_cols_kernel<K, FAMILY>, ONE geometry: a workgroup of one wave owns the chain of (sample s, new column c) for all
-// its sweeps; S * C chains in a launch.
+// its sweeps; S * C chains in a launch.  The steps below are those of btf_fold_chain.h (accumulate_blocks, prior_band, fill_band,
+// levels_start, levels_update, gibbs_finish), shared with the other three kernels of the family; this kernel's own are the
+// Polya-Gamma key, start and weights of the Binomial family.
 //   accumulation   once per chain (Binomial: once per sweep, after its Polya-Gamma draws): for every depth t the lanes walk the N rows (lane l takes rows l, l + 64, ... in
 //       ascending order: cnt and ysum lie [column][depth][row], one coalesced load per 64 rows), keep the K (K + 1) / 2 + K
 //       running sums of their rows in registers, and the 64 partial sums are added by the xor butterfly - a fixed order
@@ -31,22 +33,18 @@
 //   levels         lane = penalty row, gamma_mt (btf_kernels.h) on a generator of the row.
 // Generator: Philox keyed (seed, stream = global sample index << 32 | column, counter = slot << 44 | element << 12 | block)
 // with slot 0 the start and slot r + 1 sweep r, element = penalty row for the level draws and nD + coordinate for the
-// normals; the Polya-Gamma stream of a cell is keyed by (a Philox word of slot FOLDC_PG_SLOT, (sweep T + t) N + i) - never a
+// normals; the Polya-Gamma stream of a cell is keyed by (a Philox word of slot FOLD_CHAIN_PG_SLOT, (sweep T + t) N + i) - never a
 // thread or block index: splitting S over calls (sample0) or folding columns one at a time gives the same
 // bits.  `draws` (one flat block per chain, the layout of fold_in_cols.chain) replaces every variate.
-// LDS per workgroup: foldc_lds_bytes (41 KB band + 28 KB side arrays at T = 64, K = 5, tf = 2); beyond FOLDC_LDS_LIMIT the
-// call is refused - there is no second code path.  fp64 throughout, no floating-point atomics.
+// LDS per workgroup: foldc_lds_bytes (41 KB band + 28 KB side arrays at T = 64, K = 5, tf = 2), the count of fold_chain_layout;
+// beyond FOLDC_LDS_LIMIT the call is refused - there is no second code path.  fp64 throughout, no floating-point atomics.
 #pragma once
-#include "btf_device.h"
-#include <math.h>
+#include "btf_fold_chain.h"
 
 namespace btf {
 
 enum { FOLDC_GAUSSIAN = 0, FOLDC_BINOMIAL = 1 };
-constexpr size_t FOLDC_LDS_LIMIT = 156 * 1024;      // what one workgroup may hold of a CU's 160 KiB beside the Polya-Gamma records
-constexpr int FOLDC_MAX_TRIALS = 32;                // PG_AUTO_EXACT_MAX: the counts drawn exactly (btf_fold_in.h)
-constexpr unsigned long long FOLDC_PG_SLOT = 0xFFFFFULL;   // the generator slot of the Polya-Gamma key: sweeps stay below it
-constexpr double FOLDC_TAU2_START_CLIP = 9.0;       // _init_Tau2
+constexpr size_t FOLDC_LDS_LIMIT = FOLD_CHAIN_LDS_LIMIT;      // (beside the Polya-Gamma records)
 
 struct FoldColsArgs {
   const double* W;          // [S][N][K]
@@ -71,11 +69,8 @@ struct FoldColsArgs {
   int S, C, N, T, tf, nD, sweeps;
 };
 
-// the same count in fold_in_cols.lds_bytes
-inline size_t foldc_lds_bytes(int T, int K, int tf, int nD) {
-  const size_t n = (size_t)T * K, bw = (size_t)(tf + 1) * K, npairs = bw * (bw + 1) / 2;
-  return 8 * (n * (bw + 1) + 4 * n + (size_t)T * tri(K) + 5 * (size_t)nD + (size_t)T * (tf + 2)) + 8 * ((npairs + 3) / 4);
-}
+// the same count in fold_in_cols.lds_bytes: 8 (n (bw + 1) + 4 n + T K (K + 1) / 2 + 5 nD + T (tf + 2)) + the pair table
+inline size_t foldc_lds_bytes(int T, int K, int tf, int nD) { return fold_chain_lds_bytes(T, K, tf, (tf + 1) * K, nD, 0, false); }
 
 // the kernels live in btf_fold_in_cols.hip (a compilation unit of their own); the C-ABI unit launches them through this
 using FoldColsKernel = void (*)(FoldColsArgs);
@@ -84,214 +79,77 @@ FoldColsKernel fold_cols_fn(int K, int family);    // null outside K = 1..10, fa
 }  // namespace btf
 
 #ifdef BTF_FOLD_COLS_UNIT
-#include "btf_kernels.h"        // banded_factor_forward / banded_backward, fill_pair_table, CellRng, gamma_mt
 #include "btf_pg_exact.h"       // pgx_setup / pgx_run
 
 namespace btf {
 
-// the generator of one element of one slot of the chain `stream`
-__device__ __forceinline__ CellRng foldc_rng(unsigned long long seed, unsigned long long stream, int slot, int element) {
-  CellRng g(seed, stream);
-  g.ctr = ((unsigned long long)slot << 44) | ((unsigned long long)(unsigned)element << 12);
-  return g;
-}
-
 template <int K, int FAM>
 __global__ __launch_bounds__(WAVE) void fold_cols_kernel(FoldColsArgs a) {
-  constexpr int KK = tri(K), NA = KK + K;
   extern __shared__ double lds[];
   __shared__ uint4 rec_g[FAM == FOLDC_BINOMIAL ? WAVE : 1], rec_p[FAM == FOLDC_BINOMIAL ? WAVE : 1];
   __shared__ float pg_out[FAM == FOLDC_BINOMIAL ? WAVE : 1];
   const int lane = threadIdx.x;
-  const int T = a.T, N = a.N, nD = a.nD, D1 = a.tf + 2, n = T * K, bw = (a.tf + 1) * K, R1 = bw + 1;
+  const int T = a.T, N = a.N, nD = a.nD, D1 = a.tf + 2, n = T * K, bw = (a.tf + 1) * K;
   const int s = blockIdx.x / a.C, c = blockIdx.x - s * a.C;
-  double* B = lds;                      // [n][R1] the band of Q, then of L
-  double* rm = B + (size_t)n * R1;      // [n] b -> L^-1 b -> mean
-  double* ru = rm + n;                  // [n] z -> L^-T z -> v
-  double* invd = ru + n;                // [n] 1 / L_ii
-  double* bv = invd + n;                // [n] b
-  double* A = bv + n;                   // [T][KK] packed lower triangles of A_t
-  double* tau = A + (size_t)T * KK;     // [nD] x 4: tau2, c, b, a
-  double* lc = tau + nD;
-  double* lb = lc + nD;
-  double* la = lb + nD;
-  double* itau = la + nD;               // [nD] 1 / (lam2 tau2)
-  double* pb = itau + nD;               // [T][D1] the prior band: entry (t + d, t)
-  unsigned short* ptab = reinterpret_cast<unsigned short*>(pb + (size_t)T * D1);
+  FoldChainLds m;
+  fold_chain_layout(m, lds, T, K, a.tf, bw, nD, 0, false);
   const unsigned long long sg = (unsigned long long)(a.sample0 + s);
   const unsigned long long stream = (sg << 32) | (unsigned long long)(unsigned)c;
   const size_t chain = (size_t)s * a.C + c;
   const size_t LD = (size_t)4 * nD + (size_t)a.sweeps * (n + 4 * nD);
   const double* dr = a.draws ? a.draws + chain * LD : nullptr;
   const double lam2 = a.lam2[(size_t)s * a.lstride];
-  const double inv_nu2 = (FAM == FOLDC_GAUSSIAN) ? 1.0 / a.noise[(size_t)s * a.nstride] : 1.0;
-  const double lo = a.lo, hi = a.hi;
-  auto clip = [&](double x) { return fmin(fmax(x, lo), hi); };
+  const double* __restrict__ W = a.W + (size_t)s * N * K;
+  const double* cn = a.cnt + (size_t)c * T * N;
+  const double* ys = a.ysum + (size_t)c * T * N;
 
-  fill_pair_table(ptab, bw);
+  fill_pair_table(m.ptab, bw);
   unsigned long long pg_key = 0;
   if constexpr (FAM == FOLDC_BINOMIAL) {
     uint32_t kw[4];
-    Philox::gen(a.seed, stream, FOLDC_PG_SLOT << 44, kw);    // a counter the chain's other draws never reach
+    Philox::gen(a.seed, stream, FOLD_CHAIN_PG_SLOT << 44, kw);    // a counter the chain's other draws never reach
     pg_key = ((unsigned long long)kw[1] << 32) | kw[0];
-    for (int idx = lane; idx < n; idx += WAVE) ru[idx] = 0.0;  // the chain starts at v = 0
+    for (int idx = lane; idx < n; idx += WAVE) m.ru[idx] = 0.0;  // the chain starts at v = 0
     __syncthreads();
   }
-  // A_t and b_t, lanes along rows, every depth in turn.  Gaussian: once per chain, A_t = sum cnt w w' / nu2.  Binomial: every
-  // sweep, after omega_it ~ PG(n_it, w_i . v_t) from the current v (ru): A_t = sum omega w w', b_t = sum kappa w.
-  auto accumulate = [&](int sw) {
-    const double* __restrict__ W = a.W + (size_t)s * N * K;
-    for (int t = 0; t < T; ++t) {
-      const double* __restrict__ cn = a.cnt + ((size_t)c * T + t) * N;
-      const double* __restrict__ ys = a.ysum + ((size_t)c * T + t) * N;
-      double vt[K];
-      if constexpr (FAM == FOLDC_BINOMIAL) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) vt[k] = ru[t * K + k];
-      }
-      double acc[NA];
-#pragma unroll
-      for (int e = 0; e < NA; ++e) acc[e] = 0.0;
-      for (int i0 = 0; i0 < N; i0 += WAVE) {               // (every lane of the wave takes part in the Polya-Gamma loop)
-        const int i = i0 + lane;
-        const bool row_ok = i < N;
-        const int ic = row_ok ? i : N - 1;
-        double w[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) w[k] = W[(size_t)ic * K + k];
-        double cw = row_ok ? cn[ic] : 0.0;
-        const double y = row_ok ? ys[ic] : 0.0;
-        if constexpr (FAM == FOLDC_BINOMIAL) {
-          double psi = 0.0;
-#pragma unroll
-          for (int k = 0; k < K; ++k) psi = fma(w[k], vt[k], psi);
-          pgx_setup((int)cw, 0.0f, psi, pg_key, ((unsigned long long)sw * T + t) * N + ic, rec_g[lane], rec_p[lane]);
-          pgx_run(&rec_g[lane], &rec_p[lane], 1, &pg_out[lane], 1, 1, [&](int) { return psi; });
-          cw = (double)pg_out[lane];
-        }
-#pragma unroll
-        for (int p = 0; p < K; ++p) {
-          const double tw = cw * w[p];
-          acc[KK + p] = fma(y, w[p], acc[KK + p]);
-#pragma unroll
-          for (int q = 0; q <= p; ++q) acc[lidx(p, q)] = fma(tw, w[q], acc[lidx(p, q)]);
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < NA; ++e) acc[e] = wave_sum(acc[e]);
-      if (lane == 0) {
-#pragma unroll
-        for (int e = 0; e < KK; ++e) A[(size_t)t * KK + e] = acc[e] * inv_nu2;
-#pragma unroll
-        for (int k = 0; k < K; ++k) bv[t * K + k] = acc[KK + k] * inv_nu2;
-      }
-    }
-  };
-  if constexpr (FAM == FOLDC_GAUSSIAN) accumulate(0);
-  // ---- the start of the levels: sample_horseshoe_plus, Tau2 clipped as _init_Tau2 does
-  for (int r = lane; r < nD; r += WAVE) {
-    double g0[4];
-    if (dr) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g0[j] = dr[(size_t)j * nD + r];
-    } else {
-      CellRng g = foldc_rng(a.seed, stream, 0, r);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g0[j] = gamma_mt(0.5, g);
-    }
-    const double av = 1.0 / g0[0], bq = 1.0 / (av * g0[1]), cv = 1.0 / (bq * g0[2]);
-    la[r] = av; lb[r] = bq; lc[r] = cv;
-    tau[r] = fmin(1.0 / (cv * g0[3]), FOLDC_TAU2_START_CLIP);
-  }
+  // Gaussian: A_t = sum cnt w w' / nu2, once per chain.  Binomial: every sweep, after omega_it ~ PG(n_it, w_i . v_t) from the
+  // current v (ru): A_t = sum omega w w', b_t = sum kappa w.
+  if constexpr (FAM == FOLDC_GAUSSIAN) accumulate_blocks<K>(m.A, m.bv, lane, W, cn, ys, T, N, 1.0 / a.noise[(size_t)s * a.nstride], CellWeight());
+  levels_start(m, lane, nD, dr, nullptr, a.seed, stream);
   __syncthreads();
 
   bool ok = true;
   for (int sw = 0; sw < a.sweeps; ++sw) {
     const double* ds = dr ? dr + (size_t)4 * nD + (size_t)sw * (n + 4 * nD) : nullptr;
-    if constexpr (FAM == FOLDC_BINOMIAL) { accumulate(sw); __syncthreads(); }
-    // ---- the prior band from 1 / (lam2 tau2)
-    for (int r = lane; r < nD; r += WAVE) itau[r] = 1.0 / (lam2 * tau[r]);
-    __syncthreads();
-    for (int e0 = lane; e0 < T * D1; e0 += WAVE) {
-      double sum = 0.0;
-      for (int e = a.st_ptr[e0]; e < a.st_ptr[e0 + 1]; ++e) sum = fma(a.st_coef[e], itau[a.st_row[e]], sum);
-      pb[e0] = sum;
+    if constexpr (FAM == FOLDC_BINOMIAL) {
+      accumulate_blocks<K>(m.A, m.bv, lane, W, cn, ys, T, N, 1.0, [&](int t, int i, const double (&w)[K], double trials) {
+        double psi = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) psi = fma(w[k], m.ru[t * K + k], psi);
+        pgx_setup((int)trials, 0.0f, psi, pg_key, ((unsigned long long)sw * T + t) * N + i, rec_g[lane], rec_p[lane]);
+        pgx_run(&rec_g[lane], &rec_p[lane], 1, &pg_out[lane], 1, 1, [&](int) { return psi; });
+        return (double)pg_out[lane];
+      });
+      __syncthreads();
     }
-    __syncthreads();
-    // ---- the band of Q: column nn = t K + k holds the entries (nn + off, nn), off = 0..bw
-    for (int idx = lane; idx < n * R1; idx += WAVE) {
-      const int nn = idx / R1, off = idx - nn * R1;
-      const int t = nn / K, k = nn - t * K;
-      const int row = nn + off, t2 = row / K, k2 = row - t2 * K;
-      double v = 0.0;
-      if (row < n) {
-        if (t2 == t) v = A[(size_t)t * KK + lidx(k2, k)];
-        if (k2 == k) v += pb[t * D1 + (t2 - t)];
-      }
-      B[idx] = v;
-    }
-    for (int idx = lane; idx < n; idx += WAVE) {
-      rm[idx] = bv[idx];
-      double z;
-      if (ds) z = ds[idx];
-      else { CellRng g = foldc_rng(a.seed, stream, sw + 1, nD + idx); z = g.normal(); }
-      ru[idx] = z;
-    }
+    prior_band(m, lane, nD, T * D1, lam2, a.st_ptr, a.st_row, a.st_coef);
+    fill_band<K>(m, lane, n, bw, D1);
+    sweep_normals(m, lane, n, nD, ds, a.seed, stream, sw + 1, true);       // (and rm = b)
     __syncthreads();
     // ---- Q = L L', rm = L^-1 b; then mean = L^-T rm and u = L^-T z
-    ok = banded_factor_forward(B, rm, invd, ptab, n, bw);
+    ok = banded_factor_forward(m.B, m.rm, m.invd, m.ptab, n, bw);
     if (!ok) break;
     __syncthreads();
-    banded_backward(B, rm, invd, n, bw);
-    banded_backward(B, ru, invd, n, bw);
+    banded_backward(m.B, m.rm, m.invd, n, bw);
+    banded_backward(m.B, m.ru, m.invd, n, bw);
     __syncthreads();
-    for (int idx = lane; idx < n; idx += WAVE) ru[idx] += rm[idx];
+    for (int idx = lane; idx < n; idx += WAVE) m.ru[idx] += m.rm[idx];
     __syncthreads();
-    // ---- the levels (factor.py:136-141), lane = penalty row
-    for (int r = lane; r < nD; r += WAVE) {
-      const int t0 = a.rcol0[r];
-      double dv[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) dv[k] = 0.0;
-      for (int e = 0; e < D1; ++e) {
-        const double cf = a.rcoef[(size_t)r * D1 + e];
-        const int t = min(t0 + e, T - 1);                    // (cf = 0 past the row's end)
-#pragma unroll
-        for (int k = 0; k < K; ++k) dv[k] = fma(cf, ru[t * K + k], dv[k]);
-      }
-      double dsq = 0.0;
-#pragma unroll
-      for (int k = 0; k < K; ++k) dsq = fma(dv[k], dv[k], dsq);
-      double g4[4];
-      if (ds) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g4[j] = ds[(size_t)n + (size_t)j * nD + r];
-      } else {
-        CellRng g = foldc_rng(a.seed, stream, sw + 1, r);
-        g4[0] = gamma_mt(0.5 * (K + 1), g);
-#pragma unroll
-        for (int j = 1; j < 4; ++j) g4[j] = gamma_mt(1.0, g);
-      }
-      const double rate = dsq / (2.0 * lam2) + 1.0 / clip(lc[r]);
-      const double tv = clip(rate) / g4[0];
-      const double cv = clip(1.0 / tv + 1.0 / lb[r]) / g4[1];
-      const double bq = clip(1.0 / cv + 1.0 / la[r]) / g4[2];
-      const double av = clip(1.0 / bq + 1.0) / g4[3];
-      tau[r] = tv; lc[r] = cv; lb[r] = bq; la[r] = av;
-    }
+    levels_update<K, false>(m, lane, m.ru, nullptr, nD, T, D1, a.rcol0, a.rcoef, ds, (size_t)n, lam2, a.lo, a.hi, a.seed, stream, sw + 1);
     __syncthreads();
   }
-  // ---- the last state of the chain; nan after a failed factorisation
-  const double bad = __builtin_nan("");
-  double* __restrict__ Vo = a.V + chain * n;
-  double* __restrict__ Mo = a.Vmean + chain * n;
-  double* __restrict__ To = a.Tau2 + chain * nD;
-  for (int idx = lane; idx < n; idx += WAVE) { Vo[idx] = ok ? ru[idx] : bad; Mo[idx] = ok ? rm[idx] : bad; }
-  for (int r = lane; r < nD; r += WAVE) To[r] = ok ? tau[r] : bad;
-  if (!ok && lane == 0) {
-    a.status[0] = 1;
-    atomicMin(&a.status[1], (int)(sg * (unsigned long long)a.C + (unsigned)c));
-  }
+  gibbs_finish(m, lane, n, nD, ok, a.V + chain * n, a.Vmean + chain * n, a.Tau2 + chain * nD, a.status,
+               (int)(sg * (unsigned long long)a.C + (unsigned)c));
 }
 
 }  // namespace btf

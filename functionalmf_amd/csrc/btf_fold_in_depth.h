@@ -16,8 +16,9 @@
 // functionalmf_amd/fold_in_depth.py restates this in numpy (`conditional`, `chain`); that module is the definition.
 //
 // ONE launch, fold_depth_kernel<K, FAMILY>, ONE geometry: a workgroup of one wave owns the chain of (sample s, fitted column j)
-// for all its sweeps; S * M chains in a launch - the geometry of fold_cols_kernel (btf_fold_in_cols.h), whose accumulation,
-// band and draw this kernel repeats on a system H K wide:
+// for all its sweeps; S * M chains in a launch - the geometry of fold_cols_kernel (btf_fold_in_cols.h); accumulation, band,
+// offsets and levels are the steps of btf_fold_chain.h on a system H K wide, and this kernel's own are the start of the
+// Binomial chain at the last kept depth and its Polya-Gamma weights:
 //   kept curve     only the last L = min(T, tf + 1) depths of V_s[j] are read, once, into LDS; off follows from them.
 //   accumulation   once per chain (Binomial: once per sweep, after its Polya-Gamma draws): for every new depth the lanes walk
 //       the N rows (lane l takes rows l, l + 64, ...: cnt and ysum lie [column][depth][row]), keep the K (K + 1) / 2 + K
@@ -31,22 +32,18 @@
 //   levels         lane = new penalty row, gamma_mt (btf_kernels.h) on a generator of the row.
 // Generator: Philox keyed (seed, stream = global sample index << 32 | column, counter = slot << 44 | element << 12 | block)
 // with slot 0 the start and slot r + 1 sweep r, element = row of R for the level draws and nR + coordinate for the normals;
-// the Polya-Gamma stream of a cell is keyed by (a Philox word of slot FOLDD_PG_SLOT, (sweep H + t) N + i) - never a thread or
+// the Polya-Gamma stream of a cell is keyed by (a Philox word of slot FOLD_CHAIN_PG_SLOT, (sweep H + t) N + i) - never a thread or
 // block index: splitting S over calls (sample0) gives the same bits.  `draws` (one flat block per chain, the layout of
 // fold_in_depth.chain) replaces every variate.
-// LDS per workgroup: foldd_lds_bytes (10.1 KB at H = 8, K = 5, tf = 2); beyond FOLDD_LDS_LIMIT the call is refused - there is no
-// second code path.  fp64 throughout, no floating-point atomics.
+// LDS per workgroup: foldd_lds_bytes (10.1 KB at H = 8, K = 5, tf = 2), the count of fold_chain_layout; beyond FOLDD_LDS_LIMIT
+// the call is refused - there is no second code path.  fp64 throughout, no floating-point atomics.
 #pragma once
-#include "btf_device.h"
-#include <math.h>
+#include "btf_fold_chain.h"
 
 namespace btf {
 
 enum { FOLDD_GAUSSIAN = 0, FOLDD_BINOMIAL = 1 };
-constexpr size_t FOLDD_LDS_LIMIT = 156 * 1024;      // what one workgroup may hold of a CU's 160 KiB beside the Polya-Gamma records
-constexpr int FOLDD_MAX_TRIALS = 32;                // PG_AUTO_EXACT_MAX: the counts drawn exactly (btf_fold_in.h)
-constexpr unsigned long long FOLDD_PG_SLOT = 0xFFFFFULL;   // the generator slot of the Polya-Gamma key: sweeps stay below it
-constexpr double FOLDD_TAU2_START_CLIP = 9.0;       // _init_Tau2
+constexpr size_t FOLDD_LDS_LIMIT = FOLD_CHAIN_LDS_LIMIT;      // (beside the Polya-Gamma records)
 constexpr int FOLDD_MAX_GRID = 8192;                // ndepth + horizon: the penalty on the extended grid is built dense on the host
 
 struct FoldDepthArgs {
@@ -74,13 +71,9 @@ struct FoldDepthArgs {
   int S, M, N, H, L, tf, nR, sweeps;
 };
 
-__host__ __device__ constexpr int foldd_bandwidth(int H, int K, int tf) { return (tf + 1) * K < H * K - 1 ? (tf + 1) * K : H * K - 1; }
-
-// the same count in fold_in_depth.lds_bytes
+// the same count in fold_in_depth.lds_bytes: foldc_lds_bytes on H depths + 8 (nR K + L K) for the offsets and the tail
 inline size_t foldd_lds_bytes(int H, int K, int tf, int nR, int L) {
-  const size_t n = (size_t)H * K, bw = (size_t)foldd_bandwidth(H, K, tf), npairs = bw * (bw + 1) / 2;
-  return 8 * (n * (bw + 1) + 4 * n + (size_t)H * tri(K) + 5 * (size_t)nR + (size_t)nR * K + (size_t)H * (tf + 2) + (size_t)L * K) +
-         8 * ((npairs + 3) / 4);
+  return fold_chain_lds_bytes(H, K, tf, fold_depth_bandwidth(H, K, tf), nR, L, false);
 }
 
 // the kernels live in btf_fold_in_depth.hip (a compilation unit of their own); the C-ABI unit launches them through this
@@ -90,239 +83,79 @@ FoldDepthKernel fold_depth_fn(int K, int family);    // null outside K = 1..10, 
 }  // namespace btf
 
 #ifdef BTF_FOLD_DEPTH_UNIT
-#include "btf_kernels.h"        // banded_factor_forward / banded_backward, fill_pair_table, CellRng, gamma_mt
 #include "btf_pg_exact.h"       // pgx_setup / pgx_run
 
 namespace btf {
 
-// the generator of one element of one slot of the chain `stream`
-__device__ __forceinline__ CellRng foldd_rng(unsigned long long seed, unsigned long long stream, int slot, int element) {
-  CellRng g(seed, stream);
-  g.ctr = ((unsigned long long)slot << 44) | ((unsigned long long)(unsigned)element << 12);
-  return g;
-}
-
 template <int K, int FAM>
 __global__ __launch_bounds__(WAVE) void fold_depth_kernel(FoldDepthArgs a) {
-  constexpr int KK = tri(K), NA = KK + K;
   extern __shared__ double lds[];
   __shared__ uint4 rec_g[FAM == FOLDD_BINOMIAL ? WAVE : 1], rec_p[FAM == FOLDD_BINOMIAL ? WAVE : 1];
   __shared__ float pg_out[FAM == FOLDD_BINOMIAL ? WAVE : 1];
   const int lane = threadIdx.x;
-  const int H = a.H, N = a.N, nR = a.nR, L = a.L, D1 = a.tf + 2, n = H * K, bw = foldd_bandwidth(H, K, a.tf), R1 = bw + 1;
+  const int H = a.H, N = a.N, nR = a.nR, L = a.L, D1 = a.tf + 2, n = H * K, bw = fold_depth_bandwidth(H, K, a.tf);
   const int s = blockIdx.x / a.M, j = blockIdx.x - s * a.M;
-  double* B = lds;                      // [n][R1] the band of Q, then of L
-  double* rm = B + (size_t)n * R1;      // [n] rhs -> L^-1 rhs -> mean
-  double* ru = rm + n;                  // [n] z -> L^-T z -> v
-  double* invd = ru + n;                // [n] 1 / L_ii
-  double* bv = invd + n;                // [n] b
-  double* A = bv + n;                   // [H][KK] packed lower triangles of A_t
-  double* tau = A + (size_t)H * KK;     // [nR] x 4: tau2, c, b, a
-  double* lc = tau + nR;
-  double* lb = lc + nR;
-  double* la = lb + nR;
-  double* itau = la + nR;               // [nR] 1 / (lam2 tau2)
-  double* off = itau + nR;              // [nR][K] D_o V_s[j]
-  double* pb = off + (size_t)nR * K;    // [H][D1] the prior band: entry (t + d, t)
-  double* vt = pb + (size_t)H * D1;     // [L][K] the kept tail
-  unsigned short* ptab = reinterpret_cast<unsigned short*>(vt + (size_t)L * K);
+  FoldChainLds m;
+  fold_chain_layout(m, lds, H, K, a.tf, bw, nR, L, false);
   const unsigned long long sg = (unsigned long long)(a.sample0 + s);
   const unsigned long long stream = (sg << 32) | (unsigned long long)(unsigned)j;
   const size_t chain = (size_t)s * a.M + j;
   const size_t LD = (size_t)4 * nR + (size_t)a.sweeps * (n + 4 * nR);
   const double* dr = a.draws ? a.draws + chain * LD : nullptr;
   const double lam2 = a.lam2[(size_t)s * a.lstride];
-  const double inv_nu2 = (FAM == FOLDD_GAUSSIAN) ? 1.0 / a.noise[(size_t)s * a.nstride] : 1.0;
-  const double lo = a.lo, hi = a.hi;
-  auto clip = [&](double x) { return fmin(fmax(x, lo), hi); };
+  const double* __restrict__ W = a.W + (size_t)s * N * K;
+  const double* cn = a.cnt + (size_t)j * H * N;
+  const double* ys = a.ysum + (size_t)j * H * N;
 
-  fill_pair_table(ptab, bw);
-  // ---- the kept tail and the offsets D_o V_s[j]: row r reaches depths rcol0 + e < 0, tail index L + rcol0 + e
-  {
-    const double* __restrict__ src = a.Vtail + chain * (size_t)a.vstride;
-    for (int idx = lane; idx < L * K; idx += WAVE) vt[idx] = src[idx];
-    __syncthreads();
-    for (int idx = lane; idx < nR * K; idx += WAVE) {
-      const int r = idx / K, k = idx - r * K, t0 = a.rcol0[r];
-      double sum = 0.0;
-      for (int e = 0; e < D1; ++e) {
-        const int t = t0 + e;
-        if (t < 0 && L + t >= 0) sum = fma(a.rcoef[(size_t)r * D1 + e], vt[(L + t) * K + k], sum);
-      }
-      off[idx] = sum;
-    }
-  }
+  fill_pair_table(m.ptab, bw);
+  tail_offsets<K>(m, lane, a.Vtail + chain * (size_t)a.vstride, L, nR, D1, a.rcol0, a.rcoef);
   unsigned long long pg_key = 0;
   if constexpr (FAM == FOLDD_BINOMIAL) {
     uint32_t kw[4];
-    Philox::gen(a.seed, stream, FOLDD_PG_SLOT << 44, kw);    // a counter the chain's other draws never reach
+    Philox::gen(a.seed, stream, FOLD_CHAIN_PG_SLOT << 44, kw);    // a counter the chain's other draws never reach
     pg_key = ((unsigned long long)kw[1] << 32) | kw[0];
-    for (int idx = lane; idx < n; idx += WAVE) ru[idx] = vt[(L - 1) * K + idx % K];   // the chain starts at the last kept depth
+    for (int idx = lane; idx < n; idx += WAVE) m.ru[idx] = m.vt[(L - 1) * K + idx % K];   // the chain starts at the last kept depth
   }
   __syncthreads();
-  // A_t and b_t, lanes along rows, every new depth in turn.  Gaussian: once per chain, A_t = sum cnt w w' / nu2.  Binomial:
-  // every sweep, after omega_it ~ PG(n_it, w_i . v_t) from the current v (ru): A_t = sum omega w w', b_t = sum kappa w.
-  auto accumulate = [&](int sw) {
-    const double* __restrict__ W = a.W + (size_t)s * N * K;
-    for (int t = 0; t < H; ++t) {
-      const double* __restrict__ cn = a.cnt + ((size_t)j * H + t) * N;
-      const double* __restrict__ ys = a.ysum + ((size_t)j * H + t) * N;
-      double vcur[K];
-      if constexpr (FAM == FOLDD_BINOMIAL) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) vcur[k] = ru[t * K + k];
-      }
-      double acc[NA];
-#pragma unroll
-      for (int e = 0; e < NA; ++e) acc[e] = 0.0;
-      for (int i0 = 0; i0 < N; i0 += WAVE) {               // (every lane of the wave takes part in the Polya-Gamma loop)
-        const int i = i0 + lane;
-        const bool row_ok = i < N;
-        const int ic = row_ok ? i : N - 1;
-        double w[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) w[k] = W[(size_t)ic * K + k];
-        double cw = row_ok ? cn[ic] : 0.0;
-        const double y = row_ok ? ys[ic] : 0.0;
-        if constexpr (FAM == FOLDD_BINOMIAL) {
-          double psi = 0.0;
-#pragma unroll
-          for (int k = 0; k < K; ++k) psi = fma(w[k], vcur[k], psi);
-          pgx_setup((int)cw, 0.0f, psi, pg_key, ((unsigned long long)sw * H + t) * N + ic, rec_g[lane], rec_p[lane]);
-          pgx_run(&rec_g[lane], &rec_p[lane], 1, &pg_out[lane], 1, 1, [&](int) { return psi; });
-          cw = (double)pg_out[lane];
-        }
-#pragma unroll
-        for (int p = 0; p < K; ++p) {
-          const double tw = cw * w[p];
-          acc[KK + p] = fma(y, w[p], acc[KK + p]);
-#pragma unroll
-          for (int q = 0; q <= p; ++q) acc[lidx(p, q)] = fma(tw, w[q], acc[lidx(p, q)]);
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < NA; ++e) acc[e] = wave_sum(acc[e]);
-      if (lane == 0) {
-#pragma unroll
-        for (int e = 0; e < KK; ++e) A[(size_t)t * KK + e] = acc[e] * inv_nu2;
-#pragma unroll
-        for (int k = 0; k < K; ++k) bv[t * K + k] = acc[KK + k] * inv_nu2;
-      }
-    }
-  };
-  if constexpr (FAM == FOLDD_GAUSSIAN) accumulate(0);
-  // ---- the start of the levels: sample_horseshoe_plus, Tau2 clipped as _init_Tau2 does
-  for (int r = lane; r < nR; r += WAVE) {
-    double g0[4];
-    if (dr) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g0[q] = dr[(size_t)q * nR + r];
-    } else {
-      CellRng g = foldd_rng(a.seed, stream, 0, r);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g0[q] = gamma_mt(0.5, g);
-    }
-    const double av = 1.0 / g0[0], bq = 1.0 / (av * g0[1]), cv = 1.0 / (bq * g0[2]);
-    la[r] = av; lb[r] = bq; lc[r] = cv;
-    tau[r] = fmin(1.0 / (cv * g0[3]), FOLDD_TAU2_START_CLIP);
-  }
+  // Gaussian: A_t = sum cnt w w' / nu2 for every new depth, once per chain.  Binomial: every sweep, after omega_it ~
+  // PG(n_it, w_i . v_t) from the current v (ru): A_t = sum omega w w', b_t = sum kappa w.
+  if constexpr (FAM == FOLDD_GAUSSIAN) accumulate_blocks<K>(m.A, m.bv, lane, W, cn, ys, H, N, 1.0 / a.noise[(size_t)s * a.nstride], CellWeight());
+  levels_start(m, lane, nR, dr, nullptr, a.seed, stream);
   __syncthreads();
 
   bool ok = true;
   for (int sw = 0; sw < a.sweeps; ++sw) {
     const double* ds = dr ? dr + (size_t)4 * nR + (size_t)sw * (n + 4 * nR) : nullptr;
-    if constexpr (FAM == FOLDD_BINOMIAL) { accumulate(sw); __syncthreads(); }
-    // ---- the prior band from 1 / (lam2 tau2)
-    for (int r = lane; r < nR; r += WAVE) itau[r] = 1.0 / (lam2 * tau[r]);
-    __syncthreads();
-    for (int e0 = lane; e0 < H * D1; e0 += WAVE) {
-      double sum = 0.0;
-      for (int e = a.st_ptr[e0]; e < a.st_ptr[e0 + 1]; ++e) sum = fma(a.st_coef[e], itau[a.st_row[e]], sum);
-      pb[e0] = sum;
+    if constexpr (FAM == FOLDD_BINOMIAL) {
+      accumulate_blocks<K>(m.A, m.bv, lane, W, cn, ys, H, N, 1.0, [&](int t, int i, const double (&w)[K], double trials) {
+        double psi = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) psi = fma(w[k], m.ru[t * K + k], psi);
+        pgx_setup((int)trials, 0.0f, psi, pg_key, ((unsigned long long)sw * H + t) * N + i, rec_g[lane], rec_p[lane]);
+        pgx_run(&rec_g[lane], &rec_p[lane], 1, &pg_out[lane], 1, 1, [&](int) { return psi; });
+        return (double)pg_out[lane];
+      });
+      __syncthreads();
     }
-    __syncthreads();
-    // ---- the band of Q: column nn = t K + k holds the entries (nn + o, nn), o = 0..bw (t2 - t <= tf + 1 as o <= (tf + 1) K)
-    for (int idx = lane; idx < n * R1; idx += WAVE) {
-      const int nn = idx / R1, o = idx - nn * R1;
-      const int t = nn / K, k = nn - t * K;
-      const int row = nn + o, t2 = row / K, k2 = row - t2 * K;
-      double v = 0.0;
-      if (row < n) {
-        if (t2 == t) v = A[(size_t)t * KK + lidx(k2, k)];
-        if (k2 == k) v += pb[t * D1 + (t2 - t)];
-      }
-      B[idx] = v;
-    }
-    // ---- rhs = b - D_n' diag(1 / (lam2 tau2)) off (rows of R in ascending order), and the normals
-    for (int idx = lane; idx < n; idx += WAVE) {
-      const int t = idx / K, k = idx - t * K;
-      double sum = 0.0;
-      for (int r = 0; r < nR; ++r) {
-        const int e = t - a.rcol0[r];
-        if (e >= 0 && e < D1) sum = fma(a.rcoef[(size_t)r * D1 + e] * itau[r], off[r * K + k], sum);
-      }
-      rm[idx] = bv[idx] - sum;
-      double z;
-      if (ds) z = ds[idx];
-      else { CellRng g = foldd_rng(a.seed, stream, sw + 1, nR + idx); z = g.normal(); }
-      ru[idx] = z;
-    }
+    prior_band(m, lane, nR, H * D1, lam2, a.st_ptr, a.st_row, a.st_coef);
+    fill_band<K>(m, lane, n, bw, D1);
+    rhs_minus_offsets<K>(m, lane, n, nR, D1, a.rcol0, a.rcoef);
+    sweep_normals(m, lane, n, nR, ds, a.seed, stream, sw + 1);
     __syncthreads();
     // ---- Q = L L', rm = L^-1 rhs; then mean = L^-T rm and u = L^-T z
-    ok = banded_factor_forward(B, rm, invd, ptab, n, bw);
+    ok = banded_factor_forward(m.B, m.rm, m.invd, m.ptab, n, bw);
     if (!ok) break;
     __syncthreads();
-    banded_backward(B, rm, invd, n, bw);
-    banded_backward(B, ru, invd, n, bw);
+    banded_backward(m.B, m.rm, m.invd, n, bw);
+    banded_backward(m.B, m.ru, m.invd, n, bw);
     __syncthreads();
-    for (int idx = lane; idx < n; idx += WAVE) ru[idx] += rm[idx];
+    for (int idx = lane; idx < n; idx += WAVE) m.ru[idx] += m.rm[idx];
     __syncthreads();
-    // ---- the levels, lane = new penalty row: dv = off + D_n v
-    for (int r = lane; r < nR; r += WAVE) {
-      const int t0 = a.rcol0[r];
-      double dv[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) dv[k] = off[r * K + k];
-      for (int e = 0; e < D1; ++e) {
-        const int t = t0 + e;
-        if (t < 0 || t >= H) continue;                       // a kept depth (in off), or past the grid (coefficient 0)
-        const double cf = a.rcoef[(size_t)r * D1 + e];
-#pragma unroll
-        for (int k = 0; k < K; ++k) dv[k] = fma(cf, ru[t * K + k], dv[k]);
-      }
-      double dsq = 0.0;
-#pragma unroll
-      for (int k = 0; k < K; ++k) dsq = fma(dv[k], dv[k], dsq);
-      double g4[4];
-      if (ds) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g4[q] = ds[(size_t)n + (size_t)q * nR + r];
-      } else {
-        CellRng g = foldd_rng(a.seed, stream, sw + 1, r);
-        g4[0] = gamma_mt(0.5 * (K + 1), g);
-#pragma unroll
-        for (int q = 1; q < 4; ++q) g4[q] = gamma_mt(1.0, g);
-      }
-      const double rate = dsq / (2.0 * lam2) + 1.0 / clip(lc[r]);
-      const double tv = clip(rate) / g4[0];
-      const double cv = clip(1.0 / tv + 1.0 / lb[r]) / g4[1];
-      const double bq = clip(1.0 / cv + 1.0 / la[r]) / g4[2];
-      const double av = clip(1.0 / bq + 1.0) / g4[3];
-      tau[r] = tv; lc[r] = cv; lb[r] = bq; la[r] = av;
-    }
+    levels_update<K, true>(m, lane, m.ru, m.off, nR, H, D1, a.rcol0, a.rcoef, ds, (size_t)n, lam2, a.lo, a.hi, a.seed, stream, sw + 1);
     __syncthreads();
   }
-  // ---- the last state of the chain; nan after a failed factorisation
-  const double bad = __builtin_nan("");
-  double* __restrict__ Vo = a.V + chain * n;
-  double* __restrict__ Mo = a.Vmean + chain * n;
-  double* __restrict__ To = a.Tau2 + chain * nR;
-  for (int idx = lane; idx < n; idx += WAVE) { Vo[idx] = ok ? ru[idx] : bad; Mo[idx] = ok ? rm[idx] : bad; }
-  for (int r = lane; r < nR; r += WAVE) To[r] = ok ? tau[r] : bad;
-  if (!ok && lane == 0) {
-    a.status[0] = 1;
-    atomicMin(&a.status[1], (int)(sg * (unsigned long long)a.M + (unsigned)j));
-  }
+  gibbs_finish(m, lane, n, nR, ok, a.V + chain * n, a.Vmean + chain * n, a.Tau2 + chain * nR, a.status,
+               (int)(sg * (unsigned long long)a.M + (unsigned)j));
 }
 
 }  // namespace btf

@@ -22,7 +22,7 @@ from .utils import bayes_grid_penalty
 
 FAMILIES = {"gaussian": 0, "binomial": 1}
 MAX_SUMMARY_SAMPLES = 16384      # the limit of posterior_summary_kernel (one cell's values are sorted in LDS)
-MAX_TRIALS = 32                  # FOLDC_MAX_TRIALS of csrc/btf_fold_in_cols.h: the counts drawn exactly, as fold_in.MAX_TRIALS
+MAX_TRIALS = 32                  # FOLD_CHAIN_MAX_TRIALS of csrc/btf_fold_chain.h: the counts drawn exactly, as fold_in.MAX_TRIALS
 LDS_LIMIT = 156 * 1024           # FOLDC_LDS_LIMIT of csrc/btf_fold_in_cols.h: what one workgroup may hold of a CU's 160 KiB of LDS
 STABILITY = 1e-6                 # the models' default `stability`
 TAU2_START_CLIP = 9.0            # _init_Tau2
