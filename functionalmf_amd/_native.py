@@ -134,6 +134,13 @@ SIGNATURES = {
     "btf_collect_fold_in_depth": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [_c_dp] * 4 + [C.c_uint64, C.c_int, C.c_int64, C.c_double,
                                                                                              _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int,
                                                                                              _c_dp, _c_dp]),
+    "btf_negbin_fold_in_cols": (C.c_int, [C.c_int] * 7 + [_c_dp] * 5 + [C.c_int64] * 4 + [_c_dp, _c_dp, C.c_uint64, C.c_int, C.c_int64,
+                                                                                  C.c_double, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp,
+                                                                                  C.c_int, _c_dp, _c_dp]),
+    "btf_negbin_fold_in_depth": (C.c_int, [C.c_int] * 8 + [_c_dp] * 6 + [C.c_int64] * 4 + [_c_dp, _c_dp, C.c_uint64, C.c_int, C.c_int64,
+                                                                                   C.c_double, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp,
+                                                                                   C.c_int, _c_dp, _c_dp]),
+    "btf_negbin_fold_lds_bytes": (C.c_int64, [C.c_int] * 5),
     "btf_slice_fold_cols": (C.c_int, [C.c_int, C.c_int, C.c_double, _c_dp, _c_dp, _c_dp] + [C.c_int] * 7 + [_c_dp, _c_dp, C.c_int, _c_dp] +
                             [_c_dp] * 7 + [C.c_int, _c_dp, _c_dp, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_double, _c_dp, _c_dp, _c_dp,
                                            _c_ip, _c_ip, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),

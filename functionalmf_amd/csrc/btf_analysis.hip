@@ -1462,6 +1462,34 @@ int slice_fold_cells_check(btf_ctx* c, const std::string& name, const double* cn
       return fail(c, BTF_EINVAL, name + ": counts and fit weights must be finite and non-negative, sums finite (0 where there is nothing)");
   return BTF_OK;
 }
+// The cells and the rate of a Negative-Binomial fold-in, in the place of fold_cells_check's "integers up to 32": counts and
+// sums finite and non-negative; the rate a compact array over dims = (samples, chains, rows, depths) with every axis full or
+// shared (stride 0), finite and positive; b = ysum + count * rate below 1e15, checked with the largest of each; the replay
+// weights finite and non-negative.  nrate: the values the rate holds.
+int negbin_fold_cells_check(btf_ctx* c, const std::string& name, const double* cnt, const double* ysum, size_t ncell, const double* rate,
+                            const long long (&rs)[4], const int (&dims)[4], const double* omega, size_t nomega, size_t& nrate) {
+  double cmax = 0.0, ymax = 0.0, rmax = 0.0;
+  for (size_t e = 0; e < ncell; ++e) {
+    if (!(cnt[e] >= 0.0 && cnt[e] < 1e15) || !(ysum[e] >= 0.0 && ysum[e] < 1e15))
+      return fail(c, BTF_EINVAL, name + ": counts and their sums must be finite and non-negative (0 where nothing was observed)");
+    cmax = std::max(cmax, cnt[e]); ymax = std::max(ymax, ysum[e]);
+  }
+  nrate = 1;
+  for (int a = 3; a >= 0; --a) {
+    if (rs[a] == 0) continue;
+    if (rs[a] != (long long)nrate)
+      return fail(c, BTF_EINVAL, name + ": the rate strides must be those of a compact (sample, column, row, depth) array, 0 on a shared axis");
+    nrate *= (size_t)dims[a];
+  }
+  for (size_t e = 0; e < nrate; ++e) {
+    if (!(rate[e] > 0.0 && rate[e] < INFINITY)) return fail(c, BTF_EINVAL, name + ": the rate must be finite and positive");
+    rmax = std::max(rmax, rate[e]);
+  }
+  if (!(ymax + cmax * rmax < 1e15)) return fail(c, BTF_EINVAL, name + ": ysum + count * rate must stay below 1e15");
+  for (size_t e = 0; omega && e < nomega; ++e)
+    if (!(omega[e] >= 0.0 && omega[e] < INFINITY)) return fail(c, BTF_EINVAL, name + ": omega must be finite and non-negative");
+  return BTF_OK;
+}
 // `draws` of nch chains: 4 nlev start gammas, then per sweep n normals, nu uniforms (0: a Gibbs chain) and 4 nlev gammas
 int fold_draws_check(btf_ctx* c, const std::string& name, const double* draws, size_t nch, size_t n, size_t nu, size_t nlev, int sweeps) {
   if (!draws) return BTF_OK;
@@ -1511,6 +1539,9 @@ struct FoldCols {
   int transform;
   const double* q; int nq;
   double *mean_out, *q_out;
+  // the Negative-Binomial family (FOLDC_NEGBIN) alone: the rate, its strides (sample, column, row, depth), the replay weights
+  const double* rate; long long rs[4]; const double* omega;
+  size_t nrate;
 };
 
 // the penalty rows on the host: Delta, its CSR stencil, and every row as (first depth, tf + 2 coefficients from there on)
@@ -1557,18 +1588,43 @@ int fold_cols_check(btf_ctx* c, const FoldCols& f, FoldColsPenalty& p) {
   return fold_draws_check(c, "fold_in_cols", f.draws, (size_t)f.S * f.C, (size_t)f.T * f.K, 0, (size_t)p.nD, f.sweeps);
 }
 
+// the same for the Negative-Binomial family: the shared checks, the weight buffer in the LDS count, and a cell check of its own
+int negbin_fold_cols_check(btf_ctx* c, FoldCols& f, FoldColsPenalty& p) {
+  const std::string name = "negbin_fold_in_cols";
+  if (f.family != FOLDC_NEGBIN || f.S < 1 || f.C < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 || f.T < 2 || !f.count || !f.ysum ||
+      !f.rate || !f.V_out || !f.Vmean_out || !f.Tau2_out || f.sample0 < 0 || f.nq < 0 || (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) ||
+      f.transform < 0 || f.transform > 2 || !(f.stability > 0.0 && f.stability <= 1.0))
+    return fail(c, BTF_EINVAL, "bad " + name + " arguments");
+  if (f.draws && !f.omega) return fail(c, BTF_EINVAL, name + ": draws needs omega beside it (the chain also draws Polya-Gamma variates)");
+  if (int rc = fold_sweeps_check(c, name, f.sweeps)) return rc;
+  if (int rc = fold_sizes_check(c, name, "ncols_new", "ndepth", f.S, f.C, f.N, f.T, f.K, f.tf, f.sample0, f.mean_out != nullptr,
+                                (double)f.sweeps * f.N * f.T))
+    return rc;
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  penalty_stencil(f.T, f.tf, p.Delta, p.nD, p.ptr, p.row, p.coef);
+  if (int rc = fold_lds_check(c, name, "a column and the weights of a depth", foldc_negbin_lds_bytes(f.T, f.K, f.tf, p.nD, f.N))) return rc;
+  if (int rc = fold_cols_rows(c, name.c_str(), f.T, f.tf, p)) return rc;
+  const int dims[4] = {f.S, f.C, f.N, f.T};
+  if (int rc = negbin_fold_cells_check(c, name, f.count, f.ysum, (size_t)f.C * f.N * f.T, f.rate, f.rs, dims, f.omega,
+                                       (size_t)f.S * f.C * f.sweeps * f.T * f.N, f.nrate))
+    return rc;
+  return fold_draws_check(c, name, f.draws, (size_t)f.S * f.C, (size_t)f.T * f.K, 0, (size_t)p.nD, f.sweeps);
+}
+
 // The launches on device states dW (S,N,K) and per-sample scalars on the device (noise null: the Binomial family).  The
 // scratch's context may be null (the stateless form).  The new V stays on the device between the chains and the summary.
 int fold_cols_run(Scratch& s, const double* dW, const double* dnoise, int nstride, const double* dlam, int lstride, const FoldCols& f,
                   const FoldColsPenalty& p) {
   btf_ctx* c = s.ctx();
   const int S = f.S, C = f.C, N = f.N, T = f.T, K = f.K, nD = p.nD;
-  FoldColsKernel kern = fold_cols_fn(K, f.family);
-  if (!kern) return fail(c, BTF_EINVAL, "fold_in_cols: nembeds must be 1..10 and family 0..1");
+  const bool negbin = f.family == FOLDC_NEGBIN;
+  const std::string name = negbin ? "negbin_fold_in_cols" : "fold_in_cols";
+  FoldColsKernel kern = negbin ? fold_cols_negbin_fn(K) : fold_cols_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, name + (negbin ? ": nembeds must be 1..10" : ": nembeds must be 1..10 and family 0..1"));
   // column statistics in the kernel's [column][depth][row] layout; Binomial: kappa = successes - trials / 2
   const size_t ncell = (size_t)C * N * T;
   std::vector<double> hc(ncell), hy(ncell);
-  const double* cw = f.family == FOLDC_GAUSSIAN ? f.count : f.trials;
+  const double* cw = f.family == FOLDC_BINOMIAL ? f.trials : f.count;
   for (int j = 0; j < C; ++j)
     for (int i = 0; i < N; ++i)
       for (int t = 0; t < T; ++t) {
@@ -1584,6 +1640,11 @@ int fold_cols_run(Scratch& s, const double* dW, const double* dnoise, int nstrid
   a.W = dW; a.noise = dnoise; a.lam2 = dlam; a.nstride = nstride; a.lstride = lstride;
   a.cnt = s.upload(hc.data(), ncell); a.ysum = s.upload(hy.data(), ncell);
   if (f.draws) a.draws = s.upload(f.draws, (size_t)S * C * L);
+  if (negbin) {
+    a.rate = s.upload(f.rate, f.nrate);
+    a.rs_s = f.rs[0]; a.rs_c = f.rs[1]; a.rs_i = f.rs[2]; a.rs_t = f.rs[3];
+    if (f.omega) a.omega = s.upload(f.omega, (size_t)S * C * f.sweeps * T * N);
+  }
   a.rcol0 = s.upload(p.rcol0.data(), p.rcol0.size()); a.rcoef = s.upload(p.rcoef.data(), p.rcoef.size());
   a.st_ptr = s.upload(p.ptr.data(), p.ptr.size());
   a.st_row = s.upload(p.row.data(), p.row.size()); a.st_coef = s.upload(p.coef.data(), p.coef.size());
@@ -1591,7 +1652,7 @@ int fold_cols_run(Scratch& s, const double* dW, const double* dnoise, int nstrid
   a.status = s.upload(stat0, 2);
   a.seed = f.seed; a.sample0 = f.sample0; a.lo = f.stability; a.hi = 1.0 / f.stability;
   a.S = S; a.C = C; a.N = N; a.T = T; a.tf = f.tf; a.nD = nD; a.sweeps = f.sweeps;
-  const size_t lds = foldc_lds_bytes(T, K, f.tf, nD);
+  const size_t lds = negbin ? foldc_negbin_lds_bytes(T, K, f.tf, nD, N) : foldc_lds_bytes(T, K, f.tf, nD);
   allow_lds(s, kern, lds);
   launch_counted(s, BTF_K_CRITERIA, kern, dim3((unsigned)((size_t)S * C)), dim3(WAVE), lds, a);
   // the summary stage reads the device-resident W (S,N,K) and the new V (S,C*T,K)
@@ -1603,9 +1664,33 @@ int fold_cols_run(Scratch& s, const double* dW, const double* dnoise, int nstrid
   s.download(f.Tau2_out, a.Tau2, nT);
   const int rc = s.finish();
   if (rc) return rc;
-  return stat[0] ? fold_pivot_fail(c, "fold_in_cols", stat[1], "ncols_new", "W / nu2 / lam2") : BTF_OK;
+  return stat[0] ? fold_pivot_fail(c, name, stat[1], "ncols_new", negbin ? "W / lam2" : "W / nu2 / lam2") : BTF_OK;
 }
 }  // namespace
+
+// the Negative-Binomial family under a name of its own: count and ysum (C,N,T) are the observed replicates of a cell and their
+// sum; the rate of (sample, column, row, depth) lies at rate[s rs_sample + c rs_col + i rs_row + t rs_depth]
+int btf_negbin_fold_in_cols(int device, int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order, const double* Ws,
+                            const double* lam2, const double* count, const double* ysum, const double* rate, long long rs_sample,
+                            long long rs_col, long long rs_row, long long rs_depth, const double* omega, const double* draws,
+                            unsigned long long seed, int sweeps, long long sample0, double stability, double* V_out,
+                            double* Vmean_out, double* Tau2_out, int transform, const double* q, int nq, double* mean_out,
+                            double* q_out) {
+  FoldCols f = {FOLDC_NEGBIN, nsamples, ncols_new, nrows, ndepth, nembeds, tf_order, count, ysum, nullptr, draws, seed, sweeps, sample0,
+                stability, V_out, Vmean_out, Tau2_out, transform, q, nq, mean_out, q_out, rate,
+                {rs_sample, rs_col, rs_row, rs_depth}, omega, 0};
+  g_fold_fail_index = -1;
+  if (!Ws || !lam2) return fail(nullptr, BTF_EINVAL, "bad negbin_fold_in_cols arguments");
+  FoldColsPenalty p;
+  if (int rc = negbin_fold_cols_check(nullptr, f, p)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(lam2[s] > 0.0 && lam2[s] < INFINITY)) return fail(nullptr, BTF_EINVAL, "negbin_fold_in_cols: lam2 must be finite and positive");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dl = s.upload(lam2, (size_t)nsamples);
+  return fold_cols_run(s, dW, nullptr, 1, dl, 1, f, p);
+}
 
 int btf_fold_in_cols(int device, int family, int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order,
                      const double* Ws, const double* noise, const double* lam2, const double* count, const double* ysum,
@@ -1661,6 +1746,9 @@ struct FoldDepth {
   int transform;
   const double* q; int nq;
   double *mean_out, *q_out;
+  // the Negative-Binomial family (FOLDD_NEGBIN) alone: the rate, its strides (sample, column, row, depth), the replay weights
+  const double* rate; long long rs[4]; const double* omega;
+  size_t nrate;
 };
 
 // the new rows of the penalty on T + H points on the host: every row as (first depth counted from the first new one,
@@ -1733,6 +1821,32 @@ int fold_depth_check(btf_ctx* c, const FoldDepth& f, FoldDepthPenalty& p) {
   return fold_draws_check(c, "fold_in_depth", f.draws, (size_t)f.S * f.M, (size_t)f.H * f.K, 0, (size_t)p.nR, f.sweeps);
 }
 
+// the same for the Negative-Binomial family: the shared checks, the weight buffer in the LDS count, and a cell check of its own
+int negbin_fold_depth_check(btf_ctx* c, FoldDepth& f, FoldDepthPenalty& p) {
+  const std::string name = "negbin_fold_in_depth";
+  if (f.family != FOLDD_NEGBIN || f.S < 1 || f.M < 1 || f.N < 1 || f.K < 1 || f.K > MAX_K || f.tf < 0 || f.T < 2 || f.H < 1 || !f.count ||
+      !f.ysum || !f.rate || !f.V_out || !f.Vmean_out || !f.Tau2_out || f.sample0 < 0 || f.nq < 0 ||
+      (f.nq > 0 && (!f.q || !f.q_out || !f.mean_out)) || f.transform < 0 || f.transform > 2 || !(f.stability > 0.0 && f.stability <= 1.0))
+    return fail(c, BTF_EINVAL, "bad " + name + " arguments");
+  if (f.draws && !f.omega) return fail(c, BTF_EINVAL, name + ": draws needs omega beside it (the chain also draws Polya-Gamma variates)");
+  if (int rc = fold_sweeps_check(c, name, f.sweeps)) return rc;
+  if (int rc = fold_sizes_check(c, name, "ncols", "horizon", f.S, f.M, f.N, f.H, f.K, f.tf, f.sample0, f.mean_out != nullptr,
+                                (double)f.sweeps * f.N * f.H))
+    return rc;
+  if ((double)f.T + f.H > (double)FOLDD_MAX_GRID)
+    return fail(c, BTF_EINVAL, name + ": ndepth + horizon must stay within " + std::to_string(FOLDD_MAX_GRID));
+  if (int rc = check_percentiles(c, f.q, f.nq)) return rc;
+  if (int rc = fold_lds_check(c, name, "the new depths and the weights of a depth", foldd_negbin_lds_bytes(f.H, f.K, f.tf, f.H, 1, f.N))) return rc;
+  if (int rc = fold_depth_rows(c, name.c_str(), f.T, f.H, f.tf, p)) return rc;
+  if (int rc = fold_lds_check(c, name, "the new depths and the weights of a depth", foldd_negbin_lds_bytes(f.H, f.K, f.tf, p.nR, p.L, f.N)))
+    return rc;
+  const int dims[4] = {f.S, f.M, f.N, f.H};
+  if (int rc = negbin_fold_cells_check(c, name, f.count, f.ysum, (size_t)f.M * f.H * f.N, f.rate, f.rs, dims, f.omega,
+                                       (size_t)f.S * f.M * f.sweeps * f.H * f.N, f.nrate))
+    return rc;
+  return fold_draws_check(c, name, f.draws, (size_t)f.S * f.M, (size_t)f.H * f.K, 0, (size_t)p.nR, f.sweeps);
+}
+
 // The launches on device states dW (S,N,K), the kept tails (tail of (s, j) at dVt[(s M + j) vstride], L x K) and per-sample
 // scalars on the device (noise null: the Binomial family).  The scratch's context may be null (the stateless form).  The new
 // V stays on the device between the chains and the summary.
@@ -1740,11 +1854,13 @@ int fold_depth_run(Scratch& s, const double* dW, const double* dVt, long long vs
                    const double* dlam, int lstride, const FoldDepth& f, const FoldDepthPenalty& p) {
   btf_ctx* c = s.ctx();
   const int S = f.S, M = f.M, N = f.N, H = f.H, K = f.K, nR = p.nR;
-  FoldDepthKernel kern = fold_depth_fn(K, f.family);
-  if (!kern) return fail(c, BTF_EINVAL, "fold_in_depth: nembeds must be 1..10 and family 0..1");
+  const bool negbin = f.family == FOLDD_NEGBIN;
+  const std::string name = negbin ? "negbin_fold_in_depth" : "fold_in_depth";
+  FoldDepthKernel kern = negbin ? fold_depth_negbin_fn(K) : fold_depth_fn(K, f.family);
+  if (!kern) return fail(c, BTF_EINVAL, name + (negbin ? ": nembeds must be 1..10" : ": nembeds must be 1..10 and family 0..1"));
   // the slice statistics lie [column][depth][row] as the kernel reads them; Binomial: kappa = successes - trials / 2
   const size_t ncell = (size_t)M * H * N;
-  const double* cw = f.family == FOLDD_GAUSSIAN ? f.count : f.trials;
+  const double* cw = f.family == FOLDD_BINOMIAL ? f.trials : f.count;
   std::vector<double> hy(ncell);
   for (size_t e = 0; e < ncell; ++e)
     hy[e] = cw[e] > 0.0 ? (f.family == FOLDD_BINOMIAL ? f.ysum[e] - 0.5 * cw[e] : f.ysum[e]) : 0.0;
@@ -1755,6 +1871,11 @@ int fold_depth_run(Scratch& s, const double* dW, const double* dVt, long long vs
   a.W = dW; a.Vtail = dVt; a.vstride = vstride; a.noise = dnoise; a.lam2 = dlam; a.nstride = nstride; a.lstride = lstride;
   a.cnt = s.upload(cw, ncell); a.ysum = s.upload(hy.data(), ncell);
   if (f.draws) a.draws = s.upload(f.draws, (size_t)S * M * LD);
+  if (negbin) {
+    a.rate = s.upload(f.rate, f.nrate);
+    a.rs_s = f.rs[0]; a.rs_c = f.rs[1]; a.rs_i = f.rs[2]; a.rs_t = f.rs[3];
+    if (f.omega) a.omega = s.upload(f.omega, (size_t)S * M * f.sweeps * H * N);
+  }
   a.rcol0 = s.upload(p.rcol0.data(), p.rcol0.size()); a.rcoef = s.upload(p.rcoef.data(), p.rcoef.size());
   a.st_ptr = s.upload(p.ptr.data(), p.ptr.size());
   // (a prior that couples nothing - H = 1 rows only - still has its diagonal entries: row and coef are never empty)
@@ -1763,7 +1884,7 @@ int fold_depth_run(Scratch& s, const double* dW, const double* dVt, long long vs
   a.status = s.upload(stat0, 2);
   a.seed = f.seed; a.sample0 = f.sample0; a.lo = f.stability; a.hi = 1.0 / f.stability;
   a.S = S; a.M = M; a.N = N; a.H = H; a.L = p.L; a.tf = f.tf; a.nR = nR; a.sweeps = f.sweeps;
-  const size_t lds = foldd_lds_bytes(H, K, f.tf, nR, p.L);
+  const size_t lds = negbin ? foldd_negbin_lds_bytes(H, K, f.tf, nR, p.L, N) : foldd_lds_bytes(H, K, f.tf, nR, p.L);
   allow_lds(s, kern, lds);
   launch_counted(s, BTF_K_CRITERIA, kern, dim3((unsigned)((size_t)S * M)), dim3(WAVE), lds, a);
   // the summary stage reads the device-resident W (S,N,K) and the new V (S,M*H,K)
@@ -1775,9 +1896,51 @@ int fold_depth_run(Scratch& s, const double* dW, const double* dVt, long long vs
   s.download(f.Tau2_out, a.Tau2, nT);
   const int rc = s.finish();
   if (rc) return rc;
-  return stat[0] ? fold_pivot_fail(c, "fold_in_depth", stat[1], "ncols", "W / V / nu2 / lam2") : BTF_OK;
+  return stat[0] ? fold_pivot_fail(c, name, stat[1], "ncols", negbin ? "W / V / lam2" : "W / V / nu2 / lam2") : BTF_OK;
 }
 }  // namespace
+
+// the Negative-Binomial family under a name of its own: count and ysum (M,H,N) are the observed replicates of a cell and their
+// sum; the rate of (sample, column, row, new depth) lies at rate[s rs_sample + j rs_col + i rs_row + t rs_depth]
+int btf_negbin_fold_in_depth(int device, int nsamples, int nrows, int ncols, int ndepth, int horizon, int nembeds, int tf_order,
+                             const double* Ws, const double* Vtail, const double* lam2, const double* count, const double* ysum,
+                             const double* rate, long long rs_sample, long long rs_col, long long rs_row, long long rs_depth,
+                             const double* omega, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                             double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
+                             int nq, double* mean_out, double* q_out) {
+  FoldDepth f = {FOLDD_NEGBIN, nsamples, nrows, ncols, ndepth, horizon, nembeds, tf_order, count, ysum, nullptr, draws, seed, sweeps,
+                 sample0, stability, V_out, Vmean_out, Tau2_out, transform, q, nq, mean_out, q_out, rate,
+                 {rs_sample, rs_col, rs_row, rs_depth}, omega, 0};
+  g_fold_fail_index = -1;
+  if (!Ws || !Vtail || !lam2) return fail(nullptr, BTF_EINVAL, "bad negbin_fold_in_depth arguments");
+  FoldDepthPenalty p;
+  if (int rc = negbin_fold_depth_check(nullptr, f, p)) return rc;
+  for (int s = 0; s < nsamples; ++s)
+    if (!(lam2[s] > 0.0 && lam2[s] < INFINITY)) return fail(nullptr, BTF_EINVAL, "negbin_fold_in_depth: lam2 must be finite and positive");
+  const size_t ntail = (size_t)nsamples * ncols * p.L * nembeds;
+  if (!all_finite(Vtail, ntail)) return fail(nullptr, BTF_EINVAL, "negbin_fold_in_depth: the kept curves must be finite");
+  if (int rc = use_device(device)) return rc;
+  Scratch s(nullptr, nullptr);
+  const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
+  const double* dVt = s.upload(Vtail, ntail);
+  const double* dl = s.upload(lam2, (size_t)nsamples);
+  return fold_depth_run(s, dW, dVt, (long long)p.L * nembeds, nullptr, 1, dl, 1, f, p);
+}
+
+// LDS one chain's workgroup of the Negative-Binomial fold-ins needs: horizon 0: a new column (foldc_negbin_lds_bytes), else
+// `horizon` new depths (foldd_negbin_lds_bytes); -1 on sizes no call takes
+long long btf_negbin_fold_lds_bytes(int nrows, int ndepth, int horizon, int nembeds, int tf_order) {
+  if (nrows < 1 || ndepth < 2 || horizon < 0 || nembeds < 1 || nembeds > MAX_K || tf_order < 0 || (double)ndepth + horizon > (double)FOLDD_MAX_GRID)
+    return -1;
+  if (horizon == 0) {
+    FoldColsPenalty p;
+    penalty_stencil(ndepth, tf_order, p.Delta, p.nD, p.ptr, p.row, p.coef);
+    return (long long)foldc_negbin_lds_bytes(ndepth, nembeds, tf_order, p.nD, nrows);
+  }
+  FoldDepthPenalty p;
+  if (fold_depth_rows(nullptr, "negbin_fold_in_depth", ndepth, horizon, tf_order, p)) return -1;
+  return (long long)foldd_negbin_lds_bytes(horizon, nembeds, tf_order, p.nR, p.L, nrows);
+}
 
 int btf_fold_in_depth(int device, int family, int nsamples, int nrows, int ncols, int ndepth, int horizon, int nembeds,
                       int tf_order, const double* Ws, const double* Vtail, const double* noise, const double* lam2,

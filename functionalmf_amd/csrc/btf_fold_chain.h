@@ -14,6 +14,8 @@
 //       ascending order; the statistics lie [column][depth][row]: one coalesced load per 64 rows), keep the K (K + 1) / 2 + K
 //       running sums of their rows in registers, and the 64 partial sums are added by the xor butterfly - a fixed order
 //       that depends on N alone.  A cell without weight adds exact zeros.  A_t and b_t stay in LDS.
+//   negbin         negbin_draw_depth, negbin_accumulate: the Negative-Binomial family's weights omega ~ PG(ysum + c r, w . v)
+//       of one depth drawn into LDS in a pass of their own, then accumulate_depth with kappa = (ysum - c r) / 2.
 //   band           prior_band, fill_band: the band of Q in LDS, column nn at B[nn (bw + 1)]; within a depth the offsets reach
 //       K - 1, across depths the prior couples (t, k) with (t + d, k), d <= tf + 1, at offset d K.  The prior band is
 //       formed from 1 / (lam2 tau2) through the CSR of the Delta' Delta stencil as band_side (btf_kernels.h) does.
@@ -56,12 +58,15 @@ struct FoldChainLds {
   double* off;              // [nD][K] D_o V_s[j]
   double* pb;               // [T][tf + 2] the prior band: entry (t + d, t)
   double* vt;               // [L][K] the kept tail
+  double* om;               // [nom] the Polya-Gamma weights of one depth, nom = N (the Negative-Binomial family; null otherwise)
   unsigned short* ptab;     // [bw (bw + 1) / 2] the pair table of banded_factor_forward
 };
 
 // Carves the arrays of a chain of T depths with nD penalty rows and half bandwidth bw out of `base` and returns the bytes
-// they take; a null base only counts.  L: the kept depths of a depth kernel's tail, 0 for a column kernel.
-__host__ __device__ inline size_t fold_chain_layout(FoldChainLds& m, double* base, int T, int K, int tf, int bw, int nD, int L, bool slice) {
+// they take; a null base only counts.  L: the kept depths of a depth kernel's tail, 0 for a column kernel.  nom: the rows of
+// the Negative-Binomial family's weight buffer, 0 for every other family.
+__host__ __device__ inline size_t fold_chain_layout(FoldChainLds& m, double* base, int T, int K, int tf, int bw, int nD, int L, bool slice,
+                                                    int nom = 0) {
   const size_t n = (size_t)T * K, npairs = (size_t)bw * (bw + 1) / 2;
   size_t used = 0;
   auto take = [&](size_t count) {
@@ -79,12 +84,13 @@ __host__ __device__ inline size_t fold_chain_layout(FoldChainLds& m, double* bas
   m.off = L > 0 ? take((size_t)nD * K) : nullptr;
   m.pb = take((size_t)T * (tf + 2));
   m.vt = L > 0 ? take((size_t)L * K) : nullptr;
+  m.om = nom > 0 ? take((size_t)nom) : nullptr;
   m.ptab = reinterpret_cast<unsigned short*>(take((npairs + 3) / 4));
   return 8 * used;
 }
-inline size_t fold_chain_lds_bytes(int T, int K, int tf, int bw, int nD, int L, bool slice) {
+inline size_t fold_chain_lds_bytes(int T, int K, int tf, int bw, int nD, int L, bool slice, int nom = 0) {
   FoldChainLds m;
-  return fold_chain_layout(m, nullptr, T, K, tf, bw, nD, L, slice);
+  return fold_chain_layout(m, nullptr, T, K, tf, bw, nD, L, slice, nom);
 }
 
 }  // namespace btf
@@ -101,52 +107,117 @@ __device__ __forceinline__ CellRng chain_rng(unsigned long long seed, unsigned l
   return g;
 }
 
-// A_t = scale sum_i weight_it w_i w_i' and b_t = scale sum_i ys_it w_i for t < T, lanes along rows, every depth in turn; cn
-// and ys: [T][N].  row_weight(t, i, w, cn_it) gives the weight of a row: every lane of the wave calls it in every block of 64
-// rows (a lane past N with row N - 1 and cn = 0: its cell then adds exact zeros, which leave every running sum as it is up
-// to the sign of a zero), so it may hold wave-wide steps.
+// the right-hand side of a cell is its ys
+struct CellSum {
+  __device__ __forceinline__ double operator()(int, int, double, double ys) const { return ys; }
+};
+
+// A_t = scale sum_i weight_it w_i w_i' and b_t = scale sum_i rhs_it w_i at ONE depth t, lanes along rows; cn and ys: the [N]
+// statistics of the depth.  row_weight(t, i, w, cn_it) gives the weight of a row and row_rhs(t, i, cn_it, ys_it) its
+// right-hand side (CellSum: ys_it itself): every lane of the wave calls them in every block of 64 rows (a lane past N with
+// row N - 1 and cn = ys = 0: its cell then adds exact zeros, which leave every running sum as it is up to the sign of a
+// zero), so they may hold wave-wide steps.
+template <int K, class RowWeight, class RowRhs = CellSum>
+__device__ __forceinline__ void accumulate_depth(double* A, double* bv, int lane, const double* __restrict__ W,
+                                                 const double* __restrict__ cn, const double* __restrict__ ys, int t, int N,
+                                                 double scale, RowWeight row_weight, RowRhs row_rhs = RowRhs()) {
+  constexpr int KK = tri(K), NA = KK + K;
+  double acc[NA];
+#pragma unroll
+  for (int e = 0; e < NA; ++e) acc[e] = 0.0;
+  for (int i0 = 0; i0 < N; i0 += WAVE) {
+    const int i = i0 + lane;
+    const bool row_ok = i < N;
+    const int ic = row_ok ? i : N - 1;
+    double w[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) w[k] = W[(size_t)ic * K + k];
+    const double cv = row_ok ? cn[ic] : 0.0;
+    const double cw = row_weight(t, ic, w, cv);
+    const double y = row_rhs(t, ic, cv, row_ok ? ys[ic] : 0.0);
+#pragma unroll
+    for (int p = 0; p < K; ++p) {
+      const double tw = cw * w[p];
+      acc[KK + p] = fma(y, w[p], acc[KK + p]);
+#pragma unroll
+      for (int q = 0; q <= p; ++q) acc[lidx(p, q)] = fma(tw, w[q], acc[lidx(p, q)]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < NA; ++e) acc[e] = wave_sum(acc[e]);
+  if (lane == 0) {
+#pragma unroll
+    for (int e = 0; e < KK; ++e) A[(size_t)t * KK + e] = acc[e] * scale;
+#pragma unroll
+    for (int k = 0; k < K; ++k) bv[t * K + k] = acc[KK + k] * scale;
+  }
+}
+// the same for every depth t < T in turn; cn and ys: [T][N]
 template <int K, class RowWeight>
 __device__ __forceinline__ void accumulate_blocks(double* A, double* bv, int lane, const double* __restrict__ W, const double* cn0,
                                                   const double* ys0, int T, int N, double scale, RowWeight row_weight) {
-  constexpr int KK = tri(K), NA = KK + K;
-  for (int t = 0; t < T; ++t) {
-    const double* __restrict__ cn = cn0 + (size_t)t * N;
-    const double* __restrict__ ys = ys0 + (size_t)t * N;
-    double acc[NA];
-#pragma unroll
-    for (int e = 0; e < NA; ++e) acc[e] = 0.0;
-    for (int i0 = 0; i0 < N; i0 += WAVE) {
-      const int i = i0 + lane;
-      const bool row_ok = i < N;
-      const int ic = row_ok ? i : N - 1;
-      double w[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) w[k] = W[(size_t)ic * K + k];
-      const double cw = row_weight(t, ic, w, row_ok ? cn[ic] : 0.0);
-      const double y = row_ok ? ys[ic] : 0.0;
-#pragma unroll
-      for (int p = 0; p < K; ++p) {
-        const double tw = cw * w[p];
-        acc[KK + p] = fma(y, w[p], acc[KK + p]);
-#pragma unroll
-        for (int q = 0; q <= p; ++q) acc[lidx(p, q)] = fma(tw, w[q], acc[lidx(p, q)]);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < NA; ++e) acc[e] = wave_sum(acc[e]);
-    if (lane == 0) {
-#pragma unroll
-      for (int e = 0; e < KK; ++e) A[(size_t)t * KK + e] = acc[e] * scale;
-#pragma unroll
-      for (int k = 0; k < K; ++k) bv[t * K + k] = acc[KK + k] * scale;
-    }
-  }
+  for (int t = 0; t < T; ++t) accumulate_depth<K>(A, bv, lane, W, cn0 + (size_t)t * N, ys0 + (size_t)t * N, t, N, scale, row_weight);
 }
 // the weight of a row is its cn
 struct CellWeight {
   template <int K>
   __device__ __forceinline__ double operator()(int, int, const double (&)[K], double cn) const { return cn; }
 };
+
+// The Negative-Binomial family (factor.py:506-511, 553): a cell with c observed replicates, their sum ysum and the rate r of
+// its (sample, chain, row, depth) is the Binomial cell with pseudo-data b = ysum + c r, kappa = (ysum - c r) / 2.
+struct NegbinRate {
+  const double* rate;       // the rate of (row i, depth t) of this chain at rate[i row + t depth]: the sample's and the chain's
+  long long row, depth;     //   strides are folded into the pointer; 0 on an axis the rate is shared along
+  const double* omega;      // [T][N] the weights of this chain's sweep in the place of every draw, or null
+};
+// omega_it ~ PG(ysum_it + c_it r_it, w_i . v_t) from the current v for ONE depth, left in m.om ([N], lane l its rows l,
+// l + 64, ...): the draws have a pass of their own so that the series sampler's second generator and candidate loop never
+// meet the K (K + 1) / 2 + K running sums of accumulate_depth in the register file.  The sampler is the one the
+// Negative-Binomial sweeps draw count data with (pg_draw_series below PG_NORMAL_B, pg_draw_normal from there on) on a CellRng
+// keyed (pg_key, (sweep T + t) N + i) - the key of the Binomial family's cells, never a thread or block index.  c = 0: weight
+// 0 without a draw.  A psi that is not finite (or beyond 1e8, where the series' term count leaves an int) gives nan: the
+// factorisation then fails and the chain is flagged.
+template <int K>
+__device__ __forceinline__ void negbin_draw_depth(const FoldChainLds& m, int lane, const double* __restrict__ W,
+                                                  const double* __restrict__ cn, const double* __restrict__ ys, const double* v, int t,
+                                                  int T, int N, const NegbinRate& nb, unsigned long long pg_key, int sw) {
+  for (int i = lane; i < N; i += WAVE) {
+    const double c = cn[i];
+    double om = 0.0;
+    if (c > 0.0) {
+      if (nb.omega) om = nb.omega[(size_t)t * N + i];
+      else {
+        double psi = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) psi = fma(W[(size_t)i * K + k], v[t * K + k], psi);
+        const double b = ys[i] + c * nb.rate[i * nb.row + t * nb.depth];
+        if (!(fabs(psi) <= 1e8)) om = __builtin_nan("");
+        else {
+          CellRng g(pg_key, ((unsigned long long)sw * T + t) * N + i);
+          om = b >= (double)PG_NORMAL_B ? pg_draw_normal(b, psi, g) : pg_draw_series(b, psi, g);
+        }
+      }
+    }
+    m.om[i] = om;
+  }
+}
+// A_t = sum_i omega_it w_i w_i' and b_t = sum_i kappa_it w_i for every depth: the draw pass, then the accumulation reading it
+template <int K>
+__device__ __forceinline__ void negbin_accumulate(const FoldChainLds& m, int lane, const double* __restrict__ W, const double* cn0,
+                                                  const double* ys0, const double* v, int T, int N, const NegbinRate& nb,
+                                                  unsigned long long pg_key, int sw) {
+  for (int t = 0; t < T; ++t) {
+    const double* cn = cn0 + (size_t)t * N;
+    const double* ys = ys0 + (size_t)t * N;
+    negbin_draw_depth<K>(m, lane, W, cn, ys, v, t, T, N, nb, pg_key, sw);
+    __syncthreads();
+    accumulate_depth<K>(
+        m.A, m.bv, lane, W, cn, ys, t, N, 1.0, [&](int, int i, const double (&)[K], double c) { return c > 0.0 ? m.om[i] : 0.0; },
+        [&](int tt, int i, double c, double y) { return c > 0.0 ? 0.5 * (y - c * nb.rate[i * nb.row + tt * nb.depth]) : 0.0; });
+    __syncthreads();
+  }
+}
 
 // the start of the levels: sample_horseshoe_plus with Tau2 clipped as _init_Tau2 does, from the 4 nD gammas at `dr` or the
 // generator's slot 0; or, with `fixed` (this chain's nD scales), tau2 held there and the other levels at 1

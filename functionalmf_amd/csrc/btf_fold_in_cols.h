@@ -14,6 +14,10 @@
 // Binomial columns (factor.py:437-460) start at v = 0 and open every sweep with omega_it ~ PG(n_it, w_i . v_t) from the current
 // v by the exact sampler of btf_pg_exact.h; A_t = sum_i omega_it w_i w_i' and b_t = sum_i (y_it - n_it / 2) w_i.
 // functionalmf_amd/fold_in_cols.py restates this in numpy (`conditional`, `chain`); that module is the definition.
+// Negative-Binomial columns (FOLDC_NEGBIN, instantiated beside the two others for btf_negbin_fold_in_cols alone) are Binomial
+// columns with the pseudo-data of factor.py:506-511: omega_it ~ PG(ysum_it + c_it r_it, w_i . v_t) and kappa = (ysum - c r) / 2
+// with the rate r read through four strides; their weights are drawn by negbin_accumulate (btf_fold_chain.h), one depth at a
+// time through an [N] buffer in LDS; functionalmf_amd/negbin_fold_in.py (`chain_cols`) is their definition.
 //
 // ONE launch, fold_cols_kernel<K, FAMILY>, ONE geometry: a workgroup of one wave owns the chain of (sample s, new column c) for all
 // its sweeps; S * C chains in a launch.  The steps below are those of btf_fold_chain.h (accumulate_blocks, prior_band, fill_band,
@@ -43,7 +47,7 @@
 
 namespace btf {
 
-enum { FOLDC_GAUSSIAN = 0, FOLDC_BINOMIAL = 1 };
+enum { FOLDC_GAUSSIAN = 0, FOLDC_BINOMIAL = 1, FOLDC_NEGBIN = 2 };   // (2: btf_negbin_fold_in_cols alone, through fold_cols_negbin_fn)
 constexpr size_t FOLDC_LDS_LIMIT = FOLD_CHAIN_LDS_LIMIT;      // (beside the Polya-Gamma records)
 
 struct FoldColsArgs {
@@ -67,14 +71,21 @@ struct FoldColsArgs {
   double lo, hi;            // clip: stability, 1 / stability
   int nstride, lstride;
   int S, C, N, T, tf, nD, sweeps;
+  // the Negative-Binomial family alone (cnt: observed replicates, ysum: their sum)
+  const double* rate;       // the rate of (sample s, column c, row i, depth t) at rate[s rs_s + c rs_c + i rs_i + t rs_t]
+  const double* omega;      // [S][C][sweeps][T][N] weights in the place of every Polya-Gamma draw, or null
+  long long rs_s, rs_c, rs_i, rs_t;   // 0 on an axis the rate is shared along
 };
 
 // the same count in fold_in_cols.lds_bytes: 8 (n (bw + 1) + 4 n + T K (K + 1) / 2 + 5 nD + T (tf + 2)) + the pair table
 inline size_t foldc_lds_bytes(int T, int K, int tf, int nD) { return fold_chain_lds_bytes(T, K, tf, (tf + 1) * K, nD, 0, false); }
+// the Negative-Binomial family: + 8 N for the weights of one depth (negbin_fold_in.lds_bytes)
+inline size_t foldc_negbin_lds_bytes(int T, int K, int tf, int nD, int N) { return fold_chain_lds_bytes(T, K, tf, (tf + 1) * K, nD, 0, false, N); }
 
 // the kernels live in btf_fold_in_cols.hip (a compilation unit of their own); the C-ABI unit launches them through this
 using FoldColsKernel = void (*)(FoldColsArgs);
 FoldColsKernel fold_cols_fn(int K, int family);    // null outside K = 1..10, family = 0..1
+FoldColsKernel fold_cols_negbin_fn(int K);         // the Negative-Binomial family (btf_negbin_fold_in_cols); null outside K = 1..10
 
 }  // namespace btf
 
@@ -92,7 +103,7 @@ __global__ __launch_bounds__(WAVE) void fold_cols_kernel(FoldColsArgs a) {
   const int T = a.T, N = a.N, nD = a.nD, D1 = a.tf + 2, n = T * K, bw = (a.tf + 1) * K;
   const int s = blockIdx.x / a.C, c = blockIdx.x - s * a.C;
   FoldChainLds m;
-  fold_chain_layout(m, lds, T, K, a.tf, bw, nD, 0, false);
+  fold_chain_layout(m, lds, T, K, a.tf, bw, nD, 0, false, FAM == FOLDC_NEGBIN ? N : 0);
   const unsigned long long sg = (unsigned long long)(a.sample0 + s);
   const unsigned long long stream = (sg << 32) | (unsigned long long)(unsigned)c;
   const size_t chain = (size_t)s * a.C + c;
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(WAVE) void fold_cols_kernel(FoldColsArgs a) {
 
   fill_pair_table(m.ptab, bw);
   unsigned long long pg_key = 0;
-  if constexpr (FAM == FOLDC_BINOMIAL) {
+  if constexpr (FAM != FOLDC_GAUSSIAN) {
     uint32_t kw[4];
     Philox::gen(a.seed, stream, FOLD_CHAIN_PG_SLOT << 44, kw);    // a counter the chain's other draws never reach
     pg_key = ((unsigned long long)kw[1] << 32) | kw[0];
@@ -131,6 +142,11 @@ __global__ __launch_bounds__(WAVE) void fold_cols_kernel(FoldColsArgs a) {
         return (double)pg_out[lane];
       });
       __syncthreads();
+    }
+    if constexpr (FAM == FOLDC_NEGBIN) {                 // omega_it ~ PG(ysum + c r, w_i . v_t), kappa = (ysum - c r) / 2
+      const NegbinRate nb = {a.rate + (size_t)s * a.rs_s + (size_t)c * a.rs_c, a.rs_i, a.rs_t,
+                             a.omega ? a.omega + (chain * a.sweeps + sw) * (size_t)T * N : nullptr};
+      negbin_accumulate<K>(m, lane, W, cn, ys, m.ru, T, N, nb, pg_key, sw);
     }
     prior_band(m, lane, nD, T * D1, lam2, a.st_ptr, a.st_row, a.st_coef);
     fill_band<K>(m, lane, n, bw, D1);

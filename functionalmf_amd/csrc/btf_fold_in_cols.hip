@@ -19,4 +19,15 @@ FoldColsKernel fold_cols_fn(int K, int family) {
   }
 }
 
+// the Negative-Binomial family (btf_negbin_fold_in_cols), through a getter of its own
+FoldColsKernel fold_cols_negbin_fn(int K) {
+  switch (K) {
+#define FOLDC_K(KV) \
+  case KV: return fold_cols_kernel<KV, FOLDC_NEGBIN>;
+    FOLDC_CASES(FOLDC_K)
+#undef FOLDC_K
+    default: return nullptr;
+  }
+}
+
 }  // namespace btf

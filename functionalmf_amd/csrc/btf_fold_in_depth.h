@@ -14,6 +14,9 @@
 // btf_pg_exact.h; A_t = sum_i omega_it w_i w_i' and b_t = sum_i (y_it - n_it / 2) w_i.  A slice without any observation is
 // allowed (D_n has full column rank): the forecast.  Rows of D' on kept depths alone drop out, so no kept Tau2 is read.
 // functionalmf_amd/fold_in_depth.py restates this in numpy (`conditional`, `chain`); that module is the definition.
+// Negative-Binomial slices (FOLDD_NEGBIN, instantiated beside the two others for btf_negbin_fold_in_depth alone) are Binomial
+// slices with omega_it ~ PG(ysum_it + c_it r_it, w_i . v_t) and kappa = (ysum - c r) / 2 (negbin_accumulate, btf_fold_chain.h);
+// functionalmf_amd/negbin_fold_in.py (`chain_depth`) is their definition.
 //
 // ONE launch, fold_depth_kernel<K, FAMILY>, ONE geometry: a workgroup of one wave owns the chain of (sample s, fitted column j)
 // for all its sweeps; S * M chains in a launch - the geometry of fold_cols_kernel (btf_fold_in_cols.h); accumulation, band,
@@ -42,7 +45,7 @@
 
 namespace btf {
 
-enum { FOLDD_GAUSSIAN = 0, FOLDD_BINOMIAL = 1 };
+enum { FOLDD_GAUSSIAN = 0, FOLDD_BINOMIAL = 1, FOLDD_NEGBIN = 2 };   // (2: btf_negbin_fold_in_depth alone, through fold_depth_negbin_fn)
 constexpr size_t FOLDD_LDS_LIMIT = FOLD_CHAIN_LDS_LIMIT;      // (beside the Polya-Gamma records)
 constexpr int FOLDD_MAX_GRID = 8192;                // ndepth + horizon: the penalty on the extended grid is built dense on the host
 
@@ -69,16 +72,25 @@ struct FoldDepthArgs {
   double lo, hi;            // clip: stability, 1 / stability
   int nstride, lstride;
   int S, M, N, H, L, tf, nR, sweeps;
+  // the Negative-Binomial family alone (cnt: observed replicates, ysum: their sum)
+  const double* rate;       // the rate of (sample s, column j, row i, new depth t) at rate[s rs_s + j rs_c + i rs_i + t rs_t]
+  const double* omega;      // [S][M][sweeps][H][N] weights in the place of every Polya-Gamma draw, or null
+  long long rs_s, rs_c, rs_i, rs_t;   // 0 on an axis the rate is shared along
 };
 
 // the same count in fold_in_depth.lds_bytes: foldc_lds_bytes on H depths + 8 (nR K + L K) for the offsets and the tail
 inline size_t foldd_lds_bytes(int H, int K, int tf, int nR, int L) {
   return fold_chain_lds_bytes(H, K, tf, fold_depth_bandwidth(H, K, tf), nR, L, false);
 }
+// the Negative-Binomial family: + 8 N for the weights of one depth (negbin_fold_in.lds_bytes)
+inline size_t foldd_negbin_lds_bytes(int H, int K, int tf, int nR, int L, int N) {
+  return fold_chain_lds_bytes(H, K, tf, fold_depth_bandwidth(H, K, tf), nR, L, false, N);
+}
 
 // the kernels live in btf_fold_in_depth.hip (a compilation unit of their own); the C-ABI unit launches them through this
 using FoldDepthKernel = void (*)(FoldDepthArgs);
 FoldDepthKernel fold_depth_fn(int K, int family);    // null outside K = 1..10, family = 0..1
+FoldDepthKernel fold_depth_negbin_fn(int K);         // the Negative-Binomial family (btf_negbin_fold_in_depth); null outside K = 1..10
 
 }  // namespace btf
 
@@ -96,7 +108,7 @@ __global__ __launch_bounds__(WAVE) void fold_depth_kernel(FoldDepthArgs a) {
   const int H = a.H, N = a.N, nR = a.nR, L = a.L, D1 = a.tf + 2, n = H * K, bw = fold_depth_bandwidth(H, K, a.tf);
   const int s = blockIdx.x / a.M, j = blockIdx.x - s * a.M;
   FoldChainLds m;
-  fold_chain_layout(m, lds, H, K, a.tf, bw, nR, L, false);
+  fold_chain_layout(m, lds, H, K, a.tf, bw, nR, L, false, FAM == FOLDD_NEGBIN ? N : 0);
   const unsigned long long sg = (unsigned long long)(a.sample0 + s);
   const unsigned long long stream = (sg << 32) | (unsigned long long)(unsigned)j;
   const size_t chain = (size_t)s * a.M + j;
@@ -110,7 +122,7 @@ __global__ __launch_bounds__(WAVE) void fold_depth_kernel(FoldDepthArgs a) {
   fill_pair_table(m.ptab, bw);
   tail_offsets<K>(m, lane, a.Vtail + chain * (size_t)a.vstride, L, nR, D1, a.rcol0, a.rcoef);
   unsigned long long pg_key = 0;
-  if constexpr (FAM == FOLDD_BINOMIAL) {
+  if constexpr (FAM != FOLDD_GAUSSIAN) {
     uint32_t kw[4];
     Philox::gen(a.seed, stream, FOLD_CHAIN_PG_SLOT << 44, kw);    // a counter the chain's other draws never reach
     pg_key = ((unsigned long long)kw[1] << 32) | kw[0];
@@ -136,6 +148,11 @@ __global__ __launch_bounds__(WAVE) void fold_depth_kernel(FoldDepthArgs a) {
         return (double)pg_out[lane];
       });
       __syncthreads();
+    }
+    if constexpr (FAM == FOLDD_NEGBIN) {                 // omega_it ~ PG(ysum + c r, w_i . v_t), kappa = (ysum - c r) / 2
+      const NegbinRate nb = {a.rate + (size_t)s * a.rs_s + (size_t)j * a.rs_c, a.rs_i, a.rs_t,
+                             a.omega ? a.omega + (chain * a.sweeps + sw) * (size_t)H * N : nullptr};
+      negbin_accumulate<K>(m, lane, W, cn, ys, m.ru, H, N, nb, pg_key, sw);
     }
     prior_band(m, lane, nR, H * D1, lam2, a.st_ptr, a.st_row, a.st_coef);
     fill_band<K>(m, lane, n, bw, D1);

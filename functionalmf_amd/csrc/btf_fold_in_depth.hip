@@ -19,4 +19,15 @@ FoldDepthKernel fold_depth_fn(int K, int family) {
   }
 }
 
+// the Negative-Binomial family (btf_negbin_fold_in_depth), through a getter of its own
+FoldDepthKernel fold_depth_negbin_fn(int K) {
+  switch (K) {
+#define FOLDD_K(KV) \
+  case KV: return fold_depth_kernel<KV, FOLDD_NEGBIN>;
+    FOLDD_CASES(FOLDD_K)
+#undef FOLDD_K
+    default: return nullptr;
+  }
+}
+
 }  // namespace btf

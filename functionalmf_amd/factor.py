@@ -1195,6 +1195,77 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
         raise NotImplementedError("slice_fold_in_depth for the Negative-Binomial model: the likelihood of a new depth slice depends "
                                   "on the sampled rate R, which the slice fold-ins do not read (not supported yet)")
 
+    # ---- folding new columns and depths in with the sampled rate (functionalmf_amd/negbin_fold_in.py).  Under names of their
+    # own: fold_in_rows / fold_in_cols / fold_in_depth / slice_fold_in_depth keep refusing this model. ----
+    def _nb_fold_head(self, what, results):
+        self._unsharded(what)
+        if results is None:
+            raise RuntimeError("no samples collected on the device (the Negative-Binomial model keeps its samples on the host), "
+                               "and no results given")
+        S, Ws, Vs = self._samples(results)
+        from ._analysis import check_scalars
+        return S, Ws, Vs, check_scalars("results: lam2", results.get("lam2"), S), results["R"] if "R" in results else None
+
+    def negbin_fold_in_cols(self, Y_new, results, rate=None, seed=0, sweeps=None, summary=True, q=(5, 95), transform=None,
+                            first_sample=0, draws=None, omega=None):
+        """fold_in_cols for this model, with the sampled rate, on the GPU (csrc/btf_fold_chain.h: negbin_accumulate): curves
+        of columns the chain never saw, one short Gibbs chain per (kept sample, new column).  The chain is the Binomial
+        family's with the pseudo-data of factor.py:506-511: a cell with c observed replicates, their sum ysum and rate r
+        draws omega ~ PG(ysum + c r, w_i . v_t) and has kappa = (ysum - c r) / 2.  functionalmf_amd.negbin_fold_in.chain_cols
+        is the definition in numpy.
+
+        Y_new: counts (C,N,T) or (C,N,T,nreps), nan = missing; finite, non-negative integers of any size.
+        results: a run_gibbs result dict with W (S,N,K), lam2 one value per sample and R (S,) + the rate shape (`rdims`),
+            uploaded.  This model keeps no samples on the device: None is a RuntimeError.
+        rate: (S,) plus a shape that broadcasts against (C,N,T); overrides results["R"].  Without it the new column takes the
+            kept sample's rate, which must not vary along the columns (R (S, N|1, 1, T|1)): where it does the fit says
+            nothing about a new column's rate and the call raises ValueError.  Rates are finite and positive.  Sampling a
+            rate for the new column is out of scope.
+        seed, sweeps (default: functionalmf_amd.fold_in_cols.DEFAULT_SWEEPS), summary, q, transform, first_sample: as
+            fold_in_cols; transform="ilogit" gives success probabilities.
+        draws with omega (S,C,sweeps,N,T): every variate and every Polya-Gamma weight of every chain in the place of the
+            device generators - the replay the kernel is tested against.  draws without omega is refused.
+
+        Returns the dict of fold_in_cols: V, V_mean (S,C,T,K), Tau2 (S,C,nD), nsamples, and with summary=True mean (N,C,T)
+        and quantiles (len(q),N,C,T) from the summary kernel on the device-resident draws.  results["W"] with out["V"] goes
+        into utils.posterior_summary / posterior_predictive.  The sampler's state is not touched.  Unsharded models."""
+        from . import negbin_fold_in as _nf
+        S, Ws, _, lam2, R = self._nb_fold_head("negbin_fold_in_cols", results)
+        N, T, K = self.nrows, self.ndepth, self.nembeds
+        Y = np.asarray(Y_new, dtype=float)
+        if Y.ndim not in (3, 4) or Y.shape[0] < 1:
+            raise ValueError("Y_new %r must be (C,%d,%d) or (C,%d,%d,nreps)" % (Y.shape, N, T, N, T))
+        C = Y.shape[0]
+        cnt, ysum = _nf.cell_statistics(Y, (C, N, T))
+        r = _nf.resolve_rate("cols", R, rate, S, C, N, T)
+        return _nf.evaluate("cols", S, C, N, T, K, self.tf_order, cnt, ysum, r, Ws, lam2, draws=draws, omega=omega, seed=seed,
+                            sweeps=sweeps, summary=summary, q=q, transform=transform, first_sample=first_sample,
+                            stability=float(self.stability), device=self._ctx.device)
+
+    def negbin_fold_in_depth(self, Y_new, results, horizon=None, rate=None, seed=0, sweeps=None, summary=True, q=(5, 95),
+                             transform=None, first_sample=0, draws=None, omega=None):
+        """fold_in_depth for this model, with the sampled rate, on the GPU: curves of every fitted column at depths the chain
+        never saw (new weeks of a count series), one short Gibbs chain per (kept sample, fitted column), the Binomial family's
+        with the pseudo-data of negbin_fold_in_cols.  functionalmf_amd.negbin_fold_in.chain_depth is the definition in numpy.
+
+        Y_new: counts (N,M,H) or (N,M,H,nreps), nan = missing; None with horizon=H: the forecast (no data: the chain of the
+            Gaussian fold_in_depth on the prior given the kept curve, and no rate is read).
+        results: as negbin_fold_in_cols, with V (S,M,T,K) (its last min(T, tf_order + 1) depths are uploaded).
+        rate: (S,) plus a shape that broadcasts against (N,M,H); overrides results["R"], which otherwise must not vary along
+            the depths (R (S, N|1, M|1, 1)).
+        The other arguments and the returned dict (V, V_mean (S,M,H,K), Tau2 (S,M,nR), mean (N,M,H), quantiles): as
+        fold_in_depth; sweeps defaults to functionalmf_amd.fold_in_depth.DEFAULT_SWEEPS.  Unsharded models."""
+        from . import negbin_fold_in as _nf
+        S, Ws, Vs, lam2, R = self._nb_fold_head("negbin_fold_in_depth", results)
+        N, M, T, K = self.nrows, self.ncols, self.ndepth, self.nembeds
+        H, cnt, ysum = _nf.slice_cells(Y_new, N, M, horizon)
+        r = _nf.resolve_rate("depth", R, rate, S, M, N, H, needed=bool(cnt.any()))
+        if not np.all(np.isfinite(Vs[:, :, T - min(T, self.tf_order + 1):])):
+            raise ValueError("results: V must be finite at the last kept depths")
+        return _nf.evaluate("depth", S, M, N, T, K, self.tf_order, cnt, ysum, r, Ws, lam2, Vs=Vs, horizon=H, draws=draws, omega=omega,
+                            seed=seed, sweeps=sweeps, summary=summary, q=q, transform=transform, first_sample=first_sample,
+                            stability=float(self.stability), device=self._ctx.device)
+
     def _pred_aux(self, results, nsamples):
         """The rate tensor of every sample: results['R'] (S,) + rate shape, else the current R for all of them."""
         from . import predictive as _pred

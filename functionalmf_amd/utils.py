@@ -482,6 +482,63 @@ def fold_in_depth(Y_new, Ws, Vs, family, horizon=None, nu2=None, lam2=None, tf_o
                         device=device)
 
 
+def negbin_fold_in_cols(Y_new, Ws, R, lam2=None, tf_order=2, seed=0, sweeps=None, summary=True, q=(5, 95), transform=None,
+                        first_sample=0, stability=1e-6, draws=None, omega=None, device=0):
+    """fold_in_cols for a Negative-Binomial fit, without a model: the stateless form of
+    NegativeBinomialBayesianTensorFiltering.negbin_fold_in_cols (see there for the method and the outputs).
+
+    Ws (S,N,K); lam2 one value per sample; tf_order and stability as the model was built with.  Y_new: counts (C,N,T) or
+    (C,N,T,nreps) with nan = missing.  R: the rate of the new columns, (S,) plus a shape that broadcasts against (C,N,T) -
+    what the model's call takes as rate=.  draws with omega (S,C,sweeps,N,T): every variate and Polya-Gamma weight of every
+    chain in the place of the device generators.  functionalmf_amd.negbin_fold_in.chain_cols is the definition in numpy.
+    There is no CPU fallback."""
+    from . import _analysis, _native, negbin_fold_in as _nf
+    Ws = _native.as_f64(Ws)
+    if Ws.ndim != 3 or Ws.shape[0] < 1:
+        raise ValueError("Ws must be (S,N,K), got %r" % (Ws.shape,))
+    S, N, K = Ws.shape
+    shape = np.shape(Y_new)
+    if len(shape) not in (3, 4) or shape[0] < 1:
+        raise ValueError("Y_new %r must be (C,%d,T) or (C,%d,T,nreps)" % (shape, N, N))
+    C, T = int(shape[0]), int(shape[2])
+    cnt, ysum = _nf.cell_statistics(Y_new, (C, N, T))
+    if R is None:
+        raise ValueError("R: the rate of the new columns is required")
+    rate = _nf.resolve_rate("cols", None, R, S, C, N, T)
+    lam2 = _analysis.check_scalars("lam2", lam2, S)
+    if not 0 < float(stability) <= 1:
+        raise ValueError("stability must lie in (0, 1]")
+    return _nf.evaluate("cols", S, C, N, T, K, tf_order, cnt, ysum, rate, Ws, lam2, draws=draws, omega=omega, seed=seed, sweeps=sweeps,
+                        summary=summary, q=q, transform=transform, first_sample=first_sample, stability=stability, device=device)
+
+
+def negbin_fold_in_depth(Y_new, Ws, Vs, R, horizon=None, lam2=None, tf_order=2, seed=0, sweeps=None, summary=True, q=(5, 95),
+                         transform=None, first_sample=0, stability=1e-6, draws=None, omega=None, device=0):
+    """fold_in_depth for a Negative-Binomial fit, without a model: the stateless form of
+    NegativeBinomialBayesianTensorFiltering.negbin_fold_in_depth (see there for the method and the outputs).
+
+    Ws (S,N,K) and Vs (S,M,T,K): the kept samples; lam2 one value per sample.  Y_new: counts (N,M,H) or (N,M,H,nreps) with
+    nan = missing; None with horizon=H: the forecast (R may then be None).  R: the rate at the new depths, (S,) plus a shape
+    that broadcasts against (N,M,H).  draws with omega (S,M,sweeps,N,H) as in negbin_fold_in_cols.
+    functionalmf_amd.negbin_fold_in.chain_depth is the definition in numpy.  There is no CPU fallback."""
+    from . import _analysis, negbin_fold_in as _nf, fold_in_depth as _fd
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, M, T, K = Vs.shape
+    N = Ws.shape[1]
+    H, cnt, ysum = _nf.slice_cells(Y_new, N, M, horizon)
+    if R is None and cnt.any():
+        raise ValueError("R: the rate at the new depths is required")
+    rate = _nf.resolve_rate("depth", None, R, S, M, N, H, needed=bool(cnt.any()))
+    lam2 = _analysis.check_scalars("lam2", lam2, S)
+    if not 0 < float(stability) <= 1:
+        raise ValueError("stability must lie in (0, 1]")
+    if not np.all(np.isfinite(Vs[:, :, T - _fd.tail_depths(T, tf_order):])):
+        raise ValueError("Vs must be finite at the last kept depths")
+    return _nf.evaluate("depth", S, M, N, T, K, tf_order, cnt, ysum, rate, Ws, lam2, Vs=Vs, horizon=H, draws=draws, omega=omega,
+                        seed=seed, sweeps=sweeps, summary=summary, q=q, transform=transform, first_sample=first_sample,
+                        stability=stability, device=device)
+
+
 def slice_fold_in_rows(Y_new, Vs, family, sigma2=None, Ws=None, likelihood_param=None, Constraints=None, Row_constraints=None,
                        row_features=None, Us=None, start=None, seed=0, draws=None, sweeps=None, max_rounds=40, summary=True,
                        q=(5, 95), transform=None, first_sample=0, device=0):

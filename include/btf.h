@@ -843,6 +843,39 @@ int btf_collect_fold_in_depth(btf_ctx* ctx, int family, int nsamples, int horizo
                               double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
                               int nq, double* mean_out, double* q_out);
 
+/* ---- folding new columns and depth slices into a Negative-Binomial fit (csrc/btf_fold_chain.h) ------------------------
+ * btf_fold_in_cols / btf_fold_in_depth for the Negative-Binomial model, whose cells depend on the sampled rate: a cell
+ * with count = c observed replicates, their sum ysum and rate r is the Binomial cell with omega ~ PG(ysum + c r, w_i . v_t)
+ * and kappa = (ysum - c r) / 2 (factor.py:506-511, 553); everything else is the chain of the Binomial family, from the same
+ * start.  functionalmf_amd/negbin_fold_in.py (`chain_cols`, `chain_depth`) is the definition.  Stateless only (the model
+ * keeps its samples on the host); the argument lists are their siblings' without family, noise and trials.  count, ysum:
+ * (C,N,T) for columns, (M,H,N) for depths; counts of any size (0: missing).  rate: the rate of (sample s, column c, row i,
+ * depth t) lies at rate[s rs_sample + c rs_col + i rs_row + t rs_depth]: a compact array over those four axes in that
+ * order, every axis full or shared (stride 0); finite and positive, ysum + count * rate below 1e15.  The Polya-Gamma
+ * weights come from the sampler of the Negative-Binomial sweeps (the sum-of-gammas series below 200, the moment-matched
+ * normal from there on) on a generator keyed by the cell as in the Binomial family, so splitting the samples over calls
+ * (sample0) returns identical bits; the chain's stream holds the column's INDEX IN THE CALL, so a column folded alone has
+ * the bits it has as column 0 of a larger call, not those of a later position.  omega (S,C,sweeps,T,N) / (S,M,sweeps,H,N), or NULL: weights in
+ * the place of every Polya-Gamma draw; draws (as in the siblings) needs omega beside it, and the two together make a chain
+ * a deterministic function of its inputs.  A cell with count 0 draws nothing and adds exact zeros: a column or slice
+ * without data runs the Gaussian family's chain on the prior with the same generator keys.  LDS: the sibling's count plus
+ * 8 nrows bytes for the weights of one depth (btf_negbin_fold_lds_bytes; horizon 0: a column; -1: sizes no call takes);
+ * beyond the limit BTF_EINVAL with the byte count.  Outputs, the summary stage, failures and btf_fail_index as in the
+ * siblings.  Launches are counted under BTF_K_CRITERIA.  Synchronous.                                                    */
+int btf_negbin_fold_in_cols(int device, int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order,
+                            const double* Ws, const double* lam2, const double* count, const double* ysum, const double* rate,
+                            long long rs_sample, long long rs_col, long long rs_row, long long rs_depth, const double* omega,
+                            const double* draws, unsigned long long seed, int sweeps, long long sample0, double stability,
+                            double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q, int nq,
+                            double* mean_out, double* q_out);
+int btf_negbin_fold_in_depth(int device, int nsamples, int nrows, int ncols, int ndepth, int horizon, int nembeds, int tf_order,
+                             const double* Ws, const double* Vtail, const double* lam2, const double* count, const double* ysum,
+                             const double* rate, long long rs_sample, long long rs_col, long long rs_row, long long rs_depth,
+                             const double* omega, const double* draws, unsigned long long seed, int sweeps, long long sample0,
+                             double stability, double* V_out, double* Vmean_out, double* Tau2_out, int transform, const double* q,
+                             int nq, double* mean_out, double* q_out);
+long long btf_negbin_fold_lds_bytes(int nrows, int ndepth, int horizon, int nembeds, int tf_order);
+
 /* ---- folding new columns into a slice-sampled fit (csrc/btf_slice_fold_cols.h) ---------------------------------------
  * The same for the slice-sampled models: one chain per (kept sample s, new column c) over the column's curve v (T,K) and
  * its horseshoe+ levels given W_s and lam2_s, the curve updated by elliptical slice sampling on an ellipse centred on a
