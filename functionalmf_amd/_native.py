@@ -141,6 +141,10 @@ SIGNATURES = {
                                                                                    C.c_double, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp,
                                                                                    C.c_int, _c_dp, _c_dp]),
     "btf_negbin_fold_lds_bytes": (C.c_int64, [C.c_int] * 5),
+    "btf_negbin_fold_in_rows": (C.c_int, [C.c_int] * 6 + [_c_dp] * 5 + [C.c_int64] * 4 + [_c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double,
+                                                                                  C.c_double, _c_dp, _c_dp, _c_dp, C.c_uint64, C.c_int,
+                                                                                  C.c_int64, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp,
+                                                                                  C.c_int, _c_dp, _c_dp]),
     "btf_slice_fold_cols": (C.c_int, [C.c_int, C.c_int, C.c_double, _c_dp, _c_dp, _c_dp] + [C.c_int] * 7 + [_c_dp, _c_dp, C.c_int, _c_dp] +
                             [_c_dp] * 7 + [C.c_int, _c_dp, _c_dp, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_double, _c_dp, _c_dp, _c_dp,
                                            _c_ip, _c_ip, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp]),

@@ -14,6 +14,7 @@
 #include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
 #include "btf_monotone.h"       // monotone projection of the posterior (kernel in btf_monotone.hip)
 #include "btf_fold_in.h"        // folding new rows in (kernel in btf_fold_in.hip)
+#include "btf_negbin_fold_rows.h"  // the same for a Negative-Binomial fit, with a fixed or a sampled rate (kernel in btf_fold_in.hip)
 #include "btf_slice_fold.h"     // the same for the slice-sampled models (kernels in btf_slice_fold.hip)
 #include "btf_fold_in_cols.h"   // folding new columns in (kernel in btf_fold_in_cols.hip)
 #include "btf_fold_in_depth.h"  // folding new depth slices in (kernel in btf_fold_in_depth.hip)
@@ -1690,6 +1691,113 @@ int btf_negbin_fold_in_cols(int device, int nsamples, int ncols_new, int nrows, 
   const double* dW = s.upload(Ws, (size_t)nsamples * nrows * nembeds);
   const double* dl = s.upload(lam2, (size_t)nsamples);
   return fold_cols_run(s, dW, nullptr, 1, dl, 1, f, p);
+}
+
+// ---------------------------------------------------------------- new rows for a Negative-Binomial fit (btf_negbin_fold_rows.h)
+// rate: the fixed rate through its strides, or NULL: one sampled rate per (sample, row) from rate_init (S,R), the rows'
+// histograms hist_y / hist_n (R,nbins) and nmetropolis steps per sweep.  Stateless: everything is uploaded.
+int btf_negbin_fold_in_rows(int device, int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs,
+                            const double* sigma2, const double* count, const double* ysum, const double* rate, long long rs_sample,
+                            long long rs_row, long long rs_col, long long rs_depth, const double* rate_init, const double* hist_y,
+                            const double* hist_n, int nbins, int nmetropolis, double rpropstdev, double rstdev, const double* omega,
+                            const double* z, const double* mh, unsigned long long seed, int sweeps, long long sample0, double* W_out,
+                            double* Wmean_out, double* R_out, double* accept_out, int transform, const double* q, int nq,
+                            double* mean_out, double* q_out) {
+  const std::string name = "negbin_fold_in_rows";
+  const int S = nsamples, R = nrows_new, M = ncols, T = ndepth, K = nembeds;
+  const bool sampled = rate == nullptr;
+  g_fold_fail_index = -1;
+  if (S < 1 || R < 1 || M < 1 || T < 1 || K < 1 || K > MAX_K || !Vs || !sigma2 || !count || !ysum || !W_out || !Wmean_out || sample0 < 0 ||
+      nq < 0 || (nq > 0 && (!q || !q_out || !mean_out)) || transform < 0 || transform > 2)
+    return fail(nullptr, BTF_EINVAL, "bad " + name + " arguments");
+  if (sampled && (!rate_init || !hist_y || !hist_n || nbins < 1 || !R_out || !accept_out || nmetropolis < 1 || nmetropolis > NBROWS_MAX_STEPS ||
+                  !(rpropstdev > 0.0 && rpropstdev < INFINITY) || !(rstdev > 0.0 && rstdev < INFINITY)))
+    return fail(nullptr, BTF_EINVAL, name + ": a sampled rate needs rate_init, the rows' histograms, the outputs R and accept, nmetropolis in 1.." +
+                                         std::to_string(NBROWS_MAX_STEPS) + " and positive finite rpropstdev and rstdev");
+  if (sweeps < 1 || sweeps > NBROWS_MAX_STEPS) return fail(nullptr, BTF_EINVAL, name + ": sweeps must lie in 1.." + std::to_string(NBROWS_MAX_STEPS));
+  if ((z != nullptr || mh != nullptr) && !omega)
+    return fail(nullptr, BTF_EINVAL, name + ": z and mh need omega beside them (the chain also draws Polya-Gamma variates)");
+  if ((mh != nullptr) != (sampled && z != nullptr))
+    return fail(nullptr, BTF_EINVAL, name + ": z replays a chain together with mh when the rate is sampled, and alone when it is fixed");
+  if (mean_out && S > 16384) return fail(nullptr, BTF_EINVAL, name + ": the summary stage takes at most 16384 samples");
+  if ((double)(sample0 + S) * R >= 2147483647.0 || (double)R * M * T >= 2147483647.0)
+    return fail(nullptr, BTF_EINVAL, name + ": (sample0 + nsamples) * nrows_new and nrows_new * ncols * ndepth must stay below 2^31");
+  if (int rc = check_percentiles(nullptr, q, nq)) return rc;
+  const int MT = M * T;
+  const size_t cellsN = (size_t)R * MT, nSR = (size_t)S * R, nW = nSR * K, nom = (size_t)S * sweeps * cellsN;
+  double r0max = 0.0;
+  for (size_t e = 0; sampled && e < nSR; ++e) {
+    if (!(rate_init[e] > 0.0 && rate_init[e] < INFINITY)) return fail(nullptr, BTF_EINVAL, name + ": rate_init must be finite and positive");
+    r0max = std::max(r0max, rate_init[e]);
+  }
+  const long long rs[4] = {sampled ? 0 : rs_sample, sampled ? 0 : rs_row, sampled ? 0 : rs_col, sampled ? 0 : rs_depth};
+  const int dims[4] = {S, R, M, T};
+  size_t nrate = 0;
+  if (int rc = negbin_fold_cells_check(nullptr, name, count, ysum, cellsN, sampled ? &r0max : rate, rs, dims, omega, nom, nrate)) return rc;
+  for (size_t e = 0; sampled && e < (size_t)R * nbins; ++e)
+    if (!(hist_y[e] >= 0.0 && hist_y[e] < 1e15) || !(hist_n[e] >= 0.0 && hist_n[e] < 1e15))
+      return fail(nullptr, BTF_EINVAL, name + ": the histograms must be finite and non-negative");
+  for (size_t e = 0; z && e < nW * sweeps; ++e)
+    if (!(std::fabs(z[e]) < INFINITY)) return fail(nullptr, BTF_EINVAL, name + ": z must be finite");
+  for (size_t e = 0; mh && e < nSR * sweeps * 2 * nmetropolis; ++e) {
+    const bool uniform = (e / nmetropolis) % 2 == 1;
+    if (!(std::fabs(mh[e]) < INFINITY) || (uniform && !(mh[e] > 0.0 && mh[e] < 1.0)))
+      return fail(nullptr, BTF_EINVAL, name + ": mh must be finite, its uniforms inside (0, 1)");
+  }
+  for (int s = 0; s < S; ++s)
+    if (sigma2[s] <= 0.0) return fail(nullptr, BTF_EINVAL, name + ": sigma2 must be positive");      // (nan / inf: the kernel flags the sample)
+  NegbinFoldRowsKernel kern = negbin_fold_rows_fn(K, sampled ? 1 : 0);
+  if (!kern) return fail(nullptr, BTF_EINVAL, name + ": nembeds must be 1..10");
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, S, 0, MT, K, nullptr, Vs, st)) return rc;
+  // row statistics and histograms in the kernel's [cell][row] / [bin][row] layouts
+  std::vector<double> hc(cellsN), hy(cellsN), by, bn;
+  for (int r = 0; r < R; ++r)
+    for (int jt = 0; jt < MT; ++jt) {
+      const double cv = count[(size_t)r * MT + jt];
+      hc[(size_t)jt * R + r] = cv;
+      hy[(size_t)jt * R + r] = cv > 0.0 ? ysum[(size_t)r * MT + jt] : 0.0;
+    }
+  const int stat0[2] = {0, INT_MAX};
+  NegbinFoldRowsArgs a = {};
+  a.V = st.V; a.sigma2 = s.upload(sigma2, (size_t)S);
+  a.cnt = s.upload(hc.data(), cellsN); a.ysum = s.upload(hy.data(), cellsN);
+  if (sampled) {
+    by.resize((size_t)R * nbins); bn.resize((size_t)R * nbins);
+    for (int r = 0; r < R; ++r)
+      for (int b = 0; b < nbins; ++b) {
+        by[(size_t)b * R + r] = hist_y[(size_t)r * nbins + b];
+        bn[(size_t)b * R + r] = hist_n[(size_t)r * nbins + b];
+      }
+    a.rate0 = s.upload(rate_init, nSR);
+    a.hy = s.upload(by.data(), by.size()); a.hn = s.upload(bn.data(), bn.size());
+    a.Rout = s.alloc<double>(nSR); a.accept = s.alloc<double>(nSR);
+    a.B = nbins; a.nm = nmetropolis; a.rprop = rpropstdev; a.rstdev = rstdev;
+  } else {
+    a.rate = s.upload(rate, nrate);
+    a.rs_s = rs[0]; a.rs_r = rs[1]; a.rs_j = rs[2]; a.rs_t = rs[3];
+  }
+  if (omega) a.omega = s.upload(omega, nom);
+  if (z) a.z = s.upload(z, nW * sweeps);
+  if (mh) a.mh = s.upload(mh, nSR * sweeps * 2 * nmetropolis);
+  a.W = s.alloc<double>(nW); a.Wmean = s.alloc<double>(nW); a.status = s.upload(stat0, 2);
+  a.seed = seed; a.sample0 = sample0; a.S = S; a.R = R; a.T = T; a.MT = MT; a.sweeps = sweeps;
+  launch_counted(s, BTF_K_CRITERIA, kern, dim3(S, (R + WAVE - 1) / WAVE), dim3(FOLD_PARTS * WAVE), 0, a);
+  // the summary stage reads the device-resident W (S,R,K) and the uploaded V
+  if (mean_out) summary_stage(s, a.W, st.V, S, R, MT, K, transform, q, nq, mean_out, q_out);
+  int stat[2] = {0, INT_MAX};
+  s.download(stat, a.status, 2);
+  s.download(W_out, a.W, nW);
+  s.download(Wmean_out, a.Wmean, nW);
+  if (sampled) { s.download(R_out, a.Rout, nSR); s.download(accept_out, a.accept, nSR); }
+  const int rc = s.finish();
+  if (rc) return rc;
+  if (stat[0]) {
+    g_fold_fail_index = stat[1];
+    return fail(nullptr, BTF_ENOTPD, name + ": the precision of (sample, row) index " + std::to_string(stat[1]) +
+                                         " = sample * nrows_new + row is not positive definite (or sigma2 / V / w . v not finite); its outputs are nan");
+  }
+  return BTF_OK;
 }
 
 int btf_fold_in_cols(int device, int family, int nsamples, int ncols_new, int nrows, int ndepth, int nembeds, int tf_order,

@@ -1,7 +1,9 @@
-// Folding new rows into a fitted posterior (btf_fold_in.h): the kernel, one compilation unit of its own.  btf_analysis.hip
-// launches it through the function pointer below (counted under BTF_K_CRITERIA).  gfx950 only.
+// Folding new rows into a fitted posterior (btf_fold_in.h), and into a Negative-Binomial fit with a fixed or a sampled rate
+// (btf_negbin_fold_rows.h): the kernels, one compilation unit of their own.  btf_analysis.hip launches them through the
+// function pointers below (counted under BTF_K_CRITERIA).  gfx950 only.
 #define BTF_FOLD_UNIT
 #include "btf_fold_in.h"
+#include "btf_negbin_fold_rows.h"
 
 namespace btf {
 
@@ -13,6 +15,16 @@ FoldKernel fold_in_fn(int K, int family) {
   case KV:                                                                                  \
     return family == FOLD_GAUSSIAN ? fold_in_kernel<KV, FOLD_GAUSSIAN>                      \
            : family == FOLD_BINOMIAL ? fold_in_kernel<KV, FOLD_BINOMIAL> : nullptr;
+    FOLD_CASES(FOLD_K)
+#undef FOLD_K
+    default: return nullptr;
+  }
+}
+
+NegbinFoldRowsKernel negbin_fold_rows_fn(int K, int sampled) {
+  switch (K) {
+#define FOLD_K(KV) \
+  case KV: return sampled ? negbin_fold_rows_kernel<KV, true> : negbin_fold_rows_kernel<KV, false>;
     FOLD_CASES(FOLD_K)
 #undef FOLD_K
     default: return nullptr;

@@ -1266,6 +1266,44 @@ class NegativeBinomialBayesianTensorFiltering(BinomialBayesianTensorFiltering):
                             seed=seed, sweeps=sweeps, summary=summary, q=q, transform=transform, first_sample=first_sample,
                             stability=float(self.stability), device=self._ctx.device)
 
+    def negbin_fold_in_rows(self, Y_new, results, rate=None, sample_rate=None, rate_init=None, seed=0, sweeps=None, summary=True,
+                            q=(5, 95), transform=None, first_sample=0, draws=None, omega=None):
+        """fold_in_rows for this model, on the GPU (csrc/btf_negbin_fold_rows.h): embeddings of rows the chain never saw, one
+        short chain per (kept sample, new row) from w = 0 - the Binomial rows' chain on the pseudo-data of
+        negbin_fold_in_cols - and, where the fit has one rate per row, a SAMPLED rate for the new row: the model's own
+        random-walk Metropolis step on log r (nmetropolis, rpropstdev, rstdev of this model) in front of every sweep.
+        functionalmf_amd.negbin_fold_in.chain_rows is the definition in numpy.
+
+        Y_new: counts (R,M,T) or (R,M,T,nreps), nan = missing; finite, non-negative integers of any size.
+        results: a run_gibbs result dict with V (S,M,T,K), sigma2 one value per sample and R (S,) + the rate shape.
+        Where the rate of a new row comes from:
+            rate= given, (S,) plus a shape that broadcasts against (R,M,T)          fixed, as given
+            results["R"] (S,1,M|1,T|1): the layout does not vary along the rows     fixed, the kept sample's
+            results["R"] (S,N,1,1): one rate per row (rdims=(1, 2))                 sampled, one scalar per (sample, new row)
+            any other layout that varies along the rows                             ValueError asking for rate=
+        sample_rate=True forces sampling; False without a usable fixed rate is a ValueError.  rate_init (S,) or (S,R): the
+        start of a sampled rate, default the geometric mean of the kept sample's rates.
+        seed, summary, q, transform, first_sample: as fold_in_rows.  sweeps: default functionalmf_amd.fold_in.
+        DEFAULT_INNER_SWEEPS with a fixed rate, functionalmf_amd.negbin_fold_in.DEFAULT_SWEEPS["rows"] with a sampled one.
+        draws (S,R,sweeps (2 nmetropolis + K)) with omega (S,R,sweeps,M,T): the replay the kernel is tested against.
+
+        Returns W, W_mean (S,R,K), nsamples, with a sampled rate R (S,R) - the row's rate at the last sweep - and accept
+        (S,R), and with summary=True mean (R,M,T) and quantiles (len(q),R,M,T).  out["W"] with results["V"] and
+        out["R"][:, :, None, None] goes into utils.posterior_predictive(..., R=).  The sampler's state is not touched.
+        The model's `stability` is not read: the row chain has no horseshoe+ levels, the one place the siblings clip by
+        it, and the stateless form has no such argument.  Unsharded models."""
+        from . import utils
+        self._unsharded("negbin_fold_in_rows")
+        if results is None:
+            raise RuntimeError("no samples collected on the device (the Negative-Binomial model keeps its samples on the host), "
+                               "and no results given")
+        S, _, Vs = self._samples(results, need=("V",))
+        return utils.negbin_fold_in_rows(Y_new, Vs, results.get("sigma2"), R=results["R"] if "R" in results else None, rate=rate,
+                                         sample_rate=sample_rate, rate_init=rate_init, nmetropolis=self.nmetropolis,
+                                         rpropstdev=self.rpropstdev, rstdev=self.rstdev, seed=seed, sweeps=sweeps, summary=summary, q=q,
+                                         transform=transform, first_sample=first_sample, draws=draws, omega=omega,
+                                         device=self._ctx.device)
+
     def _pred_aux(self, results, nsamples):
         """The rate tensor of every sample: results['R'] (S,) + rate shape, else the current R for all of them."""
         from . import predictive as _pred

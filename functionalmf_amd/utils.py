@@ -539,6 +539,38 @@ def negbin_fold_in_depth(Y_new, Ws, Vs, R, horizon=None, lam2=None, tf_order=2, 
                         stability=stability, device=device)
 
 
+def negbin_fold_in_rows(Y_new, Vs, sigma2, R=None, rate=None, sample_rate=None, rate_init=None, nmetropolis=30, rpropstdev=0.1, rstdev=1,
+                        seed=0, sweeps=None, summary=True, q=(5, 95), transform=None, first_sample=0, draws=None, omega=None, device=0):
+    """Embeddings of rows a Negative-Binomial chain never saw, with a fixed or a SAMPLED rate, on the GPU, without a model:
+    the stateless form of NegativeBinomialBayesianTensorFiltering.negbin_fold_in_rows (see there for the method and the
+    outputs).
+
+    Vs (S,M,T,K); sigma2 one value per sample.  Y_new: counts (R,M,T) or (R,M,T,nreps) with nan = missing.  R: the fit's
+    results["R"], (S,) plus the model's rate shape; rate: (S,) plus a shape that broadcasts against (R,M,T).  Where the
+    rate of a new row comes from: rate= when given; else the kept sample's where R does not vary along the rows
+    (S,1,M|1,T|1); else, with one rate per row (S,N,1,1), one scalar per (sample, new row) SAMPLED by the model's
+    Metropolis step (nmetropolis, rpropstdev, rstdev as the model was built with) from rate_init, (S,) or (S,R), default
+    the geometric mean of the kept sample's rates; any other layout is a ValueError asking for rate=.  sample_rate=True
+    forces sampling, False refuses it.  draws (S,R,sweeps (2 nmetropolis + K)) with omega (S,R,sweeps,M,T): every variate
+    and Polya-Gamma weight of every chain in the place of the device generators.
+    functionalmf_amd.negbin_fold_in.chain_rows is the definition in numpy.  There is no CPU fallback."""
+    from . import _analysis, negbin_fold_in as _nf
+    Vs = _analysis.check_states(None, Vs)[1]
+    S, M, T, K = Vs.shape
+    shape = np.shape(Y_new)
+    if len(shape) not in (3, 4) or shape[0] < 1:
+        raise ValueError("Y_new %r must be (R,%d,%d) or (R,%d,%d,nreps)" % (shape, M, T, M, T))
+    nrows = int(shape[0])
+    mode, fixed = _nf.resolve_row_rate(R, rate, sample_rate, S, nrows, M, T)
+    r0 = _nf.resolve_rate_init(rate_init, R, S, nrows) if mode == "sampled" else None
+    sigma2 = _analysis.check_scalars("sigma2", sigma2, S, positive=False)
+    if np.any(sigma2 <= 0):
+        raise ValueError("sigma2 must be positive")
+    return _nf.evaluate_rows(S, nrows, M, T, K, Y_new, Vs, sigma2, rate=fixed, rate_init=r0, nmetropolis=nmetropolis,
+                             rpropstdev=rpropstdev, rstdev=rstdev, draws=draws, omega=omega, seed=seed, sweeps=sweeps, summary=summary,
+                             q=q, transform=transform, first_sample=first_sample, device=device)
+
+
 def slice_fold_in_rows(Y_new, Vs, family, sigma2=None, Ws=None, likelihood_param=None, Constraints=None, Row_constraints=None,
                        row_features=None, Us=None, start=None, seed=0, draws=None, sweeps=None, max_rounds=40, summary=True,
                        q=(5, 95), transform=None, first_sample=0, device=0):

@@ -876,6 +876,35 @@ int btf_negbin_fold_in_depth(int device, int nsamples, int nrows, int ncols, int
                              int nq, double* mean_out, double* q_out);
 long long btf_negbin_fold_lds_bytes(int nrows, int ndepth, int horizon, int nembeds, int tf_order);
 
+/* ---- folding new rows into a Negative-Binomial fit, with a fixed or a sampled rate (csrc/btf_negbin_fold_rows.h) ------
+ * One chain per (kept sample s, new row) from w = 0 with the prior N(0, sigma2_s I): the chain of btf_fold_in_rows' Binomial
+ * family on the pseudo-data above (omega ~ PG(ysum + c r, w . v_jt), kappa = (ysum - c r) / 2), `sweeps` sweeps.
+ * functionalmf_amd/negbin_fold_in.py (`chain_rows`) is the definition.  Stateless only.  Vs (S,M,T,K), sigma2 (S,);
+ * count, ysum (R,M,T): the observed replicates of a cell and their sum (0: missing), counts of any size.
+ * rate != NULL - a FIXED rate: the rate of (sample s, new row r, column j, depth t) lies at rate[s rs_sample + r rs_row +
+ *   j rs_col + t rs_depth], a compact array over those four axes in that order, every axis full or shared (stride 0);
+ *   finite and positive, ysum + count * rate below 1e15.  rate_init, hist_y, hist_n, R_out, accept_out are not read.
+ * rate == NULL - a SAMPLED rate: every (sample, row) has one scalar rate, started at rate_init (S,R) and updated in front
+ *   of every sweep by nmetropolis random-walk Metropolis steps on log r (the model's own: proposal N(log r, rpropstdev),
+ *   prior N(0, rstdev) on log r, accepted only above 1), whose count terms run over the row's histogram: hist_y (R,nbins)
+ *   the distinct counts of a row, hist_n (R,nbins) how often each was observed (0: padding).  R_out (S,R): the rate at
+ *   the last sweep; accept_out (S,R): the accepted share of the chain's steps.
+ * Generators: keyed (seed, (sample0 + s) << 32 | row) - splitting the samples over calls (sample0) or the rows' first 64 k
+ * over calls returns identical bits.  Replay: omega (S,sweeps,M*T,R) replaces every Polya-Gamma draw; z (S,R,sweeps,K) the
+ * normals of the draws of w and mh (S,R,sweeps,2,nmetropolis) the normals, then the uniforms of the Metropolis steps - z
+ * and mh need omega beside them, and mh goes with z when the rate is sampled.  W_out, Wmean_out (S,R,K): the last draw and
+ * its conditional mean.  The summary stage (mean_out (R,M,T), q_out (nq,R,M,T); transform as btf_posterior_summary) runs on
+ * the device-resident draws.  A non-positive pivot - also what a sigma2, V or w . v that is not finite ends in - returns
+ * BTF_ENOTPD with btf_fail_index(NULL) = (sample0 + s) * nrows_new + row of the smallest failing pair, whose outputs are
+ * nan.  Launches are counted under BTF_K_CRITERIA.  Synchronous.                                                         */
+int btf_negbin_fold_in_rows(int device, int nsamples, int nrows_new, int ncols, int ndepth, int nembeds, const double* Vs,
+                            const double* sigma2, const double* count, const double* ysum, const double* rate, long long rs_sample,
+                            long long rs_row, long long rs_col, long long rs_depth, const double* rate_init, const double* hist_y,
+                            const double* hist_n, int nbins, int nmetropolis, double rpropstdev, double rstdev, const double* omega,
+                            const double* z, const double* mh, unsigned long long seed, int sweeps, long long sample0, double* W_out,
+                            double* Wmean_out, double* R_out, double* accept_out, int transform, const double* q, int nq,
+                            double* mean_out, double* q_out);
+
 /* ---- folding new columns into a slice-sampled fit (csrc/btf_slice_fold_cols.h) ---------------------------------------
  * The same for the slice-sampled models: one chain per (kept sample s, new column c) over the column's curve v (T,K) and
  * its horseshoe+ levels given W_s and lam2_s, the curve updated by elliptical slice sampling on an ellipse centred on a
