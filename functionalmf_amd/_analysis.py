@@ -1,5 +1,5 @@
 """The Python front end of the posterior analysis features: summary, diagnostics, criteria / PSIS-LOO, predictive,
-functionals, ranking, feature association, monotone projection and fold-in.
+functionals, simultaneous bands, ranking, feature association, monotone projection and fold-in.
 
 Two halves.  The argument checks every feature shares, as plain functions (importable without a GPU): the transform table,
 the percentile check, the (S,N,K) / (S,M,T,K) shape check and the per-sample scalar check - the stateless forms in utils.py
@@ -325,6 +325,25 @@ class PosteriorAnalysis:
         S, Ws, Vs = self._samples(results)
         return _func.evaluate(shape, self.nembeds, S, which=which, q=q, transform=transform, x=x, level=level, exceed=exceed,
                               curves=curves, pointwise=pointwise, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device)
+
+    # ---- simultaneous credible bands: the band that holds the whole curve (functionalmf_amd/bands.py) ----
+    def posterior_bands(self, results=None, method="supt", level=95, depths=None, transform=None, curves=None, truth=None,
+                        _scratch_bytes=0):
+        """A band around every fitted curve f(w_i . v_j,:) that holds the WHOLE curve over depth with probability level / 100
+        among the kept samples, on the GPU (csrc/btf_bands.h) - where the percentiles of posterior_summary hold each cell
+        alone, and the curve as a whole far less often.
+
+        results: a run_gibbs result dict (W, V), uploaded; None: the samples the last device-collecting run_gibbs left on
+            the device (no upload).
+        The other arguments and the returned dict: functionalmf_amd.utils.posterior_bands.  The sampler's state is not
+        touched: a chain continued after the call walks the same path.  Unsharded models."""
+        from . import bands as _bands
+        self._unsharded("posterior bands")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        _bands.check_args(method, level, depths, transform, curves, truth, 2, *shape)
+        S, Ws, Vs = self._samples(results)
+        return _bands.evaluate(shape, self.nembeds, S, method=method, level=level, depths=depths, transform=transform, curves=curves,
+                               truth=truth, ctx=self._ctx, Ws=Ws, Vs=Vs, device=self._ctx.device, _scratch_bytes=_scratch_bytes)
 
     # ---- posterior ranking: which column is best for a row, with what probability (functionalmf_amd/ranking.py) ----
     def posterior_ranking(self, which="auc", along="cols", order="ascending", top=(1, 5), transform=None, x=None, level=None,

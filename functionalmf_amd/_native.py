@@ -98,6 +98,9 @@ SIGNATURES = {
                                             C.c_int, _c_ip, C.c_int] + [_c_dp] * 7),
     "btf_collect_functionals": (C.c_int, [_ctx, C.c_int, C.c_int, _c_ip, C.c_int, _c_dp, C.c_double, C.c_double, _c_dp, C.c_int, _c_ip,
                                           C.c_int] + [_c_dp] * 7),
+    "btf_posterior_bands": (C.c_int, [C.c_int] * 6 + [_c_dp, _c_dp, C.c_int, C.c_int, C.c_double, _c_ip, _c_ip, C.c_int] + [_c_dp] * 8 +
+                            [C.c_longlong]),
+    "btf_collect_bands": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, _c_ip, _c_ip, C.c_int] + [_c_dp] * 8 + [C.c_longlong]),
     "btf_posterior_ranking": (C.c_int, [C.c_int] * 6 + [_c_dp, _c_dp, C.c_int, C.c_int, _c_dp, C.c_double, C.c_int, C.c_int, _c_ip, C.c_int,
                                         _c_ip, C.c_int, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_dp, C.c_longlong]),
     "btf_collect_ranking": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _c_dp, C.c_double, C.c_int, C.c_int, _c_ip, C.c_int, _c_ip, C.c_int,

@@ -1,4 +1,4 @@
-// The posterior analyses behind the C ABI (include/btf.h): summaries, criteria, PSIS-LOO, predictive, functionals, ranking,
+// The posterior analyses behind the C ABI (include/btf.h): summaries, criteria, PSIS-LOO, predictive, functionals, bands, ranking,
 // similarity, association, monotone projection, fold-in (rows and columns: conjugate and slice-sampled), diagnostics.  Host code over kernels in units of their own.  gfx950 only.
 #include "btf_ctx.h"            // struct btf_ctx, fail, Scratch, launch_counted, K_SWITCH / FAM_SWITCH
 #include "btf_diag.h"           // convergence diagnostics (instances in btf_diag.hip)
@@ -9,6 +9,7 @@
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
 #include "btf_gg_predict.h"     // the same for the gamma-grid likelihood (kernels in btf_gg_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
+#include "btf_bands.h"          // simultaneous credible bands (kernels in btf_functionals.hip)
 #include "btf_ranking.h"        // posterior ranking (kernels in btf_ranking.hip)
 #include "btf_similarity.h"     // posterior similarity (kernels in btf_similarity.hip)
 #include "btf_assoc.h"          // posterior feature association (kernels in btf_assoc.hip)
@@ -664,6 +665,131 @@ int btf_collect_functionals(btf_ctx* c, int nsamples, int transform, const int* 
   if (int rc = resolve_pair(s, 0, "btf_collect_functionals", BTF_ESTATE, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
   return functionals_run(s, st.W, st.V, nsamples, c->N, c->M, c->T, c->K, transform, which, nwhich, x, level, exceed,
                          q, nq, curves, ncurves, o);
+}
+
+// ---------------------------------------------------------------- simultaneous credible bands (btf_bands.h)
+namespace {
+struct BandOut { double *center, *scale, *lower, *upper, *crit, *inside, *pw_inside, *stat; };
+
+// The whole evaluation on device states dW (S,N,K), dV (S,M,T,K): scratch, the launches, the downloads.  Both methods go
+// chunk by chunk of columns through a stage that scratch_bytes caps (0: FUNC_SCRATCH_BYTES; one column is the least a
+// chunk holds).  The scratch's context may be null (the stateless form).
+int bands_run(Scratch& s, const double* dW, const double* dV, int S, int N, int M, int T, int K, int transform, int method,
+              double level, const int* depths, const int* curves, int ncurves, const BandOut& o, long long scratch_bytes) {
+  BandArgs a = {};
+  a.W = dW; a.V = dV; a.S = S; a.N = N; a.M = M; a.T = T; a.ncurves = ncurves;
+  a.need = (int)std::ceil(level / 100.0 * S);
+  a.kpw = (int)std::floor((1.0 - level / 100.0) / 2.0 * S);
+  BandKernel moments = band_moments_fn(K, transform), sweep = band_sweep_fn(K, transform);
+  BandKernel depth = band_rank_depth_fn(K, transform), write = band_rank_write_fn(K, transform);
+  if (!moments || !sweep || !depth || !write) return fail(s.ctx(), BTF_EINVAL, "posterior bands: nembeds must be 1..10 and transform 0..2");
+  std::vector<int> use(T, 1);                            // (alive until finish())
+  if (depths) for (int t = 0; t < T; ++t) use[t] = depths[t] != 0;
+  a.use = s.upload(use.data(), (size_t)T);
+  const size_t NM = (size_t)N * M, NMT = NM * T;
+  a.lower = s.alloc<double>(NMT); a.upper = s.alloc<double>(NMT);
+  a.crit = s.alloc<double>(NM); a.inside = s.alloc<double>(NM);
+  double* dstat = nullptr;
+  if (ncurves) { a.curves = s.upload(curves, (size_t)2 * ncurves); dstat = s.alloc<double>((size_t)ncurves * S); }
+  const int rowblocks = (N + WAVE - 1) / WAVE, JMAX = 65535;   // (a grid's y extent)
+  if (method == BAND_SUPT) {
+    const SortGeom g = sort_geom(S, FUNC_SORT_LDS, BAND_CELLS);
+    a.P = g.P; a.cells = g.cells;
+    const size_t per_col = ((size_t)S + 2 * (size_t)T) * N, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
+    const int jc_max = (int)std::max<size_t>(1, std::min<size_t>(std::min(M, JMAX), cap / (per_col * sizeof(double))));
+    a.vals = s.alloc<double>((size_t)S * N * jc_max);
+    a.cen = s.alloc<double>((size_t)T * N * jc_max); a.scl = s.alloc<double>((size_t)T * N * jc_max);
+    a.center = s.alloc<double>(NMT); a.scale = s.alloc<double>(NMT);
+    FuncArgs ga = {};                                    // the gather of the functionals reads the same stage
+    ga.S = S; ga.N = N; ga.nslots = 1; ga.vals = a.vals;
+    allow_lds(s, band_supt_fn(), g.lds);
+    for (int j0 = 0; j0 < M; j0 += jc_max) {
+      a.j0 = ga.j0 = j0; a.jc = ga.jc = std::min(jc_max, M - j0);
+      launch_counted(s, BTF_K_CRITERIA, moments, dim3(rowblocks, a.jc, (T + BAND_TB - 1) / BAND_TB), dim3(BAND_PARTS * WAVE), 0, a);
+      launch_counted(s, BTF_K_CRITERIA, sweep, dim3(rowblocks, a.jc, func_sweep_slices(S, rowblocks, a.jc)), dim3(FUNC_WAVES * WAVE), 0, a);
+      if (ncurves) launch_counted(s, BTF_K_CRITERIA, func_gather_fn(), dim3(ncurves, 1), dim3(256), 0, ga, a.curves, ncurves, dstat);
+      launch_counted(s, BTF_K_CRITERIA, band_supt_fn(), dim3((N + a.cells - 1) / a.cells, a.jc), dim3(256), g.lds, a);
+    }
+  } else {
+    a.P = 2;
+    while (a.P < S) a.P <<= 1;
+    a.cells = std::max(1, std::min(BAND_CELLS, BAND_RANK_LDS / (a.P * BAND_RANK_BYTES)));
+    const size_t lds = (size_t)a.cells * a.P * BAND_RANK_BYTES, lds_keys = (size_t)a.cells * a.P * sizeof(double);
+    const int tiles = (N + a.cells - 1) / a.cells;
+    // slices of the depth axis: enough workgroups to fill the chip when rows x columns alone do not (geometry only)
+    const long long curves_wg = (long long)tiles * std::min(M, JMAX);
+    a.zb = (int)std::max<long long>(1, std::min<long long>(T, (2048 + curves_wg - 1) / curves_wg));
+    const size_t per_col = (size_t)a.zb * N * S, cap = scratch_bytes > 0 ? (size_t)scratch_bytes : FUNC_SCRATCH_BYTES;
+    const int jc_max = (int)std::max<size_t>(1, std::min<size_t>(std::min(M, JMAX), cap / (per_col * sizeof(int))));
+    a.dep = s.alloc<int>(per_col * jc_max);
+    a.pw_inside = s.alloc<double>(NM);
+    a.stat = dstat;
+    allow_lds(s, depth, lds);
+    allow_lds(s, write, lds_keys);
+    allow_lds(s, band_rank_k_fn(), lds_keys);
+    for (int j0 = 0; j0 < M; j0 += jc_max) {
+      a.j0 = j0; a.jc = std::min(jc_max, M - j0);
+      launch_counted(s, BTF_K_CRITERIA, depth, dim3(tiles, a.jc, a.zb), dim3(256), lds, a);
+      launch_counted(s, BTF_K_CRITERIA, band_rank_k_fn(), dim3(tiles, a.jc), dim3(256), lds_keys, a);
+      launch_counted(s, BTF_K_CRITERIA, write, dim3(tiles, a.jc, a.zb), dim3(256), lds_keys, a);
+    }
+  }
+  if (a.center) { s.download(o.center, a.center, NMT); s.download(o.scale, a.scale, NMT); }
+  s.download(o.lower, a.lower, NMT);
+  s.download(o.upper, a.upper, NMT);
+  s.download(o.crit, a.crit, NM);
+  s.download(o.inside, a.inside, NM);
+  if (a.pw_inside) s.download(o.pw_inside, a.pw_inside, NM);
+  if (ncurves) s.download(o.stat, dstat, (size_t)ncurves * S);
+  return s.finish();
+}
+
+// argument checks shared by the two entry points; everything here runs before any device call
+int bands_check(btf_ctx* c, int S, int N, int M, int T, int K, int transform, int method, double level, const int* depths,
+                const int* curves, int ncurves, const BandOut& o, long long scratch_bytes) {
+  if (N < 1 || M < 1 || K < 1 || K > MAX_K || transform < 0 || transform > 2 || ncurves < 0 || (ncurves > 0 && (!curves || !o.stat)) ||
+      scratch_bytes < 0)
+    return fail(c, BTF_EINVAL, "bad posterior bands arguments");
+  if (method != BAND_SUPT && method != BAND_RANK) return fail(c, BTF_EINVAL, "posterior bands: method must be 0 (supt) or 1 (rank)");
+  if (S < 2) return fail(c, BTF_EINVAL, "posterior bands: at least two samples");
+  if (T < 1) return fail(c, BTF_EINVAL, "posterior bands: ndepth >= 1");
+  if (!(level > 0.0 && level < 100.0)) return fail(c, BTF_EINVAL, "posterior bands: level must lie in (0, 100)");
+  const int max_s = method == BAND_SUPT ? FUNC_MAX_S : BAND_RANK_MAX_S;
+  if (S > max_s) return fail(c, BTF_EINVAL, "posterior bands: at most " + std::to_string(max_s) + " samples with this method (one curve's values are sorted in LDS)");
+  if (depths) {
+    bool any = false;
+    for (int t = 0; t < T; ++t) any = any || depths[t] != 0;
+    if (!any) return fail(c, BTF_EINVAL, "posterior bands: depths selects no depth");
+  }
+  for (int k = 0; k < ncurves; ++k)
+    if (curves[2 * k] < 0 || curves[2 * k] >= N || curves[2 * k + 1] < 0 || curves[2 * k + 1] >= M)
+      return fail(c, BTF_EINVAL, "posterior bands: curve index out of range");
+  return BTF_OK;
+}
+}  // namespace
+
+int btf_posterior_bands(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws, const double* Vs,
+                        int transform, int method, double level, const int* depths, const int* curves, int ncurves,
+                        double* center_out, double* scale_out, double* lower_out, double* upper_out, double* crit_out,
+                        double* inside_out, double* pointwise_inside_out, double* stat_out, long long scratch_bytes) {
+  const BandOut o = {center_out, scale_out, lower_out, upper_out, crit_out, inside_out, pointwise_inside_out, stat_out};
+  if (!Ws || !Vs) return fail(nullptr, BTF_EINVAL, "bad posterior bands arguments");
+  if (int rc = bands_check(nullptr, nsamples, nrows, ncols, ndepth, nembeds, transform, method, level, depths, curves, ncurves, o, scratch_bytes)) return rc;
+  Scratch s(nullptr, nullptr); States st;
+  if (int rc = resolve_pair(s, device, "", 0, nsamples, nrows, ncols * ndepth, nembeds, Ws, Vs, st)) return rc;
+  return bands_run(s, st.W, st.V, nsamples, nrows, ncols, ndepth, nembeds, transform, method, level, depths, curves, ncurves, o, scratch_bytes);
+}
+
+// the same on the first nsamples collected states, read where they lie (no upload)
+int btf_collect_bands(btf_ctx* c, int nsamples, int transform, int method, double level, const int* depths, const int* curves,
+                      int ncurves, double* center_out, double* scale_out, double* lower_out, double* upper_out, double* crit_out,
+                      double* inside_out, double* pointwise_inside_out, double* stat_out, long long scratch_bytes) {
+  if (!c) return fail(c, BTF_EINVAL, "bad posterior bands arguments");
+  const BandOut o = {center_out, scale_out, lower_out, upper_out, crit_out, inside_out, pointwise_inside_out, stat_out};
+  if (int rc = bands_check(c, nsamples, c->N, c->M, c->T, c->K, transform, method, level, depths, curves, ncurves, o, scratch_bytes)) return rc;
+  Scratch s(c, c->stream); States st;
+  if (int rc = resolve_pair(s, 0, "btf_collect_bands", BTF_ESTATE, nsamples, c->N, c->M * c->T, c->K, nullptr, nullptr, st)) return rc;
+  return bands_run(s, st.W, st.V, nsamples, c->N, c->M, c->T, c->K, transform, method, level, depths, curves, ncurves, o, scratch_bytes);
 }
 
 // ---------------------------------------------------------------- posterior ranking (btf_ranking.h)

@@ -280,6 +280,34 @@ def posterior_functionals(Ws, Vs, which=("auc",), q=(5, 95), transform=None, x=N
                                 pointwise=pointwise, Ws=Ws, Vs=Vs, device=device)
 
 
+def posterior_bands(Ws, Vs, method="supt", level=95, depths=None, transform=None, curves=None, truth=None, device=0,
+                    _scratch_bytes=0):
+    """Simultaneous credible bands per curve on the GPU, without a model: the stateless form of
+    BayesianTensorFiltering.posterior_bands, next to posterior_summary.
+
+    posterior_summary(q=(2.5, 97.5)) holds each cell with 95 %; the whole curve leaves that band somewhere far more often.
+    The band returned here holds at least ceil(level / 100 * S) of the S kept curves at every used depth at once.  On the
+    host this takes the (S,N,M,T) tensor (functionalmf_amd.bands.supt_band / rank_band are exactly that, in numpy).
+
+    method="supt": center -+ crit * scale with the per-cell mean and sd and crit an order statistic of the samples' largest
+    standardised deviation; "rank": distribution-free, the k-th smallest and k-th largest value of every cell with k from the
+    samples' rank depth - for ilogit curves near 0 or 1.  level in (0, 100); depths: a boolean mask (T,) of the depths the
+    band is simultaneous over (default all; the band is returned at every depth); transform as posterior_summary.
+
+    Returns a dict: lower, upper (N,M,T); inside (N,M) = the share of kept curves wholly inside (>= need / S); method,
+    level, need, nsamples; supt: center, scale (N,M,T), crit (N,M); rank: k (N,M) int, k_pointwise and pointwise_inside
+    (N,M) = the share of kept curves wholly inside the pointwise band of the same level - the figure that says why the
+    pointwise band is not the answer.  curves=[(i,j), ...] adds "stat" (ncurves,S), the samples' raw deviation or depth;
+    truth (N,M,T; NaN = unknown) adds covered (N,M: 1, 0, nan where no used depth is known) and coverage, their mean.
+    At least 2 and at most 8192 (supt) / 4096 (rank) samples.  There is no CPU fallback."""
+    from . import _analysis, bands
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    return bands.evaluate(shape, K, S, method=method, level=level, depths=depths, transform=transform, curves=curves, truth=truth,
+                          Ws=Ws, Vs=Vs, device=device, _scratch_bytes=_scratch_bytes)
+
+
 def posterior_ranking(Ws, Vs, which="auc", along="cols", order="ascending", top=(1, 5), transform=None, x=None, level=None,
                       pairs=None, pointwise=False, device=0, _scratch_bytes=0):
     """Which column is best for a row (or which row for a column), and with what probability, on the GPU, without a model:

@@ -615,6 +615,36 @@ int btf_collect_functionals(btf_ctx* ctx, int nsamples, int transform, const int
                             double* mean_out, double* var_out, double* q_out, double* defined_out, double* prob_out,
                             double* curves_out, double* pointwise_out);
 
+/* ---- simultaneous credible bands per curve (csrc/btf_bands.h) -------------------------------------------------------------
+ * A band that holds the WHOLE curve m_s(t) = f(w_i^s . v_jt^s) over the used depths with probability level / 100 among the
+ * kept samples, where the percentiles of btf_posterior_summary hold each cell alone.  need = ceil(level / 100 * nsamples);
+ * depths: ndepth flags (non-zero: the band is simultaneous over this depth; at least one) or NULL for all.
+ * method 0 (supt): center_out, scale_out (N,M,T) = mean and sd (ddof 1) over the samples; D_s = max over the used depths with
+ *   scale > 0 of |m_s - center| / scale (0 without one); crit_out (N,M) = the need-th smallest D_s (an order statistic, not
+ *   interpolated); lower_out, upper_out (N,M,T) = center -+ crit * scale at every depth; inside_out (N,M) = #{s : D_s <= crit}
+ *   / S >= need / S.  pointwise_inside_out is not written.  nsamples <= 8192.
+ * method 1 (rank): per cell lo_s = #{s' : m_s' < m_s} and hi_s with >; depth_s = min over the used depths of min(lo_s, hi_s);
+ *   crit_out (N,M) = k, the largest integer with #{s : depth_s >= k} >= need; lower_out, upper_out = the k-th and the
+ *   (S-1-k)-th order statistic (0-based) of every cell; inside_out = #{s : depth_s >= k} / S; pointwise_inside_out (N,M) the
+ *   same with k_pw = floor((1 - level / 100) / 2 * S): the share of kept curves wholly inside the pointwise band of the same
+ *   level.  center_out and scale_out are not written.  nsamples <= 4096.
+ * stat_out (ncurves,S): the raw D_s or depth_s of the curves[] = (i,j) pairs in sample order.  Outputs may be NULL.
+ * transform as btf_posterior_summary; nsamples >= 2, ndepth >= 1, level in (0, 100), nembeds 1..10 (BTF_EINVAL otherwise).
+ * scratch_bytes: the cap of the staging buffer, which holds whole columns (0: the default of the functionals; at least
+ * one column is staged).  fp64, no floating-point atomics, every sum in a fixed order: two calls return
+ * identical bits, whatever the chunking and wherever the states come from.  btf_collect_bands reads the first nsamples
+ * collected slots without an upload and touches none of the sampler's state; its launches are counted under
+ * BTF_K_CRITERIA.  Synchronous.                                                                                          */
+int btf_posterior_bands(int device, int nsamples, int nrows, int ncols, int ndepth, int nembeds, const double* Ws,
+                        const double* Vs, int transform, int method, double level, const int* depths, const int* curves,
+                        int ncurves, double* center_out, double* scale_out, double* lower_out, double* upper_out,
+                        double* crit_out, double* inside_out, double* pointwise_inside_out, double* stat_out,
+                        long long scratch_bytes);
+int btf_collect_bands(btf_ctx* ctx, int nsamples, int transform, int method, double level, const int* depths,
+                      const int* curves, int ncurves, double* center_out, double* scale_out, double* lower_out,
+                      double* upper_out, double* crit_out, double* inside_out, double* pointwise_inside_out, double* stat_out,
+                      long long scratch_bytes);
+
 /* ---- posterior ranking (csrc/btf_ranking.h) ----------------------------------------------------------------------------
  * The rank of every curve within its row (along 0: the ncols columns of a row are one group) or its column (along 1: the
  * nrows rows of a column), per kept sample, by the value of ONE functional `which` (the codes above; x, level, transform as
