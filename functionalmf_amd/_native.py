@@ -33,7 +33,7 @@ KERNEL_NAMES = ["stats", "w_accum", "w_solve", "v_accum", "v_banded", "gram", "p
                 "prior_band", "gram_eig", "hyper", "ess", "criteria"]
 COMM_ID_BYTES = 128               # BTF_COMM_ID_BYTES of include/btf.h
 PEER_DESC_BYTES = 256             # BTF_PEER_DESC_BYTES
-OPT_SAMPLER, OPT_NB_HISTOGRAMS, OPT_FUSE_GRAM, OPT_PG_EXACT, OPT_CURVE_COUNTS, OPT_SPLIT_ACCUM, OPT_FUSED_SWEEP, OPT_FUSED_STEP, OPT_FUSED_DATAFLOW = 0, 1, 2, 3, 4, 5, 6, 7, 8
+OPT_SAMPLER, OPT_NB_HISTOGRAMS, OPT_FUSE_GRAM, OPT_PG_EXACT, OPT_CURVE_COUNTS, OPT_SPLIT_ACCUM, OPT_FUSED_SWEEP, OPT_FUSED_STEP, OPT_FUSED_DATAFLOW, OPT_GRAM_ASIDE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ESS_HOST_LIKELIHOOD = -1          # BTF_ESS_HOST_LIKELIHOOD of include/btf.h
 CRIT_NOISE_PER_SAMPLE, CRIT_CURRENT = 1, 2   # BTF_CRIT_* flags of btf_crit_eval
 CRIT_FAMILY_GAMMA_GRID = 5        # family 5 of btf_crit_eval / btf_crit_loo (= link 5 of btf_ess_*)

@@ -229,7 +229,7 @@ void launch_accum(btf_ctx* c, int kid, int mode, const double* X, const double* 
   Prof p(c, kid);
   const int cpw = TAU_SIDE_CPW;
   cm.nside = (sw.sc.hyp ? 1 : 0) + (sw.lam.hyp ? 1 : 0) + (side.out ? 1 + eig_side_groups(sidec.ncols, acc_waves(K, mode)) : 0) +
-             (tau.Tau2 ? (tau.M + cpw - 1) / cpw : 0) + (gram.gpart ? gram.nblocks : 0) + (gram.sum_src ? 1 : 0) + (fw ? fw->owners : 0);   // the side tasks' workgroups (and the fused W launch's owners), in front
+             (tau.Tau2 ? (tau.M + cpw - 1) / cpw : 0) + (gram.gpart ? gram.nblocks : 0) + (gram.sh_out ? gram.sh_nwg : 0) + (gram.sum_src ? 1 : 0) + (fw ? fw->owners : 0);   // the side tasks' workgroups (and the fused W launch's owners), in front
   dim3 grid((ld / ACC_TILE) * nch + cm.nside);
   if (fw || fv) {              // the two-launch step: complete data, 16 waves, the tail in the same launch (btf_fused.h)
     const bool unr3 = rpb >= unr3_min_rpb();
@@ -796,6 +796,8 @@ int btf_create(btf_ctx** out, int nrows, int ncols, int ndepth, int nembeds, int
   { const char* e = std::getenv("BTF_LAM_IN_WSOLVE"); if (e) c->lam_in_wsolve = std::atoi(e) != 0; }
   { const char* e = std::getenv("BTF_BAND_IN_WSOLVE"); if (e) c->band_in_wsolve = std::atoi(e) != 0; }
   { const char* e = std::getenv("BTF_VF_DATAFLOW"); if (e) c->fused_dataflow = std::atoi(e) != 0 ? 1 : 0; }             // (A/B aid; BTF_OPT_FUSED_DATAFLOW is the interface)
+  { const char* e = std::getenv("BTF_SHARE_CPW"); if (e) c->share_cpw = std::max(1, std::atoi(e)); }                    // (A/B aid: columns per share side workgroup)
+  { const char* e = std::getenv("BTF_GRAM_ASIDE"); if (e) c->gram_aside = std::atoi(e) != 0 ? 1 : 0; }                  // (A/B aid; BTF_OPT_GRAM_ASIDE is the interface)
   if (stream) { c->stream = (hipStream_t)stream; }
   else {
     const hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -1304,7 +1306,20 @@ int ensure_fused(btf_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->fz_pub, 0, (size_t)FZ_PUB_DOUBLES * sizeof(double), c->stream));      // (the tagged granules: no stale tag may equal an epoch)
   }
   c->fz_tiles_w = tw; c->fz_tiles_v = tv;
-  c->fz_gram_total = 0; c->fz_w_total = 0;
+  c->fz_gram_total = 0; c->fz_w_total = 0; c->gv_cnt_total = 0;
+  return BTF_OK;
+}
+// BTF_OPT_GRAM_ASIDE: the columns' shares V_j'V_j the fused V launch left unformed, by a launch of their own - for whatever
+// reads gpart_v before a W accumulation launch could form them beside its stream, or runs where that side task does not
+// apply.  The tails' arithmetic (gram_share_part / gram_share_total): the same bits.
+int pay_gram_shares(btf_ctx* c) {
+  if (!c->gv_owed) return BTF_OK;
+  c->gv_owed = false;
+  if (c->ngp_v <= 0 || !c->gpart_v) return BTF_OK;        // (V has changed by other means since: nothing stands for the shares)
+  HIPCHK(c, hipSetDevice(c->dev));
+  Prof p(c, BTF_K_GRAM);
+  p.launch(colshare_kernel, dim3(c->ngp_v), dim3(GRAM_SHARE_NT), 0, (const double*)c->V, c->T, c->K, c->ngp_v, c->gpart_v);
+  HIPCHK(c, hipGetLastError());
   return BTF_OK;
 }
 // the W launch can carry w_solve's work as its tail: complete-data stream on the 16-wave instances (two rows in flight
@@ -1353,7 +1368,7 @@ int w_accum_phase(btf_ctx* c, int compat, int part = ACC_ALL, WFuseReq* wf = nul
       if (!c->gpart_v) { if ((rc = dev_alloc(c, &c->gpart_v, (size_t)c->M * KK))) return rc; }
       Prof p(c, BTF_K_GRAM);
       K_SWITCH(K, p.launch(colgram_kernel<KT>, dim3(c->ml), dim3(WAVE), 0, (const double*)c->V, c->T, c->ml, c->gpart_v));
-      c->ngp_v = c->ml;
+      c->ngp_v = c->ml; c->gv_owed = false;
     }
     use_gv = true;
   }
@@ -1436,6 +1451,38 @@ int w_accum_phase(btf_ctx* c, int compat, int part = ACC_ALL, WFuseReq* wf = nul
       fw.rows = own_rows;
       fw.owners = tiles * (ACC_TILE / own_rows);
     }
+    if (c->gv_owed) {
+      // BTF_OPT_GRAM_ASIDE: the fused V launch left the columns' shares V_j'V_j unformed.  They are formed HERE, by side
+      // workgroups in front of this launch's stream (GramSide.sh_*: share_cpw columns each - 8: 20 KB of V at C3 - so that no CU's
+      // bandwidth bounds them), ahead of the sum workgroup where there is one - but only as many as still fit the chip in one
+      // round beside everything else (rows per workgroup, hence the chunks and the order of their sums, stay what they were); where the
+      // side task does not apply - the solve as this launch's tail, sharded or weighted runs, nembeds > 8 - a launch of
+      // their own pays first
+      bool aside = false;
+      if (use_gv && c->ngp_v == c->ml && !fuse && !wt && !cv && whole && mode == 0 && !rest_only && !split_applies(c) && K <= 8 &&
+          c->T * K <= GRAM_SHARE_STAGE_MIN) {
+        const long long others = (long long)tiles * nch_launch + (tau.Tau2 ? (tau.M + TAU_SIDE_CPW - 1) / TAU_SIDE_CPW : 0) +
+                                 (sw.sc.hyp ? 1 : 0) + (gsum ? 1 : 0);
+        const long long room = (long long)acc_slots(c, K, mode, true) - others;
+        const int cols_per_wg = c->share_cpw;
+        // (a launch of several rounds anyway - long slabs - takes them all: they are done long before its stream is)
+        int nwg = (c->ml + cols_per_wg - 1) / cols_per_wg;
+        if (room >= 0) nwg = (int)std::min<long long>(nwg, std::max<long long>(room, 1));
+        const int cpw = (c->ml + nwg - 1) / nwg;
+        nwg = (c->ml + cpw - 1) / cpw;
+        gram.sh_V = c->V; gram.sh_T = c->T; gram.sh_cols = c->ml; gram.sh_cpw = cpw; gram.sh_nwg = nwg;
+        gram.sh_out = c->gpart_v; gram.status = c->status;
+        if (gsum) {                            // the sum workgroup of this launch waits for them: one counter, a running total
+          if ((rc = ensure_fused(c))) return rc;
+          gram.sh_cnt = c->fz_words + FZ_GSUM;
+          c->gv_cnt_total += (unsigned)nwg;
+          gram.sh_expected = c->gv_cnt_total;
+        }
+        aside = true;
+        c->gv_owed = false;
+      }
+      if (!aside) { if ((rc = pay_gram_shares(c))) return rc; }
+    }
     K_SWITCH(K, launch_accum<KT>(c, BTF_K_W_ACCUM, mode, c->A_wT, c->C_wT, c->C8_wT, c->V, c->srcmap_w, MT, c->ldw, rpb, nch_launch,
                                  EigSide{nullptr, 0, 0, nullptr}, EigSideCols{nullptr, 0, CurveLists{nullptr, nullptr, nullptr}, nullptr, 0.0, nullptr}, tau, gram, cm, sw,
                                  fuse ? &fw : nullptr));
@@ -1453,6 +1500,7 @@ int w_accum_phase(btf_ctx* c, int compat, int part = ACC_ALL, WFuseReq* wf = nul
     p.launch(tau2_kernel, dim3(c->M), dim3(256), 0, tau_side_of(c, c->tau_seed, 1.0, c->tau_stability), c->K);
     c->tau_pending = false;
   }
+  if (c->gv_owed) { if ((rc = pay_gram_shares(c))) return rc; }      // (a rank without rows: no launch above to carry them)
   HIPCHK(c, hipGetLastError());
   c->w_part_valid = true; c->w_part_mode = mode; c->w_part_nch = nch_total; c->w_part_rpb = rpb; c->w_part_gv = use_gv;
   c->w_part_curve = cv;
@@ -1646,7 +1694,7 @@ static int v_banded_dispatch(btf_ctx* c, int choice, const double* dz, uint64_t 
     if (!c->gpart_v) { if ((rc = dev_alloc(c, &c->gpart_v, (size_t)c->M * KK))) return rc; }
     a.gout = c->gpart_v;
   }
-  if (!prior_only) { c->ngp_v = emit_gv ? c->ml : 0; c->ngp_w = 0; }
+  if (!prior_only) { c->ngp_v = emit_gv ? c->ml : 0; c->gv_owed = false; c->ngp_w = 0; }
   if (choice == 2) {
     if ((rc = make_fill_table(c, wt))) return rc;
     a.fill = c->fill_tab; a.nfill = c->fill_n;
@@ -1817,6 +1865,7 @@ int btf_resample_V(btf_ctx* c, const double* z, uint64_t seed, int compat, doubl
         sa.gout = c->gpart_v;
       }
       c->ngp_v = emit ? c->ml : 0;
+      c->gv_owed = false;
       c->ngp_w = 0;
       const bool rg = vs_lds_bytes(T, K, c->TF, c->nD, false) > 160 * 1024;     // long depth axis: pivot records in HBM scratch
       if (rg) {
@@ -1841,6 +1890,11 @@ int btf_resample_V(btf_ctx* c, const double* z, uint64_t seed, int compat, doubl
         ++c->fz_epoch;
         FuseV fv{};
         fv.a = sa;
+        // BTF_OPT_GRAM_ASIDE: the tails store V and leave; the columns' shares are owed to the next W accumulation launch
+        // (not under BTF_OPT_FUSED_STEP 2: the owners of that W launch read the shares inside the launch - the tails keep emitting;
+        //  nor inside full sweeps - sse_out set: the next W launch carries the Tau2 chain's side workgroups and has room for ten
+        //  share workgroups at C3, 26 columns each: 25.4 -> 24.1-24.4 k full sweeps/s with the shares moved, so they stay)
+        if (emit && c->gram_aside && c->fused_step < 2 && !sa.sse_out) { fv.a.gout = nullptr; c->gv_owed = true; }
         if (!sw.lam.hyp) {
           // the prior band of every column, precomputed (rebuilt only when Tau2 / lam2 changed since): the tails load their
           // entries at kernel start.  Not when lam2 is drawn by a side workgroup of this very launch - those tails form it
@@ -3763,6 +3817,11 @@ int btf_set_option(btf_ctx* c, int option, int value) {
     case BTF_OPT_FUSED_DATAFLOW:
       c->fused_dataflow = value != 0 ? 1 : 0;
       return BTF_OK;
+    case BTF_OPT_GRAM_ASIDE: {
+      const int rc = pay_gram_shares(c);            // (shares still owed are formed before the switch: nothing is lost either way)
+      c->gram_aside = value != 0 ? 1 : 0;
+      return rc;
+    }
     case BTF_OPT_FUSED_SWEEP:
       c->fused_sweep = value != 0;
       c->sse_cols_valid = false;

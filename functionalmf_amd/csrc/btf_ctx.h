@@ -133,6 +133,12 @@ struct btf_ctx {
   double* gsum_v = nullptr; bool w_part_gsum = false;   // V'V summed by a side workgroup of the W accumulation launch (GramSide.sum_*): w_solve reads KK doubles
   double* gpart_w = nullptr; int ngp_w = 0;   // W'W partials written by w_solve (valid until W changes otherwise)
   double* gpart_v = nullptr; int ngp_v = 0;   // V'V partials written by the fast banded sampler
+  // BTF_OPT_GRAM_ASIDE: the fused V launch left the columns' shares unformed (ngp_v stands for them all the same): the next W
+  // accumulation launch forms them beside its stream, or pay_gram_shares (btf_abi.hip) before anything else reads gpart_v.
+  // Meaningful only while ngp_v > 0.
+  bool gv_owed = false; int gram_aside = 1;
+  int share_cpw = 8;                 // columns per share side workgroup of the W accumulation launch (BTF_SHARE_CPW at creation: A/B aid)
+  unsigned gv_cnt_total = 0;         // arrivals of the share side workgroups (fz_words + FZ_GSUM): a running total, never reset
   bool fuse_gram = true;
   // curve-structured replicate counts (btf_kernels.h, CurveLists): counts constant along the depth axis
   bool curve = false, curve_opt = true;

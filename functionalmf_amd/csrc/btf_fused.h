@@ -830,25 +830,10 @@ __device__ __forceinline__ void v_fused_tail(const FuseV& fv, int tile, double* 
   }
   if (a.gout) {                                            // (workgroup-uniform)
     __syncthreads();
-    int ng = NT / KK;
-    if (ng > 16) ng = 16;
-    if (ng < 1) ng = 1;
-    const int g = tid / KK, q = tid - g * KK;
-    int p = 0;
-    while ((p + 1) * (p + 2) / 2 <= q) ++p;
-    const int pq = q - p * (p + 1) / 2;
     double* scratch = base + L.gs;
-    if (ok && g < ng) {
-      double s = 0.0;
-      for (int t = g; t < T; t += ng) s = fma(xout[t * K + p], xout[t * K + pq], s);
-      scratch[g * KK + q] = s;
-    }
+    if (ok) gram_share_part(xout, T, K, KK, NT, tid, scratch);      // (btf_kernels.h: shared with the W launch's share side task)
     __syncthreads();
-    if (ok && tid < KK) {
-      double s = 0.0;
-      for (int b = 0; b < ng; ++b) s += scratch[b * KK + tid];
-      a.gout[(size_t)j * KK + tid] = s;
-    }
+    if (ok && tid < KK) a.gout[(size_t)j * KK + tid] = gram_share_total(scratch, KK, NT, tid);
   }
   TAIL_STAMP(stamps, 7);
 }
@@ -1352,7 +1337,7 @@ __device__ __forceinline__ void v_fused_df(const FuseV& fv, int tile, double* ld
       double s = 0.0;
 #pragma unroll
       for (int kk = 0; kk < K; ++kk) s = fma(Ush[k * K + kk], xs[(size_t)(kk * T + pos) * 4], s);
-      xout[idx] = s;
+      if (a.gout) xout[idx] = s;                             // (kept for the share's products only)
       a.V[(size_t)jg * n + idx] = s;
       if (a.sse_out) {
         const double xt = xs[(size_t)(k * T + pos) * 4];
@@ -1375,27 +1360,13 @@ __device__ __forceinline__ void v_fused_df(const FuseV& fv, int tile, double* ld
     df_signal(cgw + DFG_G1);
     df_wait(cgw + DFG_G1, (unsigned)VF_GROUP_WAVES, cw + DFC_BAD);      // the fresh column stands in xout (and the residual parts in flag[])
     if (a.sse_out && vw == 0 && ok && lane == 0) a.sse_out[j] = (flag[2] + flag[3]) + (flag[4] + flag[5]);
-    int ng = NT / KK;
-    if (ng > 16) ng = 16;
-    if (ng < 1) ng = 1;
-    const int g = tid / KK, q = tid - g * KK;
-    int p = 0;
-    while ((p + 1) * (p + 2) / 2 <= q) ++p;
-    const int pq = q - p * (p + 1) / 2;
+    // (gram_share_part / gram_share_total, btf_kernels.h: the share side task of the W accumulation launch forms the same bits)
     double* scratch = base + Wk.gs;
-    if (ok && g < ng) {
-      double s = 0.0;
-      for (int t = g; t < T; t += ng) s = fma(xout[t * K + p], xout[t * K + pq], s);
-      scratch[g * KK + q] = s;
-    }
+    if (ok) gram_share_part(xout, T, K, KK, NT, tid, scratch);
     df_signal(cgw + DFG_G2);
     if (tid < KK) {                                          // (virtual wave 0: KK <= 36 < 64)
       df_wait(cgw + DFG_G2, (unsigned)VF_GROUP_WAVES, cw + DFC_BAD);
-      if (ok) {
-        double s = 0.0;
-        for (int b = 0; b < ng; ++b) s += scratch[b * KK + tid];
-        a.gout[(size_t)j * KK + tid] = s;
-      }
+      if (ok) a.gout[(size_t)j * KK + tid] = gram_share_total(scratch, KK, NT, tid);
     }
   }
   if (vw == 0) TAIL_STAMP(stamps, 7);

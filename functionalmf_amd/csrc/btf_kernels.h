@@ -251,7 +251,42 @@ struct GramSide {
   // workgroup of the W solve that follows reads KK doubles instead of all the partials (30 KB each at C3: a third of its cold
   // batch of loads) and lands on the same bits.  sum_src == nullptr: none.
   const double* sum_src; int sum_n; double* sum_out; int sum_threads;
+  // ... and, in front of it, `sh_nwg` side workgroups that FORM those partials: the shares V_j'V_j of the columns the fused V
+  // launch drew and left without (BTF_OPT_GRAM_ASIDE: its tails store V and leave), read from V as stored - [sh_cols][sh_T][K]
+  // - in the tails' own arithmetic (gram_share_part / gram_share_total), sh_cpw columns per workgroup, into sum_src's rows
+  // (sh_out).  With a sum workgroup behind them (sum_src set) the shares are stored write-through, every share workgroup adds
+  // one to *sh_cnt behind its drained stores, and the sum workgroup polls the count for sh_expected (a running total, never
+  // reset; bounded - a timeout goes to status[0] = 2, status[1] = -3: BTF_EHIP) before it reads them with sc1 loads: a hand-off under the stream,
+  // which nothing else in the launch waits for.  sh_out == nullptr: none.
+  const double* sh_V; int sh_T, sh_cols, sh_cpw, sh_nwg; double* sh_out; unsigned* sh_cnt; unsigned sh_expected; int* status;
 };
+
+// One column's share V_j'V_j of the Gram, from the column x[T][K] (depth-major; LDS or global), by the NT threads that own
+// the column (tid < NT), in two fixed-order levels: ng = min(16, NT / KK) groups; thread (g = tid / KK, q = tid % KK) of
+// group g < ng adds x[t][p] x[t][pq] over the depths t = g, g + ng, ... ascending into scratch[g KK + q] (q = lidx(p, pq));
+// behind whatever makes these visible to the column's threads (a barrier, a counter hop), thread q < KK adds the groups'
+// sums, g ascending.  The tails of the V samplers and the share side task of the W accumulation launch both call these:
+// the same operations in the same order on the same doubles.
+__host__ __device__ constexpr int gram_share_groups(int NT, int KK) { return NT / KK > 16 ? 16 : (NT / KK < 1 ? 1 : NT / KK); }
+constexpr int GRAM_SHARE_NT = 256;      // threads per column: the samplers' (four waves)
+constexpr int GRAM_SHARE_STAGE_MIN = 2048;      // doubles of a column (T K) the share side task can stage in LDS in every instance that runs it
+__device__ __forceinline__ void gram_share_part(const double* x, int T, int K, int KK, int NT, int tid, double* scratch) {
+  const int ng = gram_share_groups(NT, KK);
+  const int g = tid / KK, q = tid - g * KK;
+  if (g >= ng) return;
+  int p = 0;
+  while ((p + 1) * (p + 2) / 2 <= q) ++p;
+  const int pq = q - p * (p + 1) / 2;
+  double s = 0.0;
+  for (int t = g; t < T; t += ng) s = fma(x[t * K + p], x[t * K + pq], s);
+  scratch[g * KK + q] = s;
+}
+__device__ __forceinline__ double gram_share_total(const double* scratch, int KK, int NT, int q) {
+  const int ng = gram_share_groups(NT, KK);
+  double s = 0.0;
+  for (int b = 0; b < ng; ++b) s += scratch[b * KK + q];
+  return s;
+}
 
 // Which rows of the reduction axis a launch covers, and where its partial sums go: logical chunk l of the launch takes
 // rows r0 .. min(r0 + rows_per_block, row_end) - 1 with r0 = row_base + l rows_per_block, moved up by `skip_rows` from
@@ -585,11 +620,80 @@ __global__ __launch_bounds__(WAVES * WAVE) BTF_ACC_EU_ATTR(K, MODE, WAVES, FUSE)
     }
     b -= gram.nblocks;
   }
+  if constexpr (MODE == 0 && PLAIN) {
+  if (gram.sh_out) {
+    if (b < gram.sh_nwg) {
+      // the shares of columns b sh_cpw .. (b + 1) sh_cpw - 1, in batches of as many columns as LDS holds.  A batch comes in
+      // through LDS (the columns are contiguous in V: one coalesced round of loads, all in flight); every 256-thread slice of
+      // the workgroup then runs the first level of its columns, one after the other, as the sampler's four waves did - each
+      // column into scratch of its own, so ONE barrier stands between the levels of the whole batch - and thread
+      // (column, q) the second level.  (A barrier pair and a 16-deep chain of LDS adds per column, in series: 16 columns
+      // per workgroup took longer than the 10.8 us stream beside them.)
+      constexpr int NT = WAVES * WAVE, NSL = NT / GRAM_SHARE_NT, RED = ACC_WAVES * ACC_RG * ACC_TILE;
+      static_assert(NSL >= 1 && NSL * GRAM_SHARE_NT == NT && RED >= GRAM_SHARE_STAGE_MIN + GRAM_SHARE_NT, "share side scratch");
+      const int sl = threadIdx.x / GRAM_SHARE_NT, tid = threadIdx.x - sl * GRAM_SHARE_NT;
+      const bool handoff = gram.sum_src != nullptr;
+      const int n = gram.sh_T * K;
+      const int per = RED / (n + GRAM_SHARE_NT);             // columns per batch (>= 1: the host checks n <= GRAM_SHARE_STAGE_MIN)
+      double* stage = &red[0][0][0];                          // [per][n]
+      double* scratch = stage + (size_t)per * n;              // [per][256]
+      const int c1 = min((b + 1) * gram.sh_cpw, gram.sh_cols);
+      for (int cb = b * gram.sh_cpw; cb < c1; cb += per) {
+        const int nc = min(per, c1 - cb), tot = nc * n;
+        const double* src = gram.sh_V + (size_t)cb * n;
+        for (int i0 = threadIdx.x; i0 < tot; i0 += 8 * NT) {
+          double v[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) { const int e = i0 + u * NT; v[u] = e < tot ? src[e] : 0.0; }
+#pragma unroll
+          for (int u = 0; u < 8; ++u) { const int e = i0 + u * NT; if (e < tot) stage[e] = v[u]; }
+        }
+        __syncthreads();
+        for (int ci = sl; ci < nc; ci += NSL)
+          gram_share_part(stage + (size_t)ci * n, gram.sh_T, K, KK, GRAM_SHARE_NT, tid, scratch + ci * GRAM_SHARE_NT);
+        __syncthreads();
+        for (int w = threadIdx.x; w < nc * KK; w += NT) {
+          const int ci = w / KK, q = w - ci * KK;
+          const double sv = gram_share_total(scratch + ci * GRAM_SHARE_NT, KK, GRAM_SHARE_NT, q);
+          if (handoff) store_sc1(gram.sh_out + (size_t)(cb + ci) * KK + q, sv); else gram.sh_out[(size_t)(cb + ci) * KK + q] = sv;
+        }
+        __syncthreads();
+      }
+      if (handoff) {
+        drain_stores();
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_fetch_add((gu32_t*)gram.sh_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      return;
+    }
+    b -= gram.sh_nwg;
+  }
+  }
   if (gram.sum_src) {
     if (b == 0) {
       // thread (l, q) of the first sum_threads adds the partials l, l + lanes, ... in batches of eight (reduce_gram's order for
       // a sum_threads-wide workgroup), then KK threads add the lanes' sums in order
       double* scratch = &red[0][0][0];
+      bool sc1 = false;
+      if constexpr (MODE == 0 && PLAIN) {
+        if (gram.sh_out) {
+          // the partials are being formed by the share workgroups in front (lower block indices: dispatched first, and they
+          // wait for nothing): one lane polls their count, bounded
+          unsigned* word = reinterpret_cast<unsigned*>(&red[1][0][0]);
+          if (threadIdx.x == 0) {
+            bool seen = false;
+            for (unsigned spins = 0; spins < (1u << 22); ++spins) {
+              if (__hip_atomic_load((const gu32_t*)gram.sh_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gram.sh_expected) { seen = true; break; }
+              __builtin_amdgcn_s_sleep(8);
+            }
+            word[0] = seen ? 1u : 0u;
+            if (!seen && atomicCAS(&gram.status[0], 0, 2) == 0) gram.status[1] = -3;
+          }
+          __syncthreads();
+          if (word[0] == 0u) return;
+          sc1 = true;
+        }
+      }
       const int lanes = gram.sum_threads / KK > 32 ? 32 : (gram.sum_threads / KK < 1 ? 1 : gram.sum_threads / KK);
       const int l = threadIdx.x / KK, q = threadIdx.x - l * KK;
       if ((int)threadIdx.x < gram.sum_threads && l < lanes) {
@@ -597,7 +701,10 @@ __global__ __launch_bounds__(WAVES * WAVE) BTF_ACC_EU_ATTR(K, MODE, WAVES, FUSE)
         for (int b0 = l; b0 < gram.sum_n; b0 += 8 * lanes) {
           double x[8];
 #pragma unroll
-          for (int u = 0; u < 8; ++u) x[u] = b0 + u * lanes < gram.sum_n ? gram.sum_src[(size_t)(b0 + u * lanes) * KK + q] : 0.0;
+          for (int u = 0; u < 8; ++u) {
+            const double* ps = gram.sum_src + (size_t)(b0 + u * lanes) * KK + q;
+            x[u] = b0 + u * lanes < gram.sum_n ? (sc1 ? load_sc1(ps) : *ps) : 0.0;
+          }
 #pragma unroll
           for (int u = 0; u < 8; ++u) sg += x[u];
         }
@@ -1117,6 +1224,18 @@ __global__ __launch_bounds__(WAVE) void colgram_kernel(const double* __restrict_
     const double t = wave_sum(acc[q]);
     if (lane == 0) out[(size_t)j * KK + q] = t;
   }
+}
+// the same blocks IN THE SAMPLERS' ARITHMETIC (gram_share_part / gram_share_total, 256 threads per column): what the tails of
+// the V samplers would have emitted for the column as it is stored - BTF_OPT_GRAM_ASIDE, where no W accumulation launch
+// can form the shares beside its stream (pay_gram_shares, btf_abi.hip)
+static __global__ __launch_bounds__(GRAM_SHARE_NT) void colshare_kernel(const double* __restrict__ V, int T, int K, int ncols,
+                                                                        double* __restrict__ out) {
+  __shared__ double scratch[GRAM_SHARE_NT];
+  const int j = blockIdx.x, tid = threadIdx.x, KK = tri(K);
+  if (j >= ncols) return;
+  gram_share_part(V + (size_t)j * T * K, T, K, KK, GRAM_SHARE_NT, tid, scratch);
+  __syncthreads();
+  if (tid < KK) out[(size_t)j * KK + tid] = gram_share_total(scratch, KK, GRAM_SHARE_NT, tid);
 }
 
 // ============================================================================

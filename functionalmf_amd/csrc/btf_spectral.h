@@ -712,25 +712,10 @@ __global__ __launch_bounds__(VS_THREADS) void v_spectral_kernel(VSpecArgs a) {
   }
   if (a.gout) {
     __syncthreads();
-    int ng = VS_THREADS / KK;
-    if (ng > 16) ng = 16;
-    if (ng < 1) ng = 1;
-    const int g = tid / KK, q = tid - g * KK;
-    int p = 0;
-    while ((p + 1) * (p + 2) / 2 <= q) ++p;
-    const int pq = q - p * (p + 1) / 2;
     double* scratch = lds + L.gs;
-    if (g < ng) {
-      double s = 0.0;
-      for (int t = g; t < T; t += ng) s = fma(xout[t * K + p], xout[t * K + pq], s);
-      scratch[g * KK + q] = s;
-    }
+    gram_share_part(xout, T, K, KK, VS_THREADS, tid, scratch);      // (btf_kernels.h: shared with the W launch's share side task)
     __syncthreads();
-    if (tid < KK) {
-      double s = 0.0;
-      for (int b = 0; b < ng; ++b) s += scratch[b * KK + tid];
-      a.gout[(size_t)j * KK + tid] = s;
-    }
+    if (tid < KK) a.gout[(size_t)j * KK + tid] = gram_share_total(scratch, KK, VS_THREADS, tid);
   }
   stamp[5] = __builtin_amdgcn_s_memtime();
   if (a.dbg && tid == 0)

@@ -101,6 +101,14 @@ enum {
                                 stream ends, while the other waves still stream, reduce and rotate; LDS counters order the
                                 stages.  Bit-identical to the barrier tail and to the four-launch form.  Measured at
                                 (512,256,64) nembeds 5: 20.4 us per V launch against 21.0.  0: the barrier tail. */
+  BTF_OPT_GRAM_ASIDE = 9,    /* 1 (default): the per-column shares V_j'V_j of the Gram that the next W half-sweep needs are not formed at
+                                the end of the fused V launch (BTF_OPT_FUSED_STEP >= 1: its tails store V and leave) but by side
+                                workgroups of the NEXT W accumulation launch, beside its stream, from V as stored - whole contexts,
+                                complete Gaussian data, nembeds <= 8; anything else that needs the shares first gets them from a small
+                                launch of the same device function.  Same operations in the same order: bit-identical
+                                (tests/test_gpu_gram_aside.py).  Acts on bare W+V steps only: inside full sweeps (the V launch also leaves
+                                the residual parts) and under BTF_OPT_FUSED_STEP 2 the tails keep forming the shares, whatever the
+                                value.  0: the tails form the shares.                          */
   BTF_OPT_SPLIT_ACCUM = 5,   /* sharded Gaussian contexts: 1 - the streaming accumulation of a half-sweep runs in two launches: the
                                 chunks that reduce over this rank's OWN block of the fixed factor (its columns of V for the W
                                 half-sweep, its rows of W for the V half-sweep) are queued right behind the kernel that drew
