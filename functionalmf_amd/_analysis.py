@@ -1,5 +1,5 @@
 """The Python front end of the posterior analysis features: summary, diagnostics, criteria / PSIS-LOO, predictive,
-functionals, simultaneous bands, ranking, feature association, monotone projection and fold-in.
+predictive checks, functionals, simultaneous bands, ranking, feature association, monotone projection and fold-in.
 
 Two halves.  The argument checks every feature shares, as plain functions (importable without a GPU): the transform table,
 the percentile check, the (S,N,K) / (S,M,T,K) shape check and the per-sample scalar check - the stateless forms in utils.py
@@ -305,6 +305,48 @@ class PosteriorAnalysis:
             seed = self._next_seed()
         return _pred.evaluate(self._ctx, (self.nrows, self.ncols, self.ndepth), self.nembeds, family, S, Ws, Vs, param=param,
                               aux=aux, aux_flags=flags, trials=trials, Y=Y, q=q, draws_per_sample=R, seed=seed, cells=cells)
+
+    # ---- posterior predictive checks: predictive p-values of whole-curve discrepancies (functionalmf_amd/checks.py) ----
+    def posterior_checks(self, results=None, data=None, which=None, reps=1, seed=None, trials=None, curves=None):
+        """Posterior predictive checks on the GPU (csrc/btf_checks.h): is a statistic of a whole observed curve plausible
+        among the same statistic of curves replicated from the fitted model?  For every curve (i,j), kept sample s and
+        rho < reps a replicated curve y_rep ~ p(y | theta_s) is drawn at the curve's observed slots and compared with the
+        data through T(y_rep, theta_s) >= T(y, theta_s); functionalmf_amd.checks is the written definition.
+
+        results, data, seed, trials: as posterior_predictive (data is required: the bound data, another tensor, a (Y, N) pair).
+        which: names of checks.DISCREPANCIES - "chisq" (dispersion), "max", "lag1" (residual correlation along depth: over-
+            or under-smoothing), "total", "zeros"; None: all five for the count families, the first four for Gaussian.
+        reps: replicated data sets per kept sample; there are nsets = S * reps of them, and no limit on their number.
+        curves: flat indices i * ncols + j or (i,j) pairs of curves whose raw T values come back.
+
+        Returns a dict: for each requested name a dict of (N,M) arrays p_ge, p_gt (the share of the sets with T_rep >= / >
+        T_obs among the `defined` ones), defined, t_obs, t_rep (the means of both sides); nobs (N,M); overall[name] = p_ge,
+        p_gt, defined, T_obs (S,), T_rep (nsets,) of the discrepancy pooled over all curves; with curves: curves = {index
+        (L,2), T_obs (L,nwhich,S), T_rep (L,nwhich,nsets)}; which, nsamples, reps, nsets, ndraws, seed.  Curves without
+        observations and curves with a slot nothing can be drawn at are nan and left out of the pool.
+        checks.two_sided(p_ge, p_gt) gives a two-sided p-value.  The sampler's state is not touched.  Unsharded models;
+        gamma_grid and Python-callable likelihoods are not supported."""
+        from . import checks as _checks
+        family, param, per_sample = self._pred_family()
+        self._unsharded("posterior checks")
+        shape = (self.nrows, self.ncols, self.ndepth)
+        codes = _checks.check_which(which, family)
+        if data is None:
+            data = getattr(self, "_data_ref", None)
+        Y = data
+        if isinstance(data, (tuple, list)):               # Binomial (Y, N): successes of N trials
+            Y = data[0]
+            if trials is None:
+                trials = data[1]
+        Y4 = _checks.check_data(Y, shape)
+        _checks.check_curves(curves, shape)
+        S, Ws, Vs = self._samples(results)
+        S, reps = _checks.check_reps(S, reps, Y4.shape[3])
+        aux, flags = self._pred_aux(results, S) if per_sample else (None, 0)
+        if seed is None:
+            seed = self._next_seed()
+        return _checks.evaluate(self._ctx, shape, self.nembeds, family, S, Ws, Vs, param=param, aux=aux, aux_flags=flags,
+                                trials=trials, Y=Y4, which=codes, reps=reps, seed=seed, curves=curves)
 
     # ---- posterior curve functionals: AUC, peak, level crossing (functionalmf_amd/functionals.py) ----
     def posterior_functionals(self, results=None, which=("auc",), q=(5, 95), transform=None, x=None, level=None, exceed=None,

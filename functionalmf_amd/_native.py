@@ -180,6 +180,8 @@ SIGNATURES = {
     "btf_predict_batch": (C.c_int, [C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, C.c_uint64, _c_dp]),
     "btf_predict_eval": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, C.c_int,
                                    C.c_uint64, _c_dp, C.c_int, _c_ip, C.c_int] + [_c_dp] * 11),
+    "btf_predict_check": (C.c_int, [_ctx, C.c_int, C.c_double, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, C.c_int,
+                                    C.c_uint64, _c_ip, C.c_int, _c_ip, C.c_int, C.c_int] + [_c_dp] * 6),
     "btf_predict_gg_eval": (C.c_int, [_ctx, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_uint64, _c_dp, C.c_int, _c_ip, C.c_int] +
                             [_c_dp] * 11),
     "btf_predict_gg_batch": (C.c_int, [C.c_int, C.c_int64, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, C.c_uint64, _c_dp, _c_ip]),

@@ -7,6 +7,7 @@
 #include "btf_nb_criteria.h"    // the same for the Negative-Binomial model's sampled rate (kernels in btf_nb_criteria.hip)
 #include "btf_loo.h"            // PSIS-LOO (instances in btf_loo.hip)
 #include "btf_predict.h"        // posterior predictive (instances in btf_predict.hip)
+#include "btf_checks.h"         // posterior predictive checks (instances in btf_predict.hip)
 #include "btf_gg_predict.h"     // the same for the gamma-grid likelihood (kernels in btf_gg_predict.hip)
 #include "btf_functionals.h"    // posterior curve functionals (kernels in btf_functionals.hip)
 #include "btf_bands.h"          // simultaneous credible bands (kernels in btf_functionals.hip)
@@ -436,26 +437,15 @@ PredKernels pred_kernels(int family) {
   return k;
 }
 
-// btf_predict_eval (families 0..4) and btf_predict_gg_eval (family 5: the context's table, param = its mbar) under the
-// name `who`: one set of limits and refusals, one launch geometry
-int predict_run(btf_ctx* c, const std::string& who, int family, double param, int nsamples, const double* Ws, const double* Vs,
-                const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps, int draws_per_sample,
-                uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells, const PredOut& o) {
-  double *const mean_out = o.mean, *const ymean_out = o.ymean, *const yvar_out = o.yvar, *const q_out = o.q, *const pit_lo_out = o.pit_lo,
-         *const pit_hi_out = o.pit_hi, *const inside_out = o.inside, *const nobs_out = o.nobs, *const rmse_out = o.rmse,
-         *const mae_out = o.mae, *const draws_out = o.draws;
-  const bool gamma_grid = family == PRED_FAM_GAMMA_GRID;
-  if (!c || (!gamma_grid && (family < 0 || family >= PRED_FAM_COUNT)) || nsamples < 1 || draws_per_sample < 1 || (!Ws) != (!Vs) || nq < 0 ||
-      (nq > 0 && !q) || (q_out && nq < 1) || ncells < 0 || (ncells > 0 && (!cells || !draws_out)) || (Y && nreps < 1) ||
-      (aux_flags & ~(BTF_PRED_AUX_PER_SAMPLE | BTF_PRED_AUX_ROWS | BTF_PRED_AUX_COLS | BTF_PRED_AUX_DEPTH)))
-    return fail(c, BTF_EINVAL, "bad " + who + " arguments");
-  if (gamma_grid && c->gg_pred.empty())
-    return fail(c, BTF_ESTATE, who + ": the gamma-grid family needs its table (btf_set_likelihood_table)");
-  if (!Y && (pit_lo_out || pit_hi_out || inside_out || nobs_out || rmse_out || mae_out))
-    return fail(c, BTF_EINVAL, who + ": pit / inside / nobs / rmse / mae compare with observations: pass Y");
-  if ((long long)nsamples * draws_per_sample > PRED_MAX_DRAWS)
-    return fail(c, BTF_EINVAL, who + ": nsamples * draws_per_sample = " + std::to_string((long long)nsamples * draws_per_sample) +
-                " exceeds 16384 (the draws of a cell are sorted in LDS)");
+// What btf_predict_eval, btf_predict_gg_eval and btf_predict_check decide alike, under the name `who`.
+// the arguments every one of them takes the same way
+bool pred_head_bad(int nsamples, const double* Ws, const double* Vs, int aux_flags) {
+  return nsamples < 1 || (!Ws) != (!Vs) ||
+         (aux_flags & ~(BTF_PRED_AUX_PER_SAMPLE | BTF_PRED_AUX_ROWS | BTF_PRED_AUX_COLS | BTF_PRED_AUX_DEPTH));
+}
+// the context, the states and the family's parameter: refused here, in this order
+int pred_states_ok(btf_ctx* c, const std::string& who, int family, double param, int nsamples, const double* Ws, const double* aux_sample,
+                   int aux_flags) {
   if (c->nl != c->N || c->ml != c->M) return fail(c, BTF_ESTATE, who + " needs an unsharded context");
   if (!Ws && !has_collected(c, nsamples)) return no_collected(c, BTF_ESTATE, who);
   const bool per_sample = (aux_flags & BTF_PRED_AUX_PER_SAMPLE) != 0;
@@ -465,6 +455,46 @@ int predict_run(btf_ctx* c, const std::string& who, int family, double param, in
     return fail(c, BTF_EINVAL, "per-sample parameters of uploaded states (and every Negative-Binomial rate): pass aux_sample");
   if (!per_sample && needs_par && !(param > 0.0))
     return fail(c, BTF_EINVAL, "the Gaussian (variance) and Negative-Binomial (rate) families need param > 0");
+  return BTF_OK;
+}
+// the extent of the per-sample parameter along rows / columns / depth into `a`; returns its size per sample
+size_t pred_aux_layout(PredArgs& a, int family, int aux_flags, int N, int M, int T) {
+  a.aux_n0 = a.aux_n1 = a.aux_n2 = 1;
+  if ((aux_flags & BTF_PRED_AUX_PER_SAMPLE) && family == PRED_FAM_NEGBIN) {
+    a.aux_n0 = (aux_flags & BTF_PRED_AUX_ROWS) ? N : 1; a.aux_n1 = (aux_flags & BTF_PRED_AUX_COLS) ? M : 1; a.aux_n2 = (aux_flags & BTF_PRED_AUX_DEPTH) ? T : 1;
+  }
+  return (size_t)a.aux_n0 * a.aux_n1 * a.aux_n2;
+}
+// the states, the per-sample parameter, the trials and the observations on the device, into `a`
+void pred_upload(btf_ctx* c, Scratch& s, PredArgs& a, int S, const double* Ws, const double* Vs, bool per_sample, const double* aux_sample,
+                 size_t naux, const double* trials, const double* Y, int nreps, size_t ncell) {
+  const States st = resolve_states(c, s, S, Ws, Vs, false, per_sample, aux_sample, naux);
+  a.W = st.W; a.V = st.V; a.aux = st.noise; a.aux_stride = st.noise_stride;
+  if (trials) a.trials = s.upload(trials, ncell);
+  if (Y) { a.Y = s.upload(Y, ncell * (size_t)nreps); a.nreps = nreps; }
+}
+
+// btf_predict_eval (families 0..4) and btf_predict_gg_eval (family 5: the context's table, param = its mbar) under the
+// name `who`: one set of limits and refusals, one launch geometry
+int predict_run(btf_ctx* c, const std::string& who, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps, int draws_per_sample,
+                uint64_t seed, const double* q, int nq, const int32_t* cells, int ncells, const PredOut& o) {
+  double *const mean_out = o.mean, *const ymean_out = o.ymean, *const yvar_out = o.yvar, *const q_out = o.q, *const pit_lo_out = o.pit_lo,
+         *const pit_hi_out = o.pit_hi, *const inside_out = o.inside, *const nobs_out = o.nobs, *const rmse_out = o.rmse,
+         *const mae_out = o.mae, *const draws_out = o.draws;
+  const bool gamma_grid = family == PRED_FAM_GAMMA_GRID;
+  if (!c || (!gamma_grid && (family < 0 || family >= PRED_FAM_COUNT)) || pred_head_bad(nsamples, Ws, Vs, aux_flags) || draws_per_sample < 1 ||
+      nq < 0 || (nq > 0 && !q) || (q_out && nq < 1) || ncells < 0 || (ncells > 0 && (!cells || !draws_out)) || (Y && nreps < 1))
+    return fail(c, BTF_EINVAL, "bad " + who + " arguments");
+  if (gamma_grid && c->gg_pred.empty())
+    return fail(c, BTF_ESTATE, who + ": the gamma-grid family needs its table (btf_set_likelihood_table)");
+  if (!Y && (pit_lo_out || pit_hi_out || inside_out || nobs_out || rmse_out || mae_out))
+    return fail(c, BTF_EINVAL, who + ": pit / inside / nobs / rmse / mae compare with observations: pass Y");
+  if ((long long)nsamples * draws_per_sample > PRED_MAX_DRAWS)
+    return fail(c, BTF_EINVAL, who + ": nsamples * draws_per_sample = " + std::to_string((long long)nsamples * draws_per_sample) +
+                " exceeds 16384 (the draws of a cell are sorted in LDS)");
+  if (int rc = pred_states_ok(c, who, family, param, nsamples, Ws, aux_sample, aux_flags)) return rc;
+  const bool per_sample = (aux_flags & BTF_PRED_AUX_PER_SAMPLE) != 0;
   if (int rc = check_percentiles(c, q, nq)) return rc;
   const int S = nsamples, R = draws_per_sample, N = c->N, M = c->M, T = c->T, K = c->K, MT = M * T, n = S * R;
   const size_t ncell = (size_t)N * MT;
@@ -473,21 +503,14 @@ int predict_run(btf_ctx* c, const std::string& who, int family, double param, in
     if (cells[k] < 0 || (size_t)cells[k] >= ncell) return fail(c, BTF_EINVAL, who + ": cell index out of range");
   HIPCHK(c, hipSetDevice(c->dev));
   PredArgs a{};
-  a.aux_n0 = a.aux_n1 = a.aux_n2 = 1;
-  if (per_sample && family == PRED_FAM_NEGBIN) {
-    a.aux_n0 = (aux_flags & BTF_PRED_AUX_ROWS) ? N : 1; a.aux_n1 = (aux_flags & BTF_PRED_AUX_COLS) ? M : 1; a.aux_n2 = (aux_flags & BTF_PRED_AUX_DEPTH) ? T : 1;
-  }
-  const size_t naux = (size_t)a.aux_n0 * a.aux_n1 * a.aux_n2;
+  const size_t naux = pred_aux_layout(a, family, aux_flags, N, M, T);
   const SortGeom g = sort_geom(n, pred_row_budget(gamma_grid ? GGP_TAB_DOUBLES * sizeof(double) : 0), PRED_SORT_CELLS);
   const size_t nblk = (size_t)N * ((MT + g.cells - 1) / g.cells);
   if (nblk > 0x7fffffffULL) return fail(c, BTF_EINVAL, who + ": too many workgroups for one launch");
   const int chunks = (int)((ncell + PRED_SCORE_CELLS - 1) / PRED_SCORE_CELLS);
   const bool score = rmse_out || mae_out;
   Scratch s(c, c->stream);
-  const States st = resolve_states(c, s, S, Ws, Vs, false, per_sample, aux_sample, naux);
-  a.W = st.W; a.V = st.V; a.aux = st.noise; a.aux_stride = st.noise_stride;
-  if (trials) a.trials = s.upload(trials, ncell);
-  if (Y) { a.Y = s.upload(Y, ncell * (size_t)nreps); a.nreps = nreps; }
+  pred_upload(c, s, a, S, Ws, Vs, per_sample, aux_sample, naux, trials, Y, nreps, ncell);
   if (nq) a.q = s.upload(q, (size_t)nq);
   a.nq = nq;
   if (ncells) { a.list = s.upload(cells, (size_t)ncells); a.nlist = ncells; a.draws = s.alloc<double>((size_t)ncells * n); }
@@ -537,6 +560,108 @@ int btf_predict_gg_eval(btf_ctx* c, int nsamples, const double* Ws, const double
   return predict_run(c, "btf_predict_gg_eval", PRED_FAM_GAMMA_GRID, c ? c->gg_mbar : 0.0, nsamples, Ws, Vs, nullptr, 0, nullptr, Y, nreps,
                      draws_per_sample, seed, q, nq, cells, ncells, PredOut{mean_out, ymean_out, yvar_out, q_out, pit_lo_out, pit_hi_out,
                                                                            inside_out, nobs_out, rmse_out, mae_out, draws_out});
+}
+
+// ---------------------------------------------------------- posterior predictive checks (btf_checks.h)
+int btf_predict_check(btf_ctx* c, int family, double param, int nsamples, const double* Ws, const double* Vs, const double* aux_sample,
+                      int aux_flags, const double* trials, const double* Y, int nreps, int reps, uint64_t seed, const int32_t* which,
+                      int nwhich, const int32_t* curves, int ncurves, int chunk_rows, double* curve_out, double* nobs_out,
+                      double* pool_obs_out, double* pool_rep_out, double* tobs_out, double* trep_out) {
+  const std::string who = "btf_predict_check";
+  if (!c || family < 0 || family >= PRED_FAM_COUNT || pred_head_bad(nsamples, Ws, Vs, aux_flags) || !Y || nreps < 1 || !which || nwhich < 1 ||
+      nwhich > CHK_COUNT || ncurves < 0 || (ncurves > 0 && (!curves || !tobs_out || !trep_out)) || chunk_rows < 0)
+    return fail(c, BTF_EINVAL, "bad " + who + " arguments");
+  if (reps < 1) return fail(c, BTF_EINVAL, who + ": reps must be >= 1");
+  bool seen[CHK_COUNT] = {false};
+  for (int k = 0; k < nwhich; ++k) {
+    if (which[k] < 0 || which[k] >= CHK_COUNT || seen[which[k]]) return fail(c, BTF_EINVAL, who + ": discrepancy codes must be distinct and in 0..4");
+    seen[which[k]] = true;
+  }
+  if (int rc = pred_states_ok(c, who, family, param, nsamples, Ws, aux_sample, aux_flags)) return rc;
+  const bool per_sample = (aux_flags & BTF_PRED_AUX_PER_SAMPLE) != 0;
+  const int S = nsamples, N = c->N, M = c->M, T = c->T, K = c->K;
+  static_assert(CHK_MAX_K == MAX_K, "chk_kernel keeps w in MAX_K registers");
+  const size_t NM = (size_t)N * M, ncell = NM * T;
+  if (ncell > 0x7fffffffULL) return fail(c, BTF_EINVAL, who + ": more than 2^31 - 1 cells");
+  const long long nsets_ll = (long long)S * reps, Rr_ll = (long long)reps * nreps;
+  // the draw index g = cell n + d owns PRED_BLOCKS generator blocks: g PRED_BLOCKS stays below 2^64
+  if (nsets_ll > 0x7fffffffLL || Rr_ll > 0x7fffffffLL || (double)ncell * (double)nsets_ll * (double)nreps >= 18446744073709551616.0 / PRED_BLOCKS)
+    return fail(c, BTF_EINVAL, who + ": nsamples * reps * nreps = " + std::to_string(nsets_ll * nreps) + " draws a cell overflow the 64-bit draw index");
+  for (int k = 0; k < ncurves; ++k)
+    if (curves[k] < 0 || (size_t)curves[k] >= NM) return fail(c, BTF_EINVAL, who + ": curve index out of range");
+  const int nsets = (int)nsets_ll, tiles = (M + CHK_TILE - 1) / CHK_TILE;
+  // rows per launch: what CHK_PART_BYTES of pooled partials hold (one row is the least), or the caller's chunk
+  const size_t row_bytes = (size_t)tiles * 2 * CHK_SLOTS * nsets * sizeof(double);
+  long long rows_max = std::max<long long>(1, (long long)(CHK_PART_BYTES / row_bytes));
+  if (chunk_rows > 0) rows_max = std::min<long long>(rows_max, chunk_rows);
+  rows_max = std::min<long long>(rows_max, N);
+  if ((unsigned long long)rows_max * tiles > 0x7fffffffULL) return fail(c, BTF_EINVAL, who + ": too many workgroups for one launch");
+  HIPCHK(c, hipSetDevice(c->dev));
+  ChkArgs a{};
+  const size_t naux = pred_aux_layout(a.p, family, aux_flags, N, M, T);
+  Scratch s(c, c->stream);
+  pred_upload(c, s, a.p, S, Ws, Vs, per_sample, aux_sample, naux, trials, Y, nreps, ncell);
+  a.p.par = param; a.p.S = S; a.p.R = (int)Rr_ll; a.p.N = N; a.p.M = M; a.p.T = T; a.p.K = K; a.p.seed = seed;
+  a.reps = reps; a.nsets = nsets; a.tiles = tiles;
+  // listed curves: each distinct one gets a slot of the device arrays; the host copies slots to the rows of the list
+  std::vector<int> slot_of, list_slot(ncurves);
+  int nslots = 0;
+  if (ncurves) {
+    slot_of.assign(NM, -1);
+    for (int k = 0; k < ncurves; ++k) {
+      if (slot_of[curves[k]] < 0) slot_of[curves[k]] = nslots++;
+      list_slot[k] = slot_of[curves[k]];
+    }
+    a.listed = s.upload(slot_of.data(), NM);
+    a.t_obs = s.alloc<double>((size_t)nslots * CHK_COUNT * nsets);
+    a.t_rep = s.alloc<double>((size_t)nslots * CHK_COUNT * nsets);
+  }
+  a.cur = s.alloc<double>((size_t)CHK_OUTS * CHK_COUNT * NM);
+  a.nobs = s.alloc<double>(NM);
+  a.part = s.alloc<double>((size_t)rows_max * row_bytes / sizeof(double));
+  const size_t npool = (size_t)2 * CHK_SLOTS * nsets;
+  double* tot = s.alloc<double>(npool);
+  void (*kern)(ChkArgs) = nullptr;
+  FAM_SWITCH(family, kern = chk_kernel<FT>);
+  for (int row0 = 0; row0 < N; row0 += (int)rows_max) {
+    a.row0 = row0; a.rows = std::min<int>((int)rows_max, N - row0);
+    s.launch(kern, dim3((unsigned)((size_t)a.rows * tiles)), dim3(CHK_THREADS), 0, a);
+    s.launch(chk_pool_kernel, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, (const double*)a.part, (long long)a.rows * tiles, nsets,
+             row0 == 0 ? 1 : 0, tot);
+  }
+  std::vector<double> htot(npool), hto, htr;
+  s.download(htot.data(), (const double*)tot, npool);
+  for (int o = 0; o < CHK_OUTS; ++o)
+    for (int k = 0; k < nwhich; ++k)
+      s.download(curve_out ? curve_out + ((size_t)o * nwhich + k) * NM : nullptr, (const double*)a.cur + ((size_t)o * CHK_COUNT + which[k]) * NM, NM);
+  s.download(nobs_out, (const double*)a.nobs, NM);
+  if (ncurves) {
+    hto.resize((size_t)nslots * CHK_COUNT * nsets); htr.resize(hto.size());
+    s.download(hto.data(), (const double*)a.t_obs, hto.size());
+    s.download(htr.data(), (const double*)a.t_rep, htr.size());
+  }
+  if (int rc = s.finish()) return rc;
+  // the pooled discrepancies of every set from their slots (lag1 = num / den); T_obs of sample s from its first set
+  const auto pooled = [&](int side, int code, int e) {
+    const auto at = [&](int slot) { return htot[((size_t)side * CHK_SLOTS + slot) * nsets + e]; };
+    switch (code) {
+      case CHK_CHISQ: return at(CHK_S_CHISQ);
+      case CHK_MAX: return at(CHK_S_MAX);
+      case CHK_LAG1: return (at(CHK_S_PAIR) != 0.0 && at(CHK_S_DEN) != 0.0) ? at(CHK_S_NUM) / at(CHK_S_DEN) : std::nan("");
+      case CHK_TOTAL: return at(CHK_S_TOTAL);
+      default: return at(CHK_S_ZEROS);
+    }
+  };
+  for (int k = 0; k < nwhich; ++k) {
+    if (pool_rep_out) for (int e = 0; e < nsets; ++e) pool_rep_out[(size_t)k * nsets + e] = pooled(0, which[k], e);
+    if (pool_obs_out) for (int sm = 0; sm < S; ++sm) pool_obs_out[(size_t)k * S + sm] = pooled(1, which[k], sm * reps);
+    for (int l = 0; l < ncurves; ++l) {
+      const size_t src = ((size_t)list_slot[l] * CHK_COUNT + which[k]) * nsets;
+      for (int e = 0; e < nsets; ++e) trep_out[((size_t)l * nwhich + k) * nsets + e] = htr[src + e];
+      for (int sm = 0; sm < S; ++sm) tobs_out[((size_t)l * nwhich + k) * S + sm] = hto[src + (size_t)sm * reps];
+    }
+  }
+  return BTF_OK;
 }
 
 int btf_predict_gg_batch(int device, int64_t n, const double* eta, int G, const double* shape, const double* scale, const double* prob,

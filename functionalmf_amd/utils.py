@@ -129,6 +129,42 @@ def posterior_predictive(Ws, Vs, family, data=None, q=(2.5, 97.5), draws_per_sam
         ctx.close()
 
 
+def posterior_checks(Ws, Vs, family, data, which=None, reps=1, seed=0, param=None, nu2=None, R=None, trials=None, curves=None,
+                     device=0, _chunk_rows=0):
+    """Posterior predictive checks from samples on the host, without a model: the stateless form of
+    BayesianTensorFiltering.posterior_checks (see there for `which`, `reps`, `curves` and the outputs; functionalmf_amd.checks
+    is the written definition), beside posterior_predictive.
+
+    Ws, Vs, family, param / nu2 / R, trials and data as posterior_predictive; data is required.  Needs ndepth >= 2 (a
+    context is opened for the call).  No CPU fallback."""
+    from . import _analysis, _native, checks, predictive
+    Ws, Vs = _analysis.check_states(Ws, Vs)
+    code = predictive.family_code(family)
+    S, N, K = Ws.shape
+    shape = (N,) + Vs.shape[1:3]
+    codes = checks.check_which(which, code)
+    Y = data
+    if isinstance(data, (tuple, list)):
+        Y = data[0]
+        trials = data[1] if trials is None else trials
+    Y4 = checks.check_data(Y, shape)
+    checks.check_reps(S, reps, Y4.shape[3])
+    checks.check_curves(curves, shape)
+    aux, flags = None, 0
+    if code == predictive.FAMILY_GAUSSIAN and nu2 is not None:
+        aux, flags = np.asarray(nu2, dtype=float).reshape(S), _native.PRED_AUX_PER_SAMPLE
+    elif code == predictive.FAMILY_NEGBIN and R is not None:
+        aux, flags = predictive.rate_layout(R, S, shape)
+    elif code in (predictive.FAMILY_GAUSSIAN, predictive.FAMILY_NEGBIN) and param is None:
+        raise ValueError("the Gaussian family needs nu2= or param= (variance), the Negative-Binomial R= or param= (rate)")
+    ctx = _native.Context(N, shape[1], shape[2], K, 0, device=device)
+    try:
+        return checks.evaluate(ctx, shape, K, code, S, Ws, Vs, param=param, aux=aux, aux_flags=flags, trials=trials, Y=Y4, which=codes,
+                               reps=reps, seed=seed, curves=curves, _chunk_rows=_chunk_rows)
+    finally:
+        ctx.close()
+
+
 def _gamma_grid_context(Ws, Vs, Y, likelihood, device):
     """A context for one model-free gamma-grid criteria call: the table set, the statistics of Y in slot 0.  Returns
     (ctx, head of btf_crit_eval / btf_crit_loo, (N,M,T), observed-curve mask); the caller closes ctx."""

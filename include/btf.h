@@ -1151,6 +1151,34 @@ int btf_predict_eval(btf_ctx* ctx, int family, double param, int nsamples, const
                      double* pit_hi_out, double* inside_out, double* nobs_out, double* rmse_out, double* mae_out,
                      double* draws_out);
 
+/* ---- posterior predictive checks: predictive p-values of whole-curve discrepancies (csrc/btf_checks.h; the written
+ * definition is functionalmf_amd/checks.py) ----
+ * btf_predict_check: family, param, states, aux_sample / aux_flags, trials and their refusals as btf_predict_eval; Y
+ *   (N,M,T,nreps) is required.  For every kept sample s and rho < reps a replicated data set is drawn at the observed
+ *   slots of Y: slot (i,j,t,rep) of set e = s reps + rho is draw number cell n + s Rr + rho nreps + rep of the family's
+ *   sampler, Rr = reps nreps, n = nsamples Rr - the draw btf_predict_eval returns for that cell with draws_per_sample = Rr
+ *   and the same seed.  There is no 16384 limit (nothing is sorted); BTF_EINVAL where the 64-bit draw index overflows.
+ *   which: nwhich distinct discrepancy codes, 0 chisq, 1 max, 2 lag1, 3 total, 4 zeros, each T(y, theta_s) of a curve
+ *   (i,j) over its observed slots, t ascending then rep ascending: sum (y - mu)^2 / v; max |y - mu| / sqrt(v);
+ *   sum_{t,t+1 defined} e_t e_{t+1} / sum_t e_t^2 with e_t = sum_rep (y - mu_t) / sqrt(v_t m_t), m_t the observed
+ *   replicates at t (nan without an adjacent pair or with a zero denominator); sum y; #{y == 0}.  mu = E[y | theta_s],
+ *   v = Var[y | theta_s]; slots with v == 0 are left out of codes 0..2.
+ *   curve_out (5, nwhich, N, M): the number of sets with T(y_rep) >= T(y), with >, with both defined, and the sums of
+ *   T(y) and of T(y_rep) over those sets; nobs_out (N,M): observed slots.  A curve without observations, and a bad curve
+ *   (an observed slot nothing can be drawn at in some sample: eta <= 0 under the identity link, a missing trial count), is
+ *   nan in both.  pool_obs_out (nwhich, nsamples), pool_rep_out (nwhich, nsamples reps): the discrepancies pooled over all
+ *   other curves per sample / per set - chisq, total, zeros add, max is the maximum, lag1 pools numerator and denominator
+ *   - the curves in row-major order in tiles of 8 columns, the tiles added in index order.  curves: ncurves flat curve
+ *   indices i M + j whose raw values come back as tobs_out (ncurves, nwhich, nsamples) and trep_out (ncurves, nwhich,
+ *   nsamples reps).  chunk_rows: rows per launch (0: what 192 MiB of pooled partials hold); no bit depends on it, on
+ *   `which` or on where the states come from.  No floating-point atomics.  Touches none of the sampler's state.
+ *   Unsharded contexts.  Synchronises.                                                                              */
+int btf_predict_check(btf_ctx* ctx, int family, double param, int nsamples, const double* Ws, const double* Vs,
+                      const double* aux_sample, int aux_flags, const double* trials, const double* Y, int nreps, int reps,
+                      uint64_t seed, const int32_t* which, int nwhich, const int32_t* curves, int ncurves, int chunk_rows,
+                      double* curve_out, double* nobs_out, double* pool_obs_out, double* pool_rep_out, double* tobs_out,
+                      double* trep_out);
+
 /* ---- the same for the gamma-grid likelihood (doseresponse/fit.py:475-478: likelihood.sample and the 5 / 95 percentiles
  * per curve), csrc/btf_gg_predict.h ----
  * The draw: y | eta = eta s_g Gamma(a_g, 1) with the component g chosen by the weights w_g = p_g / sum_h p_h of the table
